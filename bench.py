@@ -9,6 +9,10 @@ steps (barrier + device sync on both sides, max over ranks).
 
 The boundary hands over HOST buffers (Annex-B bytes in, tight YUV out), so `value` is the end-to-end rate:
 host entropy decode + H2D job lists + kernels + pack-out + D2H + the memcpy into the caller's buffer.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else it can measure or check -- the bit-exact
+pass against the CPU oracle, the CPU baseline, the single-stream, push / pull and device-resident legs, the extra BASELINE
+configurations -- runs only with --full.  --dump-outputs DIR writes what the timed path returned in its last step as .npy files.
 """
 import argparse
 import ctypes as C
@@ -56,8 +60,14 @@ def main():
         "(jm_amddec_output_frame_device), no D2H copy -- "
                     "under rocprofv3 the runtime replaces copy-engine transfers by blit kernels, which perturbs the decode kernels")
     ap.add_argument("--parse-only", action="store_true", help="diagnostic: host stages only (no device work, frames carry no pixels)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the untimed extra legs (c4_slice, c2_4k, c3_4k) that the default invocation appends")
+    ap.add_argument("--no-extra", action="store_true", help="skip the untimed extra legs (c4_slice, c2_4k, c3_4k) that --full appends")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the untimed bit-exact check against the CPU oracle, the CPU "
+                    "baseline, the single-stream / push-pull / device-resident legs and, for the headline workload, the extra legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path returned in its last step (rank 0) to DIR/<name>.npy: a fixed, "
+                    "seeded sample of the last frame of every handle, the first handle's last frame whole, and the frames each handle returned")
     args = ap.parse_args()
+    if args.dump_outputs and (args.device_output or args.parse_only):
+        ap.error("--dump-outputs needs frames in host buffers (not with --device-output or --parse-only)")
 
     ctx = setup_process(args)
     line = measure(args, ctx)
@@ -65,8 +75,8 @@ def main():
     if ctx["rank"] == 0 and line is not None:
         # ---- untimed extra legs: the other BASELINE configurations, driver-visible.  The headline line and its timed region above
         # are unchanged; each leg is a full measure() of its own (fresh handles, warm-up, timed steps, bit-exact check against the oracle) reduced to a
-        # compact object.  Only in the default invocation (N = 1, the headline workload): diagnostics and multi-rank runs skip them. ----
-        if ctx["world"] == 1 and default_workload(args) and not args.no_extra:
+        # compact object.  Only with --full and the headline workload (N = 1): diagnostics and multi-rank runs skip them. ----
+        if args.full and ctx["world"] == 1 and default_workload(args) and not args.no_extra:
             # (the measured headline must survive whatever a leg does -- it goes to stderr before the legs start, and a leg that raises ANYTHING
             # becomes an {"error": ...} entry of the one JSON line instead of taking the line with it)
             print("bench.py: headline before the extra legs (repeated in the final line): " +
@@ -106,7 +116,7 @@ def default_workload(args):
 def leg_args(args, over):
     import copy
     a = copy.copy(args)
-    a.no_cpu_baseline = True; a.no_single = True; a.leg = True
+    a.no_cpu_baseline = True; a.no_single = True; a.leg = True; a.dump_outputs = None
     for k, v in over.items():
         setattr(a, k, v)
     if os.environ.get("JM_BENCH_TEST_LEGS"):      # "WxH": the legs' code path on a host without a GPU (tests/test_sharding.py)
@@ -126,6 +136,32 @@ def compact_leg(l, wall_s):
             "engine": {k: l["engine"][k] for k in ("chain_batches", "chain_i_batches", "chain_recoveries", "device_wait_errors", "pictures_per_batch",
                                                       "chain_launches_with_clock_gaps")},
             "stream_generation_s": l["config"]["stream_generation_s"], "leg_wall_s": round(wall_s, 1)}
+
+
+DUMP_BYTES = 64 << 20
+DUMP_SAMPLE = 131072        # bytes of every handle's last frame in frame_sample.npy
+DUMP_SEED = 0x4A4D
+
+
+def dump_outputs(path, frames, counts, frame_bytes):
+    """--dump-outputs: what the timed path handed its callers in its last step, as float32 / float64 .npy files of at most DUMP_BYTES in all.
+
+    frame_sample.npy (S x n): the bytes of the last I420 frame each handle returned, at n fixed positions drawn with a fixed seed
+    (frame_sample_index.npy); last_frame_stream0.npy: the first handle's last frame whole, when it fits; frames_returned.npy (S): frames each
+    handle returned over the timed steps."""
+    import numpy as np
+    S = len(frames)
+    n = min(frame_bytes, DUMP_SAMPLE, DUMP_BYTES // 2 // (4 * S + 8))       # the sample and its index take at most half the budget
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(frame_bytes, n, replace=False))
+    last = [np.frombuffer(f.raw, np.uint8, frame_bytes) for f in frames]
+    out = {"frame_sample": np.stack([f[idx] for f in last]).astype(np.float32), "frame_sample_index": idx.astype(np.float64),
+           "frames_returned": np.asarray(counts, np.float64)}
+    if sum(a.nbytes for a in out.values()) + 4 * frame_bytes <= DUMP_BYTES:
+        out["last_frame_stream0"] = last[0].astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"bench.py: wrote {', '.join(out)} ({sum(a.nbytes for a in out.values()) / 1e6:.1f} MB) to {path}", file=sys.stderr, flush=True)
 
 
 def setup_process(args):
@@ -269,6 +305,7 @@ def measure(args, ctx):
 
     feeder_cpu = [0.0] * S          # CPU seconds of each handle's calling thread (they exit before the per-thread /proc snapshot)
     out_bufs = [C.create_string_buffer(frame_bytes) for _ in range(S)]
+    last_out = list(out_bufs)       # the buffer each handle's last pass returned its frames in (--dump-outputs)
 
     def run_passes(i, passes):
         """test_nv_dec's hot loop: one NAL per jm_nvdec_decode_frame call, pull a frame whenever got_frame == 1."""
@@ -278,6 +315,8 @@ def measure(args, ctx):
         # pass, freed when the pass ends (rounds 1-5; the munmap of a buffer that the output route had page-locked is suspected of taking the process's
         # queues off the device for ~25 ms: profiles/r06_chain_soak.txt)
         out = C.create_string_buffer(frame_bytes) if os.environ.get("JM_BENCH_FRESH_BUFFERS") else out_bufs[i]
+        if args.dump_outputs:
+            last_out[i] = out
         got = C.c_int(0)
         n = C.c_int(0)
         cnt = 0
@@ -413,6 +452,8 @@ def measure(args, ctx):
         v in tc1.items()}
     by_thread = {k: v for k, v in by_thread.items() if v["user_s"] + v["sys_s"] >= 0.05}
     frames_local = sum(counts)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out, counts, frame_bytes)
 
     frames_total, dt_max = shard.reduce_result(dist, frames_local, dt, device=red_dev)     # SUM of frames, MAX of seconds over ranks
 
@@ -490,8 +531,8 @@ def measure(args, ctx):
     A = surf * (p_frac * 2 + (1 - p_frac) * 1) + frame_bytes + J
     kernel_s_per_frame = sum(tot_ns[k] for k in names) * 1e-9 / max(pictures, 1)
 
-    # ---- untimed: prove "+ bit-exact YUV" on the TIMED CONFIGURATION.  One more pass over every handle, all S handles concurrently exactly as in
-    # the timed region (same engine batching, same mix of output routes), every frame MD5'd; the handles are then flushed and closed.  The digests
+    # ---- untimed, --full only: prove "+ bit-exact YUV" on the TIMED CONFIGURATION.  One more pass over every handle, all S handles concurrently exactly
+    # as in the timed region (same engine batching, same mix of output routes), every frame MD5'd; the handles are then flushed and closed.  The digests
     # are compared with the CPU oracle (oracle/, checker only) decoding the first IDR period of the same stream: every handle at N=1, two per
     # rank otherwise (N ranks share the node's host cores). ----
     import hashlib
@@ -525,9 +566,9 @@ def measure(args, ctx):
                 pull()
         check_digests[i] = digs[-F:]                           # frames a reordering DPB still held from the timed passes come out first
 
-    bit_exact, frames_checked, check_note = None, 0, "skipped (--parse-only)"
+    bit_exact, frames_checked, check_note = None, 0, "skipped (--parse-only)" if args.parse_only else "not run (runs with --full)"
     oracle_dt, oracle_frames, oracle_one = 0.0, 0, None
-    if not args.parse_only:
+    if not args.parse_only and args.full:
         ts = [threading.Thread(target=check_pass, args=(i,)) for i in range(S)]
         for t in ts:
             t.start()
@@ -596,7 +637,7 @@ def measure(args, ctx):
     # ---- untimed: ONE handle fed exactly like test_nv_dec.cpp:184-250 (the reference harness's own shape: one stream, one thread) ----
     memtrace("handles released")
     single = None
-    if world == 1 and not args.parse_only and not args.no_single:
+    if args.full and world == 1 and not args.parse_only and not args.no_single:
         h = jmcodec_amd.jm_nvdec_create_handle()
         if jmcodec_amd.jm_nvdec_init(1 if is_hevc else 0, 1, None, 0, h) == 0:
             out = C.create_string_buffer(frame_bytes)
@@ -617,7 +658,7 @@ def measure(args, ctx):
     # buffer per turn, set_eof when the input ran out, until is_exit.  A first copy of the stream is pushed through the same handle untimed (allocations,
     # first launches), like the single-stream leg. ----
     c0_leg = None
-    if world == 1 and not args.parse_only and not args.no_single:
+    if args.full and world == 1 and not args.parse_only and not args.no_single:
         h = L.jm_amdintel_create_handle()
         if L.jm_amdintel_init(1 if is_hevc else 0, 1, h) == 0:
             out = (C.c_ubyte * frame_bytes)()
@@ -655,7 +696,7 @@ def measure(args, ctx):
     # ---- untimed: the same S streams with DEVICE-RESIDENT output (jm_amddec_output_frame_device: frames stay in HBM, nothing crosses PCIe on the way
     # out, no frame copy on the CPU) -- the rate the contract calls "inputs and outputs resident in HBM"; `value` above is the PCIe-inclusive one ----
     dev_leg = None
-    if world == 1 and not args.parse_only and not args.no_single and not args.device_output:
+    if args.full and world == 1 and not args.parse_only and not args.no_single and not args.device_output:
         hs = []
         for _ in range(S):
             h = jmcodec_amd.jm_nvdec_create_handle()
@@ -807,8 +848,8 @@ def measure(args, ctx):
         mem["needed_for_8_gpus_mb"] = round(8 * peak_rss_timed_mb, 0)
         mem["job_slots_mb"] = job_slot_mb
         mem["job_slots_grown"] = job_regrown
-        mem["note"] = ("peak_rss_mb includes the untimed check pass and the CPU oracle; peak_rss_timed_region_mb is the high-water mark when the timed region "
-                       "ends (Python / torch runtime, the bitstreams, the handles) and what needed_for_8_gpus_mb multiplies; job_slots_mb = page-locked job "
+        mem["note"] = (("peak_rss_mb includes the untimed check pass and the CPU oracle; " if args.full else "") +
+                       "peak_rss_timed_region_mb is the high-water mark when the timed region ends (Python / torch runtime, the bitstreams, the handles) and what needed_for_8_gpus_mb multiplies; job_slots_mb = page-locked job "
                        "buffers of this "
                        "rank's handles (ordinary-picture size; three worst-case buffers per handle are lent to I pictures)")
         line["host_memory"] = mem

@@ -2,9 +2,7 @@
 C++-mangled jm_nvdec_* names of the reference header, and the reference's own harness links against it."""
 import os
 import re
-import shutil
 import subprocess
-import tempfile
 
 import pytest
 
@@ -53,25 +51,21 @@ def test_product_does_not_link_the_oracle():
         assert "oracle/" not in src and "orc_h264" not in src, f
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/test_nv_dec/test_nv_dec.cpp"), reason="reference sources only exist in the build container")
+def _ref_binary(name):
+    """A reference harness that build() compiled in place against this library into oracle/_ref/ (oracle/Makefile `ref`; the sources are never
+    copied into the repository)."""
+    exe = os.path.join(ROOT, "oracle", "_ref", name)
+    assert os.path.exists(exe), f"oracle/_ref/{name} is missing: build() makes it with `make -C oracle ref`"
+    return exe
+
+
 def test_reference_harness_links_against_the_library():
-    """Compile /root/reference/test_nv_dec/test_nv_dec.cpp IN PLACE (never copied) with a two-file shim for
-    <Windows.h>/<conio.h> and link it against libjm_amd_dec.so: every jm_nvdec_* symbol it uses must resolve."""
-    if shutil.which("g++") is None or not os.path.exists("/root/reference/test_nv_dec/test_nv_dec.cpp"):
-        pytest.skip("g++ or the reference tree is missing")
-    with tempfile.TemporaryDirectory() as td:
-        open(os.path.join(td, "Windows.h"), "w").write("#include <string.h>\n#include <stdlib.h>\n")
-        open(os.path.join(td, "conio.h"), "w").write("static inline int _kbhit(void){return 0;}\nstatic inline int getch(void){return 0;}\n")
-        exe = os.path.join(td, "test_nv_dec")
-        cmd = ["g++", "-w", "-fpermissive", "-I" + td, "-I/root/reference/nv_dec",
-               "-DJMDLL_FUNC=__attribute__((visibility(\"default\")))", "-DJMDLL_API=",
-               "/root/reference/test_nv_dec/test_nv_dec.cpp", "-o", exe,
-               "-L" + os.path.dirname(api.lib_path()), "-ljm_amd_dec", "-Wl,-rpath," + os.path.dirname(api.lib_path())]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        und = subprocess.check_output(["nm", "-u", exe], text=True)
-        used = set(re.findall(r"_Z\d+jm_nvdec_\w+", und))
-        assert len(used) == 8 and used <= set(MANGLED)
+    """The reference's test_nv_dec.cpp, built with a two-file shim for <Windows.h>/<conio.h> and linked against libjm_amd_dec.so: every jm_nvdec_*
+    symbol it uses is one the library exports."""
+    und = subprocess.check_output(["nm", "-u", _ref_binary("test_nv_dec")], text=True)
+    used = set(re.findall(r"_Z\d+jm_nvdec_\w+", und))
+    assert len(used) == 8 and used <= set(MANGLED)
+    assert used <= _exports(), used - _exports()
 
 
 # ---- push/pull API of intel_dec/jm_intel_dec.h (SURVEY 8f f1) ----
@@ -91,30 +85,21 @@ def test_intel_api_symbols():
     assert set(INTEL_MANGLED) <= exp, set(INTEL_MANGLED) - exp
 
 
-def test_reference_intel_harness_links_against_the_library():
-    """/root/reference/test_intel_dec/test_intel_dec.cpp compiled in place (never copied) links against the library."""
-    if shutil.which("g++") is None or not os.path.exists("/root/reference/test_intel_dec/test_intel_dec.cpp"):
-        pytest.skip("g++ or the reference tree is missing")
-    with tempfile.TemporaryDirectory() as td:
-        open(os.path.join(td, "Windows.h"), "w").write("#include <string.h>\n#include <stdlib.h>\n")
-        open(os.path.join(td, "conio.h"), "w").write("static inline int _kbhit(void){return 0;}\nstatic inline int getch(void){return 0;}\n")
-        exe = os.path.join(td, "test_intel_dec")
-        cmd = ["g++", "-w", "-fpermissive", "-Wno-format-security", "-I" + td, "-I/root/reference/intel_dec",
-               "-DJMDLL_FUNC=__attribute__((visibility(\"default\")))", "-DJMDLL_API=",
-               "/root/reference/test_intel_dec/test_intel_dec.cpp", "-o", exe,
-               "-L" + os.path.dirname(api.lib_path()), "-ljm_amd_dec", "-Wl,-rpath," + os.path.dirname(api.lib_path())]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        und = subprocess.check_output(["nm", "-u", exe], text=True)
-        used = set(re.findall(r"_Z\d+jm_intel_\w+", und))
-        assert len(used) >= 9 and used <= set(INTEL_MANGLED), used - set(INTEL_MANGLED)
-        # host-side run of the reference's own loop (parse-only: no GPU here): it must terminate and report the frame count
-        from util import golden_stream
-        src = os.path.join(td, "in.h264")
-        open(src, "wb").write(golden_stream("ip_fuzz_96x80"))
-        env = dict(os.environ, JM_AMD_DEC_PARSE_ONLY="1")
-        r = subprocess.run([exe, src], capture_output=True, text=True, env=env, timeout=60, cwd=td)   # the harness opens its hard-coded output name in the cwd
-        assert "Frame Count:\t8" in r.stdout, r.stdout + r.stderr
+def test_reference_intel_harness_links_against_the_library(tmp_path):
+    """The reference's test_intel_dec.cpp, built the same way, links against the library and runs its own loop on the host."""
+    exe = _ref_binary("test_intel_dec")
+    und = subprocess.check_output(["nm", "-u", exe], text=True)
+    used = set(re.findall(r"_Z\d+jm_intel_\w+", und))
+    assert len(used) >= 9 and used <= set(INTEL_MANGLED), used - set(INTEL_MANGLED)
+    assert used <= _exports(), used - _exports()
+    # host-side run of the reference's own loop (parse-only: no kernels): it must terminate and report the frame count
+    from util import golden_stream
+    src = tmp_path / "in.h264"
+    src.write_bytes(golden_stream("ip_fuzz_96x80"))
+    env = dict(os.environ, JM_AMD_DEC_PARSE_ONLY="1")
+    # (the harness opens its hard-coded output name in the cwd)
+    r = subprocess.run([exe, str(src)], capture_output=True, text=True, env=env, timeout=60, cwd=str(tmp_path))
+    assert "Frame Count:\t8" in r.stdout, r.stdout + r.stderr
 
 
 def _harness():

@@ -77,7 +77,7 @@ def test_bench_two_ranks_gloo_parse_only():
 
 
 def test_bench_extra_legs_parse_only(tmp_path):
-    """the default bench invocation appends untimed legs for the other BASELINE configurations -- c4_slice (8 x 1080p Baseline), c2_4k
+    """bench.py --full appends untimed legs for the other BASELINE configurations -- c4_slice (8 x 1080p Baseline), c2_4k
     (16 x 4K High I B B P), c3_4k (16 x 4K HEVC) -- each a compact object with its own bit-exact flag and roofline block.  Here: the same code path at a toy
     size without a GPU (--parse-only, JM_BENCH_TEST_LEGS): one JSON line, the headline keys unchanged, the three legs present with the promised fields."""
     import json
@@ -85,7 +85,7 @@ def test_bench_extra_legs_parse_only(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--parse-only", "--streams", "2", "--frames", "8", "--width", "176",
-           "--height", "144"]
+           "--height", "144", "--full"]
     env = dict(os.environ, JM_BENCH_CACHE=str(tmp_path), JM_BENCH_TEST_LEGS="176x144")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -31,7 +31,7 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--command", default="python3 bench.py --steps 1 --warmup 1 --frames 30 --streams 1 --no-cpu-baseline")
+    ap.add_argument("--command", default="python3 bench.py --steps 1 --warmup 1 --frames 30 --streams 1 --no-cpu-baseline --full")
     # environment of the profiled run, written IN FRONT of rocprofv3 in the recipe (behind the `--` it would be the program rocprofv3 tries to
     # start, and `-- env VAR=1 python3 ...` is an exec hop behind an initialised GPU, which this pool forbids under --pmc)
     ap.add_argument("--env", default="", help='e.g. "JM_AMD_DEC_CHAIN_DEPTH=1"')
