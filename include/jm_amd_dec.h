@@ -60,6 +60,7 @@ int  jm_amddec_is_hw_support(void);
  *       engine-wide after init: "chain_depth" (pictures of one stream per chain launch; 0 = the defaults: 8, and 16 while one or two streams are active),
  *       "chain_lag", "chain_streams", "debug_stall" (DESIGN.md 4b); before init: "job_slots" (pictures in flight per handle, 8..64; default 40 for H.264 up
  *       to 1080p, else 24);
+ *       "crop_x" / "crop_y" / "crop_w" / "crop_h" / "target_width" / "target_height" (before init: scaled and cropped output, see below);
  *       tests only: "fast_parse" (0 = every macroblock through the general parser path), "job_digest" (1 = digest of the job lists; implies sync) */
 /* like jm_amddec_decode_frame without input: *got_frame = 1 when a display-order frame became ready (never signals end of stream) */
 int  jm_amddec_poll_frame(int *got_frame, jm_amddec_handle h);
@@ -78,7 +79,7 @@ int  jm_amddec_set_option(jm_amddec_handle h, const char *key, long long value);
  *       "threads", "elapsed_us", "display_poc:<n>", "fps_num" / "fps_den" (frame rate from the VUI timing information, 0 / 0 = not transmitted),
  *       "frames_waiting" (display frames decided and not yet made current by a decode / poll call), "frames_done_unfetched" (those of them whose samples are there), "device_wait_errors", "direct_frames" / "direct_ns" (frames that left by one copy-engine
  *       transfer into the caller's buffer, and the time their callers waited), "copy_engines" (SDMA engines used for that, bit mask),
- *       "job_digest", "eng_*" / "k_*" (engine and per-kernel counters, bench.py) */
+ *       "job_digest", "eng_*" / "k_*" (engine and per-kernel counters, bench.py), "out_width" / "out_height" / "scaled_frames" (see below) */
 long long jm_amddec_get_stat(jm_amddec_handle h, const char *key);
 const char *jm_amddec_last_error(jm_amddec_handle h);
 
@@ -95,6 +96,24 @@ int  jm_amddec_output_frame_device(void **dev, int *len, jm_amddec_handle h);
 int  jm_amddec_output_argb_device(void *dev_dst, int pitch, jm_amddec_handle h);
 int  jm_amddec_packout_device(const void *d_src, int pitch, int width, int height, int out_fmt,
                               void *d_dst, void *stream);
+/* Scaled and cropped output (INTEGRATION.md "Scaled and cropped output" defines the resampler exactly).  Options, before init, even values only
+ * (set_option returns -1 after init and for odd or negative values):
+ *   "crop_x", "crop_y", "crop_w", "crop_h": the crop rectangle inside the display area (w / h 0 = up to the display area's right / bottom edge);
+ *   "target_width", "target_height": the size of the frames handed out (0 = the crop size).
+ * Per axis the crop may be at most 8x the target and the target at most 4x the crop.  The geometry is checked against the display area when a
+ * sequence starts; a geometry that does not fit fails the handle with a jm_amddec_last_error text that says why.  stream_info, output_frame,
+ * output_frame_device, output_argb_device and output_nv12_pitch_device then work on the target-size frame.  Stats: "out_width", "out_height",
+ * "scaled_frames" (display frames that went through the resampler; 0 when the geometry is the identity).
+ *   jm_amddec_scale_taps: the tap table of one axis, src_len -> dst_len samples (host only): first[j] = first source sample of output j (not
+ *     clamped), weights[j * max_taps + k] = the weight (1/16384) of source sample clamp(first[j] + k).  Returns the taps per output, or -1 (invalid
+ *     ratio, or more taps than max_taps); first == NULL or weights == NULL: only returns the taps per output.
+ *   jm_amddec_scale_device: stand-alone crop + resample + pack of one pitch-linear NV12 surface in device memory (luma rows at `pitch`, the UV rows
+ *     from byte chroma_offset; display area w x h; lone_field 0, or 1 / 2 = show only the top / bottom field's lines, each twice) into a tight
+ *     frame of tw x th (out_fmt 0 NV12, 1 I420) at d_dst.  stream: a hipStream_t or NULL.  Returns 0, -1 for invalid arguments, or a negative
+ *     hipError. */
+int  jm_amddec_scale_taps(int src_len, int dst_len, int *first, short *weights, int max_taps);
+int  jm_amddec_scale_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int lone_field, int crop_x, int crop_y, int crop_w,
+                            int crop_h, int tw, int th, int out_fmt, void *d_dst, void *stream);
 /* SURVEY 8f f4 -- the encoder-side pre-processing of the reference (/root/reference/nv_enc/nv_enc.cpp:1022-1079: cuMemcpy2D of the luma plane +
  * the InterleaveUV kernel; the CPU loop of intel_enc.cpp:316-387) as one HIP kernel, device to device: a tight frame (src_fmt 1 = I420
  * planar Y,U,V; 0 = tight NV12) becomes a pitch-linear NV12 surface (luma rows at `pitch`, interleaved UV rows from row `height`), the layout an

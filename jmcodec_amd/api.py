@@ -62,6 +62,9 @@ def lib():
     L.jm_amddec_last_error.restype = cp
     L.jm_amddec_packout_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.jm_amddec_output_frame_device.argtypes = [C.POINTER(C.c_void_p), ip, vp]
+    L.jm_amddec_scale_taps.argtypes = [C.c_int, C.c_int, ip, C.POINTER(C.c_short), C.c_int]
+    L.jm_amddec_scale_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, vp, vp]
     L.jm_amddec_feed_annexb.argtypes = [cp, C.c_long, C.c_int, C.POINTER(C.c_ubyte), C.c_int, vp]
     L.jm_amddec_feed_annexb.restype = C.c_long
     L.jm_amddec_poll_frame.argtypes = [ip, vp]
@@ -141,6 +144,22 @@ def jm_nvdec_is_exit(handle):
 
 def jm_nvdec_show_dec_info(handle):
     return lib().jm_amddec_show_dec_info(handle).decode()
+
+
+# ---- scaled and cropped output (include/jm_amd_dec.h; the resampler is defined in INTEGRATION.md) ----------
+def scale_taps(src_len, dst_len, max_taps=9):
+    """Tap table of one axis, src_len -> dst_len samples: (first, weights) -- first[j] the first source sample of output j (not clamped),
+    weights[j] the list of its weights (1/16384) for source samples clamp(first[j] + k).  None when the ratio is invalid."""
+    first, w = (C.c_int * max(dst_len, 1))(), (C.c_short * max(dst_len * max_taps, 1))()
+    taps = lib().jm_amddec_scale_taps(src_len, dst_len, first, w, max_taps)
+    if taps < 0:
+        return None
+    return list(first[:dst_len]), [list(w[j * max_taps:j * max_taps + taps]) for j in range(dst_len)]
+
+
+def scale_device(src, pitch, chroma_offset, width, height, crop, target, out_fmt, dst, lone_field=0, stream=None):
+    """jm_amddec_scale_device: crop = (x, y, w, h), target = (tw, th); src / dst device addresses.  Returns 0 or < 0."""
+    return lib().jm_amddec_scale_device(src, pitch, chroma_offset, width, height, lone_field, *crop, *target, out_fmt, dst, stream)
 
 
 # ---- the reference harness's NAL scanner (test_nv_dec.cpp:30-86), vectorised -----------------

@@ -146,6 +146,12 @@ int Decoder::set_option(const char *key, long long v) {
     else if (k == "sync") sync_mode_ = v != 0;
     else if (k == "device_output") device_output_ = v != 0;        // frames stay in device memory (no D2H); see output_device()
     else if (k == "device") device_ = (int)v;
+    else if (k == "crop_x" || k == "crop_y" || k == "crop_w" || k == "crop_h" || k == "target_width" || k == "target_height") {
+        // scaled / cropped output: fixed at init (NVDEC's create-time geometry); even values only (4:2:0 chroma)
+        if (inited_ || v < 0 || v > 32768 || (v & 1)) return -1;
+        static const char *const keys[6] = {"crop_x", "crop_y", "crop_w", "crop_h", "target_width", "target_height"};
+        for (int i = 0; i < 6; i++) if (k == keys[i]) geo_[i] = (int)v;
+    }
     else if (k == "profile") { profile_ = v != 0; if (engine_) engine_->set_profile(profile_); }
     else if (k.rfind("chain_", 0) == 0 || k == "debug_stall" || k == "debug_no_bi" || k == "early_intra_ahead") {    // engine-wide knobs (every handle of the device), after init
         if (!engine_ || !engine_->set_knob(k, v)) return -1;
@@ -164,6 +170,9 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "field_pictures") return stat_field_pics_.load();
     if (k == "lone_fields") return stat_lone_fields_.load();
     if (k == "frames") return num_frames_;
+    if (k == "out_width") return out_w_;              // size of the frames handed out (the target size of a scaled handle)
+    if (k == "out_height") return out_h_;
+    if (k == "scaled_frames") return stat_scaled_;    // display frames that went out through k_scale_pack
     if (k == "pictures") return stat_pictures_;
     if (k == "job_bytes") return stat_job_bytes_;
     if (k == "job_regrown") return stat_job_regrown_;          // job slots grown on demand (a few per handle, then none)
@@ -379,6 +388,7 @@ void Decoder::gpu_free_sequence() {
     if (resid_) { hipFree(resid_); resid_ = nullptr; }
     for (auto &w : hevc_work_) if (w) { hipFree(w); w = nullptr; }
     if (hevc_bs_) { hipFree(hevc_bs_); hevc_bs_ = nullptr; }
+    if (scale_dev_) { hipFree(scale_dev_); scale_dev_ = nullptr; }
     free_job_buffers();
     free_out_slots(true);
 }
@@ -403,10 +413,87 @@ void Decoder::gpu_close() {
     gpu_open_ = false;
 }
 
+// ---- scaled / cropped output (INTEGRATION.md "Scaled and cropped output": the resampler R_G) ----
+int build_scale_taps(int S, int D, std::vector<int32_t> &first, std::vector<int16_t> &w) {
+    if (S <= 0 || D <= 0 || (long long)S > 8ll * D || (long long)D > 4ll * S) return -1;
+    const long long s = S, d = D;
+    int taps = 2;                                         // D >= S: bilinear, half-sample centres
+    if (D < S) { taps = 0; for (long long j = 0; j < d; j++) taps = std::max(taps, (int)(((j + 1) * s + d - 1) / d - j * s / d)); }    // area average
+    first.assign((size_t)D, 0);
+    w.assign((size_t)D * taps, 0);
+    for (long long j = 0; j < d; j++) {
+        int16_t *wj = &w[(size_t)j * taps];
+        if (D >= S) {
+            const long long num = (2 * j + 1) * s - d, d2 = 2 * d;
+            const long long i0 = num >= 0 ? num / d2 : -((-num + d2 - 1) / d2);     // floor division
+            const long long w1 = ((num - d2 * i0) * 16384 + d) / d2;
+            first[j] = (int32_t)i0; wj[0] = (int16_t)(16384 - w1); wj[1] = (int16_t)w1;
+        } else {
+            const long long lo = j * s / d, hi = ((j + 1) * s + d - 1) / d;          // source samples lo .. hi - 1 overlap output j
+            long long sum = 0, best = 0; int bk = 0;
+            for (long long i = lo; i < hi; i++) {
+                const long long a = std::min((i + 1) * d, (j + 1) * s) - std::max(i * d, j * s);   // overlap; they sum to S
+                wj[i - lo] = (int16_t)(a * 16384 / s); sum += wj[i - lo];
+                if (a > best) { best = a; bk = (int)(i - lo); }
+            }
+            first[j] = (int32_t)lo; wj[bk] = (int16_t)(wj[bk] + 16384 - sum);      // the rounding remainder to the first largest overlap
+        }
+    }
+    return taps;
+}
+
+bool upload_scale_tables(int w, int h, int tw, int th, uint8_t **dev, ScaleAxis ax[4]) {
+    const int S[4] = {w, h, w / 2, h / 2}, D[4] = {tw, th, tw / 2, th / 2};
+    std::vector<int32_t> first[4]; std::vector<int16_t> wt[4];
+    size_t off[4][2], total = 0;
+    for (int a = 0; a < 4; a++) {
+        const int T = build_scale_taps(S[a], D[a], first[a], wt[a]);
+        if (T < 0 || T > kScaleMaxTaps) return false;
+        ax[a].taps = T; ax[a].src_len = S[a];
+        off[a][0] = total; total += (first[a].size() * sizeof(int32_t) + 255) & ~(size_t)255;
+        off[a][1] = total; total += (wt[a].size() * sizeof(int16_t) + 255) & ~(size_t)255;
+    }
+    std::vector<uint8_t> host(total, 0);
+    for (int a = 0; a < 4; a++) { memcpy(host.data() + off[a][0], first[a].data(), first[a].size() * sizeof(int32_t));
+        memcpy(host.data() + off[a][1], wt[a].data(), wt[a].size() * sizeof(int16_t)); }
+    *dev = nullptr;
+    if (!HIP_OK(hipMalloc((void **)dev, total))) { *dev = nullptr; return false; }
+    if (!HIP_OK(hipMemcpy(*dev, host.data(), total, hipMemcpyHostToDevice))) { hipFree(*dev); *dev = nullptr; return false; }
+    for (int a = 0; a < 4; a++) { ax[a].first = (const int32_t *)(*dev + off[a][0]); ax[a].w = (const int16_t *)(*dev + off[a][1]); }
+    return true;
+}
+
+// the geometry options against the display area of the sequence being activated (the crop rectangle is checked again at every new sequence; the
+// target stays what it was at init)
+bool Decoder::resolve_geometry() {
+    const int W = disp_w_, H = disp_h_;
+    out_w_ = W; out_h_ = H; crop_[0] = crop_[1] = 0; crop_[2] = W; crop_[3] = H; scaled_ = false;
+    if (!(geo_[0] | geo_[1] | geo_[2] | geo_[3] | geo_[4] | geo_[5])) return true;
+    const int cx = geo_[0], cy = geo_[1], cw = geo_[2] ? geo_[2] : W - cx, ch = geo_[3] ? geo_[3] : H - cy;
+    const int tw = geo_[4] ? geo_[4] : cw, th = geo_[5] ? geo_[5] : ch;
+    char msg[256];
+    if (cw <= 0 || ch <= 0 || cx + cw > W || cy + ch > H) {
+        snprintf(msg, sizeof msg, "output geometry: the crop rectangle %dx%d at (%d, %d) does not lie inside the display area %dx%d", cw, ch, cx, cy, W, H);
+        fail(msg); return false;
+    }
+    if ((cw | ch) & 1) {
+        snprintf(msg, sizeof msg, "output geometry: the crop size %dx%d (display area %dx%d) is odd", cw, ch, W, H);
+        fail(msg); return false;
+    }
+    if (cw > 8 * tw || ch > 8 * th || tw > 4 * cw || th > 4 * ch) {
+        snprintf(msg, sizeof msg, "output geometry: the scaling ratio %dx%d -> %dx%d is out of range (per axis at most 8:1 down and 1:4 up)", cw, ch, tw, th);
+        fail(msg); return false;
+    }
+    crop_[0] = cx; crop_[1] = cy; crop_[2] = cw; crop_[3] = ch; out_w_ = tw; out_h_ = th;
+    scaled_ = !(cx == 0 && cy == 0 && cw == W && ch == H && tw == cw && th == ch);     // the identity geometry keeps k_packout
+    return true;
+}
+
 // nvdec_create_decoder (nv_dec.cpp:496-540): surfaces sized by the coded picture, NV12
 bool Decoder::gpu_alloc_sequence() {
     size_t n_mbs = (size_t)mb_w_ * mb_h_;
-    frame_bytes_ = (size_t)disp_w_ * disp_h_ * 3 / 2;
+    if (!resolve_geometry()) return false;
+    frame_bytes_ = (size_t)out_w_ * out_h_ * 3 / 2;
     // MbRec + worst-case coefficients + motion records (16 vectors; 72 int16 for B / weighted slices) + slice tables
     // (always the Main / High layout: a later SPS of the same size may switch profile without re-activation, and a PPS may enable weighted
     //  prediction under any profile_idc)
@@ -434,6 +521,9 @@ bool Decoder::gpu_alloc_sequence() {
         return true;
     }
     hipSetDevice(device_);
+    // (re-activation: nothing is in flight any more, activate() drained the handle)
+    if (scale_dev_) { hipFree(scale_dev_); scale_dev_ = nullptr; }
+    if (scaled_ && !upload_scale_tables(crop_[2], crop_[3], out_w_, out_h_, &scale_dev_, scale_ax_)) { fail("scale table allocation failed"); return false; }
     pitch_ = (mb_w_ * 16 + 127) & ~127;
     chroma_off_ = pitch_ * mb_h_ * 16;
     surf_bytes_ = (size_t)pitch_ * mb_h_ * 16 * 3 / 2;
@@ -488,7 +578,7 @@ bool Decoder::gpu_alloc_sequence() {
 OutSlot *Decoder::alloc_out_slot() {   // mtx_ held
     while (!free_out_.empty()) {
         OutSlot *o = free_out_.back(); free_out_.pop_back();
-        if (o->bytes == frame_bytes_ || parse_only_) { o->ready = false; o->has_data = false; o->w = disp_w_; o->h = disp_h_; return o; }
+        if (o->bytes == frame_bytes_ || parse_only_) { o->ready = false; o->has_data = false; o->w = out_w_; o->h = out_h_; return o; }
         // a slot of the previous resolution came back: release it
         all_out_.erase(std::remove(all_out_.begin(), all_out_.end(), o), all_out_.end());
         if (o->host) hipHostFree(o->host);
@@ -496,7 +586,7 @@ OutSlot *Decoder::alloc_out_slot() {   // mtx_ held
         delete o;
     }
     OutSlot *o = new OutSlot();
-    o->w = disp_w_; o->h = disp_h_;
+    o->w = out_w_; o->h = out_h_;
     if (!parse_only_) {
         hipSetDevice(device_);
         if (!device_output_ && out_route_ != 1 && out_route_ != 3 && !HIP_OK(hipHostMalloc((void **)&o->host, frame_bytes_,
@@ -1456,7 +1546,7 @@ void Decoder::submit_ready() {
 }
 
 // a display frame leaves the DPB: reserve an output slot (display order) and describe the pack-out for the engine
-void Decoder::enqueue_output(int slot_and_lone, std::vector<PackJob> &jobs, std::vector<OutSlot *> &slots) {
+void Decoder::enqueue_output(int slot_and_lone, std::vector<PackJob> &jobs, std::vector<ScaleJob> &sjobs, std::vector<OutSlot *> &slots) {
     const int slot = slot_and_lone & 255, lone = slot_and_lone >> 8;       // store_done: bits 8.. = the one field that was decoded, if only one was
     OutSlot *o;
     { std::lock_guard<std::mutex> lk(mtx_); o = alloc_out_slot(); ready_.push_back(o); num_frames_++; }   // nv_dec.cpp:48 num_frames++
@@ -1464,7 +1554,12 @@ void Decoder::enqueue_output(int slot_and_lone, std::vector<PackJob> &jobs, std:
     // k_packout packs the tight frame into device staging and a copy engine moves it to the pinned slot -- or, in direct mode,
     // the kernel stores straight into the pinned host slot (see Engine::launch for why the copy engine is the default)
     // (a frame of which only one field was decoded is shown with that field's lines repeated: PackJob.lone_field)
-    jobs.push_back(PackJob{surf_[slot], o->dev ? o->dev : o->host, pitch_, chroma_off_, disp_w_, disp_h_, out_fmt_, lone});
+    // (a scaled handle: k_scale_pack crops, resamples and packs in one pass, with the same row mapping)
+    if (scaled_) {
+        ScaleJob sj{surf_[slot], o->dev ? o->dev : o->host, pitch_, chroma_off_, crop_[0], crop_[1], out_w_, out_h_, out_fmt_, lone, {}};
+        for (int a = 0; a < 4; a++) sj.ax[a] = scale_ax_[a];
+        sjobs.push_back(sj); stat_scaled_++;
+    } else jobs.push_back(PackJob{surf_[slot], o->dev ? o->dev : o->host, pitch_, chroma_off_, disp_w_, disp_h_, out_fmt_, lone});
     slots.push_back(o);
     o->has_data = true;
     // route of this frame (see Decoder::init): fetch when the device's synchronous-copy queue is idle right now
@@ -1476,7 +1571,7 @@ void Decoder::submit_task(PicTask *t) {
     EnginePic ep;
     ep.dec = this; ep.has_picture = t->has_picture && !parse_only_ && !failed_; ep.job_slot = t->job_slot;
     ep.mb_w = mb_w_; ep.mb_h = mb_h_; ep.disp_w = disp_w_; ep.disp_h = disp_h_; ep.wait_prev_pack = t->wait_prev_pack;
-    for (int s : t->out_before) { enqueue_output(s, ep.out_before, ep.slots_before); ep.out_mask |= 1u << (s & 255); }
+    for (int s : t->out_before) { enqueue_output(s, ep.out_before, ep.scale_before, ep.slots_before); ep.out_mask |= 1u << (s & 255); }
     memset(&ep.pp, 0, sizeof ep.pp);
     if (ep.has_picture && t->hevc) hevc_fill_engine_pic(t, ep);
     else if (ep.has_picture) {
@@ -1537,8 +1632,9 @@ void Decoder::submit_task(PicTask *t) {
         ep.alg_bytes[1] = is_i ? S : (long long)t->n_intra * 384;
         ep.alg_bytes[2] = 2 * S;
     }
-    ep.alg_bytes[3] = (long long)surf_bytes_ + (long long)frame_bytes_;
-    for (int s : t->out_after) { enqueue_output(s, ep.out_after, ep.slots_after); ep.out_mask |= 1u << (s & 255); }
+    // (a scaled handle reads the crop rectangle of the surface)
+    ep.alg_bytes[3] = (scaled_ ? (long long)crop_[2] * crop_[3] * 3 / 2 : (long long)surf_bytes_) + (long long)frame_bytes_;
+    for (int s : t->out_after) { enqueue_output(s, ep.out_after, ep.scale_after, ep.slots_after); ep.out_mask |= 1u << (s & 255); }
     stat_submit_ns_ += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - st0).count();
     if (parse_only_ || failed_ || !engine_) { on_engine_done(ep); return; }
     engine_->submit(std::move(ep));
@@ -1652,7 +1748,7 @@ int Decoder::decode(const uint8_t *buf, int len, int *got_frame) {
                      "Elapsed Time:\t%d ms\n"
                      "Decode FPS:\t%f fps\n"
                      "==========================================\n",
-                     codec_ == 0 ? "H.264" : "H.265", disp_w_, disp_h_, out_fmt_ == 0 ? "NV12" : "YV12", (int)num_frames_,
+                     codec_ == 0 ? "H.264" : "H.265", out_w_, out_h_, out_fmt_ == 0 ? "NV12" : "YV12", (int)num_frames_,
                      (int)elapsed_ms_, elapsed_ms_ > 0 ? (double)num_frames_ * 1000.0 / elapsed_ms_ : 0.0);
         }
     }
@@ -1713,7 +1809,7 @@ int Decoder::output_argb_device(void *dev_dst, int pitch) {
 int Decoder::stream_info(int *w, int *h) const {
     // the frame the caller is about to fetch, else the current sequence (they differ only around a resolution change)
     if (cur_out_) { *w = cur_out_->w; *h = cur_out_->h; return 0; }
-    *w = disp_w_; *h = disp_h_;
+    *w = out_w_; *h = out_h_;
     return 0;
 }
 

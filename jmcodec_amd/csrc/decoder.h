@@ -121,6 +121,14 @@ struct OutSlot {                       // one display frame in pinned host memor
 
 class HostCopier;
 
+// Scaled / cropped output: the tap table of one axis of the resampler R_G, S source samples -> D output samples.
+// first[j] = first source index of output j (not clamped), w[j * taps + k] = weight of source index first[j] + k (1/16384; they sum to 16384).
+// Returns taps (the same for every output; unused taps weigh 0), or -1 when S, D are not positive or the ratio is outside 1/8 .. 4.
+int build_scale_taps(int S, int D, std::vector<int32_t> &first, std::vector<int16_t> &w);
+// the four tables of a geometry (crop w x h -> target tw x th: luma x, luma y, chroma x, chroma y) in ONE device allocation *dev (the caller
+// frees it); ax[] points into it.  Synchronous (activation time).  false: invalid sizes or a failed allocation.
+bool upload_scale_tables(int w, int h, int tw, int th, uint8_t **dev, ScaleAxis ax[4]);
+
 class Decoder {
 public:
     Decoder();
@@ -197,7 +205,8 @@ private:
     void gpu_close();
     void submit_ready();
     void submit_task(PicTask *t);
-    void enqueue_output(int slot, std::vector<PackJob> &jobs, std::vector<OutSlot *> &slots);
+    void enqueue_output(int slot, std::vector<PackJob> &jobs, std::vector<ScaleJob> &sjobs, std::vector<OutSlot *> &slots);
+    bool resolve_geometry();                   // options crop_* / target_* against the display size of the sequence being activated
     OutSlot *alloc_out_slot();
 
     // configuration
@@ -216,6 +225,12 @@ private:
     ParamSets ps_;
     bool seq_active_ = false; SeqParams seq_;
     int mb_w_ = 0, mb_h_ = 0, disp_w_ = 0, disp_h_ = 0, dpb_size_ = 1, reorder_depth_ = 0, n_surf_ = 0;
+    // scaled / cropped output (options before init): crop x, y, w, h (w / h 0: to the display area's edge), target w, h (0: the crop size)
+    int geo_[6] = {0, 0, 0, 0, 0, 0};
+    // ... resolved per sequence (resolve_geometry): the size of the frames handed out, the crop rectangle; scaled_ = not the identity
+    int out_w_ = 0, out_h_ = 0, crop_[4] = {0, 0, 0, 0}; bool scaled_ = false;
+    uint8_t *scale_dev_ = nullptr; ScaleAxis scale_ax_[4] = {};     // the sequence's tap tables on the device (k_scale_pack)
+    std::atomic<long long> stat_scaled_{0};
 
     // DPB / picture state (front end only)
     DpbPic dpb_[kMaxSurfaces];

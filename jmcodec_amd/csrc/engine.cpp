@@ -92,6 +92,8 @@ Engine::Engine(int device) : device_(device) {
             if (hipMalloc((void **)&b.d_groups, sizeof(uint32_t) * kMaxChainGroups) != hipSuccess) return;
             if (hipHostMalloc((void **)&b.h_jobs, sizeof(PackJob) * 4 * kMaxBatch, hipHostMallocDefault) != hipSuccess) return;
             if (hipMalloc((void **)&b.d_jobs, sizeof(PackJob) * 4 * kMaxBatch) != hipSuccess) return;
+            if (hipHostMalloc((void **)&b.h_sjobs, sizeof(ScaleJob) * 4 * kMaxBatch, hipHostMallocDefault) != hipSuccess) return;
+            if (hipMalloc((void **)&b.d_sjobs, sizeof(ScaleJob) * 4 * kMaxBatch) != hipSuccess) return;
             if (hipEventCreateWithFlags(&b.done, hipEventDisableTiming) != hipSuccess) return;
             if (hipEventCreateWithFlags(&b.kdone, hipEventDisableTiming) != hipSuccess) return;
             if (hipEventCreateWithFlags(&b.packed, hipEventDisableTiming) != hipSuccess) return;
@@ -280,7 +282,7 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
     auto account = [&](EnginePic &p, EngineDecoderState &es) {
         if (p.has_picture) es.batch_written |= 1u << (p.codec == 0 ? p.pp.cur : p.hp.cur);
         es.batch_read |= p.ref_mask | p.out_mask;
-        n_pre += p.out_before.size(); n_post += p.out_after.size();
+        n_pre += p.n_before(); n_post += p.n_after();
     };
     // (the walk ends once every decoder that has pictures pending has been seen: with the engine as the bottleneck some 1,100 pictures are pending at 32 streams,
     //  the decoders' oldest ones among the first hundred or two -- and this runs under m_, which every submitting thread needs, on every turn of the engine loop)
@@ -300,7 +302,7 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
         else if (es.inflight > es.lane_inflight[lane_idx] && !(relaxed && others_done(d, lane_idx, it->seq))) why = 2;
         // the pack-job tables hold 2 * kMaxBatch entries each: a picture whose display frames no longer fit waits for the next batch
         // (a flush or an IDR picture can release a whole DPB at once: up to 16 frames from one handle)
-        else if (n_pre + it->out_before.size() > (size_t)2 * kMaxBatch || n_post + it->out_after.size() > (size_t)2 * kMaxBatch) why = 3;
+        else if (n_pre + it->n_before() > (size_t)2 * kMaxBatch || n_post + it->n_after() > (size_t)2 * kMaxBatch) why = 3;
         if (why) {
             if (lane_idx == kOrdinaryLane && it->codec == 0) { std::lock_guard<std::mutex> lk(sm_);
                 (why == 1 ? st_.rej_other_lane : why == 2 ? st_.rej_cross_lane : st_.rej_tables)++;
@@ -346,7 +348,7 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
             if (es.scan_tag != tag) { es.scan_tag = tag; es.scan_touched = 0; es.scan_ahead = 0;
                 es.scan_closed = std::find(members.begin(), members.end(), d) != members.end(); }
             const uint32_t own = it->has_picture ? 1u << (it->codec == 0 ? it->pp.cur : it->hp.cur) : 0u;
-            if (!es.scan_closed && it->codec == 0 && it->has_picture && it->lane(false) == kIntraLane && it->ref_mask == 0 && it->out_before.empty() &&
+            if (!es.scan_closed && it->codec == 0 && it->has_picture && it->lane(false) == kIntraLane && it->ref_mask == 0 && it->before_empty() &&
                 !it->wait_prev_pack && !(it->out_mask & ~own)) {
                 es.scan_closed = true;                      // only a decoder's first intra picture is looked at
                 uint32_t infl; inflight_masks(d, infl);
@@ -372,11 +374,11 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
             for (auto &c : cand) pos.push_back((size_t)(c - pending_.begin()));
             for (size_t k = pos.size(); k-- > 0 && (int)b.pics.size() < kMaxBatch;) {
                 auto it = pending_.begin() + (std::ptrdiff_t)pos[k];
-                if (n_post + it->out_after.size() > (size_t)2 * kMaxBatch) continue;
+                if (n_post + it->n_after() > (size_t)2 * kMaxBatch) continue;
                 EngineDecoderState &es = it->dec->engine_state();
                 es.inflight++; es.lane_inflight[lane_idx]++;
                 LANE_TRACE("early dec %p seq %llu\n", (void *)it->dec, it->seq);
-                n_post += it->out_after.size();
+                n_post += it->n_after();
                 took(es);
                 b.pics.push_back(std::move(*it));
                 pending_.erase(it);
@@ -418,8 +420,8 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
                 // the next picture joins only if it runs inside k_chain, packs nothing BEFORE the kernels (such frames may not be decoded yet),
                 // and decodes into a surface that no earlier picture of this decoder in the batch writes, references or displays
                 const bool ok = it != pending_.end() && it->lane(true) == lane_idx && it->has_picture && (it->chain_ok || it->chain_intra) &&
-                                it->out_before.empty() && !it->wait_prev_pack &&
-                                !((1u << it->pp.cur) & (es.batch_written | es.batch_read)) && n_post + it->out_after.size() <= (size_t)2 * kMaxBatch;
+                                it->before_empty() && !it->wait_prev_pack &&
+                                !((1u << it->pp.cur) & (es.batch_written | es.batch_read)) && n_post + it->n_after() <= (size_t)2 * kMaxBatch;
                 int nb = 0, ng = 0;
                 if (ok) chain_cost(*it, nb, ng);
                 if (!ok || tot_bands + nb > band_limit(any_intra || it->chain_intra) || tot_groups + ng > kMaxChainGroups) { es.batch_stop = true; continue; }
@@ -445,10 +447,10 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
             EngineDecoderState &es = d->engine_state();
             while (es.in_batch < kHevcWorkSets && (int)b.pics.size() < kMaxBatch) {
                 auto it = std::find_if(pending_.begin(), pending_.end(), [&](const EnginePic &p) { return p.dec == d; });
-                if (it == pending_.end() || !it->has_picture || it->codec != 1 || it->lane(false) != lane_idx || !it->out_before.empty() ||
+                if (it == pending_.end() || !it->has_picture || it->codec != 1 || it->lane(false) != lane_idx || !it->before_empty() ||
                     it->wait_prev_pack) break;
                 if ((it->ref_mask & es.batch_written) || ((1u << it->hp.cur) & (es.batch_written | es.batch_read)) ||
-                    n_post + it->out_after.size() > (size_t)2 * kMaxBatch) break;
+                    n_post + it->n_after() > (size_t)2 * kMaxBatch) break;
                 es.inflight++; es.lane_inflight[lane_idx]++; es.in_batch++;
                 es.batch_written |= 1u << it->hp.cur;
                 account(*it, es);
@@ -478,7 +480,7 @@ void Engine::launch(Lane &ln, Batch &b) {
     bool wait_pack = false, any_hevc = false;
     HevcBatchDims hd;
     const EnginePic *last_upload[4] = {nullptr, nullptr, nullptr, nullptr};      // per copy stream (upload k went to stream k % n_copy_)
-    b.n_pre = b.n_post = 0; b.pmask = 0;
+    b.n_pre = b.n_post = 0; b.n_spre = b.n_spost = 0; b.s_tiles = 0; b.pmask = 0;
     for (int k = 0; k < 5; k++) { b.alg[k] = 0; b.npics[k] = 0; }
     // pack jobs: [0, n_pre) before the decode kernels, [2*kMaxBatch, 2*kMaxBatch + n_post) after them
     for (int i = 0; i < n; i++) {
@@ -527,6 +529,9 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (p.wait_prev_pack) wait_pack = true;
         for (auto &j : p.out_before) b.h_jobs[b.n_pre++] = j;                           // form() keeps both tables within 2 * kMaxBatch
         for (auto &j : p.out_after) b.h_jobs[2 * kMaxBatch + b.n_post++] = j;
+        // (scaled handles: the same two tables for k_scale_pack, launched beside k_packout)
+        for (auto &j : p.scale_before) { b.h_sjobs[b.n_spre++] = j; b.s_tiles = std::max(b.s_tiles, scale_tiles(j.tw, j.th)); }
+        for (auto &j : p.scale_after) { b.h_sjobs[2 * kMaxBatch + b.n_spost++] = j; b.s_tiles = std::max(b.s_tiles, scale_tiles(j.tw, j.th)); }
         if (!p.out_before.empty() || !p.out_after.empty()) { max_w = std::max(max_w, p.disp_w); max_h = std::max(max_h, p.disp_h); }
         int st = b.h_pics[i].stages;
         if (hevc && p.has_picture) { const int hs = p.hp.stages; if (hs & (HPS_MC | HPS_RESID)) { b.alg[0] += p.alg_bytes[0]; b.npics[0]++; }
@@ -535,8 +540,8 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (st & (PS_INTRA_LDS | PS_INTRA_V1)) { b.alg[1] += p.alg_bytes[1]; b.npics[1]++; }
         if (st & (PS_DEBLOCK_LDS | PS_DEBLOCK_V1)) { b.alg[2] += p.alg_bytes[2]; b.npics[2]++; }
         if (st & PS_CHAIN) { b.alg[4] += ((st & PS_RECON) ? 0 : p.alg_bytes[0]) + ((st & PS_CHAIN_INTRA) ? p.alg_bytes[1] : 0) + p.alg_bytes[2]; b.npics[4]++; }
-        b.alg[3] += p.alg_bytes[3] * (long long)(p.out_before.size() + p.out_after.size());
-        b.npics[3] += (int)(p.out_before.size() + p.out_after.size());
+        b.alg[3] += p.alg_bytes[3] * (long long)(p.n_before() + p.n_after());
+        b.npics[3] += (int)(p.n_before() + p.n_after());
     }
     // surfaces this batch displays, per decoder: a later batch that decodes into one of them must wait for this batch's pack-out
     // (per lane: pictures of a decoder on different lanes are kept apart by Engine::form)
@@ -564,6 +569,8 @@ void Engine::launch(Lane &ln, Batch &b) {
     else hipMemcpyAsync(b.d_pics, b.h_pics, sizeof(PicParams) * n, hipMemcpyHostToDevice, ps);
     if (b.n_pre) hipMemcpyAsync(b.d_jobs, b.h_jobs, sizeof(PackJob) * b.n_pre, hipMemcpyHostToDevice, ps);
     if (b.n_post) hipMemcpyAsync(b.d_jobs + 2 * kMaxBatch, b.h_jobs + 2 * kMaxBatch, sizeof(PackJob) * b.n_post, hipMemcpyHostToDevice, ps);
+    if (b.n_spre) hipMemcpyAsync(b.d_sjobs, b.h_sjobs, sizeof(ScaleJob) * b.n_spre, hipMemcpyHostToDevice, ps);
+    if (b.n_spost) hipMemcpyAsync(b.d_sjobs + 2 * kMaxBatch, b.h_sjobs + 2 * kMaxBatch, sizeof(ScaleJob) * b.n_spost, hipMemcpyHostToDevice, ps);
     // job lists were copied on the (in-order) copy stream when the pictures were parsed: waiting for the most recently
     // issued one of this batch covers them all without waiting for uploads of later pictures
     for (const EnginePic *lu : last_upload) if (lu) hipStreamWaitEvent(ps, lu->uploaded, 0);
@@ -579,7 +586,7 @@ void Engine::launch(Lane &ln, Batch &b) {
     // The decoder never reuses a displayed surface for the very next picture (DPB cooling, decoder.cpp), so the decode
     // kernels of this batch only have to wait for the pack-out launched TWO batches ago.
     if (ln.pack_hist[1]) hipStreamWaitEvent(st, ln.pack_hist[1], 0);
-    if ((wait_pack || b.n_pre) && ln.pack_hist[0]) hipStreamWaitEvent(st, ln.pack_hist[0], 0);
+    if ((wait_pack || b.n_pre || b.n_spre) && ln.pack_hist[0]) hipStreamWaitEvent(st, ln.pack_hist[0], 0);
     auto mark = [&](int i, hipStream_t s) { if (profile_) hipEventRecord(b.pev[i], s); };
     mark(0, st);
     // Pack-out: k_packout writes the tight frames into device staging and a copy engine (SDMA) moves them to the pinned slots.
@@ -587,7 +594,11 @@ void Engine::launch(Lane &ln, Batch &b) {
     // queues with everything else: k_recon_inter of the next batch ran 4x slower next to it (0.56 -> 2.3 ms for 32 pictures).
     auto copy_out = [&](const std::vector<OutSlot *> &slots, hipStream_t s) { for (OutSlot *o : slots) if (o->dev && o->host &&
         !o->fetch) hipMemcpyAsync(o->host, o->dev, o->bytes, hipMemcpyDeviceToHost, s); };
-    if (b.n_pre) { launch_packout(b.d_jobs, b.n_pre, max_w, max_h, st); b.pmask |= 1; for (auto &p : b.pics) copy_out(p.slots_before, st); }
+    if (b.n_pre || b.n_spre) {
+        if (b.n_pre) launch_packout(b.d_jobs, b.n_pre, max_w, max_h, st);
+        if (b.n_spre) launch_scale_pack(b.d_sjobs, b.n_spre, b.s_tiles, st);
+        b.pmask |= 1; for (auto &p : b.pics) copy_out(p.slots_before, st);
+    }
     mark(1, st);
     if (any_hevc && (hd.max_pus || hd.max_tbs || hd.any_intra || hd.any_deblock || hd.any_sao)) {
         // HEVC batch (its own lane, so never mixed with H.264 pictures): MC + residual | intra diagonals | deblocking + SAO
@@ -687,6 +698,7 @@ void Engine::launch(Lane &ln, Batch &b) {
     hipStreamWaitEvent(pst, b.kdone, 0);
     mark(5, pst);
     if (b.n_post) { launch_packout(b.d_jobs + 2 * kMaxBatch, b.n_post, max_w, max_h, pst); b.pmask |= 16; }
+    if (b.n_spost) { launch_scale_pack(b.d_sjobs + 2 * kMaxBatch, b.n_spost, b.s_tiles, pst); b.pmask |= 16; }
     mark(6, pst);
     hipEventRecord(b.packed, pst);                            // from here on the displayed surfaces may be decoded into again
     for (auto &p : b.pics) copy_out(p.slots_after, pst);
@@ -723,7 +735,7 @@ void Engine::recover(Lane &ln, Batch &b, const std::vector<std::pair<Decoder *, 
             if (p.dec != d) continue;
             ext_refs |= p.ref_mask & ~written;                 // references decoded before this batch
             shown |= p.out_mask;
-            if (!p.out_before.empty()) shown_before |= p.out_mask;
+            if (!p.before_empty()) shown_before |= p.out_mask;
             if (p.has_picture && p.codec == 0) written |= 1u << p.pp.cur;
         }
         for (auto &e : later) if (e.first == d) lw |= e.second;
@@ -731,8 +743,9 @@ void Engine::recover(Lane &ln, Batch &b, const std::vector<std::pair<Decoder *, 
         if ((lw & (ext_refs | shown)) || (b.redo && (written & shown_before))) taint(d);
     }
     // 2. frames this batch packed before its kernels showed pictures of the recovered batch: again, from the pictures as they are now
-    if (b.redo && b.n_pre) {
-        launch_packout(b.d_jobs, b.n_pre, b.max_w, b.max_h, st);
+    if (b.redo && (b.n_pre || b.n_spre)) {
+        if (b.n_pre) launch_packout(b.d_jobs, b.n_pre, b.max_w, b.max_h, st);
+        if (b.n_spre) launch_scale_pack(b.d_sjobs, b.n_spre, b.s_tiles, st);
         for (auto &p : b.pics) for (OutSlot *o : p.slots_before) if (o->dev && o->host && !o->fetch) hipMemcpyAsync(o->host, o->dev, o->bytes,
             hipMemcpyDeviceToHost, st);
         hipStreamSynchronize(st);
@@ -761,8 +774,9 @@ void Engine::recover(Lane &ln, Batch &b, const std::vector<std::pair<Decoder *, 
         if (stages & PS_DEBLOCK_V1) launch_deblock(b.d_pics, n, st);
         hipStreamSynchronize(st);                              // h_pics is rewritten for the next depth
     }
-    if (b.n_post) {                                            // the display frames of the batch again, from the pictures as they are now
-        launch_packout(b.d_jobs + 2 * kMaxBatch, b.n_post, b.max_w, b.max_h, st);
+    if (b.n_post || b.n_spost) {                               // the display frames of the batch again, from the pictures as they are now
+        if (b.n_post) launch_packout(b.d_jobs + 2 * kMaxBatch, b.n_post, b.max_w, b.max_h, st);
+        if (b.n_spost) launch_scale_pack(b.d_sjobs + 2 * kMaxBatch, b.n_spost, b.s_tiles, st);
         for (auto &p : b.pics) for (OutSlot *o : p.slots_after) if (o->dev && o->host && !o->fetch) hipMemcpyAsync(o->host, o->dev, o->bytes,
             hipMemcpyDeviceToHost, st);
         hipStreamSynchronize(st);

@@ -61,6 +61,10 @@ struct EnginePic {
     int job_slot = -1;
     ihipEvent_t *uploaded = nullptr; unsigned long long upload_seq = 0;   // job list copy (copy stream), see Engine::upload
     std::vector<PackJob> out_before, out_after;     // display frames to pack before / after this picture's kernels
+    std::vector<ScaleJob> scale_before, scale_after;    // ... of handles with scaled / cropped output (k_scale_pack)
+    size_t n_before() const { return out_before.size() + scale_before.size(); }
+    size_t n_after() const { return out_after.size() + scale_after.size(); }
+    bool before_empty() const { return n_before() == 0; }
     std::vector<OutSlot *> slots_before, slots_after;
     int mb_w = 0, mb_h = 0, disp_w = 0, disp_h = 0;
     bool wait_prev_pack = false;                    // this picture reuses a surface whose pack-out may still be running
@@ -153,6 +157,8 @@ private:
         int max_mbs = 0, max_mb_h = 0, max_w = 0, max_h = 0; bool any_bipred = false, any_field = false;
         uint32_t *h_groups = nullptr, *d_groups = nullptr;     // work list of k_chain (chain.hip), kMaxChainGroups entries
         PackJob *h_jobs = nullptr, *d_jobs = nullptr;         // 4 * kMaxBatch entries
+        ScaleJob *h_sjobs = nullptr, *d_sjobs = nullptr;      // the same for k_scale_pack
+        int n_spre = 0, n_spost = 0, s_tiles = 0;             // (s_tiles: the grid of launch_scale_pack)
         // packed: surfaces were read by k_packout (before the copies)
         ihipEvent_t *done = nullptr, *kdone = nullptr, *packed = nullptr, *pre_done = nullptr, *pev[10] = {nullptr};
         std::vector<EnginePic> pics;

@@ -108,6 +108,37 @@ __attribute__((visibility("default"))) int jm_amddec_packout_device(const void *
     return e == hipSuccess ? 0 : -(int)e;
 }
 
+__attribute__((visibility("default"))) int jm_amddec_scale_taps(int src_len, int dst_len, int *first, short *weights, int max_taps) {
+    std::vector<int32_t> f; std::vector<int16_t> w;
+    const int taps = jmamd::build_scale_taps(src_len, dst_len, f, w);
+    if (taps < 0 || !first || !weights) return taps;          // (no buffers: how many taps a table of this ratio has)
+    if (taps > max_taps) return -1;
+    for (int j = 0; j < dst_len; j++) {
+        first[j] = f[j];
+        for (int k = 0; k < max_taps; k++) weights[(size_t)j * max_taps + k] = k < taps ? w[(size_t)j * taps + k] : 0;
+    }
+    return taps;
+}
+__attribute__((visibility("default"))) int jm_amddec_scale_device(const void *src, int pitch, int chroma_offset, int w, int hgt, int lone_field, int crop_x,
+    int crop_y, int crop_w, int crop_h, int tw, int th, int out_fmt, void *dst, void *stream) {
+    if (!src || !dst || w <= 0 || hgt <= 0 || pitch < w || lone_field < 0 || lone_field > 2 || (out_fmt != 0 && out_fmt != 1)) return -1;
+    if ((crop_x | crop_y | crop_w | crop_h | tw | th) & 1) return -1;
+    if (crop_x < 0 || crop_y < 0 || crop_w <= 0 || crop_h <= 0 || crop_x + crop_w > w || crop_y + crop_h > hgt || tw <= 0 || th <= 0) return -1;
+    if (crop_w > 8 * tw || crop_h > 8 * th || tw > 4 * crop_w || th > 4 * crop_h) return -1;
+    jmamd::ScaleJob job{static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), pitch, chroma_offset, crop_x, crop_y, tw, th, out_fmt, lone_field, {}};
+    uint8_t *tables = nullptr;
+    if (!jmamd::upload_scale_tables(crop_w, crop_h, tw, th, &tables, job.ax)) return -1;
+    jmamd::ScaleJob *d_job = nullptr;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hipMalloc((void **)&d_job, sizeof job) != hipSuccess) { hipFree(tables); return -1; }
+    hipMemcpyAsync(d_job, &job, sizeof job, hipMemcpyHostToDevice, st);
+    jmamd::launch_scale_pack(d_job, 1, jmamd::scale_tiles(tw, th), st);
+    hipError_t e = hipGetLastError();
+    hipStreamSynchronize(st);
+    hipFree(d_job); hipFree(tables);
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
 __attribute__((visibility("default"))) long jm_amddec_feed_annexb(const unsigned char *buf, long len, int passes, unsigned char *out, int out_cap,
     jm_amddec_handle h) {
     if (!h || !buf || len < 4) return -1;       // out == NULL: frames stay on the device (jm_amddec_output_frame_device), nothing is copied

@@ -131,4 +131,21 @@ struct PackJob {                  // one display frame to pack out (k_packout, b
     int lone_field;               // 0; 1 / 2: only the top / bottom field of the frame was decoded -- its lines are shown twice
 };
 
+// Scaled / cropped output (k_scale_pack; the resampler R_G of INTEGRATION.md).  One axis of one plane's tap table, built on the host
+// (build_scale_taps, decoder.cpp): output sample j is sum_k w[j * taps + k] * src[clamp(first[j] + k)], k < taps, clamp to [0, src_len - 1]
+// (weights in 1/16384; a table has the same number of taps for every output, unused ones have weight 0)
+struct ScaleAxis {
+    const int32_t *first; const int16_t *w;
+    int taps, src_len;
+};
+constexpr int kScaleMaxTaps = 9;  // 1/8 downscale: at most ceil(8) + 1 source samples per output
+struct ScaleJob {                 // one display frame to crop + resample + pack (k_scale_pack, blockIdx.y = job)
+    const uint8_t *src; uint8_t *dst;
+    int pitch, chroma_offset;
+    int crop_x, crop_y;           // origin of the crop rectangle in the display frame (luma samples, even); its size is ax[0 / 1].src_len
+    int tw, th, out_fmt;          // target size (even), 0 = tight NV12, 1 = I420
+    int lone_field;               // as PackJob::lone_field
+    ScaleAxis ax[4];              // luma x, luma y, chroma x, chroma y (device pointers into the handle's tap tables)
+};
+
 }  // namespace jmamd

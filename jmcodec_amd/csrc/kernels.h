@@ -34,6 +34,9 @@ int  chain_tail_head_ints(); int chain_tail_wait_limit();                       
 int  chain_tail_ints();                                                                        // kChainTail: ints behind the pictures' blocks
 // pitch-linear NV12 surface -> tight frame (out_fmt 0 = NV12, 1 = I420 order), nv_dec.cpp:782-820
 void launch_packout(const PackJob *d_jobs, int n, int max_width, int max_height, hipStream_t st);
+// pitch-linear NV12 surface -> cropped, resampled tight frame at the job's target size (k_scale_pack); max_tiles: the largest scale_tiles() of the jobs
+int  scale_tiles(int tw, int th);
+void launch_scale_pack(const ScaleJob *d_jobs, int n, int max_tiles, hipStream_t st);
 // tight I420 (fmt 1) / NV12 (fmt 0) frame in device memory -> ARGB32 in device memory
 void launch_frame_to_argb(const uint8_t *d_src, int w, int h, int fmt, uint8_t *d_dst, int dst_pitch, hipStream_t st);
 // tight I420 / NV12 -> pitch NV12 (encoder input)

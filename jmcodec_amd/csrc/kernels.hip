@@ -613,6 +613,109 @@ void launch_frame_to_nv12_pitch(const uint8_t *d_src, int w, int h, int fmt, uin
     hipLaunchKernelGGL(k_frame_to_nv12_pitch, dim3(((w + 3) / 4 + 255) / 256, h + h / 2), dim3(256), 0, st, d_src, w, h, fmt, d_dst, pitch);
 }
 
+// ------------------------------------------------------------------------------------------
+// k_scale_pack: k_packout with a crop rectangle and a resampler (options crop_* / target_*, INTEGRATION.md "Scaled and cropped output").
+// Output = R_G(F), F = the frame k_packout would produce (lone-field row mapping included): separable fixed-point filter, horizontal pass
+// h = (sum wx * p + 64) >> 7 (int16), vertical pass out = min(255, (sum wy * h + 2^20) >> 21), taps from the handle's tables (ScaleAxis).
+// One workgroup per output tile: 64 luma columns x 16 rows, or 32 chroma columns (both channels) x 16 chroma rows; luma tiles first, then
+// chroma tiles.  The horizontal pass writes the tile's filtered source rows (every row its vertical taps reach) into LDS as int16, the
+// vertical pass writes 4 output bytes per lane.
+// ------------------------------------------------------------------------------------------
+constexpr int kScaleTileW = 64, kScaleTileH = 16;
+// source rows one tile can reach: 15 output rows of at most 8 source rows each + 1 (floor), + kScaleMaxTaps - 1, + 1; with slack
+constexpr int kScaleMaxRows = 136;
+__device__ __forceinline__ int clamp_to(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+__global__ __launch_bounds__(256) void k_scale_pack(const ScaleJob *jobs) {
+    __shared__ int16_t hbuf[kScaleMaxRows * kScaleTileW];   // [source row][64 columns]: luma, or 32 chroma columns x (U, V)
+    const ScaleJob &jb = jobs[blockIdx.y];
+    const int tw = jb.tw, th = jb.th, cw = tw >> 1, ch = th >> 1;
+    const int txl = (tw + kScaleTileW - 1) / kScaleTileW, nl = txl * ((th + kScaleTileH - 1) / kScaleTileH);
+    const int txc = (cw + kScaleTileW / 2 - 1) / (kScaleTileW / 2), nc = txc * ((ch + kScaleTileH - 1) / kScaleTileH);
+    int t = blockIdx.x;
+    if (t >= nl + nc) return;
+    const bool chroma = t >= nl;
+    if (chroma) t -= nl;
+    const int ntx = chroma ? txc : txl, cols = chroma ? kScaleTileW / 2 : kScaleTileW;
+    const int ow = chroma ? cw : tw, oh = chroma ? ch : th;
+    const int j0 = (t % ntx) * cols, i0 = (t / ntx) * kScaleTileH;
+    const int jn = min(cols, ow - j0), in = min(kScaleTileH, oh - i0);
+    const ScaleAxis ax = jb.ax[chroma ? 2 : 0], ay = jb.ax[chroma ? 3 : 1];
+    const int Sx = ax.src_len, Sy = ay.src_len;
+    // the source rows the tile's vertical taps reach (clamping is monotonic: every tap of the tile lies in [r0, r1])
+    const int r0 = clamp_to(ay.first[i0], Sy), r1 = clamp_to(ay.first[i0 + in - 1] + ay.taps - 1, Sy);
+    const int nrows = r1 - r0 + 1;
+    if (nrows > kScaleMaxRows) return;                       // (cannot happen within the validated ratios: S <= 8 D)
+    const uint8_t *plane = jb.src + (chroma ? jb.chroma_offset : 0);
+    const int ox = chroma ? jb.crop_x >> 1 : jb.crop_x, oy = chroma ? jb.crop_y >> 1 : jb.crop_y;
+    const int pitch = jb.pitch, lone = jb.lone_field;
+
+    // horizontal pass: lane column c = output column (luma) or output chroma column c / 2, channel c & 1; rows threadIdx.x / 64, + 4, ...
+    {
+        const int c = threadIdx.x & (kScaleTileW - 1);
+        const int jj = chroma ? c >> 1 : c;
+        if (jj < jn) {
+            const int j = j0 + jj, f = ax.first[j], T = ax.taps;
+            int xs[kScaleMaxTaps], wv[kScaleMaxTaps];
+#pragma unroll
+            for (int k = 0; k < kScaleMaxTaps; k++) {
+                const int x = ox + clamp_to(f + k, Sx);
+                xs[k] = chroma ? 2 * x + (c & 1) : x;
+                wv[k] = k < T ? ax.w[j * T + k] : 0;
+            }
+            for (int r = threadIdx.x >> 6; r < nrows; r += 4) {
+                const int sy = oy + r0 + r;                  // row of the display frame F ...
+                const uint8_t *p = plane + (size_t)(lone ? ((sy & ~1) | (lone - 1)) : sy) * pitch;    // ... and of the surface (k_packout's mapping)
+                int acc = 64;
+#pragma unroll
+                for (int k = 0; k < kScaleMaxTaps; k++) if (k < T) acc += wv[k] * p[xs[k]];
+                hbuf[r * kScaleTileW + c] = (int16_t)(acc >> 7);
+            }
+        }
+    }
+    __syncthreads();
+
+    // vertical pass: 16 lanes per output row, 4 output bytes each (luma / NV12 chroma: bytes 4q..4q+3 of the tile's row = hbuf columns 4q..4q+3;
+    // I420 chroma: lanes q < 8 write U columns 4q.., lanes q >= 8 V columns 4(q-8).., i.e. hbuf columns 2 * column + channel)
+    const int r = threadIdx.x >> 4, q = threadIdx.x & 15;
+    if (r >= in) return;
+    const int i = i0 + r, fy = ay.first[i], Ty = ay.taps;
+    const bool planar = chroma && jb.out_fmt == 1;
+    int col[4], n_valid = 0;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const int b = planar ? 4 * (q & 7) + e : 4 * q + e;          // output byte of the tile's row (planar: in its U or V row)
+        col[e] = planar ? 2 * b + (q >> 3) : b;
+        if ((planar ? b : (chroma ? b >> 1 : b)) < jn) n_valid = e + 1;
+    }
+    int acc[4] = {1 << 20, 1 << 20, 1 << 20, 1 << 20};
+#pragma unroll
+    for (int k = 0; k < kScaleMaxTaps; k++) {
+        if (k >= Ty) break;
+        const int w = ay.w[i * Ty + k];
+        const int16_t *hr = hbuf + (clamp_to(fy + k, Sy) - r0) * kScaleTileW;
+#pragma unroll
+        for (int e = 0; e < 4; e++) acc[e] += w * hr[col[e]];
+    }
+    uint32_t v = 0;
+#pragma unroll
+    for (int e = 0; e < 4; e++) v |= (uint32_t)min(255, acc[e] >> 21) << (8 * e);
+    uint8_t *d;
+    if (!chroma) d = jb.dst + (size_t)i * tw + j0 + 4 * q;
+    else if (!planar) d = jb.dst + (size_t)tw * th + (size_t)i * tw + 2 * j0 + 4 * q;
+    else d = jb.dst + (size_t)tw * th + (size_t)(q >> 3) * cw * ch + (size_t)i * cw + j0 + 4 * (q & 7);
+    if (n_valid == 4 && !(((uintptr_t)d) & 3)) *(uint32_t *)d = v;
+    else for (int e = 0; e < n_valid; e++) d[e] = (uint8_t)(v >> (8 * e));
+}
+
+int scale_tiles(int tw, int th) {
+    return ((tw + kScaleTileW - 1) / kScaleTileW) * ((th + kScaleTileH - 1) / kScaleTileH) +
+           ((tw / 2 + kScaleTileW / 2 - 1) / (kScaleTileW / 2)) * ((th / 2 + kScaleTileH - 1) / kScaleTileH);
+}
+void launch_scale_pack(const ScaleJob *d_jobs, int n, int max_tiles, hipStream_t st) {
+    if (n > 0 && max_tiles > 0) hipLaunchKernelGGL(k_scale_pack, dim3(max_tiles, n), dim3(256), 0, st, d_jobs);
+}
+
 void launch_packout(const PackJob *d_jobs, int n, int max_width, int max_height, hipStream_t st) {
     int chunks = ((max_width + 15) >> 4) * (max_height + (max_height >> 1));
     int blocks = (chunks + 255) / 256;
