@@ -114,6 +114,31 @@ int  jm_amddec_packout_device(const void *d_src, int pitch, int width, int heigh
 int  jm_amddec_scale_taps(int src_len, int dst_len, int *first, short *weights, int max_taps);
 int  jm_amddec_scale_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int lone_field, int crop_x, int crop_y, int crop_w,
                             int crop_h, int tw, int th, int out_fmt, void *d_dst, void *stream);
+/* RGB output (INTEGRATION.md "RGB output" defines the conversion C exactly).  A handle with an RGB spec hands out every display frame as
+ * C(R_G(F)): three samples per pixel of the target size, planar (CHW) or interleaved (HWC), R,G,B or B,G,R order, u8 / f32 / f16 / bf16
+ * (f16 and bf16 as their 16-bit patterns), frame bytes 3 * w * h * sizeof(sample).  matrix 0 / range 0 = from the stream's VUI (matrix: the VUI
+ * value when supported, else BT.709 above 576 display lines and BT.601 otherwise; range: the VUI flag, else limited).  The float samples are
+ * fl32(fl32(v * scale[c] / 16384) + bias[c]) of the 14-fractional-bit value v, per storage position c (scale / bias are ignored for u8).
+ *   jm_amddec_set_rgb: before init; NULL = Y'CbCr output again.  0, or -1 after init or for an invalid spec.  output_frame, output_frame_device and
+ *     feed_annexb then hand out RGB frames; output_argb_device and output_nv12_pitch_device return -1.  Stats: "out_frame_bytes" (of the frame
+ *     current or about to be fetched), "rgb_frames", "color_matrix" / "color_range" (in use: H.273 MatrixCoefficients, 1 limited / 2 full),
+ *     "vui_matrix" / "vui_primaries" / "vui_transfer" / "vui_full_range" (as transmitted, -1 = absent), "out_slot_bytes" (device + page-locked
+ *     output-slot memory).  Without an explicit "job_slots" an RGB handle keeps at most 1 GiB of output slots (never fewer than 8 job slots).
+ *   jm_amddec_color_coefs: the five 14-bit coefficients cy, crv, cgu, cgv, cbu of a matrix (1, 4, 5, 6, 7, 9) and range (host only); -1 unsupported.
+ *   jm_amddec_rgb_device: stand-alone crop + resample + convert of one pitch-linear NV12 surface (arguments as jm_amddec_scale_device; matrix must
+ *     be explicit, d_dst aligned to the sample size).  Returns 0, -1 for invalid arguments, or a negative hipError. */
+typedef struct {
+    int dtype;                  /* 0 u8, 1 f32, 2 f16, 3 bf16 */
+    int planar;                 /* 1 CHW, 0 HWC */
+    int bgr;                    /* 0 R,G,B; 1 B,G,R */
+    int matrix;                 /* 0 auto (VUI), else 1, 4, 5, 6, 7, 9 */
+    int range;                  /* 0 auto, 1 limited, 2 full */
+    float scale[3], bias[3];    /* per storage position; ignored for u8 */
+} jm_amddec_rgb_spec;
+int  jm_amddec_set_rgb(jm_amddec_handle h, const jm_amddec_rgb_spec *spec);
+int  jm_amddec_color_coefs(int matrix, int full_range, int coefs[5]);
+int  jm_amddec_rgb_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int lone_field, int crop_x, int crop_y, int crop_w,
+                          int crop_h, int tw, int th, const jm_amddec_rgb_spec *spec, void *d_dst, void *stream);
 /* SURVEY 8f f4 -- the encoder-side pre-processing of the reference (/root/reference/nv_enc/nv_enc.cpp:1022-1079: cuMemcpy2D of the luma plane +
  * the InterleaveUV kernel; the CPU loop of intel_enc.cpp:316-387) as one HIP kernel, device to device: a tight frame (src_fmt 1 = I420
  * planar Y,U,V; 0 = tight NV12) becomes a pitch-linear NV12 surface (luma rows at `pitch`, interleaved UV rows from row `height`), the layout an

@@ -88,6 +88,10 @@ def lib():
     L.jm_amdintel_run_pushpull.restype = C.c_long
     L.jm_amdintel_decoder.argtypes = [vp]
     L.jm_amdintel_decoder.restype = vp
+    L.jm_amddec_set_rgb.argtypes = [vp, C.POINTER(RgbSpec)]
+    L.jm_amddec_color_coefs.argtypes = [C.c_int, C.c_int, ip]
+    L.jm_amddec_rgb_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(RgbSpec), vp, vp]
     _LIB = L
     return L
 
@@ -160,6 +164,73 @@ def scale_taps(src_len, dst_len, max_taps=9):
 def scale_device(src, pitch, chroma_offset, width, height, crop, target, out_fmt, dst, lone_field=0, stream=None):
     """jm_amddec_scale_device: crop = (x, y, w, h), target = (tw, th); src / dst device addresses.  Returns 0 or < 0."""
     return lib().jm_amddec_scale_device(src, pitch, chroma_offset, width, height, lone_field, *crop, *target, out_fmt, dst, stream)
+
+
+# ---- RGB output (include/jm_amd_dec.h; the conversion C is defined in INTEGRATION.md "RGB output") ----------
+class RgbSpec(C.Structure):
+    """jm_amddec_rgb_spec."""
+    _fields_ = [("dtype", C.c_int), ("planar", C.c_int), ("bgr", C.c_int), ("matrix", C.c_int), ("range", C.c_int),
+                ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+RGB_DTYPES = {"u8": 0, "f32": 1, "f16": 2, "bf16": 3}
+RGB_SAMPLE_BYTES = {0: 1, 1: 4, 2: 2, 3: 2}
+
+
+def rgb_spec(dtype="f16", planar=True, bgr=False, matrix=0, range=0, mean=None, std=None, scale=None, bias=None):
+    """An RgbSpec.  dtype: "u8" / "f32" / "f16" / "bf16" (or 0..3).  scale / bias per storage position; mean / std (per storage position, on the
+    0..1 scale) give the normalisation scale = 1 / (255 std), bias = -mean / std.  Without any of them: scale 1, bias 0 (floats in [0, 255])."""
+    s = RgbSpec()
+    s.dtype = RGB_DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+    s.planar, s.bgr, s.matrix, s.range = int(bool(planar)), int(bool(bgr)), int(matrix), int(range)
+    sc, bi = [1.0] * 3, [0.0] * 3
+    if mean is not None or std is not None:
+        m = list(mean) if mean is not None else [0.0] * 3
+        d = list(std) if std is not None else [1.0] * 3
+        sc = [1.0 / (255.0 * d[c]) for c in (0, 1, 2)]
+        bi = [-m[c] / d[c] for c in (0, 1, 2)]
+    if scale is not None:
+        sc = list(scale)
+    if bias is not None:
+        bi = list(bias)
+    for c in (0, 1, 2):
+        s.scale[c], s.bias[c] = sc[c], bi[c]
+    return s
+
+
+def set_rgb(handle, dtype="f16", planar=True, bgr=False, matrix=0, range=0, mean=None, std=None, scale=None, bias=None):
+    """jm_amddec_set_rgb before init (the arguments as rgb_spec; an RgbSpec as dtype is used as it is; dtype=None: Y'CbCr output again).
+    Returns 0 or -1."""
+    if dtype is None:
+        return lib().jm_amddec_set_rgb(handle, None)
+    s = dtype if isinstance(dtype, RgbSpec) else rgb_spec(dtype, planar, bgr, matrix, range, mean, std, scale, bias)
+    return lib().jm_amddec_set_rgb(handle, C.byref(s))
+
+
+def color_coefs(matrix, full_range):
+    """jm_amddec_color_coefs: (cy, crv, cgu, cgv, cbu), or None when the matrix is not supported."""
+    c = (C.c_int * 5)()
+    return tuple(c) if lib().jm_amddec_color_coefs(matrix, int(full_range), c) == 0 else None
+
+
+def rgb_device(src, pitch, chroma_offset, width, height, crop, target, spec, dst, lone_field=0, stream=None):
+    """jm_amddec_rgb_device: crop = (x, y, w, h), target = (tw, th), spec an RgbSpec with an explicit matrix; src / dst device addresses.
+    Returns 0 or < 0."""
+    return lib().jm_amddec_rgb_device(src, pitch, chroma_offset, width, height, lone_field, *crop, *target, C.byref(spec), dst, stream)
+
+
+def bf16_to_f32(bits):
+    """bf16 samples (uint16 bit patterns, as rgb_array returns them) as float32."""
+    import numpy as np
+    return (np.asarray(bits, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
+
+
+def rgb_array(buf, w, h, spec):
+    """An RGB frame (bytes) as a numpy array: (3, h, w) planar or (h, w, 3) interleaved; u8 / float32 / float16, bf16 as uint16 bit patterns."""
+    import numpy as np
+    dt = {0: np.uint8, 1: np.float32, 2: np.float16, 3: np.uint16}[spec.dtype]
+    a = np.frombuffer(bytes(buf), dtype=dt, count=3 * w * h)
+    return a.reshape((3, h, w) if spec.planar else (h, w, 3))
 
 
 # ---- the reference harness's NAL scanner (test_nv_dec.cpp:30-86), vectorised -----------------
@@ -238,10 +309,15 @@ def annexb_to_hvcc(data, length_size=4):
 class JmAmdDec:
     """Convenience wrapper reproducing test_nv_dec's main loop (test_nv_dec.cpp:163-259)."""
 
-    def __init__(self, codec_type=0, out_fmt=1, options=None, extra_data=None):
+    def __init__(self, codec_type=0, out_fmt=1, options=None, extra_data=None, rgb=None):
         self.h = jm_nvdec_create_handle()
         for k, v in (options or {}).items():
             lib().jm_amddec_set_option(self.h, k.encode(), int(v))
+        # rgb: an RgbSpec, or a dict of set_rgb's keyword arguments -- frames then leave as RGB (rgb_array turns them into arrays)
+        if rgb is not None and (set_rgb(self.h, rgb) if isinstance(rgb, RgbSpec) else set_rgb(self.h, **rgb)) != 0:
+            jm_nvdec_deinit(self.h)
+            self.h = None
+            raise ValueError("invalid RGB spec")
         rc = jm_nvdec_init(codec_type, out_fmt, extra_data, len(extra_data) if extra_data else 0, self.h)
         if rc != 0:
             err = lib().jm_amddec_last_error(self.h).decode()
@@ -255,9 +331,9 @@ class JmAmdDec:
         return lib().jm_amddec_get_stat(self.h, key.encode())
 
     def _pull(self, frames):
-        w, h = jm_nvdec_stream_info(self.h)                    # size of the frame about to be fetched (it can change at an IDR picture)
-        if self.out_buf is None or len(self.out_buf) < w * h * 3 // 2:
-            self.out_buf = C.create_string_buffer(max(w * h * 3 // 2, 16))
+        need = self.stat("out_frame_bytes")                    # bytes of the frame about to be fetched (it can change at an IDR picture)
+        if self.out_buf is None or len(self.out_buf) < need:
+            self.out_buf = C.create_string_buffer(max(need, 16))
         ret, n = jm_nvdec_output_frame(self.out_buf, len(self.out_buf), self.h)
         if n > 0 and frames is not None:
             frames.append(self.out_buf.raw[:n])

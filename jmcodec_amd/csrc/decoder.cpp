@@ -172,7 +172,19 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "frames") return num_frames_;
     if (k == "out_width") return out_w_;              // size of the frames handed out (the target size of a scaled handle)
     if (k == "out_height") return out_h_;
-    if (k == "scaled_frames") return stat_scaled_;    // display frames that went out through k_scale_pack
+    if (k == "scaled_frames") return stat_scaled_;    // display frames that went through the resampler (k_scale_pack, or k_rgb_pack with a geometry)
+    // RGB output: frames converted, bytes of the frame current or about to be fetched, the colour description and what is in use
+    if (k == "rgb_frames") return stat_rgb_;
+    if (k == "out_frame_bytes") { std::lock_guard<std::mutex> lk(const_cast<std::mutex &>(mtx_));
+        return (long long)(cur_out_ ? cur_out_->fbytes : !ready_.empty() ? ready_.front()->fbytes : frame_bytes_); }
+    if (k == "out_slot_bytes") { std::lock_guard<std::mutex> lk(const_cast<std::mutex &>(mtx_)); long long n = 0;
+        for (const OutSlot *o : all_out_) n += (o->host ? (long long)o->bytes : 0) + (o->dev ? (long long)o->bytes : 0); return n; }
+    if (k == "vui_full_range") return vui_[0];
+    if (k == "vui_primaries") return vui_[1];
+    if (k == "vui_transfer") return vui_[2];
+    if (k == "vui_matrix") return vui_[3];
+    if (k == "color_matrix") return color_matrix_;
+    if (k == "color_range") return color_range_;
     if (k == "pictures") return stat_pictures_;
     if (k == "job_bytes") return stat_job_bytes_;
     if (k == "job_regrown") return stat_job_regrown_;          // job slots grown on demand (a few per handle, then none)
@@ -211,10 +223,10 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "wait_slot_ns") return stat_wait_slot_ns_;
     if (k == "parse_ns_p") return stat_parse_ns_p_;
     if (k.rfind("k_", 0) == 0 || k.rfind("eng_", 0) == 0) {          // engine-wide (all handles on this device), profile option
-        static const char *kn[5] = {"inter", "intra", "deblock", "packout", "chain"};
+        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack"};
         if (!engine_) return 0;
         EngineStats es = engine_->stats();
-        for (int i = 0; i < 5; i++) {
+        for (int i = 0; i < kKernelClasses; i++) {
             if (k == std::string("k_") + kn[i] + "_ns") return (long long)es.ns[i];
             if (k == std::string("k_") + kn[i] + "_n") return es.launches[i];
             if (k == std::string("k_") + kn[i] + "_pics") return es.pics[i];
@@ -463,6 +475,58 @@ bool upload_scale_tables(int w, int h, int tw, int th, uint8_t **dev, ScaleAxis 
     return true;
 }
 
+// ---- RGB output (INTEGRATION.md "RGB output": the conversion C) ----
+// Kr, Kb of H.273 Table 4 in 1/10000: exact decimals, so the coefficients are exact rationals rounded once (half away from zero; all are positive)
+bool color_coefs(int matrix, bool full_range, int c[5]) {
+    long long kr, kb;
+    switch (matrix) {
+        case 1: kr = 2126; kb = 722; break;                  // BT.709
+        case 4: kr = 3000; kb = 1100; break;                 // FCC
+        case 5: case 6: kr = 2990; kb = 1140; break;         // BT.601 (BT.470BG, SMPTE 170M)
+        case 7: kr = 2120; kb = 870; break;                  // SMPTE 240M
+        case 9: kr = 2627; kb = 593; break;                  // BT.2020 non-constant luminance
+        default: return false;
+    }
+    const long long kg = 10000 - kr - kb, syn = full_range ? 1 : 255, syd = full_range ? 1 : 219, scn = full_range ? 1 : 255, scd = full_range ? 1 : 224;
+    auto rnd = [](long long n, long long d) { return (int)((2 * n + d) / (2 * d)); };
+    c[0] = rnd(syn * 16384, syd);                                                  // cy
+    c[1] = rnd(scn * 2 * (10000 - kr) * 16384, scd * 10000);                      // crv
+    c[2] = rnd(scn * 2 * kb * (10000 - kb) * 16384, scd * 10000 * kg);            // cgu
+    c[3] = rnd(scn * 2 * kr * (10000 - kr) * 16384, scd * 10000 * kg);            // cgv
+    c[4] = rnd(scn * 2 * (10000 - kb) * 16384, scd * 10000);                      // cbu
+    return true;
+}
+bool rgb_spec_valid(const RgbSpec &s, bool need_matrix) {
+    const int m = s.matrix;
+    return s.dtype >= RGB_U8 && s.dtype <= RGB_BF16 && (s.planar == 0 || s.planar == 1) && (s.bgr == 0 || s.bgr == 1) && s.range >= 0 && s.range <= 2 &&
+           (m == 1 || m == 4 || m == 5 || m == 6 || m == 7 || m == 9 || (m == 0 && !need_matrix));
+}
+bool fill_rgb_color(RgbJob &j, const RgbSpec &s, int matrix, bool full_range) {
+    int c[5];
+    if (!color_coefs(matrix, full_range, c)) return false;
+    j.cy = c[0]; j.crv = c[1]; j.cgu = c[2]; j.cgv = c[3]; j.cbu = c[4]; j.yo = full_range ? 0 : 16;
+    j.dtype = s.dtype; j.planar = s.planar; j.bgr = s.bgr;
+    for (int k = 0; k < 3; k++) { j.k[k] = s.scale[k] * (1.0f / 16384.0f); j.b[k] = s.bias[k]; }       // (exact: a power of two)
+    return true;
+}
+
+int Decoder::set_rgb(const RgbSpec *spec) {
+    if (inited_) return -1;
+    if (!spec) { rgb_ = false; return 0; }
+    if (!rgb_spec_valid(*spec, false)) return -1;
+    rgb_spec_ = *spec; rgb_ = true;
+    return 0;
+}
+
+// auto matrix: the VUI value when supported, else BT.709 above 576 display lines and BT.601 below; auto range: the VUI flag, else limited
+void Decoder::resolve_color(const int vui[4], int disp_h) {
+    for (int i = 0; i < 4; i++) vui_[i] = vui[i];
+    int m = rgb_ ? rgb_spec_.matrix : 0, c[5];
+    if (m == 0) m = vui[3] >= 0 && color_coefs(vui[3], false, c) ? vui[3] : (disp_h > 576 ? 1 : 6);
+    const int r = rgb_ && rgb_spec_.range ? rgb_spec_.range : (vui[0] == 1 ? 2 : 1);
+    color_matrix_ = m; color_range_ = r;
+}
+
 // the geometry options against the display area of the sequence being activated (the crop rectangle is checked again at every new sequence; the
 // target stays what it was at init)
 bool Decoder::resolve_geometry() {
@@ -493,7 +557,7 @@ bool Decoder::resolve_geometry() {
 bool Decoder::gpu_alloc_sequence() {
     size_t n_mbs = (size_t)mb_w_ * mb_h_;
     if (!resolve_geometry()) return false;
-    frame_bytes_ = (size_t)out_w_ * out_h_ * 3 / 2;
+    frame_bytes_ = rgb_ ? (size_t)out_w_ * out_h_ * 3 * rgb_sample_bytes(rgb_spec_.dtype) : (size_t)out_w_ * out_h_ * 3 / 2;
     // MbRec + worst-case coefficients + motion records (16 vectors; 72 int16 for B / weighted slices) + slice tables
     // (always the Main / High layout: a later SPS of the same size may switch profile without re-activation, and a PPS may enable weighted
     //  prediction under any profile_idc)
@@ -514,6 +578,14 @@ bool Decoder::gpu_alloc_sequence() {
     if (getenv("JM_AMD_DEC_JOB_WORST_CASE")) job_cap_ = job_cap_max_;
     if (codec_ == 1) job_cap_ = n_mbs * 128 + (1u << 20);            // HEVC job lists vary a lot in size: start small, grow on demand (ensure_job_cap)
     if (!n_jobs_set_) n_jobs_ = codec_ == 0 && n_mbs <= 8704 ? kJobSlotsSmall : kJobSlots;      // (decoder.h)
+    if (!n_jobs_set_ && rgb_ && !parse_only_) {
+        // an RGB frame is 2-8x an NV12 one and the handle keeps n_jobs_ + 4 output slots: at most 1 GiB of them (device staging + page-locked), at least
+        // 8 job slots
+        const size_t copies = (size_t)((!device_output_ && out_route_ != 1 && out_route_ != 3) ? 1 : 0) + ((out_via_copy_engine_ || device_output_) ? 1 : 0);
+        const long long fit = (long long)((1ull << 30) / std::max<size_t>(1, frame_bytes_ * copies)) - 4;
+        n_jobs_ = (int)std::max(8ll, std::min((long long)n_jobs_, fit));
+        display_delay_ = std::min(display_delay_, n_jobs_ - 4);
+    }
     const bool lend_big = codec_ == 0 && job_cap_ < job_cap_max_;
     if (parse_only_) {
         for (int i = 0; i < n_jobs_; i++) { jobs_[i].host = (uint8_t *)malloc(job_cap_); jobs_[i].cap = job_cap_; }
@@ -578,7 +650,8 @@ bool Decoder::gpu_alloc_sequence() {
 OutSlot *Decoder::alloc_out_slot() {   // mtx_ held
     while (!free_out_.empty()) {
         OutSlot *o = free_out_.back(); free_out_.pop_back();
-        if (o->bytes == frame_bytes_ || parse_only_) { o->ready = false; o->has_data = false; o->w = out_w_; o->h = out_h_; return o; }
+        if (o->bytes == frame_bytes_ || parse_only_) { o->ready = false; o->has_data = false; o->w = out_w_; o->h = out_h_; o->fbytes = frame_bytes_;
+            return o; }
         // a slot of the previous resolution came back: release it
         all_out_.erase(std::remove(all_out_.begin(), all_out_.end(), o), all_out_.end());
         if (o->host) hipHostFree(o->host);
@@ -586,7 +659,7 @@ OutSlot *Decoder::alloc_out_slot() {   // mtx_ held
         delete o;
     }
     OutSlot *o = new OutSlot();
-    o->w = out_w_; o->h = out_h_;
+    o->w = out_w_; o->h = out_h_; o->fbytes = frame_bytes_;
     if (!parse_only_) {
         hipSetDevice(device_);
         if (!device_output_ && out_route_ != 1 && out_route_ != 3 && !HIP_OK(hipHostMalloc((void **)&o->host, frame_bytes_,
@@ -717,6 +790,8 @@ bool Decoder::activate(const SeqParams &sps) {
     // cropping does (hevc_activate compares the display size too); job buffers are sized for every profile, so a Baseline -> High switch
     // at the same size needs nothing
     bool changed = !seq_active_ || sps.mb_w != mb_w_ || sps.mb_h != mb_h_ || sps.disp_w() != disp_w_ || sps.disp_h() != disp_h_;
+    // (the colour of every sequence, size change or not: pictures decoded before keep theirs in DpbPic::color)
+    { const int vui[4] = {sps.vui_full_range, sps.vui_primaries, sps.vui_transfer, sps.vui_matrix}; resolve_color(vui, sps.disp_h()); }
     seq_ = sps;
     dpb_size_ = sps.dpb_frames();
     // display order == decode order when POC type 2 (8.2.1.3): no bumping delay needed
@@ -808,7 +883,7 @@ void Decoder::flush_dpb(std::vector<int> &out) {
         int best = -1;
         for (int i = 0; i < n_surf_; i++) if (i != cur_ && dpb_[i].in_use && dpb_[i].wait_output && (best < 0 || dpb_[i].poc < dpb_[best].poc)) best = i;
         if (best < 0) break;
-        out.push_back(best | dpb_[best].lone << 8); dpb_[best].wait_output = false; display_pocs_.push_back(dpb_[best].poc);
+        out.push_back(display_entry(best)); dpb_[best].wait_output = false; display_pocs_.push_back(dpb_[best].poc);
         dpb_[best].out_at = decode_count_ - 1;
     }
     for (int i = 0; i < n_surf_; i++) if (i != cur_ && dpb_[i].in_use && !dpb_[i].ref && !dpb_[i].wait_output) dpb_[i].in_use = false;
@@ -837,7 +912,7 @@ void Decoder::infer_frame(int fn) {
         int best = -1;                                      // C.4.5.3: no empty frame buffer -> the picture first in output order goes
         for (int i = 0; i < n_surf_; i++) if (dpb_[i].wait_output && !dpb_[i].waiting_second && (best < 0 || dpb_[i].poc < dpb_[best].poc)) best = i;
         if (best < 0) { stat_errors_++; return; }
-        carry_out_.push_back(best | dpb_[best].lone << 8); display_pocs_.push_back(dpb_[best].poc); dpb_[best].wait_output = false;
+        carry_out_.push_back(display_entry(best)); display_pocs_.push_back(dpb_[best].poc); dpb_[best].wait_output = false;
         dpb_[best].out_at = decode_count_ - 1;
     }
     DpbPic &c = dpb_[slot];
@@ -900,7 +975,7 @@ bool Decoder::start_picture(const SliceHeader &sh, const SeqParams &sps, const P
                 dpb_[best].set_ref(0); dpb_[best].in_use = false; slot = best; stat_errors_++;
                 break;
             }
-            carry_out_.push_back(best | dpb_[best].lone << 8); display_pocs_.push_back(dpb_[best].poc); dpb_[best].wait_output = false;
+            carry_out_.push_back(display_entry(best)); display_pocs_.push_back(dpb_[best].poc); dpb_[best].wait_output = false;
             dpb_[best].out_at = decode_count_ - 1;
             if (!dpb_[best].ref) { dpb_[best].in_use = false; slot = best; wait_pack = true; }
         }
@@ -913,6 +988,7 @@ bool Decoder::start_picture(const SliceHeader &sh, const SeqParams &sps, const P
     }
     cur_ = slot;
     DpbPic &c = dpb_[slot];
+    c.color = color_matrix_ | color_range_ << 4;      // (the matrix and range this picture's frame is converted with)
     const int poc = compute_poc(sh, c);
     if (!second) c.poc = poc;
     cur_field_ = sh.field_pic ? 1 + (int)sh.bottom_field : 0; cur_second_ = second;
@@ -1267,7 +1343,7 @@ void Decoder::store_done(int slot, std::vector<int> &out) {
     if (cur.mmco5) {
         int b;
         while ((b = smallest(slot)) >= 0) {
-            out.push_back(b | dpb_[b].lone << 8); display_pocs_.push_back(dpb_[b].poc); dpb_[b].wait_output = false;
+            out.push_back(display_entry(b)); display_pocs_.push_back(dpb_[b].poc); dpb_[b].wait_output = false;
             dpb_[b].out_at = decode_count_ - 1;
         }
         const int tmp = std::min(cur.fpoc[0], cur.fpoc[1]);
@@ -1276,7 +1352,7 @@ void Decoder::store_done(int slot, std::vector<int> &out) {
     }
     int w = smallest(slot);
     cur.lone = cur.have == 3 || codec_ == 1 ? 0 : cur.have;
-    if (!cur.ref && (w < 0 || dpb_[w].poc > cur.poc)) { out.push_back(slot | cur.lone << 8); display_pocs_.push_back(cur.poc); cur.out_at = decode_count_ - 1;
+    if (!cur.ref && (w < 0 || dpb_[w].poc > cur.poc)) { out.push_back(display_entry(slot)); display_pocs_.push_back(cur.poc); cur.out_at = decode_count_ - 1;
         cur.in_use = false; cur.wait_output = false; }
     else {
         cur.wait_output = true;
@@ -1286,7 +1362,7 @@ void Decoder::store_done(int slot, std::vector<int> &out) {
             if (used <= dpb_size_ && waiting <= reorder_depth_) break;
             int b = smallest(-1);
             if (b < 0) break;
-            out.push_back(b | dpb_[b].lone << 8); display_pocs_.push_back(dpb_[b].poc); dpb_[b].wait_output = false; dpb_[b].out_at = decode_count_ - 1;
+            out.push_back(display_entry(b)); display_pocs_.push_back(dpb_[b].poc); dpb_[b].wait_output = false; dpb_[b].out_at = decode_count_ - 1;
         }
     }
     for (int i = 0; i < n_surf_; i++) if (dpb_[i].in_use && i != pending_first_ && !dpb_[i].ref && !dpb_[i].wait_output) dpb_[i].in_use = false;
@@ -1546,8 +1622,10 @@ void Decoder::submit_ready() {
 }
 
 // a display frame leaves the DPB: reserve an output slot (display order) and describe the pack-out for the engine
-void Decoder::enqueue_output(int slot_and_lone, std::vector<PackJob> &jobs, std::vector<ScaleJob> &sjobs, std::vector<OutSlot *> &slots) {
-    const int slot = slot_and_lone & 255, lone = slot_and_lone >> 8;       // store_done: bits 8.. = the one field that was decoded, if only one was
+void Decoder::enqueue_output(int entry, std::vector<PackJob> &jobs, std::vector<ScaleJob> &sjobs, std::vector<RgbJob> &rjobs,
+                             std::vector<OutSlot *> &slots) {
+    // display_entry: bits 8..15 = the one field that was decoded, if only one was; bits 16.. = the matrix and range of the picture's sequence
+    const int slot = entry & 255, lone = (entry >> 8) & 255, color = entry >> 16;
     OutSlot *o;
     { std::lock_guard<std::mutex> lk(mtx_); o = alloc_out_slot(); ready_.push_back(o); num_frames_++; }   // nv_dec.cpp:48 num_frames++
     if (parse_only_ || failed_) { std::lock_guard<std::mutex> lk(mtx_); o->ready = true; done_unfetched_++; return; }
@@ -1555,7 +1633,16 @@ void Decoder::enqueue_output(int slot_and_lone, std::vector<PackJob> &jobs, std:
     // the kernel stores straight into the pinned host slot (see Engine::launch for why the copy engine is the default)
     // (a frame of which only one field was decoded is shown with that field's lines repeated: PackJob.lone_field)
     // (a scaled handle: k_scale_pack crops, resamples and packs in one pass, with the same row mapping)
-    if (scaled_) {
+    // (an RGB handle: k_rgb_pack crops, resamples and converts with the matrix and range of the sequence the picture was decoded in)
+    if (rgb_) {
+        RgbJob rj = {};
+        rj.s = ScaleJob{surf_[slot], o->dev ? o->dev : o->host, pitch_, chroma_off_, crop_[0], crop_[1], out_w_, out_h_, 0, lone, {}};
+        for (int a = 0; a < 4; a++) rj.s.ax[a] = scale_ax_[a];
+        rj.identity = scaled_ ? 0 : 1;
+        fill_rgb_color(rj, rgb_spec_, color & 15, (color >> 4) == 2);
+        rjobs.push_back(rj); stat_rgb_++;
+        if (scaled_) stat_scaled_++;
+    } else if (scaled_) {
         ScaleJob sj{surf_[slot], o->dev ? o->dev : o->host, pitch_, chroma_off_, crop_[0], crop_[1], out_w_, out_h_, out_fmt_, lone, {}};
         for (int a = 0; a < 4; a++) sj.ax[a] = scale_ax_[a];
         sjobs.push_back(sj); stat_scaled_++;
@@ -1571,7 +1658,7 @@ void Decoder::submit_task(PicTask *t) {
     EnginePic ep;
     ep.dec = this; ep.has_picture = t->has_picture && !parse_only_ && !failed_; ep.job_slot = t->job_slot;
     ep.mb_w = mb_w_; ep.mb_h = mb_h_; ep.disp_w = disp_w_; ep.disp_h = disp_h_; ep.wait_prev_pack = t->wait_prev_pack;
-    for (int s : t->out_before) { enqueue_output(s, ep.out_before, ep.scale_before, ep.slots_before); ep.out_mask |= 1u << (s & 255); }
+    for (int s : t->out_before) { enqueue_output(s, ep.out_before, ep.scale_before, ep.rgb_before, ep.slots_before); ep.out_mask |= 1u << (s & 255); }
     memset(&ep.pp, 0, sizeof ep.pp);
     if (ep.has_picture && t->hevc) hevc_fill_engine_pic(t, ep);
     else if (ep.has_picture) {
@@ -1633,8 +1720,9 @@ void Decoder::submit_task(PicTask *t) {
         ep.alg_bytes[2] = 2 * S;
     }
     // (a scaled handle reads the crop rectangle of the surface)
-    ep.alg_bytes[3] = (scaled_ ? (long long)crop_[2] * crop_[3] * 3 / 2 : (long long)surf_bytes_) + (long long)frame_bytes_;
-    for (int s : t->out_after) { enqueue_output(s, ep.out_after, ep.scale_after, ep.slots_after); ep.out_mask |= 1u << (s & 255); }
+    // (an RGB handle reads the crop rectangle too, and writes its RGB frame)
+    ep.alg_bytes[3] = (scaled_ || rgb_ ? (long long)crop_[2] * crop_[3] * 3 / 2 : (long long)surf_bytes_) + (long long)frame_bytes_;
+    for (int s : t->out_after) { enqueue_output(s, ep.out_after, ep.scale_after, ep.rgb_after, ep.slots_after); ep.out_mask |= 1u << (s & 255); }
     stat_submit_ns_ += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - st0).count();
     if (parse_only_ || failed_ || !engine_) { on_engine_done(ep); return; }
     engine_->submit(std::move(ep));
@@ -1739,6 +1827,10 @@ int Decoder::decode(const uint8_t *buf, int len, int *got_frame) {
         if (drained && eos_sent_ && !is_exit_) {            // nv_dec.cpp:460-466
             elapsed_ms_ = timer_started_ ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0_).count() : 0.0;
             is_exit_ = true;
+            char fmt[64];
+            if (rgb_) { static const char *const dt[4] = {"u8", "f32", "f16", "bf16"};
+                snprintf(fmt, sizeof fmt, "%s %s %s", rgb_spec_.bgr ? "BGR" : "RGB", rgb_spec_.planar ? "planar" : "interleaved", dt[rgb_spec_.dtype & 3]); }
+            else snprintf(fmt, sizeof fmt, "%s", out_fmt_ == 0 ? "NV12" : "YV12");
             snprintf(info_, sizeof info_,
                      "==========================================\n"
                      "Codec:\t\t%s\n"
@@ -1748,7 +1840,7 @@ int Decoder::decode(const uint8_t *buf, int len, int *got_frame) {
                      "Elapsed Time:\t%d ms\n"
                      "Decode FPS:\t%f fps\n"
                      "==========================================\n",
-                     codec_ == 0 ? "H.264" : "H.265", out_w_, out_h_, out_fmt_ == 0 ? "NV12" : "YV12", (int)num_frames_,
+                     codec_ == 0 ? "H.264" : "H.265", out_w_, out_h_, fmt, (int)num_frames_,
                      (int)elapsed_ms_, elapsed_ms_ > 0 ? (double)num_frames_ * 1000.0 / elapsed_ms_ : 0.0);
         }
     }
@@ -1759,7 +1851,7 @@ int Decoder::decode(const uint8_t *buf, int len, int *got_frame) {
 // device (k_packout), so what is left of it on the host is one tight memcpy.
 int Decoder::output(uint8_t *out, int *out_len) {
     if (!cur_out_ || (!cur_out_->has_data && !parse_only_)) return -1;
-    int need = cur_out_->w * cur_out_->h * 3 / 2;
+    int need = (int)cur_out_->fbytes;
     if (*out_len < need) return -2;
     *out_len = 0;
     // (streaming stores were slower than glibc's copy on Zen 5: 10.4 k vs 11.4 k frames/s)
@@ -1796,10 +1888,11 @@ int Decoder::output(uint8_t *out, int *out_len) {
 // the current display frame as it sits in device memory (tight NV12 / I420), valid until the next decode call
 int Decoder::output_device(void **dev, int *len) {
     if (!cur_out_ || !cur_out_->has_data || !cur_out_->dev) return -1;
-    *dev = cur_out_->dev; *len = cur_out_->w * cur_out_->h * 3 / 2;
+    *dev = cur_out_->dev; *len = (int)cur_out_->fbytes;
     return *len;
 }
 int Decoder::output_argb_device(void *dev_dst, int pitch) {
+    if (rgb_) return -1;                       // (the frame is not Y'CbCr)
     if (!cur_out_ || !cur_out_->has_data || !cur_out_->dev || pitch < cur_out_->w * 4) return -1;
     hipSetDevice(device_);
     launch_frame_to_argb(cur_out_->dev, cur_out_->w, cur_out_->h, out_fmt_, (uint8_t *)dev_dst, pitch, nullptr);
@@ -1814,6 +1907,7 @@ int Decoder::stream_info(int *w, int *h) const {
 }
 
 int Decoder::output_nv12_pitch_device(void *dev_dst, int pitch) {
+    if (rgb_) return -1;
     if (!cur_out_ || !cur_out_->has_data || !cur_out_->dev || pitch < cur_out_->w) return -1;
     hipSetDevice(device_);
     launch_frame_to_nv12_pitch(cur_out_->dev, cur_out_->w, cur_out_->h, out_fmt_, (uint8_t *)dev_dst, pitch, nullptr);

@@ -41,6 +41,7 @@ struct DpbPic {                                // one frame store (C.4.5): a fra
     bool waiting_second = false, first_was_ref = false, coded_as_fields = false;
     bool non_existing = false;                 // a frame inferred from a gap in frame_num (8.2.5.2): a short-term reference without samples, never displayed
     int lone = 0;                              // set when the store is complete: 1 / 2 = only its top / bottom field was decoded
+    int color = 0;                             // matrix | range << 4 of the sequence the picture was decoded in (RGB output)
     void set_ref(int v) { fmark[0] = fmark[1] = v; ref = v; }
     void sync_ref() { ref = (fmark[0] == 1 && fmark[1] == 1) ? 1 : (fmark[0] == 2 && fmark[1] == 2) ? 2 : (fmark[0] || fmark[1]) ? 3 : 0; }
     bool any_short() const { return fmark[0] == 1 || fmark[1] == 1; }
@@ -82,7 +83,7 @@ struct PicTask {
     SeqParams sps; PicParamSet pps;
     std::vector<SliceTask> slices;
     std::unique_ptr<HevcTask> hevc;            // codec_type 1
-    std::vector<int> out_before, out_after;    // DPB slots to display before / after this picture
+    std::vector<int> out_before, out_after;    // frames to display before / after this picture (Decoder::display_entry)
     bool wait_prev_pack = false;               // current surface was displayed by the previous picture (no cooling slack)
     // written by the parse worker
     std::atomic<int> state{0};                 // 0 queued, 1 parsed
@@ -115,6 +116,7 @@ struct OutSlot {                       // one display frame in pinned host memor
     uint8_t *dev = nullptr;            // device staging of the packed frame (copy-engine mode, see Engine::launch)
     size_t bytes = 0;
     int w = 0, h = 0;                  // display size of the frame held (a stream may change resolution at an IDR picture)
+    size_t fbytes = 0;                 // bytes of the frame held (w * h * 3 / 2, or the RGB frame's)
     bool has_data = false, ready = false;
     bool fetch = false;                // this frame waits in device staging and jm_nvdec_output_frame copies it with one synchronous DMA (Decoder::init)
 };
@@ -128,6 +130,15 @@ int build_scale_taps(int S, int D, std::vector<int32_t> &first, std::vector<int1
 // the four tables of a geometry (crop w x h -> target tw x th: luma x, luma y, chroma x, chroma y) in ONE device allocation *dev (the caller
 // frees it); ax[] points into it.  Synchronous (activation time).  false: invalid sizes or a failed allocation.
 bool upload_scale_tables(int w, int h, int tw, int th, uint8_t **dev, ScaleAxis ax[4]);
+
+// RGB output (INTEGRATION.md "RGB output"): the spec of jm_amddec_set_rgb (same layout as jm_amddec_rgb_spec)
+struct RgbSpec { int dtype, planar, bgr, matrix, range; float scale[3], bias[3]; };
+bool rgb_spec_valid(const RgbSpec &s, bool need_matrix);
+inline int rgb_sample_bytes(int dtype) { return dtype == RGB_U8 ? 1 : (dtype == RGB_F32 ? 4 : 2); }
+// cy, crv, cgu, cgv, cbu of H.273 MatrixCoefficients `matrix` (1, 4, 5, 6, 7, 9), limited or full range; false when unsupported
+bool color_coefs(int matrix, bool full_range, int c[5]);
+// the colour part of an RgbJob (coefficients, offset, sample type, layout, k / b) for a resolved matrix and range
+bool fill_rgb_color(RgbJob &j, const RgbSpec &s, int matrix, bool full_range);
 
 class Decoder {
 public:
@@ -148,6 +159,7 @@ public:
     char *info() { return info_; }
     const char *last_error();
     int  set_option(const char *key, long long v);
+    int  set_rgb(const RgbSpec *spec);         // before init; nullptr = Y'CbCr output again
     long long get_stat(const char *key) const;
     void set_device(int d) { device_ = d; }
     int  numa_node() const { return numa_node_; }   // NUMA node of this handle's GPU (-1: unknown / one-node host): which parse pool it uses
@@ -178,6 +190,8 @@ private:
     void build_frame_ref_lists(const SliceHeader &sh, SliceTask &task);
     void mark_current_field(const SliceHeader &sh);
     void store_done(int slot, std::vector<int> &out);
+    // a display frame as the engine gets it: slot | lone field << 8 | colour << 16 (DpbPic::lone, DpbPic::color), taken when the frame is queued
+    int  display_entry(int slot) const { return slot | dpb_[slot].lone << 8 | dpb_[slot].color << 16; }
     void infer_frame(int frame_num);
     void bump_after_current(std::vector<int> &out);
     void flush_dpb(std::vector<int> &out);
@@ -205,8 +219,11 @@ private:
     void gpu_close();
     void submit_ready();
     void submit_task(PicTask *t);
-    void enqueue_output(int slot, std::vector<PackJob> &jobs, std::vector<ScaleJob> &sjobs, std::vector<OutSlot *> &slots);
+    void enqueue_output(int entry, std::vector<PackJob> &jobs, std::vector<ScaleJob> &sjobs, std::vector<RgbJob> &rjobs, std::vector<OutSlot *> &slots);
     bool resolve_geometry();                   // options crop_* / target_* against the display size of the sequence being activated
+    // the colour description of the sequence being activated (vui: full range, primaries, transfer, matrix as transmitted, -1 = absent): the
+    // matrix and range its frames are converted with
+    void resolve_color(const int vui[4], int disp_h);
     OutSlot *alloc_out_slot();
 
     // configuration
@@ -231,6 +248,11 @@ private:
     int out_w_ = 0, out_h_ = 0, crop_[4] = {0, 0, 0, 0}; bool scaled_ = false;
     uint8_t *scale_dev_ = nullptr; ScaleAxis scale_ax_[4] = {};     // the sequence's tap tables on the device (k_scale_pack)
     std::atomic<long long> stat_scaled_{0};
+    // RGB output (jm_amddec_set_rgb, before init): every display frame leaves as C(R_G(F)) through k_rgb_pack
+    bool rgb_ = false; RgbSpec rgb_spec_ = {};
+    int vui_[4] = {-1, -1, -1, -1};            // the active sequence's VUI: full range, primaries, transfer, matrix (-1 = absent)
+    int color_matrix_ = 0, color_range_ = 0;   // ... resolved (resolve_color): H.273 matrix, 1 limited / 2 full
+    std::atomic<long long> stat_rgb_{0};
 
     // DPB / picture state (front end only)
     DpbPic dpb_[kMaxSurfaces];

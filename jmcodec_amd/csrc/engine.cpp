@@ -94,6 +94,8 @@ Engine::Engine(int device) : device_(device) {
             if (hipMalloc((void **)&b.d_jobs, sizeof(PackJob) * 4 * kMaxBatch) != hipSuccess) return;
             if (hipHostMalloc((void **)&b.h_sjobs, sizeof(ScaleJob) * 4 * kMaxBatch, hipHostMallocDefault) != hipSuccess) return;
             if (hipMalloc((void **)&b.d_sjobs, sizeof(ScaleJob) * 4 * kMaxBatch) != hipSuccess) return;
+            if (hipHostMalloc((void **)&b.h_rjobs, sizeof(RgbJob) * 4 * kMaxBatch, hipHostMallocDefault) != hipSuccess) return;
+            if (hipMalloc((void **)&b.d_rjobs, sizeof(RgbJob) * 4 * kMaxBatch) != hipSuccess) return;
             if (hipEventCreateWithFlags(&b.done, hipEventDisableTiming) != hipSuccess) return;
             if (hipEventCreateWithFlags(&b.kdone, hipEventDisableTiming) != hipSuccess) return;
             if (hipEventCreateWithFlags(&b.packed, hipEventDisableTiming) != hipSuccess) return;
@@ -480,8 +482,8 @@ void Engine::launch(Lane &ln, Batch &b) {
     bool wait_pack = false, any_hevc = false;
     HevcBatchDims hd;
     const EnginePic *last_upload[4] = {nullptr, nullptr, nullptr, nullptr};      // per copy stream (upload k went to stream k % n_copy_)
-    b.n_pre = b.n_post = 0; b.n_spre = b.n_spost = 0; b.s_tiles = 0; b.pmask = 0;
-    for (int k = 0; k < 5; k++) { b.alg[k] = 0; b.npics[k] = 0; }
+    b.n_pre = b.n_post = 0; b.n_spre = b.n_spost = 0; b.s_tiles = 0; b.n_rpre = b.n_rpost = 0; b.r_tiles[0] = b.r_tiles[1] = 0; b.pmask = 0;
+    for (int k = 0; k < kKernelClasses; k++) { b.alg[k] = 0; b.npics[k] = 0; }
     // pack jobs: [0, n_pre) before the decode kernels, [2*kMaxBatch, 2*kMaxBatch + n_post) after them
     for (int i = 0; i < n; i++) {
         EnginePic &p = b.pics[i];
@@ -532,6 +534,12 @@ void Engine::launch(Lane &ln, Batch &b) {
         // (scaled handles: the same two tables for k_scale_pack, launched beside k_packout)
         for (auto &j : p.scale_before) { b.h_sjobs[b.n_spre++] = j; b.s_tiles = std::max(b.s_tiles, scale_tiles(j.tw, j.th)); }
         for (auto &j : p.scale_after) { b.h_sjobs[2 * kMaxBatch + b.n_spost++] = j; b.s_tiles = std::max(b.s_tiles, scale_tiles(j.tw, j.th)); }
+        // (RGB handles: a third pair of tables for k_rgb_pack)
+        for (auto &j : p.rgb_before) { b.h_rjobs[b.n_rpre++] = j; b.r_tiles[!j.identity] = std::max(b.r_tiles[!j.identity], rgb_tiles(j.s.tw, j.s.th)); }
+        for (auto &j : p.rgb_after) { b.h_rjobs[2 * kMaxBatch + b.n_rpost++] = j;
+            b.r_tiles[!j.identity] = std::max(b.r_tiles[!j.identity], rgb_tiles(j.s.tw, j.s.th)); }
+        b.alg[5] += p.alg_bytes[3] * (long long)(p.rgb_before.size() + p.rgb_after.size());
+        b.npics[5] += (int)(p.rgb_before.size() + p.rgb_after.size());
         if (!p.out_before.empty() || !p.out_after.empty()) { max_w = std::max(max_w, p.disp_w); max_h = std::max(max_h, p.disp_h); }
         int st = b.h_pics[i].stages;
         if (hevc && p.has_picture) { const int hs = p.hp.stages; if (hs & (HPS_MC | HPS_RESID)) { b.alg[0] += p.alg_bytes[0]; b.npics[0]++; }
@@ -571,6 +579,8 @@ void Engine::launch(Lane &ln, Batch &b) {
     if (b.n_post) hipMemcpyAsync(b.d_jobs + 2 * kMaxBatch, b.h_jobs + 2 * kMaxBatch, sizeof(PackJob) * b.n_post, hipMemcpyHostToDevice, ps);
     if (b.n_spre) hipMemcpyAsync(b.d_sjobs, b.h_sjobs, sizeof(ScaleJob) * b.n_spre, hipMemcpyHostToDevice, ps);
     if (b.n_spost) hipMemcpyAsync(b.d_sjobs + 2 * kMaxBatch, b.h_sjobs + 2 * kMaxBatch, sizeof(ScaleJob) * b.n_spost, hipMemcpyHostToDevice, ps);
+    if (b.n_rpre) hipMemcpyAsync(b.d_rjobs, b.h_rjobs, sizeof(RgbJob) * b.n_rpre, hipMemcpyHostToDevice, ps);
+    if (b.n_rpost) hipMemcpyAsync(b.d_rjobs + 2 * kMaxBatch, b.h_rjobs + 2 * kMaxBatch, sizeof(RgbJob) * b.n_rpost, hipMemcpyHostToDevice, ps);
     // job lists were copied on the (in-order) copy stream when the pictures were parsed: waiting for the most recently
     // issued one of this batch covers them all without waiting for uploads of later pictures
     for (const EnginePic *lu : last_upload) if (lu) hipStreamWaitEvent(ps, lu->uploaded, 0);
@@ -586,7 +596,7 @@ void Engine::launch(Lane &ln, Batch &b) {
     // The decoder never reuses a displayed surface for the very next picture (DPB cooling, decoder.cpp), so the decode
     // kernels of this batch only have to wait for the pack-out launched TWO batches ago.
     if (ln.pack_hist[1]) hipStreamWaitEvent(st, ln.pack_hist[1], 0);
-    if ((wait_pack || b.n_pre || b.n_spre) && ln.pack_hist[0]) hipStreamWaitEvent(st, ln.pack_hist[0], 0);
+    if ((wait_pack || b.n_pre || b.n_spre || b.n_rpre) && ln.pack_hist[0]) hipStreamWaitEvent(st, ln.pack_hist[0], 0);
     auto mark = [&](int i, hipStream_t s) { if (profile_) hipEventRecord(b.pev[i], s); };
     mark(0, st);
     // Pack-out: k_packout writes the tight frames into device staging and a copy engine (SDMA) moves them to the pinned slots.
@@ -594,9 +604,10 @@ void Engine::launch(Lane &ln, Batch &b) {
     // queues with everything else: k_recon_inter of the next batch ran 4x slower next to it (0.56 -> 2.3 ms for 32 pictures).
     auto copy_out = [&](const std::vector<OutSlot *> &slots, hipStream_t s) { for (OutSlot *o : slots) if (o->dev && o->host &&
         !o->fetch) hipMemcpyAsync(o->host, o->dev, o->bytes, hipMemcpyDeviceToHost, s); };
-    if (b.n_pre || b.n_spre) {
+    if (b.n_pre || b.n_spre || b.n_rpre) {
         if (b.n_pre) launch_packout(b.d_jobs, b.n_pre, max_w, max_h, st);
         if (b.n_spre) launch_scale_pack(b.d_sjobs, b.n_spre, b.s_tiles, st);
+        if (b.n_rpre) { mark(10, st); launch_rgb_pack(b.d_rjobs, b.n_rpre, b.r_tiles[0], b.r_tiles[1], st); mark(11, st); b.pmask |= 64; }
         b.pmask |= 1; for (auto &p : b.pics) copy_out(p.slots_before, st);
     }
     mark(1, st);
@@ -699,6 +710,7 @@ void Engine::launch(Lane &ln, Batch &b) {
     mark(5, pst);
     if (b.n_post) { launch_packout(b.d_jobs + 2 * kMaxBatch, b.n_post, max_w, max_h, pst); b.pmask |= 16; }
     if (b.n_spost) { launch_scale_pack(b.d_sjobs + 2 * kMaxBatch, b.n_spost, b.s_tiles, pst); b.pmask |= 16; }
+    if (b.n_rpost) { mark(12, pst); launch_rgb_pack(b.d_rjobs + 2 * kMaxBatch, b.n_rpost, b.r_tiles[0], b.r_tiles[1], pst); mark(13, pst); b.pmask |= 16 | 128; }
     mark(6, pst);
     hipEventRecord(b.packed, pst);                            // from here on the displayed surfaces may be decoded into again
     for (auto &p : b.pics) copy_out(p.slots_after, pst);
@@ -743,9 +755,10 @@ void Engine::recover(Lane &ln, Batch &b, const std::vector<std::pair<Decoder *, 
         if ((lw & (ext_refs | shown)) || (b.redo && (written & shown_before))) taint(d);
     }
     // 2. frames this batch packed before its kernels showed pictures of the recovered batch: again, from the pictures as they are now
-    if (b.redo && (b.n_pre || b.n_spre)) {
+    if (b.redo && (b.n_pre || b.n_spre || b.n_rpre)) {
         if (b.n_pre) launch_packout(b.d_jobs, b.n_pre, b.max_w, b.max_h, st);
         if (b.n_spre) launch_scale_pack(b.d_sjobs, b.n_spre, b.s_tiles, st);
+        if (b.n_rpre) launch_rgb_pack(b.d_rjobs, b.n_rpre, b.r_tiles[0], b.r_tiles[1], st);
         for (auto &p : b.pics) for (OutSlot *o : p.slots_before) if (o->dev && o->host && !o->fetch) hipMemcpyAsync(o->host, o->dev, o->bytes,
             hipMemcpyDeviceToHost, st);
         hipStreamSynchronize(st);
@@ -774,9 +787,10 @@ void Engine::recover(Lane &ln, Batch &b, const std::vector<std::pair<Decoder *, 
         if (stages & PS_DEBLOCK_V1) launch_deblock(b.d_pics, n, st);
         hipStreamSynchronize(st);                              // h_pics is rewritten for the next depth
     }
-    if (b.n_post || b.n_spost) {                               // the display frames of the batch again, from the pictures as they are now
+    if (b.n_post || b.n_spost || b.n_rpost) {                  // the display frames of the batch again, from the pictures as they are now
         if (b.n_post) launch_packout(b.d_jobs + 2 * kMaxBatch, b.n_post, b.max_w, b.max_h, st);
         if (b.n_spost) launch_scale_pack(b.d_sjobs + 2 * kMaxBatch, b.n_spost, b.s_tiles, st);
+        if (b.n_rpost) launch_rgb_pack(b.d_rjobs + 2 * kMaxBatch, b.n_rpost, b.r_tiles[0], b.r_tiles[1], st);
         for (auto &p : b.pics) for (OutSlot *o : p.slots_after) if (o->dev && o->host && !o->fetch) hipMemcpyAsync(o->host, o->dev, o->bytes,
             hipMemcpyDeviceToHost, st);
         hipStreamSynchronize(st);
@@ -878,8 +892,8 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
             if (hipEventElapsedTime(&ms, b.pev[e0], b.pev[e1]) == hipSuccess) { st_.ns[cls] += ms * 1e6; st_.launches[cls]++; }
         };
         add(3, 0, 1, b.pmask & 1); add(0, 1, 2, b.pmask & 2); add(1, 2, 3, b.pmask & 4); add(2, 3, 4, b.pmask & 8); add(3, 5, 6, b.pmask & 16);
-        add(4, 4, 7, b.pmask & 32);
-        for (int k = 0; k < 5; k++) { st_.pics[k] += b.npics[k]; st_.alg_bytes[k] += b.alg[k]; }
+        add(4, 4, 7, b.pmask & 32); add(5, 10, 11, b.pmask & 64); add(5, 12, 13, b.pmask & 128);
+        for (int k = 0; k < kKernelClasses; k++) { st_.pics[k] += b.npics[k]; st_.alg_bytes[k] += b.alg[k]; }
         st_.batches++; st_.batch_pics += (long long)b.pics.size();
         // the lane's time line: how long this batch's kernels held the lane's stream, and how long the stream sat idle since the previous batch's last kernel
         const int li = (int)(&ln - lanes_);

@@ -62,8 +62,9 @@ struct EnginePic {
     ihipEvent_t *uploaded = nullptr; unsigned long long upload_seq = 0;   // job list copy (copy stream), see Engine::upload
     std::vector<PackJob> out_before, out_after;     // display frames to pack before / after this picture's kernels
     std::vector<ScaleJob> scale_before, scale_after;    // ... of handles with scaled / cropped output (k_scale_pack)
-    size_t n_before() const { return out_before.size() + scale_before.size(); }
-    size_t n_after() const { return out_after.size() + scale_after.size(); }
+    std::vector<RgbJob> rgb_before, rgb_after;          // ... of handles with RGB output (k_rgb_pack)
+    size_t n_before() const { return out_before.size() + scale_before.size() + rgb_before.size(); }
+    size_t n_after() const { return out_after.size() + scale_after.size() + rgb_after.size(); }
     bool before_empty() const { return n_before() == 0; }
     std::vector<OutSlot *> slots_before, slots_after;
     int mb_w = 0, mb_h = 0, disp_w = 0, disp_h = 0;
@@ -86,9 +87,11 @@ struct EnginePic {
     }
 };
 
-// per kernel class: 0 recon_inter, 1 intra, 2 deblock (prep+lds), 3 packout, 4 chain (k_chain: recon + deblock)
+// per kernel class: 0 recon_inter, 1 intra, 2 deblock (prep+lds), 3 packout (every pack-out kernel), 4 chain (k_chain: recon + deblock),
+// 5 rgb_pack (k_rgb_pack alone: its frames are counted in class 3 too)
+constexpr int kKernelClasses = 6;
 struct EngineStats {
-    double ns[5] = {0, 0, 0, 0, 0}; long long launches[5] = {0, 0, 0, 0, 0}, pics[5] = {0, 0, 0, 0, 0}, alg_bytes[5] = {0, 0, 0, 0, 0};
+    double ns[kKernelClasses] = {}; long long launches[kKernelClasses] = {}, pics[kKernelClasses] = {}, alg_bytes[kKernelClasses] = {};
     long long batches = 0, batch_pics = 0, chain_batches = 0, chain_pics = 0, wait_errors = 0, chain_recoveries = 0;
     long long chain_i_batches = 0;                  // chain launches that ran k_chain_i (the variant with the intra role); the others ran k_chain
     long long forms = 0, form_decoders = 0, form_pending = 0;   // ordinary-lane batches formed; decoders that had a picture waiting then; pictures waiting then
@@ -159,11 +162,14 @@ private:
         PackJob *h_jobs = nullptr, *d_jobs = nullptr;         // 4 * kMaxBatch entries
         ScaleJob *h_sjobs = nullptr, *d_sjobs = nullptr;      // the same for k_scale_pack
         int n_spre = 0, n_spost = 0, s_tiles = 0;             // (s_tiles: the grid of launch_scale_pack)
+        RgbJob *h_rjobs = nullptr, *d_rjobs = nullptr;        // the same for k_rgb_pack
+        int n_rpre = 0, n_rpost = 0, r_tiles[2] = {0, 0};       // (r_tiles: the grids of launch_rgb_pack, identity / resampled jobs)
         // packed: surfaces were read by k_packout (before the copies)
-        ihipEvent_t *done = nullptr, *kdone = nullptr, *packed = nullptr, *pre_done = nullptr, *pev[10] = {nullptr};
+        // (profile events 10 / 11 and 12 / 13 bracket the k_rgb_pack launches before / after the decode kernels)
+        ihipEvent_t *done = nullptr, *kdone = nullptr, *packed = nullptr, *pre_done = nullptr, *pev[14] = {nullptr};
         std::vector<EnginePic> pics;
         int n_pre = 0, n_post = 0; unsigned pmask = 0;
-        long long alg[5] = {0, 0, 0, 0, 0}; int npics[5] = {0, 0, 0, 0, 0};
+        long long alg[kKernelClasses] = {}; int npics[kKernelClasses] = {};
         int last_ev = -1;                                     // index of the profile event behind the batch's last decode kernel
         bool launched_dry = false;                            // diagnostic: the lane's previous batch had already ended when this one was launched
         unsigned long long serial = 0;                        // position of the batch in its lane's sequence of launches

@@ -120,7 +120,8 @@ std::string ParamSets::parse_sps(BitReader &br) {
     if (br.u1()) {   // VUI (E.1.1): the bitstream restriction sizes the DPB; the timing information is what jm_intel_get_stream_info reports
         if (br.u1()) { if (br.u(8) == 255) { br.u(16); br.u(16); } }
         if (br.u1()) br.u1();
-        if (br.u1()) { br.u(3); br.u1(); if (br.u1()) { br.u(8); br.u(8); br.u(8); } }
+        if (br.u1()) { br.u(3); s.vui_full_range = (int)br.u1();                                   // video_signal_type
+            if (br.u1()) { s.vui_primaries = (int)br.u(8); s.vui_transfer = (int)br.u(8); s.vui_matrix = (int)br.u(8); } }
         if (br.u1()) { br.ue(); br.ue(); }
         if (br.u1()) { s.num_units_in_tick = br.u(32); s.time_scale = br.u(32); s.fixed_frame_rate = br.u1(); }   // timing_info_present_flag
         bool nal_hrd = br.u1(); if (nal_hrd) skip_hrd(br);

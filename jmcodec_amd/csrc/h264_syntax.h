@@ -27,6 +27,9 @@ struct SeqParams {
     // VUI timing_info (E.2.1): a field lasts num_units_in_tick / time_scale seconds, so the frame rate is time_scale / (2 * num_units_in_tick) --
     // what Media SDK's DecodeHeader puts into FrameRateExtN / FrameRateExtD and the reference divides (intel_dec.cpp:975-990).  0 / 0 = not transmitted.
     uint32_t num_units_in_tick = 0, time_scale = 0; bool fixed_frame_rate = false;
+    // VUI video_signal_type (E.1.1): as transmitted, -1 = absent (colour_primaries / transfer_characteristics / matrix_coefficients need
+    // colour_description_present_flag too).  The RGB output picks its matrix and range from them (decoder.cpp resolve_color).
+    int vui_full_range = -1, vui_primaries = -1, vui_transfer = -1, vui_matrix = -1;
     int coded_w() const { return mb_w * 16; }
     int coded_h() const { return mb_h * 16; }
     // nv_dec.cpp:513-519: target size = display_area right-left x bottom-top (origin forced to 0,0)

@@ -82,6 +82,7 @@ bool Decoder::hevc_activate(const HevcSps &sps) {
     const int mbw = (sps.width + 15) / 16, mbh = (sps.height + 15) / 16;
     const bool changed = !seq_active_ || mbw != mb_w_ || mbh != mb_h_ || sps.width != hsps_.width || sps.height != hsps_.height || sps.disp_w() != disp_w_ ||
         sps.disp_h() != disp_h_;
+    { const int vui[4] = {sps.vui_full_range, sps.vui_primaries, sps.vui_transfer, sps.vui_matrix}; resolve_color(vui, sps.disp_h()); }
     h_max_dpb_ = sps.max_dec_pic_buffering; h_reorder_ = sps.max_num_reorder;
     if (!changed) return true;
     if (seq_active_) {
@@ -116,7 +117,7 @@ void Decoder::hevc_bump(std::vector<int> &out, bool all, bool use_fullness) {
         for (int i = 0; i < n_surf_; i++) if (dpb_[i].in_use && i != cur_) { full++; if (dpb_[i].wait_output) { n_out++;
             if (best < 0 || dpb_[i].poc < dpb_[best].poc) best = i; } }
         if (best < 0 || !(all || n_out > h_reorder_ || (use_fullness && full >= h_max_dpb_))) break;
-        out.push_back(best); dpb_[best].wait_output = false; display_pocs_.push_back(dpb_[best].poc); dpb_[best].out_at = decode_count_ - 1;
+        out.push_back(display_entry(best)); dpb_[best].wait_output = false; display_pocs_.push_back(dpb_[best].poc); dpb_[best].out_at = decode_count_ - 1;
         if (!dpb_[best].ref) dpb_[best].in_use = false;
     }
 }
@@ -168,13 +169,14 @@ bool Decoder::hevc_start_picture(const HevcSliceHeader &sh, int nal_type, int ti
     if (slot < 0) {                                // non-conformant stream: make room
         int best = -1;
         for (int i = 0; i < n_surf_; i++) if (dpb_[i].wait_output && (best < 0 || dpb_[i].poc < dpb_[best].poc)) best = i;
-        if (best >= 0) { carry_out_.push_back(best); display_pocs_.push_back(dpb_[best].poc); dpb_[best].wait_output = false; }
+        if (best >= 0) { carry_out_.push_back(display_entry(best)); display_pocs_.push_back(dpb_[best].poc); dpb_[best].wait_output = false; }
         else { for (int i = 0; i < n_surf_; i++) if (best < 0 || dpb_[i].poc < dpb_[best].poc) best = i; }
         dpb_[best].ref = 0; dpb_[best].in_use = false; slot = best; stat_errors_++;
     }
     cur_ = slot;
     DpbPic &c = dpb_[slot];
     c = DpbPic(); c.in_use = true; c.decode_idx = decode_count_++; c.poc = poc;
+    c.color = color_matrix_ | color_range_ << 4;        // (the matrix and range this picture's frame is converted with)
     c.hcol = std::make_shared<HevcColMotion>();
     c.wait_output = sh.pic_output && !((nal_type == 8 || nal_type == 9) && h_no_rasl_output_);
     if (tid == 0 && !(nal_type >= 6 && nal_type <= 9) && !(nal_type <= 14 && (nal_type & 1) == 0)) h_poc_tid0_ = poc;

@@ -3,6 +3,7 @@
 #include "decoder.h"
 #include "kernels.h"
 #include <hip/hip_runtime_api.h>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
@@ -136,6 +137,43 @@ __attribute__((visibility("default"))) int jm_amddec_scale_device(const void *sr
     hipError_t e = hipGetLastError();
     hipStreamSynchronize(st);
     hipFree(d_job); hipFree(tables);
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
+static_assert(sizeof(jm_amddec_rgb_spec) == sizeof(jmamd::RgbSpec) && offsetof(jm_amddec_rgb_spec, bias) == offsetof(jmamd::RgbSpec, bias),
+              "RgbSpec restates jm_amddec_rgb_spec");
+__attribute__((visibility("default"))) int jm_amddec_set_rgb(jm_amddec_handle h, const jm_amddec_rgb_spec *spec) {
+    if (!h) return -1;
+    return D(h)->set_rgb(reinterpret_cast<const jmamd::RgbSpec *>(spec));
+}
+__attribute__((visibility("default"))) int jm_amddec_color_coefs(int matrix, int full_range, int coefs[5]) {
+    int c[5];
+    if (!jmamd::color_coefs(matrix, full_range != 0, c)) return -1;
+    if (coefs) for (int k = 0; k < 5; k++) coefs[k] = c[k];
+    return 0;
+}
+__attribute__((visibility("default"))) int jm_amddec_rgb_device(const void *src, int pitch, int chroma_offset, int w, int hgt, int lone_field, int crop_x,
+    int crop_y, int crop_w, int crop_h, int tw, int th, const jm_amddec_rgb_spec *spec, void *dst, void *stream) {
+    if (!src || !dst || !spec || w <= 0 || hgt <= 0 || pitch < w || lone_field < 0 || lone_field > 2) return -1;
+    const jmamd::RgbSpec &s = *reinterpret_cast<const jmamd::RgbSpec *>(spec);
+    if (!jmamd::rgb_spec_valid(s, true) || ((uintptr_t)dst % (uintptr_t)jmamd::rgb_sample_bytes(s.dtype))) return -1;
+    if ((crop_x | crop_y | crop_w | crop_h | tw | th) & 1) return -1;
+    if (crop_x < 0 || crop_y < 0 || crop_w <= 0 || crop_h <= 0 || crop_x + crop_w > w || crop_y + crop_h > hgt || tw <= 0 || th <= 0) return -1;
+    if (crop_w > 8 * tw || crop_h > 8 * th || tw > 4 * crop_w || th > 4 * crop_h) return -1;
+    jmamd::RgbJob job = {};
+    job.s = jmamd::ScaleJob{static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), pitch, chroma_offset, crop_x, crop_y, tw, th, 0, lone_field, {}};
+    job.identity = tw == crop_w && th == crop_h;
+    jmamd::fill_rgb_color(job, s, s.matrix, s.range == 2);
+    uint8_t *tables = nullptr;
+    if (!job.identity && !jmamd::upload_scale_tables(crop_w, crop_h, tw, th, &tables, job.s.ax)) return -1;
+    jmamd::RgbJob *d_job = nullptr;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hipMalloc((void **)&d_job, sizeof job) != hipSuccess) { if (tables) hipFree(tables); return -1; }
+    hipMemcpyAsync(d_job, &job, sizeof job, hipMemcpyHostToDevice, st);
+    jmamd::launch_rgb_pack(d_job, 1, job.identity ? jmamd::rgb_tiles(tw, th) : 0, job.identity ? 0 : jmamd::rgb_tiles(tw, th), st);
+    hipError_t e = hipGetLastError();
+    hipStreamSynchronize(st);
+    hipFree(d_job); if (tables) hipFree(tables);
     return e == hipSuccess ? 0 : -(int)e;
 }
 

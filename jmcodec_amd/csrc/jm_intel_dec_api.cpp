@@ -79,8 +79,8 @@ struct Ctx {
     // callback mode: hand every finished frame to the callback (the reference stores the callback and never calls it, intel_dec.cpp:369-376)
     void deliver() {
         while (cb && take(0)) {
-            int w = 0, h = 0; jm_amddec_stream_info(&w, &h, dec);
-            const size_t cap = (size_t)w * h * 3 / 2 + 16;
+            // (the frame's size: w * h * 3 / 2, or an RGB frame's)
+            const size_t cap = (size_t)jm_amddec_get_stat(dec, "out_frame_bytes") + 16;
             if (cb_buf.size() < cap) cb_buf.resize(cap);
             int n = (int)cb_buf.size();
             have = false;
@@ -130,8 +130,7 @@ JM_EXPORT int jm_amdintel_output_frame(unsigned char *out_buf, int *out_len, jm_
     if (c->cb) { c->deliver(); *out_len = 0; return -1; }                 // frames go to the callback
     // (no frame ready: sleep for it only when the caller has nothing better to do -- no input is wanted)
     if (!c->take(c->room() < (size_t)kInputChunk / 2 || c->eof ? kWaitUs : 0)) { *out_len = 0; return -1; }   // intel_dec.cpp:251-255
-    int w = 0, hh = 0; jm_amddec_stream_info(&w, &hh, c->dec);
-    const int need = w * hh * 3 / 2;
+    const int need = (int)jm_amddec_get_stat(c->dec, "out_frame_bytes");
     if (!out_buf) { *out_len = need; return 0; }                          // size query (jm_intel_dec.h:74); the frame stays current
     if (*out_len < need) { *out_len = 0; return -2; }                     // intel_dec.cpp:266-270; the frame stays current
     int n = *out_len;

@@ -148,4 +148,15 @@ struct ScaleJob {                 // one display frame to crop + resample + pack
     ScaleAxis ax[4];              // luma x, luma y, chroma x, chroma y (device pointers into the handle's tap tables)
 };
 
+// RGB output (k_rgb_pack; the conversion C of INTEGRATION.md "RGB output" applied to R_G(F)).  The geometry fields are ScaleJob's; out_fmt is unused.
+enum : int { RGB_U8 = 0, RGB_F32 = 1, RGB_F16 = 2, RGB_BF16 = 3 };
+struct RgbJob {                   // one display frame to crop + resample + convert (k_rgb_pack, blockIdx.y = job)
+    ScaleJob s;                   // identity geometry (target size == crop size): s.ax[] is not read
+    int identity;                 // 1: no resampling -- the kernel reads the surface directly
+    int cy, crv, cgu, cgv, cbu;   // 14-bit coefficients (jm_amddec_color_coefs)
+    int yo;                       // luma offset: 16 limited, 0 full range
+    int dtype, planar, bgr;       // RGB_*; 1 CHW, 0 HWC; 1 B,G,R order
+    float k[3], b[3];             // float samples: fl32(fl32(v * k[c]) + b[c]), c = storage position (k = scale / 16384)
+};
+
 }  // namespace jmamd

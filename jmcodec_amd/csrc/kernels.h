@@ -37,6 +37,10 @@ void launch_packout(const PackJob *d_jobs, int n, int max_width, int max_height,
 // pitch-linear NV12 surface -> cropped, resampled tight frame at the job's target size (k_scale_pack); max_tiles: the largest scale_tiles() of the jobs
 int  scale_tiles(int tw, int th);
 void launch_scale_pack(const ScaleJob *d_jobs, int n, int max_tiles, hipStream_t st);
+// ... -> RGB frame C(R_G(F)) at the job's target size (k_rgb_pack); identity_tiles / scaled_tiles: the largest rgb_tiles() of the identity / the
+// resampled jobs (0: none of that kind)
+int  rgb_tiles(int tw, int th);
+void launch_rgb_pack(const RgbJob *d_jobs, int n, int identity_tiles, int scaled_tiles, hipStream_t st);
 // tight I420 (fmt 1) / NV12 (fmt 0) frame in device memory -> ARGB32 in device memory
 void launch_frame_to_argb(const uint8_t *d_src, int w, int h, int fmt, uint8_t *d_dst, int dst_pitch, hipStream_t st);
 // tight I420 / NV12 -> pitch NV12 (encoder input)

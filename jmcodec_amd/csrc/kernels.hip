@@ -7,6 +7,7 @@
 //   k_recon_intra   Intra4x4 / Intra16x16 / chroma intra prediction + residual        (MB wavefront)
 //   k_deblock       in-loop deblocking filter, clause 8.7 order                        (MB wavefront)
 //   k_packout       pitch NV12 surface -> tight NV12 / I420 display frame              (fully parallel)
+//   k_scale_pack    ... cropped and resampled;  k_rgb_pack  ... and converted to RGB   (fully parallel)
 // All arithmetic is 8-bit integer pixel work: HBM/LDS bound, no MFMA.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -714,6 +715,188 @@ int scale_tiles(int tw, int th) {
 }
 void launch_scale_pack(const ScaleJob *d_jobs, int n, int max_tiles, hipStream_t st) {
     if (n > 0 && max_tiles > 0) hipLaunchKernelGGL(k_scale_pack, dim3(max_tiles, n), dim3(256), 0, st, d_jobs);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_rgb_pack: output C(R_G(F)) -- k_scale_pack's crop and resampler followed by the colour conversion C (INTEGRATION.md "RGB output").
+// One workgroup per output tile of 64 x 16 pixels.  C needs luma AND chroma of the same pixels, so a scaled job resamples both in one workgroup:
+// the tile's luma (64 x 16) and its chroma (32 x 8, both channels) go through k_scale_pack's horizontal pass into LDS, the vertical chroma results
+// into LDS again (the integer steps are k_scale_pack's, so G is bit-identical), then every lane filters 4 luma samples of one row.  An identity job
+// (target size == crop size) reads the surface directly, no tap tables.  Then every lane converts its 4 pixels and stores 3 x 4 samples.
+// ------------------------------------------------------------------------------------------
+constexpr int kRgbTileW = 64, kRgbTileH = 16;
+
+__device__ __forceinline__ uint32_t rgb_u8(int a) { const int v = (a + 8192) >> 14; return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+__device__ __forceinline__ float rgb_f32(int a, float k, float b) {
+#pragma clang fp contract(off)
+    const int c = a < 0 ? 0 : (a > 255 * 16384 ? 255 * 16384 : a);        // exact in fp32 (< 2^24)
+    const float m = (float)c * k;                                           // two roundings, never an FMA: numpy float32 restates them
+    return m + b;
+}
+__device__ __forceinline__ uint32_t f32_to_bf16(float f) {                 // round to nearest even
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;        // NaN stays a (quiet) NaN
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+__device__ __forceinline__ uint32_t f32_to_f16(float f) { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f); }
+
+// 4 consecutive samples of sz bytes (their bit patterns in s[]), n of them valid: one vector store when all are and the address allows it
+__device__ __forceinline__ void store4(uint8_t *d, int sz, const uint32_t s[4], int n) {
+    if (n <= 0) return;
+    const uintptr_t a = (uintptr_t)d;
+    if (sz == 1) {
+        if (n >= 4 && !(a & 3)) *(uint32_t *)d = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
+        else for (int k = 0; k < 4; k++) { if (k < n) d[k] = (uint8_t)s[k]; }
+    } else if (sz == 2) {
+        if (n >= 4 && !(a & 7)) *(uint2 *)d = make_uint2(s[0] | (s[1] << 16), s[2] | (s[3] << 16));
+        else for (int k = 0; k < 4; k++) { if (k < n) ((uint16_t *)d)[k] = (uint16_t)s[k]; }
+    } else {
+        if (n >= 4 && !(a & 15)) *(uint4 *)d = make_uint4(s[0], s[1], s[2], s[3]);
+        else for (int k = 0; k < 4; k++) { if (k < n) ((uint32_t *)d)[k] = s[k]; }
+    }
+}
+
+// Two instantiations over the same job table, each for the jobs of its kind: SCALED = false (identity jobs) uses no LDS, so its occupancy is set by
+// registers alone; SCALED = true holds the two passes' LDS buffers.
+template <bool SCALED>
+__global__ __launch_bounds__(256) void k_rgb_pack(const RgbJob *jobs) {
+    const RgbJob &jb = jobs[blockIdx.y];
+    if (jb.identity == (SCALED ? 1 : 0)) return;             // (a job of the other instantiation)
+    const ScaleJob &sj = jb.s;
+    const int tw = sj.tw, th = sj.th;
+    const int ntx = (tw + kRgbTileW - 1) / kRgbTileW, t = blockIdx.x;
+    if (t >= ntx * ((th + kRgbTileH - 1) / kRgbTileH)) return;
+    const int j0 = (t % ntx) * kRgbTileW, i0 = (t / ntx) * kRgbTileH;
+    const int jn = min(kRgbTileW, tw - j0), in = min(kRgbTileH, th - i0);      // (both even: tw, th are)
+    const int pitch = sj.pitch, lone = sj.lone_field;
+    const uint8_t *luma = sj.src, *chroma = sj.src + sj.chroma_offset;
+    const int r = threadIdx.x >> 4, q = threadIdx.x & 15;   // the lane's row of the tile and its columns 4q .. 4q + 3
+    const int i = i0 + r;
+    int Y[4] = {0, 0, 0, 0}, U[2] = {128, 128}, V[2] = {128, 128};
+    if constexpr (SCALED) {
+        __shared__ int16_t hy[kScaleMaxRows * kRgbTileW];    // luma source rows after the horizontal pass
+        __shared__ int16_t hc[kScaleMaxRows * kRgbTileW];    // chroma source rows after the horizontal pass: 32 columns x (U, V)
+        __shared__ uint8_t gc[kRgbTileH / 2][kRgbTileW];     // the tile's chroma of G: 8 rows x 32 columns x (U, V)
+        const ScaleAxis ax = sj.ax[0], ay = sj.ax[1], cax = sj.ax[2], cay = sj.ax[3];
+        const int Sx = ax.src_len, Sy = ay.src_len, Sxc = cax.src_len, Syc = cay.src_len;
+        const int ic0 = i0 >> 1, icn = in >> 1, jc0 = j0 >> 1, jcn = jn >> 1;
+        // the source rows the tile's vertical taps reach, luma and chroma (clamping is monotonic)
+        const int r0 = clamp_to(ay.first[i0], Sy), nrows = clamp_to(ay.first[i0 + in - 1] + ay.taps - 1, Sy) - r0 + 1;
+        const int cr0 = clamp_to(cay.first[ic0], Syc), ncrows = clamp_to(cay.first[ic0 + icn - 1] + cay.taps - 1, Syc) - cr0 + 1;
+        if (nrows > kScaleMaxRows || ncrows > kScaleMaxRows) return;      // (cannot happen within the validated ratios: S <= 8 D)
+        const int cx = sj.crop_x, cy = sj.crop_y;
+        // horizontal passes (k_scale_pack's): lane column c = output luma column, and output chroma column c / 2, channel c & 1
+        {
+            const int c = threadIdx.x & (kRgbTileW - 1);
+            int xs[kScaleMaxTaps], wv[kScaleMaxTaps];
+            if (c < jn) {
+                const int j = j0 + c, f = ax.first[j], T = ax.taps;
+#pragma unroll
+                for (int k = 0; k < kScaleMaxTaps; k++) { xs[k] = cx + clamp_to(f + k, Sx); wv[k] = k < T ? ax.w[j * T + k] : 0; }
+                for (int rr = threadIdx.x >> 6; rr < nrows; rr += 4) {
+                    const int sy = cy + r0 + rr;
+                    const uint8_t *p = luma + (size_t)(lone ? ((sy & ~1) | (lone - 1)) : sy) * pitch;
+                    int acc = 64;
+#pragma unroll
+                    for (int k = 0; k < kScaleMaxTaps; k++) if (k < T) acc += wv[k] * p[xs[k]];
+                    hy[rr * kRgbTileW + c] = (int16_t)(acc >> 7);
+                }
+            }
+            if ((c >> 1) < jcn) {
+                const int j = jc0 + (c >> 1), f = cax.first[j], T = cax.taps;
+#pragma unroll
+                for (int k = 0; k < kScaleMaxTaps; k++) { xs[k] = 2 * ((cx >> 1) + clamp_to(f + k, Sxc)) + (c & 1); wv[k] = k < T ? cax.w[j * T + k] : 0; }
+                for (int rr = threadIdx.x >> 6; rr < ncrows; rr += 4) {
+                    const int sy = (cy >> 1) + cr0 + rr;
+                    const uint8_t *p = chroma + (size_t)(lone ? ((sy & ~1) | (lone - 1)) : sy) * pitch;
+                    int acc = 64;
+#pragma unroll
+                    for (int k = 0; k < kScaleMaxTaps; k++) if (k < T) acc += wv[k] * p[xs[k]];
+                    hc[rr * kRgbTileW + c] = (int16_t)(acc >> 7);
+                }
+            }
+        }
+        __syncthreads();
+        // vertical chroma pass: the tile's 8 x 64 chroma values of G
+        for (int e = threadIdx.x; e < (kRgbTileH / 2) * kRgbTileW; e += 256) {
+            const int rr = e / kRgbTileW, c = e % kRgbTileW;
+            if (rr < icn && (c >> 1) < jcn) {
+                const int ic = ic0 + rr, fy = cay.first[ic], Ty = cay.taps;
+                int acc = 1 << 20;
+#pragma unroll
+                for (int k = 0; k < kScaleMaxTaps; k++) if (k < Ty) acc += cay.w[ic * Ty + k] * hc[(clamp_to(fy + k, Syc) - cr0) * kRgbTileW + c];
+                gc[rr][c] = (uint8_t)min(255, acc >> 21);
+            }
+        }
+        // vertical luma pass: the lane's 4 samples
+        if (r < in) {
+            const int fy = ay.first[i], Ty = ay.taps;
+            int acc[4] = {1 << 20, 1 << 20, 1 << 20, 1 << 20};
+#pragma unroll
+            for (int k = 0; k < kScaleMaxTaps; k++) {
+                if (k >= Ty) break;
+                const int w = ay.w[i * Ty + k];
+                const int16_t *hr = hy + (clamp_to(fy + k, Sy) - r0) * kRgbTileW + 4 * q;
+#pragma unroll
+                for (int e = 0; e < 4; e++) acc[e] += w * hr[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; e++) Y[e] = min(255, acc[e] >> 21);
+        }
+        __syncthreads();
+        if (r < in) {
+#pragma unroll
+            for (int k = 0; k < 2; k++) { U[k] = gc[r >> 1][2 * (2 * q + k)]; V[k] = gc[r >> 1][2 * (2 * q + k) + 1]; }
+        }
+    } else if (r < in && 4 * q < jn) {
+        // identity geometry: Y = F_Y[crop_y + i][crop_x + j], chroma of F row (crop_y / 2 + i / 2), byte pair crop_x + 2 * (j / 2) (k_packout's row mapping)
+        const int sy = sj.crop_y + i, sc = (sj.crop_y >> 1) + (i >> 1);
+        const uint8_t *py = luma + (size_t)(lone ? ((sy & ~1) | (lone - 1)) : sy) * pitch + sj.crop_x + j0 + 4 * q;
+        const uint8_t *pc = chroma + (size_t)(lone ? ((sc & ~1) | (lone - 1)) : sc) * pitch + sj.crop_x + j0 + 4 * q;
+#pragma unroll
+        for (int e = 0; e < 4; e++) if (4 * q + e < jn) Y[e] = py[e];
+#pragma unroll
+        for (int k = 0; k < 2; k++) if (4 * q + 2 * k < jn) { U[k] = pc[2 * k]; V[k] = pc[2 * k + 1]; }
+    }
+    if (r >= in) return;
+    const int n = min(4, jn - 4 * q);
+    if (n <= 0) return;
+    // C: 14-bit fixed-point accumulators, then the sample type of the job
+    uint32_t s[3][4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const int yv = jb.cy * (Y[e] - jb.yo), d = U[e >> 1] - 128, f = V[e >> 1] - 128;
+        const int aR = yv + jb.crv * f, aG = yv - jb.cgu * d - jb.cgv * f, aB = yv + jb.cbu * d;
+        const int a[3] = {jb.bgr ? aB : aR, aG, jb.bgr ? aR : aB};          // storage positions
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            if (jb.dtype == RGB_U8) s[c][e] = rgb_u8(a[c]);
+            else {
+                const float v = rgb_f32(a[c], jb.k[c], jb.b[c]);
+                s[c][e] = jb.dtype == RGB_F32 ? __float_as_uint(v) : jb.dtype == RGB_F16 ? f32_to_f16(v) : f32_to_bf16(v);
+            }
+        }
+    }
+    const int sz = jb.dtype == RGB_U8 ? 1 : (jb.dtype == RGB_F32 ? 4 : 2);
+    const size_t px = (size_t)i * tw + j0 + 4 * q;
+    if (jb.planar) {
+        const size_t P = (size_t)tw * th;
+#pragma unroll
+        for (int c = 0; c < 3; c++) store4(sj.dst + (c * P + px) * sz, sz, s[c], n);
+    } else {
+        uint32_t v[12];
+#pragma unroll
+        for (int e = 0; e < 4; e++) for (int c = 0; c < 3; c++) v[3 * e + c] = s[c][e];
+        uint8_t *d = sj.dst + 3 * px * sz;
+#pragma unroll
+        for (int g = 0; g < 3; g++) store4(d + 4 * g * sz, sz, v + 4 * g, 3 * n - 4 * g);
+    }
+}
+
+int rgb_tiles(int tw, int th) { return ((tw + kRgbTileW - 1) / kRgbTileW) * ((th + kRgbTileH - 1) / kRgbTileH); }
+void launch_rgb_pack(const RgbJob *d_jobs, int n, int identity_tiles, int scaled_tiles, hipStream_t st) {
+    if (n > 0 && identity_tiles > 0) hipLaunchKernelGGL(k_rgb_pack<false>, dim3(identity_tiles, n), dim3(256), 0, st, d_jobs);
+    if (n > 0 && scaled_tiles > 0) hipLaunchKernelGGL(k_rgb_pack<true>, dim3(scaled_tiles, n), dim3(256), 0, st, d_jobs);
 }
 
 void launch_packout(const PackJob *d_jobs, int n, int max_width, int max_height, hipStream_t st) {

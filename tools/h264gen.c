@@ -74,6 +74,10 @@ typedef struct {
                                    decodes the primary picture and must leave these alone (Baseline tool) */
     int vui_fps;                /* > 0: the SPS carries VUI timing_info (num_units_in_tick 1, time_scale 2 * vui_fps, fixed_frame_rate_flag 1) and an
                                    aspect ratio -- nothing in it influences decoding; jm_intel_get_stream_info reports the frame rate from it */
+    int vui_matrix, vui_primaries, vui_transfer;   /* any > 0: the VUI carries video_signal_type with a colour description (these three values, as
+                                   matrix_coefficients / colour_primaries / transfer_characteristics) -- what the RGB output converts with */
+    int vui_full_range;         /* 1: video_full_range_flag 1 (video_signal_type is then written even without a colour description); all four 0: no
+                                   video_signal_type */
 } GenParams;
 
 /* ------------------------------ RNG --------------------------------------- */
@@ -1967,11 +1971,21 @@ static void write_sps_pps(Enc *e) {
     else { bw_put(w, 1, 1); bw_put(w, 1, (uint32_t)p->dinf8); }           /* frame_mbs_only, direct_8x8_inference */
     int cr = (e->W - p->width) / 2, cb = (e->H - p->height) / (p->fmo0 ? 4 : 2);   /* CropUnitY = 2 * (2 - frame_mbs_only_flag) */
     if (cr || cb) { bw_put(w, 1, 1); bw_ue(w, 0); bw_ue(w, cr); bw_ue(w, 0); bw_ue(w, cb); } else bw_put(w, 1, 0);
-    if (p->vui_fps > 0) {                                                 /* vui_parameters() (E.1.1) */
+    const int colour_desc = p->vui_matrix > 0 || p->vui_primaries > 0 || p->vui_transfer > 0, signal_type = colour_desc || p->vui_full_range > 0;
+    if (p->vui_fps > 0 || signal_type) {                                  /* vui_parameters() (E.1.1) */
         bw_put(w, 1, 1);
         bw_put(w, 1, 1); bw_put(w, 8, 1);                                 /* aspect_ratio_info_present_flag, aspect_ratio_idc 1 (square) */
-        bw_put(w, 1, 0); bw_put(w, 1, 0); bw_put(w, 1, 0);                /* no overscan info, video signal type, chroma location */
-        bw_put(w, 1, 1); bw_put(w, 32, 1); bw_put(w, 32, 2u * (uint32_t)p->vui_fps); bw_put(w, 1, 1);   /* timing_info: tick, time_scale, fixed rate */
+        bw_put(w, 1, 0);                                                  /* no overscan info */
+        bw_put(w, 1, (uint32_t)signal_type);                              /* video_signal_type_present_flag */
+        if (signal_type) {
+            bw_put(w, 3, 5); bw_put(w, 1, (uint32_t)(p->vui_full_range > 0)); bw_put(w, 1, (uint32_t)colour_desc);  /* video_format 5, full range, desc */
+            if (colour_desc) { bw_put(w, 8, (uint32_t)p->vui_primaries & 255); bw_put(w, 8, (uint32_t)p->vui_transfer & 255);
+                bw_put(w, 8, (uint32_t)p->vui_matrix & 255); }
+        }
+        bw_put(w, 1, 0);                                                  /* no chroma location */
+        if (p->vui_fps > 0) { bw_put(w, 1, 1); bw_put(w, 32, 1); bw_put(w, 32, 2u * (uint32_t)p->vui_fps); bw_put(w, 1, 1); }  /* timing_info: tick,
+                                                                             time_scale, fixed rate */
+        else bw_put(w, 1, 0);
         bw_put(w, 1, 0); bw_put(w, 1, 0);                                 /* no NAL / VCL HRD parameters */
         bw_put(w, 1, 0); bw_put(w, 1, 0);                                 /* pic_struct_present_flag, bitstream_restriction_flag */
     } else bw_put(w, 1, 0);                                               /* no VUI */
@@ -2656,6 +2670,7 @@ int main(int argc, char **argv) {
         OPT("--cabac", cabac) OPT("--cabac-idc", cabac_idc) OPT("--t8x8", t8x8)
         OPT("--bframes", bframes) OPT("--direct-temporal", direct_temporal) OPT("--wp", wp) OPT("--dinf8", dinf8) OPT("--scaling", scaling) OPT("--rplm",
             rplm) OPT("--mmco", mmco) OPT("--nc-corner", nc_corner) OPT("--no-intra", no_intra) OPT("--fmo0", fmo0) OPT("--poc-bottom", poc_bottom) OPT("--paff", paff) OPT("--gaps", gaps) OPT("--redundant", redundant) OPT("--vui-fps", vui_fps)
+        OPT("--vui-matrix", vui_matrix) OPT("--vui-primaries", vui_primaries) OPT("--vui-transfer", vui_transfer) OPT("--vui-full-range", vui_full_range)
         if (!strcmp(a, "-o")) { outp = v; i++; continue; }
         if (!strcmp(a, "--recon")) { recon = v; i++; continue; }
         fprintf(stderr, "unknown option %s\n", a); return 2;

@@ -53,6 +53,8 @@ typedef struct {
     int open_gop; /* 1: intra periods after the first start with a CRA picture whose leading B pictures are RASL (gop 1..3, period a multiple of gop + 1);
     parameter sets are repeated there */
     int vui_fps;                /* > 0: the SPS carries vui_parameters() with vui_timing_info (num_units_in_tick 1, time_scale vui_fps); no effect on decoding */
+    int vui_matrix, vui_primaries, vui_transfer;   /* any > 0: the VUI carries video_signal_type with a colour description (these three values) */
+    int vui_full_range;         /* 1: video_full_range_flag 1; all four 0: no video_signal_type */
 } HevcGenParams;
 
 /* ------------------------------ RNG ------------------------------ */
@@ -1442,14 +1444,24 @@ static void write_sps(Enc *e, BitW *out, int max_dpb, int reorder) {
     bw_put(&w, 1, (uint32_t)p->lt_ref);
     if (p->lt_ref) bw_ue(&w, 0);
     bw_put(&w, 1, (uint32_t)p->tmvp); bw_put(&w, 1, (uint32_t)p->strong_intra);
-    if (p->vui_fps > 0) {                                             /* vui_parameters() (E.2.1) */
+    const int colour_desc = p->vui_matrix > 0 || p->vui_primaries > 0 || p->vui_transfer > 0, signal_type = colour_desc || p->vui_full_range > 0;
+    if (p->vui_fps > 0 || signal_type) {                              /* vui_parameters() (E.2.1) */
         bw_put(&w, 1, 1);
         bw_put(&w, 1, 1); bw_put(&w, 8, 1);                           /* aspect_ratio_info_present_flag, aspect_ratio_idc 1 */
-        bw_put(&w, 1, 0); bw_put(&w, 1, 0); bw_put(&w, 1, 0);         /* overscan, video signal type, chroma location: absent */
+        bw_put(&w, 1, 0);                                             /* overscan: absent */
+        bw_put(&w, 1, (uint32_t)signal_type);                         /* video_signal_type_present_flag */
+        if (signal_type) {
+            bw_put(&w, 3, 5); bw_put(&w, 1, (uint32_t)(p->vui_full_range > 0)); bw_put(&w, 1, (uint32_t)colour_desc);   /* video_format 5, range, desc */
+            if (colour_desc) { bw_put(&w, 8, (uint32_t)p->vui_primaries & 255); bw_put(&w, 8, (uint32_t)p->vui_transfer & 255);
+                bw_put(&w, 8, (uint32_t)p->vui_matrix & 255); }
+        }
+        bw_put(&w, 1, 0);                                             /* chroma location: absent */
         bw_put(&w, 1, 0); bw_put(&w, 1, 0); bw_put(&w, 1, 0);         /* neutral_chroma_indication, field_seq, frame_field_info_present */
         bw_put(&w, 1, 0);                                             /* default_display_window_flag */
-        bw_put(&w, 1, 1); bw_put(&w, 32, 1); bw_put(&w, 32, (uint32_t)p->vui_fps);     /* vui_timing_info: num_units_in_tick, time_scale */
-        bw_put(&w, 1, 0); bw_put(&w, 1, 0);                           /* poc_proportional_to_timing, vui_hrd_parameters_present */
+        if (p->vui_fps > 0) {
+            bw_put(&w, 1, 1); bw_put(&w, 32, 1); bw_put(&w, 32, (uint32_t)p->vui_fps);     /* vui_timing_info: num_units_in_tick, time_scale */
+            bw_put(&w, 1, 0); bw_put(&w, 1, 0);                       /* poc_proportional_to_timing, vui_hrd_parameters_present */
+        } else bw_put(&w, 1, 0);                                      /* vui_timing_info_present_flag */
         bw_put(&w, 1, 0);                                             /* bitstream_restriction_flag */
     } else bw_put(&w, 1, 0);                                          /* no VUI */
     bw_put(&w, 1, 0);                                                 /* no extension */
@@ -1889,7 +1901,9 @@ int main(int argc, char **argv) {
         {"--wpp", &p.wpp}, {"--tile-cols", &p.tile_cols}, {"--tile-rows", &p.tile_rows}, {"--slice-ctus", &p.slice_ctus}, {"--dep-slices", &p.dep_slices},
             {"--merge-cand", &p.merge_cand},
         {"--cabac-init", &p.cabac_init}, {"--par-mrg", &p.par_mrg}, {"--cb-qp-off", &p.cb_qp_off}, {"--cr-qp-off", &p.cr_qp_off}, {"--search", &p.search},
-            {"--rps-sps", &p.rps_sps}, {"--open-gop", &p.open_gop}, {"--vui-fps", &p.vui_fps} };
+            {"--rps-sps", &p.rps_sps}, {"--open-gop", &p.open_gop}, {"--vui-fps", &p.vui_fps},
+            {"--vui-matrix", &p.vui_matrix}, {"--vui-primaries", &p.vui_primaries}, {"--vui-transfer", &p.vui_transfer},
+            {"--vui-full-range", &p.vui_full_range} };
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-o") && i + 1 < argc) { outp = argv[++i]; continue; }
         if (!strcmp(argv[i], "--recon") && i + 1 < argc) { recon = argv[++i]; continue; }
