@@ -585,7 +585,9 @@ bool Decoder::gpu_alloc_sequence() {
     // parse workers, 10.9 -> 9.6 k frames/s against round 2's worst-case slots on the same box).
     // (Main / Extended: 224 -- B pictures, no 8x8 transform.)
     const size_t per_mb = seq_.profile_idc == 66 ? 128 : (seq_.profile_idc < 100 ? 224 : 320);
-    job_cap_ = std::min(job_cap_max_, n_mbs * (sizeof(MbRec) + per_mb) + 256 * (sizeof(SliceRec) + sizeof(SliceWp)) + 4096);
+    // (the allowance for weight tables is a fixed 113 KB -- what 256 tables took while the weights were eight bits wide -- not the worst case: tables
+    //  that do not fit behind the levels grow the slot like anything else, parse_task)
+    job_cap_ = std::min(job_cap_max_, n_mbs * (sizeof(MbRec) + per_mb) + 256 * (sizeof(SliceRec) + 452) + 4096);
     if (getenv("JM_AMD_DEC_JOB_WORST_CASE")) job_cap_ = job_cap_max_;
     if (codec_ == 1) job_cap_ = n_mbs * 128 + (1u << 20);            // HEVC job lists vary a lot in size: start small, grow on demand (ensure_job_cap)
     if (!n_jobs_set_) n_jobs_ = codec_ == 0 && n_mbs <= 8704 ? kJobSlotsSmall : kJobSlots;      // (decoder.h)
@@ -1133,8 +1135,8 @@ void Decoder::build_ref_lists(const SliceHeader &sh, SliceTask &task) {
         wp.mode = (uint8_t)mode; wp.logwd_y = (uint8_t)sh.luma_log2_wd; wp.logwd_c = (uint8_t)sh.chroma_log2_wd;
         if (mode == 1) {
             for (int l = 0; l < nlists; l++) for (int i = 0; i < 16 && i < sh.num_ref_idx[l]; i++) {
-                wp.w[l][i][0] = (int8_t)sh.luma_w[l][i]; wp.o[l][i][0] = (int8_t)sh.luma_o[l][i];
-                for (int c = 0; c < 2; c++) { wp.w[l][i][1 + c] = (int8_t)sh.chroma_w[l][i][c]; wp.o[l][i][1 + c] = (int8_t)sh.chroma_o[l][i][c]; }
+                wp.w[l][i][0] = sh.luma_w[l][i]; wp.o[l][i][0] = (int8_t)sh.luma_o[l][i];
+                for (int c = 0; c < 2; c++) { wp.w[l][i][1 + c] = sh.chroma_w[l][i][c]; wp.o[l][i][1 + c] = (int8_t)sh.chroma_o[l][i][c]; }
             }
         } else {
             for (int i = 0; i < 16; i++) for (int j = 0; j < 16; j++) {
@@ -1224,7 +1226,10 @@ void Decoder::build_frame_ref_lists(const SliceHeader &sh, SliceTask &task) {
 }
 
 void Decoder::add_slice(const SliceHeader &sh, std::vector<uint8_t> &&rbsp, size_t rbsp_len) {
-    if (pending_->slices.size() >= 255) { stat_errors_++; return; }
+    // MbRec.slice numbers a picture's slices with eight bits and the job buffer holds SliceRec[256]: a picture with more slices cannot be decoded.
+    // Dropping the slice would hand out a frame with macroblocks no slice covered as if it were good, so the handle fails and says why.
+    if (pending_->slices.size() >= kMaxSlicesPerPicture) { stat_errors_++;
+        fail("more than 255 slices in one picture: not supported (the job list numbers the slices of a picture with eight bits)"); return; }
     pending_->slices.emplace_back();
     SliceTask &s = pending_->slices.back();
     s.sh = sh; s.rbsp = std::move(rbsp); s.rbsp_len = rbsp_len;

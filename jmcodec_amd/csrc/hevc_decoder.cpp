@@ -66,7 +66,9 @@ void Decoder::hevc_handle_nal(const uint8_t *nal, size_t len) {
     else if (!pending_ || !pending_->hevc) { stat_errors_++; note_error("slice segment of a picture whose first segment is missing"); return; }
     HevcTask &ht = *pending_->hevc;
     if (!ht.slices.empty() && sh.pps_id != ht.slices[0].sh.pps_id) { stat_errors_++; note_error("slices of one picture refer to different PPSs"); return; }
-    if (ht.slices.size() >= 600) { stat_errors_++; return; }
+    // 600 slice segments per picture is the most any level allows (Table A.8, levels 6 .. 6.2).  A picture with more is not decoded in part and
+    // handed out as if it were good: the handle fails and says why.
+    if (ht.slices.size() >= 600) { stat_errors_++; fail("more than 600 slice segments in one picture: not supported (the limit of level 6.2)"); return; }
     HevcSliceTask st;
     st.sh = sh;
     if (sh.dependent && !ht.slices.empty()) st.refs = ht.slices.back().refs;

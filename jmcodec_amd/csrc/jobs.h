@@ -67,6 +67,8 @@ static_assert(sizeof(MbRec) == 32, "MbRec must stay 32 bytes");
 //   chroma : 16 levels (raster, [0] unused) per set bit of cbp_cac, ascending
 //   MB_PCM : 384 raw bytes (256 Y, 64 Cb, 64 Cr) = 192 int16 slots, nothing else
 
+constexpr int kMaxSlicesPerPicture = 255;     // MbRec.slice is eight bits; decoder.cpp fails the handle at the 256th slice of a picture
+
 struct SliceRec {         // 4 bytes
     int8_t  alpha_off;    // FilterOffsetA
     int8_t  beta_off;     // FilterOffsetB
@@ -78,11 +80,11 @@ struct SliceRec {         // 4 bytes
 struct SliceWp {
     uint8_t mode;             // 0 default, 1 explicit, 2 implicit (bi-predicted blocks only)
     uint8_t logwd_y, logwd_c, pad;
-    int8_t  w[2][16][3];      // explicit weights [list][ref_idx][Y, Cb, Cr]
+    int16_t w[2][16][3];      // explicit weights [list][ref_idx][Y, Cb, Cr]: -128..127 when coded, 2^logwd (up to 128) when the entry's flag is off
     int8_t  o[2][16][3];      // explicit offsets
     uint8_t imp_w1[16][16];   // implicit: 64 + w1 of the pair (ref_idx_l0, ref_idx_l1), w1 in [-64, 128]; w0 = 64 - w1
 };
-static_assert(sizeof(SliceWp) == 4 + 96 + 96 + 256, "SliceWp layout");
+static_assert(sizeof(SliceWp) == 4 + 192 + 96 + 256, "SliceWp layout");
 
 constexpr int kMaxSurfaces = 20;
 
