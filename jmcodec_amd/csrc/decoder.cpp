@@ -1652,16 +1652,11 @@ int Decoder::display_entry(int slot) {
 }
 
 // a display frame leaves the DPB: reserve an output slot (display order) and describe the pack-out for the engine
-void Decoder::enqueue_output(int entry, EnginePic &ep, bool after) {
+void Decoder::enqueue_output(int entry, OutSide &out) {
     // display_entry: bits 8..15 = the one field that was decoded, if only one was; bits 16..23 = the matrix and range of the picture's sequence;
     // bits 24.. = the field the deinterlacer keeps (0: the frame is not deinterlaced)
     const int slot = entry & 255, color = (entry >> 16) & 255, field = entry >> 24;
     int lone = (entry >> 8) & 255;
-    std::vector<PackJob> &jobs = after ? ep.out_after : ep.out_before;
-    std::vector<ScaleJob> &sjobs = after ? ep.scale_after : ep.scale_before;
-    std::vector<RgbJob> &rjobs = after ? ep.rgb_after : ep.rgb_before;
-    std::vector<DeintReq> &djobs = after ? ep.deint_after : ep.deint_before;
-    std::vector<OutSlot *> &slots = after ? ep.slots_after : ep.slots_before;
     OutSlot *o;
     { std::lock_guard<std::mutex> lk(mtx_); o = alloc_out_slot(); ready_.push_back(o); num_frames_++; }   // nv_dec.cpp:48 num_frames++
     if (parse_only_ || failed_) { std::lock_guard<std::mutex> lk(mtx_); o->ready = true; done_unfetched_++; if (field) stat_deint_++; return; }
@@ -1678,11 +1673,11 @@ void Decoder::enqueue_output(int entry, EnginePic &ep, bool after) {
         DeintReq r{DeintJob{surf_[slot], o->dev ? o->dev : o->host, pitch_, chroma_off_, disp_w_, disp_h_, disp_w_, disp_w_ * disp_h_, out_fmt_, lone ? 1 : deint_mode_,
                             field - 1, 4 * t * t}, 0, 0};
         if (rgb_ || scaled_) {
-            r.feeds = rgb_ ? 2 : 1; r.index = (int)(rgb_ ? rjobs.size() : sjobs.size());
+            r.feeds = rgb_ ? 2 : 1; r.index = (int)(rgb_ ? out.rgb.size() : out.scale.size());
             r.job.dst = nullptr; r.job.dst_pitch = pitch_; r.job.dst_chroma_offset = src_chroma = pitch_ * disp_h_; r.job.out_fmt = 0;
             src = nullptr; lone = 0;
         }
-        djobs.push_back(r); stat_deint_++;
+        out.deint.push_back(r); stat_deint_++;
     }
     if (rgb_) {
         RgbJob rj = {};
@@ -1690,14 +1685,14 @@ void Decoder::enqueue_output(int entry, EnginePic &ep, bool after) {
         for (int a = 0; a < 4; a++) rj.s.ax[a] = scale_ax_[a];
         rj.identity = scaled_ ? 0 : 1;
         fill_rgb_color(rj, rgb_spec_, color & 15, (color >> 4) == 2);
-        rjobs.push_back(rj); stat_rgb_++;
+        out.rgb.push_back(rj); stat_rgb_++;
         if (scaled_) stat_scaled_++;
     } else if (scaled_) {
         ScaleJob sj{src, o->dev ? o->dev : o->host, pitch_, src_chroma, crop_[0], crop_[1], out_w_, out_h_, out_fmt_, lone, {}};
         for (int a = 0; a < 4; a++) sj.ax[a] = scale_ax_[a];
-        sjobs.push_back(sj); stat_scaled_++;
-    } else if (!field) jobs.push_back(PackJob{surf_[slot], o->dev ? o->dev : o->host, pitch_, chroma_off_, disp_w_, disp_h_, out_fmt_, lone});
-    slots.push_back(o);
+        out.scale.push_back(sj); stat_scaled_++;
+    } else if (!field) out.plain.push_back(PackJob{surf_[slot], o->dev ? o->dev : o->host, pitch_, chroma_off_, disp_w_, disp_h_, out_fmt_, lone});
+    out.slots.push_back(o);
     o->has_data = true;
     // route of this frame (see Decoder::init): fetch when the device's synchronous-copy queue is idle right now
     o->fetch = o->dev && (!o->host || (out_route_ == 0 && engine_ && engine_->fetchers() < fetch_limit_));
@@ -1708,7 +1703,7 @@ void Decoder::submit_task(PicTask *t) {
     EnginePic ep;
     ep.dec = this; ep.has_picture = t->has_picture && !parse_only_ && !failed_; ep.job_slot = t->job_slot;
     ep.mb_w = mb_w_; ep.mb_h = mb_h_; ep.disp_w = disp_w_; ep.disp_h = disp_h_; ep.wait_prev_pack = t->wait_prev_pack;
-    for (int s : t->out_before) { enqueue_output(s, ep, false); ep.out_mask |= 1u << (s & 255); }
+    for (int s : t->out_before) { enqueue_output(s, ep.out[kBefore]); ep.out_mask |= 1u << (s & 255); }
     memset(&ep.pp, 0, sizeof ep.pp);
     if (ep.has_picture && t->hevc) hevc_fill_engine_pic(t, ep);
     else if (ep.has_picture) {
@@ -1773,7 +1768,7 @@ void Decoder::submit_task(PicTask *t) {
     // (an RGB handle reads the crop rectangle too, and writes its RGB frame)
     ep.alg_bytes[3] = (scaled_ || rgb_ ? (long long)crop_[2] * crop_[3] * 3 / 2 : (long long)surf_bytes_) + (long long)frame_bytes_;
     ep.alg_bytes[4] = 2ll * disp_w_ * disp_h_ * 3 / 2;       // (k_deint reads the display area and writes as much)
-    for (int s : t->out_after) { enqueue_output(s, ep, true); ep.out_mask |= 1u << (s & 255); }
+    for (int s : t->out_after) { enqueue_output(s, ep.out[kAfter]); ep.out_mask |= 1u << (s & 255); }
     stat_submit_ns_ += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - st0).count();
     if (parse_only_ || failed_ || !engine_) { on_engine_done(ep); return; }
     engine_->submit(std::move(ep));
@@ -1798,9 +1793,8 @@ void Decoder::on_engine_done(const EnginePic &p, bool failed) {
             if (j.big >= 0) { big_[j.big].busy = false; j.host = j.own_host; j.dev = j.own_dev; j.cap = j.own_cap; j.big = -1; }
             j.busy = false;
         }
-        for (OutSlot *o : p.slots_before) { o->ready = true; if (failed) o->has_data = false; }
-        for (OutSlot *o : p.slots_after) { o->ready = true; if (failed) o->has_data = false; }
-        done_unfetched_ += (int)(p.slots_before.size() + p.slots_after.size());
+        for (auto &side : p.out) for (OutSlot *o : side.slots) { o->ready = true; if (failed) o->has_data = false; }
+        done_unfetched_ += (int)(p.out[kBefore].slots.size() + p.out[kAfter].slots.size());
         outstanding_--;
         cv_.notify_all();                  // under the lock: the handle may be destroyed as soon as the count reaches zero
     }

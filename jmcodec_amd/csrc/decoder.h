@@ -222,7 +222,7 @@ private:
     void gpu_close();
     void submit_ready();
     void submit_task(PicTask *t);
-    void enqueue_output(int entry, EnginePic &ep, bool after);
+    void enqueue_output(int entry, OutSide &out);
     bool resolve_geometry();                   // options crop_* / target_* against the display size of the sequence being activated
     // the colour description of the sequence being activated (vui: full range, primaries, transfer, matrix as transmitted, -1 = absent): the
     // matrix and range its frames are converted with

@@ -68,7 +68,6 @@ Engine::Engine(int device) : device_(device) {
     for (int k = 0; k < n_copy_; k++) if (hipStreamCreateWithPriority(&copy_streams_[k], hipStreamNonBlocking, copy_prio) != hipSuccess) {
         (void)hipGetLastError();
         if (hipStreamCreateWithFlags(&copy_streams_[k], hipStreamNonBlocking) != hipSuccess) return; }
-    copy_stream_ = copy_streams_[0];
     mem_trace("engine: copy stream");
     for (auto &ln : lanes_) {
         hipStream_t s, p, q;
@@ -90,14 +89,11 @@ Engine::Engine(int device) : device_(device) {
             memset(b.h_err, 0, sizeof(int) * (kMaxBatch + 4));
             if (hipHostMalloc((void **)&b.h_groups, sizeof(uint32_t) * kMaxChainGroups, hipHostMallocDefault) != hipSuccess) return;
             if (hipMalloc((void **)&b.d_groups, sizeof(uint32_t) * kMaxChainGroups) != hipSuccess) return;
-            if (hipHostMalloc((void **)&b.h_jobs, sizeof(PackJob) * 4 * kMaxBatch, hipHostMallocDefault) != hipSuccess) return;
-            if (hipMalloc((void **)&b.d_jobs, sizeof(PackJob) * 4 * kMaxBatch) != hipSuccess) return;
-            if (hipHostMalloc((void **)&b.h_sjobs, sizeof(ScaleJob) * 4 * kMaxBatch, hipHostMallocDefault) != hipSuccess) return;
-            if (hipMalloc((void **)&b.d_sjobs, sizeof(ScaleJob) * 4 * kMaxBatch) != hipSuccess) return;
-            if (hipHostMalloc((void **)&b.h_rjobs, sizeof(RgbJob) * 4 * kMaxBatch, hipHostMallocDefault) != hipSuccess) return;
-            if (hipMalloc((void **)&b.d_rjobs, sizeof(RgbJob) * 4 * kMaxBatch) != hipSuccess) return;
-            if (hipHostMalloc((void **)&b.h_djobs, sizeof(DeintJob) * 4 * kMaxBatch, hipHostMallocDefault) != hipSuccess) return;
-            if (hipMalloc((void **)&b.d_djobs, sizeof(DeintJob) * 4 * kMaxBatch) != hipSuccess) return;
+            bool tables_ok = true;                            // the four output kernels' job tables: both sides (out_tables.h)
+            b.out.each([&](auto &t) { const size_t bytes = sizeof(*t.host) * 2 * kOutSideCap;
+                tables_ok = tables_ok && hipHostMalloc((void **)&t.host, bytes, hipHostMallocDefault) == hipSuccess &&
+                            hipMalloc((void **)&t.dev, bytes) == hipSuccess; });
+            if (!tables_ok) return;
             if (hipEventCreateWithFlags(&b.done, hipEventDisableTiming) != hipSuccess) return;
             if (hipEventCreateWithFlags(&b.kdone, hipEventDisableTiming) != hipSuccess) return;
             if (hipEventCreateWithFlags(&b.packed, hipEventDisableTiming) != hipSuccess) return;
@@ -286,7 +282,7 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
     auto account = [&](EnginePic &p, EngineDecoderState &es) {
         if (p.has_picture) es.batch_written |= 1u << (p.codec == 0 ? p.pp.cur : p.hp.cur);
         es.batch_read |= p.ref_mask | p.out_mask;
-        n_pre += p.n_before(); n_post += p.n_after();
+        n_pre += p.out[kBefore].frames(); n_post += p.out[kAfter].frames();
     };
     // (the walk ends once every decoder that has pictures pending has been seen: with the engine as the bottleneck some 1,100 pictures are pending at 32 streams,
     //  the decoders' oldest ones among the first hundred or two -- and this runs under m_, which every submitting thread needs, on every turn of the engine loop)
@@ -304,9 +300,9 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
         int why = 0;
         if (it->lane(chaining) != lane_idx) why = 1;
         else if (es.inflight > es.lane_inflight[lane_idx] && !(relaxed && others_done(d, lane_idx, it->seq))) why = 2;
-        // the pack-job tables hold 2 * kMaxBatch entries each: a picture whose display frames no longer fit waits for the next batch
+        // the output tables hold kOutSideCap frames per side: a picture whose display frames no longer fit waits for the next batch
         // (a flush or an IDR picture can release a whole DPB at once: up to 16 frames from one handle)
-        else if (n_pre + it->n_before() > (size_t)2 * kMaxBatch || n_post + it->n_after() > (size_t)2 * kMaxBatch) why = 3;
+        else if (n_pre + it->out[kBefore].frames() > (size_t)kOutSideCap || n_post + it->out[kAfter].frames() > (size_t)kOutSideCap) why = 3;
         if (why) {
             if (lane_idx == kOrdinaryLane && it->codec == 0) { std::lock_guard<std::mutex> lk(sm_);
                 (why == 1 ? st_.rej_other_lane : why == 2 ? st_.rej_cross_lane : st_.rej_tables)++;
@@ -324,9 +320,8 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
         if (lane_idx == kOrdinaryLane && es.blocked_since) { std::lock_guard<std::mutex> lk(sm_); st_.blocked_ns += now_ns - es.blocked_since; st_.blocked_n++;
             LANE_TRACE("rejoined dec %p seq %llu after %.3f ms\n", (void *)d, it->seq, (now_ns - es.blocked_since) * 1e-6);
             es.blocked_since = 0; }
-        es.lane = lane_idx; es.inflight++; es.lane_inflight[lane_idx]++;
+        es.inflight++; es.lane_inflight[lane_idx]++;
         es.in_batch = 1; es.batch_written = es.batch_read = 0; es.batch_stop = false;
-        es.batch_resid = it->has_picture && it->codec == 0 && (it->pp.stages & (PS_INTRA_LDS | PS_INTRA_V1)) != 0;
         account(*it, es);
         members.push_back(d);
         took(es);
@@ -378,11 +373,11 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
             for (auto &c : cand) pos.push_back((size_t)(c - pending_.begin()));
             for (size_t k = pos.size(); k-- > 0 && (int)b.pics.size() < kMaxBatch;) {
                 auto it = pending_.begin() + (std::ptrdiff_t)pos[k];
-                if (n_post + it->n_after() > (size_t)2 * kMaxBatch) continue;
+                if (n_post + it->out[kAfter].frames() > (size_t)kOutSideCap) continue;
                 EngineDecoderState &es = it->dec->engine_state();
                 es.inflight++; es.lane_inflight[lane_idx]++;
                 LANE_TRACE("early dec %p seq %llu\n", (void *)it->dec, it->seq);
-                n_post += it->n_after();
+                n_post += it->out[kAfter].frames();
                 took(es);
                 b.pics.push_back(std::move(*it));
                 pending_.erase(it);
@@ -425,11 +420,11 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
                 // and decodes into a surface that no earlier picture of this decoder in the batch writes, references or displays
                 const bool ok = it != pending_.end() && it->lane(true) == lane_idx && it->has_picture && (it->chain_ok || it->chain_intra) &&
                                 it->before_empty() && !it->wait_prev_pack &&
-                                !((1u << it->pp.cur) & (es.batch_written | es.batch_read)) && n_post + it->n_after() <= (size_t)2 * kMaxBatch;
+                                !((1u << it->pp.cur) & (es.batch_written | es.batch_read)) && n_post + it->out[kAfter].frames() <= (size_t)kOutSideCap;
                 int nb = 0, ng = 0;
                 if (ok) chain_cost(*it, nb, ng);
                 if (!ok || tot_bands + nb > band_limit(any_intra || it->chain_intra) || tot_groups + ng > kMaxChainGroups) { es.batch_stop = true; continue; }
-                tot_bands += nb; tot_groups += ng; any_intra |= it->chain_intra; es.batch_resid |= it->chain_intra;
+                tot_bands += nb; tot_groups += ng; any_intra |= it->chain_intra;
                 es.inflight++; es.lane_inflight[lane_idx]++; es.in_batch++;
                 account(*it, es);
                 took(es);
@@ -454,7 +449,7 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
                 if (it == pending_.end() || !it->has_picture || it->codec != 1 || it->lane(false) != lane_idx || !it->before_empty() ||
                     it->wait_prev_pack) break;
                 if ((it->ref_mask & es.batch_written) || ((1u << it->hp.cur) & (es.batch_written | es.batch_read)) ||
-                    n_post + it->n_after() > (size_t)2 * kMaxBatch) break;
+                    n_post + it->out[kAfter].frames() > (size_t)kOutSideCap) break;
                 es.inflight++; es.lane_inflight[lane_idx]++; es.in_batch++;
                 es.batch_written |= 1u << it->hp.cur;
                 account(*it, es);
@@ -464,7 +459,6 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
             }
         }
     }
-    (void)ln;
     return true;
 }
 
@@ -480,35 +474,22 @@ void Engine::launch(Lane &ln, Batch &b) {
             if (ended) { std::lock_guard<std::mutex> lk(sm_); st_.lane_dry[li]++; } }
     }
     LANE_TRACE("launch lane %d batch %llu pics %d\n", li, b.serial, n);
-    int max_mbs = 0, max_mb_h = 0, max_mb_w = 0, max_w = 0, max_h = 0, stages = 0;
+    int max_mbs = 0, max_mb_h = 0, max_mb_w = 0, stages = 0;
     bool wait_pack = false, any_hevc = false;
     HevcBatchDims hd;
     const EnginePic *last_upload[4] = {nullptr, nullptr, nullptr, nullptr};      // per copy stream (upload k went to stream k % n_copy_)
-    b.n_pre = b.n_post = 0; b.n_spre = b.n_spost = 0; b.s_tiles = 0; b.n_rpre = b.n_rpost = 0; b.r_tiles[0] = b.r_tiles[1] = 0; b.pmask = 0;
-    b.n_dpre = b.n_dpost = 0; b.d_items = 0;
+    b.pmask = 0;
     for (int k = 0; k < kKernelClasses; k++) { b.alg[k] = 0; b.npics[k] = 0; }
     // deinterlaced frames of scaled / RGB handles: one scratch surface each.  The batch's earlier launch has completed (its slot of the ring was free),
     // so nothing reads the old allocation; growing it synchronises the device, which a handful of first batches pay
-    auto scratch_bytes = [](const DeintJob &j) { return ((size_t)j.dst_pitch * j.height * 3 / 2 + 255) & ~(size_t)255; };
-    size_t d_need = 0, d_used = 0;
-    for (auto &p : b.pics) for (auto *v : {&p.deint_before, &p.deint_after}) for (auto &r : *v) if (r.feeds) d_need += scratch_bytes(r.job);
+    size_t d_need = 0;
+    for (auto &p : b.pics) for (auto &o : p.out) d_need += OutTables::bytes_needed(o);
     if (d_need > b.deint_cap) {
         if (b.deint_scratch) hipFree(b.deint_scratch);
         b.deint_scratch = nullptr; b.deint_cap = std::max(d_need, 2 * b.deint_cap);
         if (hipMalloc((void **)&b.deint_scratch, b.deint_cap) != hipSuccess) { (void)hipGetLastError(); b.deint_scratch = nullptr; b.deint_cap = 0; }
     }
-    // (no scratch: the frames that need it are not produced, and their handles fail)
-    auto add_deint = [&](EnginePic &p, const DeintReq &r, int at, int &n, ScaleJob *sj, RgbJob *rj) {
-        DeintJob j = r.job;
-        if (r.feeds) {
-            const uint8_t **src = r.feeds == 1 ? &sj[r.index].src : &rj[r.index].s.src;
-            if (!b.deint_scratch) { p.dec->on_engine_error("hipMalloc(deinterlace scratch) failed"); *src = j.src; return; }
-            j.dst = b.deint_scratch + d_used; *src = j.dst; d_used += scratch_bytes(j);
-        }
-        b.h_djobs[at + n++] = j; b.d_items = std::max(b.d_items, deint_items(j.width, j.height));
-        b.alg[6] += p.alg_bytes[4]; b.npics[6]++;
-    };
-    // pack jobs: [0, n_pre) before the decode kernels, [2*kMaxBatch, 2*kMaxBatch + n_post) after them
+    b.out.reset(b.deint_scratch);
     for (int i = 0; i < n; i++) {
         EnginePic &p = b.pics[i];
         const bool hevc = p.codec == 1;
@@ -553,22 +534,9 @@ void Engine::launch(Lane &ln, Batch &b) {
             if (p.uploaded) { const EnginePic *&lu = last_upload[p.upload_seq % (unsigned)n_copy_]; if (!lu || p.upload_seq > lu->upload_seq) lu = &p; }
         }
         if (p.wait_prev_pack) wait_pack = true;
-        const int sb = b.n_spre, sa = 2 * kMaxBatch + b.n_spost, rb = b.n_rpre, ra = 2 * kMaxBatch + b.n_rpost;     // this picture's first entries
-        for (auto &j : p.out_before) b.h_jobs[b.n_pre++] = j;                           // form() keeps both tables within 2 * kMaxBatch
-        for (auto &j : p.out_after) b.h_jobs[2 * kMaxBatch + b.n_post++] = j;
-        // (scaled handles: the same two tables for k_scale_pack, launched beside k_packout)
-        for (auto &j : p.scale_before) { b.h_sjobs[b.n_spre++] = j; b.s_tiles = std::max(b.s_tiles, scale_tiles(j.tw, j.th)); }
-        for (auto &j : p.scale_after) { b.h_sjobs[2 * kMaxBatch + b.n_spost++] = j; b.s_tiles = std::max(b.s_tiles, scale_tiles(j.tw, j.th)); }
-        // (RGB handles: a third pair of tables for k_rgb_pack)
-        for (auto &j : p.rgb_before) { b.h_rjobs[b.n_rpre++] = j; b.r_tiles[!j.identity] = std::max(b.r_tiles[!j.identity], rgb_tiles(j.s.tw, j.s.th)); }
-        for (auto &j : p.rgb_after) { b.h_rjobs[2 * kMaxBatch + b.n_rpost++] = j;
-            b.r_tiles[!j.identity] = std::max(b.r_tiles[!j.identity], rgb_tiles(j.s.tw, j.s.th)); }
-        // (deinterlaced frames: a fourth pair for k_deint; the ScaleJob / RgbJob of a scaled / RGB one reads what k_deint wrote)
-        for (auto &r : p.deint_before) add_deint(p, r, 0, b.n_dpre, b.h_sjobs + sb, b.h_rjobs + rb);
-        for (auto &r : p.deint_after) add_deint(p, r, 2 * kMaxBatch, b.n_dpost, b.h_sjobs + sa, b.h_rjobs + ra);
-        b.alg[5] += p.alg_bytes[3] * (long long)(p.rgb_before.size() + p.rgb_after.size());
-        b.npics[5] += (int)(p.rgb_before.size() + p.rgb_after.size());
-        if (!p.out_before.empty() || !p.out_after.empty()) { max_w = std::max(max_w, p.disp_w); max_h = std::max(max_h, p.disp_h); }
+        // its display frames, into the output tables (form() keeps each side within kOutSideCap).  No scratch: the frames that need it are not produced
+        for (int side : {kBefore, kAfter}) if (!b.out.add(p.out[side], side, p.disp_w, p.disp_h, p.alg_bytes[3], p.alg_bytes[4]))
+            p.dec->on_engine_error("hipMalloc(deinterlace scratch) failed");
         int st = b.h_pics[i].stages;
         if (hevc && p.has_picture) { const int hs = p.hp.stages; if (hs & (HPS_MC | HPS_RESID)) { b.alg[0] += p.alg_bytes[0]; b.npics[0]++; }
             if (hs & HPS_INTRA) { b.alg[1] += p.alg_bytes[1]; b.npics[1]++; } if (hs & (HPS_DEBLOCK | HPS_SAO)) { b.alg[2] += p.alg_bytes[2]; b.npics[2]++; } }
@@ -576,14 +544,14 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (st & (PS_INTRA_LDS | PS_INTRA_V1)) { b.alg[1] += p.alg_bytes[1]; b.npics[1]++; }
         if (st & (PS_DEBLOCK_LDS | PS_DEBLOCK_V1)) { b.alg[2] += p.alg_bytes[2]; b.npics[2]++; }
         if (st & PS_CHAIN) { b.alg[4] += ((st & PS_RECON) ? 0 : p.alg_bytes[0]) + ((st & PS_CHAIN_INTRA) ? p.alg_bytes[1] : 0) + p.alg_bytes[2]; b.npics[4]++; }
-        b.alg[3] += p.alg_bytes[3] * (long long)(p.n_before() + p.n_after());
-        b.npics[3] += (int)(p.n_before() + p.n_after());
     }
+    b.alg[3] = b.out.alg_pack; b.npics[3] = b.out.n_frames; b.alg[5] = b.out.alg_rgb; b.npics[5] = b.out.n_rgb;
+    b.alg[6] = b.out.alg_deint; b.npics[6] = b.out.n_deint;
     // surfaces this batch displays, per decoder: a later batch that decodes into one of them must wait for this batch's pack-out
     // (per lane: pictures of a decoder on different lanes are kept apart by Engine::form)
     for (auto &p : b.pics) p.dec->engine_state().displayed[li] = 0;
     for (auto &p : b.pics) p.dec->engine_state().displayed[li] |= p.out_mask;
-    b.max_mbs = max_mbs; b.max_mb_h = max_mb_h; b.max_w = max_w; b.max_h = max_h; b.redo = false;
+    b.max_mbs = max_mbs; b.max_mb_h = max_mb_h; b.redo = false;
     hipStream_t st = ln.stream, pst = ln.pack_stream;
     // What does not depend on the lane's previous batch -- clearing the control blocks, the parameter / pack-job tables, the deblocking pre-pass (it only
     // reads the job lists) -- is issued on the lane's pre-stream, so it runs WHILE the previous batch's kernels are still busy instead of in the gap behind
@@ -603,14 +571,8 @@ void Engine::launch(Lane &ln, Batch &b) {
         } }
     if (any_hevc) hipMemcpyAsync(b.d_hpics, b.h_hpics, sizeof(HevcPicParams) * n, hipMemcpyHostToDevice, ps);
     else hipMemcpyAsync(b.d_pics, b.h_pics, sizeof(PicParams) * n, hipMemcpyHostToDevice, ps);
-    if (b.n_pre) hipMemcpyAsync(b.d_jobs, b.h_jobs, sizeof(PackJob) * b.n_pre, hipMemcpyHostToDevice, ps);
-    if (b.n_post) hipMemcpyAsync(b.d_jobs + 2 * kMaxBatch, b.h_jobs + 2 * kMaxBatch, sizeof(PackJob) * b.n_post, hipMemcpyHostToDevice, ps);
-    if (b.n_spre) hipMemcpyAsync(b.d_sjobs, b.h_sjobs, sizeof(ScaleJob) * b.n_spre, hipMemcpyHostToDevice, ps);
-    if (b.n_spost) hipMemcpyAsync(b.d_sjobs + 2 * kMaxBatch, b.h_sjobs + 2 * kMaxBatch, sizeof(ScaleJob) * b.n_spost, hipMemcpyHostToDevice, ps);
-    if (b.n_rpre) hipMemcpyAsync(b.d_rjobs, b.h_rjobs, sizeof(RgbJob) * b.n_rpre, hipMemcpyHostToDevice, ps);
-    if (b.n_rpost) hipMemcpyAsync(b.d_rjobs + 2 * kMaxBatch, b.h_rjobs + 2 * kMaxBatch, sizeof(RgbJob) * b.n_rpost, hipMemcpyHostToDevice, ps);
-    if (b.n_dpre) hipMemcpyAsync(b.d_djobs, b.h_djobs, sizeof(DeintJob) * b.n_dpre, hipMemcpyHostToDevice, ps);
-    if (b.n_dpost) hipMemcpyAsync(b.d_djobs + 2 * kMaxBatch, b.h_djobs + 2 * kMaxBatch, sizeof(DeintJob) * b.n_dpost, hipMemcpyHostToDevice, ps);
+    b.out.each([&](auto &t) { for (int side : {kBefore, kAfter}) if (t.n[side])
+        hipMemcpyAsync(t.dev + side * kOutSideCap, t.h(side), sizeof(*t.host) * t.n[side], hipMemcpyHostToDevice, ps); });
     // job lists were copied on the (in-order) copy stream when the pictures were parsed: waiting for the most recently
     // issued one of this batch covers them all without waiting for uploads of later pictures
     for (const EnginePic *lu : last_upload) if (lu) hipStreamWaitEvent(ps, lu->uploaded, 0);
@@ -626,22 +588,9 @@ void Engine::launch(Lane &ln, Batch &b) {
     // The decoder never reuses a displayed surface for the very next picture (DPB cooling, decoder.cpp), so the decode
     // kernels of this batch only have to wait for the pack-out launched TWO batches ago.
     if (ln.pack_hist[1]) hipStreamWaitEvent(st, ln.pack_hist[1], 0);
-    if ((wait_pack || b.n_pre || b.n_spre || b.n_rpre || b.n_dpre) && ln.pack_hist[0]) hipStreamWaitEvent(st, ln.pack_hist[0], 0);
+    if ((wait_pack || b.out.any(kBefore)) && ln.pack_hist[0]) hipStreamWaitEvent(st, ln.pack_hist[0], 0);
     auto mark = [&](int i, hipStream_t s) { if (profile_) hipEventRecord(b.pev[i], s); };
-    mark(0, st);
-    // Pack-out: k_packout writes the tight frames into device staging and a copy engine (SDMA) moves them to the pinned slots.
-    // Letting the kernel store into host memory directly saves that hop but its PCIe-bound stores share the L2 / fabric write
-    // queues with everything else: k_recon_inter of the next batch ran 4x slower next to it (0.56 -> 2.3 ms for 32 pictures).
-    auto copy_out = [&](const std::vector<OutSlot *> &slots, hipStream_t s) { for (OutSlot *o : slots) if (o->dev && o->host &&
-        !o->fetch) hipMemcpyAsync(o->host, o->dev, o->bytes, hipMemcpyDeviceToHost, s); };
-    if (b.n_pre || b.n_spre || b.n_rpre || b.n_dpre) {
-        if (b.n_dpre) { mark(14, st); launch_deint(b.d_djobs, b.n_dpre, b.d_items, st); mark(15, st); b.pmask |= 256; }
-        if (b.n_pre) launch_packout(b.d_jobs, b.n_pre, max_w, max_h, st);
-        if (b.n_spre) launch_scale_pack(b.d_sjobs, b.n_spre, b.s_tiles, st);
-        if (b.n_rpre) { mark(10, st); launch_rgb_pack(b.d_rjobs, b.n_rpre, b.r_tiles[0], b.r_tiles[1], st); mark(11, st); b.pmask |= 64; }
-        b.pmask |= 1; for (auto &p : b.pics) copy_out(p.slots_before, st);
-    }
-    mark(1, st);
+    run_side(b, kBefore, st, true);
     if (any_hevc && (hd.max_pus || hd.max_tbs || hd.any_intra || hd.any_deblock || hd.any_sao)) {
         // HEVC batch (its own lane, so never mixed with H.264 pictures): MC + residual | intra diagonals | deblocking + SAO
         hipEvent_t ev[4] = {b.pev[1], b.pev[2], b.pev[3], b.pev[4]};
@@ -738,18 +687,30 @@ void Engine::launch(Lane &ln, Batch &b) {
     }
     hipEventRecord(b.kdone, st);
     hipStreamWaitEvent(pst, b.kdone, 0);
-    mark(5, pst);
-    if (b.n_dpost) { mark(16, pst); launch_deint(b.d_djobs + 2 * kMaxBatch, b.n_dpost, b.d_items, pst); mark(17, pst); b.pmask |= 16 | 512; }
-    if (b.n_post) { launch_packout(b.d_jobs + 2 * kMaxBatch, b.n_post, max_w, max_h, pst); b.pmask |= 16; }
-    if (b.n_spost) { launch_scale_pack(b.d_sjobs + 2 * kMaxBatch, b.n_spost, b.s_tiles, pst); b.pmask |= 16; }
-    if (b.n_rpost) { mark(12, pst); launch_rgb_pack(b.d_rjobs + 2 * kMaxBatch, b.n_rpost, b.r_tiles[0], b.r_tiles[1], pst); mark(13, pst); b.pmask |= 16 | 128; }
-    mark(6, pst);
-    hipEventRecord(b.packed, pst);                            // from here on the displayed surfaces may be decoded into again
-    for (auto &p : b.pics) copy_out(p.slots_after, pst);
+    run_side(b, kAfter, pst, true);
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) fprintf(stderr, "jm_amd_dec: kernel launch failed: %s\n", hipGetErrorString(le));
     hipEventRecord(b.done, pst);
     ln.pack_hist[1] = ln.pack_hist[0]; ln.pack_hist[0] = b.packed;
+}
+
+// Pack-out: the kernels write the tight frames into device staging and a copy engine (SDMA) moves them to the pinned slots.
+// Letting the kernel store into host memory directly saves that hop but its PCIe-bound stores share the L2 / fabric write
+// queues with everything else: k_recon_inter of the next batch ran 4x slower next to it (0.56 -> 2.3 ms for 32 pictures).
+void Engine::run_side(Batch &b, int side, hipStream_t s, bool in_launch) {
+    const OutTables &t = b.out;
+    auto mark = [&](int i) { if (in_launch && profile_) hipEventRecord(b.pev[i], s); };
+    mark(side ? 5 : 0);
+    if (t.deint.n[side]) { mark(14 + 2 * side); launch_deint(t.deint.d(side), t.deint.n[side], t.d_items, s); mark(15 + 2 * side); b.pmask |= side ? 512 : 256; }
+    if (t.plain.n[side]) launch_packout(t.plain.d(side), t.plain.n[side], t.max_w, t.max_h, s);
+    if (t.scale.n[side]) launch_scale_pack(t.scale.d(side), t.scale.n[side], t.s_tiles, s);
+    if (t.rgb.n[side]) { mark(10 + 2 * side); launch_rgb_pack(t.rgb.d(side), t.rgb.n[side], t.r_tiles[0], t.r_tiles[1], s); mark(11 + 2 * side);
+        b.pmask |= side ? 128 : 64; }
+    if (t.any(side)) b.pmask |= side ? 16 : 1;
+    if (in_launch && side) { mark(6); hipEventRecord(b.packed, s); }      // from here on the displayed surfaces may be decoded into again
+    if (t.any(side)) for (auto &p : b.pics) for (OutSlot *o : p.out[side].slots) if (o->dev && o->host && !o->fetch)
+        hipMemcpyAsync(o->host, o->dev, o->bytes, hipMemcpyDeviceToHost, s);
+    if (in_launch && !side) mark(1);
 }
 
 // A wait inside a chain launch gave up: the launch assumed slots that were not there (another process on the GPU, a long kernel of another stream).  Its
@@ -787,15 +748,8 @@ void Engine::recover(Lane &ln, Batch &b, const std::vector<std::pair<Decoder *, 
         if ((lw & (ext_refs | shown)) || (b.redo && (written & shown_before))) taint(d);
     }
     // 2. frames this batch packed before its kernels showed pictures of the recovered batch: again, from the pictures as they are now
-    if (b.redo && (b.n_pre || b.n_spre || b.n_rpre || b.n_dpre)) {
-        if (b.n_dpre) launch_deint(b.d_djobs, b.n_dpre, b.d_items, st);         // (the job tables and the scratch are the launch's own: still in place)
-        if (b.n_pre) launch_packout(b.d_jobs, b.n_pre, b.max_w, b.max_h, st);
-        if (b.n_spre) launch_scale_pack(b.d_sjobs, b.n_spre, b.s_tiles, st);
-        if (b.n_rpre) launch_rgb_pack(b.d_rjobs, b.n_rpre, b.r_tiles[0], b.r_tiles[1], st);
-        for (auto &p : b.pics) for (OutSlot *o : p.slots_before) if (o->dev && o->host && !o->fetch) hipMemcpyAsync(o->host, o->dev, o->bytes,
-            hipMemcpyDeviceToHost, st);
-        hipStreamSynchronize(st);
-    }
+    // (the job tables and the scratch are the launch's own: still in place)
+    if (b.redo && b.out.any(kBefore)) { run_side(b, kBefore, st, false); hipStreamSynchronize(st); }
     // 3. the pictures again, one per stream at a time
     std::vector<int> depth(n, 0); int max_depth = 0;
     for (int i = 0; i < n; i++) { for (int j = 0; j < i; j++) if (b.pics[j].dec == b.pics[i].dec && b.pics[j].has_picture) depth[i]++;
@@ -820,15 +774,8 @@ void Engine::recover(Lane &ln, Batch &b, const std::vector<std::pair<Decoder *, 
         if (stages & PS_DEBLOCK_V1) launch_deblock(b.d_pics, n, st);
         hipStreamSynchronize(st);                              // h_pics is rewritten for the next depth
     }
-    if (b.n_post || b.n_spost || b.n_rpost || b.n_dpost) {     // the display frames of the batch again, from the pictures as they are now
-        if (b.n_dpost) launch_deint(b.d_djobs + 2 * kMaxBatch, b.n_dpost, b.d_items, st);
-        if (b.n_post) launch_packout(b.d_jobs + 2 * kMaxBatch, b.n_post, b.max_w, b.max_h, st);
-        if (b.n_spost) launch_scale_pack(b.d_sjobs + 2 * kMaxBatch, b.n_spost, b.s_tiles, st);
-        if (b.n_rpost) launch_rgb_pack(b.d_rjobs + 2 * kMaxBatch, b.n_rpost, b.r_tiles[0], b.r_tiles[1], st);
-        for (auto &p : b.pics) for (OutSlot *o : p.slots_after) if (o->dev && o->host && !o->fetch) hipMemcpyAsync(o->host, o->dev, o->bytes,
-            hipMemcpyDeviceToHost, st);
-        hipStreamSynchronize(st);
-    }
+    // the display frames of the batch again, from the pictures as they are now
+    if (b.out.any(kAfter)) { run_side(b, kAfter, st, false); hipStreamSynchronize(st); }
     // 4. what could not be redone from intact data stays an error of its handle (complete() reports the words that are set)
     for (int i = 0; i < n; i++) if (is_tainted(b.pics[i].dec) && !b.h_err[i]) b.h_err[i] = kErrNotRecovered;
     { std::lock_guard<std::mutex> lk(sm_); st_.chain_recoveries++; }

@@ -14,6 +14,7 @@
 // There is no reference counterpart: the reference drives one NVDEC session synchronously (nv_dec.cpp:33-41).
 #pragma once
 #include "jobs.h"
+#include "out_tables.h"
 #include "hevc_jobs.h"
 #include <atomic>
 #include <condition_variable>
@@ -28,9 +29,7 @@ struct ihipStream_t; struct ihipEvent_t;
 namespace jmamd {
 
 class Decoder;
-struct OutSlot;
 
-constexpr int kMaxBatch = 64;
 constexpr int kBatchRing = 4;
 constexpr int kMaxChainGroups = 128 * 1024;         // work list of one chain launch (1080p: 1025 groups per picture, 4K: 4059)
 // band workgroups of one chain launch, upper bound: half of what a whole MI355X holds at 3 workgroups per CU (k_chain)
@@ -60,15 +59,8 @@ struct EnginePic {
     HevcPicParams hp;
     int job_slot = -1;
     ihipEvent_t *uploaded = nullptr; unsigned long long upload_seq = 0;   // job list copy (copy stream), see Engine::upload
-    std::vector<PackJob> out_before, out_after;     // display frames to pack before / after this picture's kernels
-    std::vector<ScaleJob> scale_before, scale_after;    // ... of handles with scaled / cropped output (k_scale_pack)
-    std::vector<RgbJob> rgb_before, rgb_after;          // ... of handles with RGB output (k_rgb_pack)
-    std::vector<DeintReq> deint_before, deint_after;    // ... that are deinterlaced first, or -- plain handles -- deinterlaced and packed (k_deint)
-    static size_t n_plain(const std::vector<DeintReq> &v) { size_t n = 0; for (auto &r : v) n += r.feeds == 0; return n; }
-    size_t n_before() const { return out_before.size() + scale_before.size() + rgb_before.size() + n_plain(deint_before); }
-    size_t n_after() const { return out_after.size() + scale_after.size() + rgb_after.size() + n_plain(deint_after); }
-    bool before_empty() const { return n_before() == 0; }
-    std::vector<OutSlot *> slots_before, slots_after;
+    OutSide out[2];                                 // display frames to pack before (kBefore) / after (kAfter) this picture's kernels
+    bool before_empty() const { return out[kBefore].frames() == 0; }
     int mb_w = 0, mb_h = 0, disp_w = 0, disp_h = 0;
     bool wait_prev_pack = false;                    // this picture reuses a surface whose pack-out may still be running
     // chain launches (chain.hip): the picture may run inside k_chain, i.e. in the same launch as the pictures before it in its stream
@@ -114,7 +106,7 @@ struct EngineStats {
 
 // engine-private state kept inside each Decoder (touched only by the engine thread)
 struct EngineDecoderState {
-    int lane = -1, inflight = 0;                    // lane of the decoder's most recent in-order picture; pictures in flight (all lanes)
+    int inflight = 0;                               // pictures in flight (all lanes)
     int lane_inflight[4] = {0, 0, 0, 0};            // ... per lane
     uint32_t displayed[4] = {0, 0, 0, 0};           // per lane: surfaces displayed by this decoder's pictures in the lane's most recently launched batch
     unsigned long long next_seq = 0;                // decode-order numbering of the decoder's pictures (Engine::submit, m_)
@@ -123,7 +115,7 @@ struct EngineDecoderState {
     unsigned long long scan_tag = 0; uint32_t scan_touched = 0; int scan_ahead = 0; bool scan_closed = false;   // scratch of the look for intra pictures (Engine::form)
     long long blocked_since = 0;                    // diagnostic: when an ordinary-lane batch first left this decoder out (0: not left out)
     // scratch of Engine::form (one batch at a time): what the decoder's pictures already in the batch write / read
-    int in_batch = 0; uint32_t batch_written = 0, batch_read = 0; bool batch_chain = false, batch_stop = false, batch_resid = false;
+    int in_batch = 0; uint32_t batch_written = 0, batch_read = 0; bool batch_stop = false;
 };
 
 void mem_trace(const char *tag);      // developer aid: JM_AMD_DEC_MEMTRACE=1 prints the process's resident memory at set-up steps (engine.cpp)
@@ -159,23 +151,18 @@ private:
         int *h_err = nullptr, *d_err = nullptr;               // error words, one per picture: pinned host memory and its device address
         // redo: an earlier batch of the lane was recovered, this one read its (then damaged) output
         bool any_chain = false, chain_with_intra = false, redo = false; int max_depth = 1;
-        int max_mbs = 0, max_mb_h = 0, max_w = 0, max_h = 0; bool any_bipred = false, any_field = false;
+        int max_mbs = 0, max_mb_h = 0; bool any_bipred = false, any_field = false;
         uint32_t *h_groups = nullptr, *d_groups = nullptr;     // work list of k_chain (chain.hip), kMaxChainGroups entries
-        PackJob *h_jobs = nullptr, *d_jobs = nullptr;         // 4 * kMaxBatch entries
-        ScaleJob *h_sjobs = nullptr, *d_sjobs = nullptr;      // the same for k_scale_pack
-        int n_spre = 0, n_spost = 0, s_tiles = 0;             // (s_tiles: the grid of launch_scale_pack)
-        RgbJob *h_rjobs = nullptr, *d_rjobs = nullptr;        // the same for k_rgb_pack
-        int n_rpre = 0, n_rpost = 0, r_tiles[2] = {0, 0};       // (r_tiles: the grids of launch_rgb_pack, identity / resampled jobs)
-        DeintJob *h_djobs = nullptr, *d_djobs = nullptr;      // the same for k_deint, which runs ahead of the three
-        int n_dpre = 0, n_dpost = 0, d_items = 0;             // (d_items: the grid of launch_deint)
+        OutTables out;                                        // job tables, counts and grids of the four output kernels, both sides (out_tables.h)
         // D(F) of the batch's scaled / RGB frames, one surface each: written by k_deint and read by the pack kernel launched right behind it on the
-        // same stream.  Allocated when the first such frame arrives and grown when a batch needs more (Engine::launch)
+        // same stream.  Allocated when the first such frame arrives and grown when a batch needs more (Engine::launch);
+        // OutTables hands out its surfaces
         uint8_t *deint_scratch = nullptr; size_t deint_cap = 0;
         // packed: surfaces were read by k_packout (before the copies)
         // (profile events 10 / 11 and 12 / 13 bracket the k_rgb_pack launches before / after the decode kernels, 14 / 15 and 16 / 17 k_deint's)
         ihipEvent_t *done = nullptr, *kdone = nullptr, *packed = nullptr, *pre_done = nullptr, *pev[18] = {nullptr};
         std::vector<EnginePic> pics;
-        int n_pre = 0, n_post = 0; unsigned pmask = 0;
+        unsigned pmask = 0;
         long long alg[kKernelClasses] = {}; int npics[kKernelClasses] = {};
         int last_ev = -1;                                     // index of the profile event behind the batch's last decode kernel
         bool launched_dry = false;                            // diagnostic: the lane's previous batch had already ended when this one was launched
@@ -220,7 +207,10 @@ private:
     std::vector<std::vector<uint32_t>> group_buckets_;
     std::vector<uint32_t> bucket_tmp_;                                 // scratch of append_bucket_by_xcd (chain_order.h)
     void launch(Lane &ln, Batch &b);
-    void launch_hevc(Lane &ln, Batch &b);
+    // One side of a batch's output stage on stream s: k_deint, k_packout, k_scale_pack, k_rgb_pack -- in this order: k_deint feeds the scale / RGB jobs behind
+    // it on the same stream -- then the copies of the frames to their pinned slots.  in_launch: the batch's first run, with its profile events (before:
+    // 0 / 1 around everything, after: 5 / 6 around the kernels; 10-13 k_rgb_pack, 14-17 k_deint) and, after the after side's kernels, its `packed` event
+    void run_side(Batch &b, int side, ihipStream_t *s, bool in_launch);
     void complete(Lane &ln, Batch &b, bool failed);
     void dump_chain_state(Batch &b);                         // JM_AMD_DEC_VERBOSE: counters of a chain launch that gave up
     // decode a batch's pictures again with the stage kernels (a chain launch's wait gave up).  `later` = surfaces the lane's NEXT batch, which has
@@ -231,8 +221,8 @@ private:
     // another process has queues on this GPU (checked about once a second): no chain launches
     unsigned kfd_gpu_id_ = 0; std::atomic<bool> gpu_shared_{false}; std::atomic<long long> shared_checked_ns_{0};
     void look_for_other_users();                    // engine thread, no lock held
-    ihipStream_t *copy_stream_ = nullptr;           // job-list uploads (Engine::upload); copy_streams_[0]
-    ihipStream_t *copy_streams_[4] = {nullptr, nullptr, nullptr, nullptr}; int n_copy_ = 2;     // upload k goes to stream k % n_copy_ (JM_AMD_DEC_COPY_STREAMS)
+    // job-list uploads (Engine::upload): upload k goes to stream k % n_copy_ (JM_AMD_DEC_COPY_STREAMS)
+    ihipStream_t *copy_streams_[4] = {nullptr, nullptr, nullptr, nullptr}; int n_copy_ = 2;
     std::mutex um_; unsigned long long upload_seq_ = 0;
     Lane lanes_[kLanes];
     std::mutex m_; std::condition_variable cv_;

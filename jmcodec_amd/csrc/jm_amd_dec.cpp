@@ -38,6 +38,20 @@ template <class F> static int guarded(jm_amddec_handle h, F &&f) {
     return -1;
 }
 
+// The stand-alone *_device entry points run ONE job of an output kernel: upload it, launch(d_job, stream), wait for the stream, free it.
+// 0, -1 (no memory for the job) or minus the HIP error the launch left
+template <class Job, class Launch> static int run_one_job(const Job &job, void *stream, Launch &&launch) {
+    Job *d_job = nullptr;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hipMalloc((void **)&d_job, sizeof job) != hipSuccess) return -1;
+    hipMemcpyAsync(d_job, &job, sizeof job, hipMemcpyHostToDevice, st);
+    launch(d_job, st);
+    hipError_t e = hipGetLastError();
+    hipStreamSynchronize(st);
+    hipFree(d_job);
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
 extern "C" {
 
 __attribute__((visibility("default"))) jm_amddec_handle jm_amddec_create_handle(void) { return new Decoder(); }
@@ -98,15 +112,7 @@ __attribute__((visibility("default"))) int jm_amddec_i420_to_nv12_device(const v
 }
 __attribute__((visibility("default"))) int jm_amddec_packout_device(const void *src, int pitch, int w, int hgt, int fmt, void *dst, void *stream) {
     jmamd::PackJob job{static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), pitch, pitch * hgt, w, hgt, fmt, 0};
-    jmamd::PackJob *d_job = nullptr;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipMalloc((void **)&d_job, sizeof job) != hipSuccess) return -1;
-    hipMemcpyAsync(d_job, &job, sizeof job, hipMemcpyHostToDevice, st);
-    jmamd::launch_packout(d_job, 1, w, hgt, st);
-    hipError_t e = hipGetLastError();
-    hipStreamSynchronize(st);
-    hipFree(d_job);
-    return e == hipSuccess ? 0 : -(int)e;
+    return run_one_job(job, stream, [&](const jmamd::PackJob *d_job, hipStream_t st) { jmamd::launch_packout(d_job, 1, w, hgt, st); });
 }
 
 __attribute__((visibility("default"))) int jm_amddec_scale_taps(int src_len, int dst_len, int *first, short *weights, int max_taps) {
@@ -129,15 +135,10 @@ __attribute__((visibility("default"))) int jm_amddec_scale_device(const void *sr
     jmamd::ScaleJob job{static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), pitch, chroma_offset, crop_x, crop_y, tw, th, out_fmt, lone_field, {}};
     uint8_t *tables = nullptr;
     if (!jmamd::upload_scale_tables(crop_w, crop_h, tw, th, &tables, job.ax)) return -1;
-    jmamd::ScaleJob *d_job = nullptr;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipMalloc((void **)&d_job, sizeof job) != hipSuccess) { hipFree(tables); return -1; }
-    hipMemcpyAsync(d_job, &job, sizeof job, hipMemcpyHostToDevice, st);
-    jmamd::launch_scale_pack(d_job, 1, jmamd::scale_tiles(tw, th), st);
-    hipError_t e = hipGetLastError();
-    hipStreamSynchronize(st);
-    hipFree(d_job); hipFree(tables);
-    return e == hipSuccess ? 0 : -(int)e;
+    const int r = run_one_job(job, stream, [&](const jmamd::ScaleJob *d_job, hipStream_t st) {
+        jmamd::launch_scale_pack(d_job, 1, jmamd::scale_tiles(tw, th), st); });
+    hipFree(tables);
+    return r;
 }
 
 __attribute__((visibility("default"))) int jm_amddec_deinterlace_device(const void *src, int pitch, int chroma_offset, int w, int hgt, int mode, int keep_field,
@@ -148,15 +149,7 @@ __attribute__((visibility("default"))) int jm_amddec_deinterlace_device(const vo
     const int t = threshold ? threshold : 10;
     jmamd::DeintJob job{static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), pitch, chroma_offset, w, hgt, dst_pitch, dst_chroma_offset, 0, mode,
         keep_field - 1, 4 * t * t};
-    jmamd::DeintJob *d_job = nullptr;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipMalloc((void **)&d_job, sizeof job) != hipSuccess) return -1;
-    hipMemcpyAsync(d_job, &job, sizeof job, hipMemcpyHostToDevice, st);
-    jmamd::launch_deint(d_job, 1, jmamd::deint_items(w, hgt), st);
-    hipError_t e = hipGetLastError();
-    hipStreamSynchronize(st);
-    hipFree(d_job);
-    return e == hipSuccess ? 0 : -(int)e;
+    return run_one_job(job, stream, [&](const jmamd::DeintJob *d_job, hipStream_t st) { jmamd::launch_deint(d_job, 1, jmamd::deint_items(w, hgt), st); });
 }
 
 static_assert(sizeof(jm_amddec_rgb_spec) == sizeof(jmamd::RgbSpec) && offsetof(jm_amddec_rgb_spec, bias) == offsetof(jmamd::RgbSpec, bias),
@@ -185,15 +178,10 @@ __attribute__((visibility("default"))) int jm_amddec_rgb_device(const void *src,
     jmamd::fill_rgb_color(job, s, s.matrix, s.range == 2);
     uint8_t *tables = nullptr;
     if (!job.identity && !jmamd::upload_scale_tables(crop_w, crop_h, tw, th, &tables, job.s.ax)) return -1;
-    jmamd::RgbJob *d_job = nullptr;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipMalloc((void **)&d_job, sizeof job) != hipSuccess) { if (tables) hipFree(tables); return -1; }
-    hipMemcpyAsync(d_job, &job, sizeof job, hipMemcpyHostToDevice, st);
-    jmamd::launch_rgb_pack(d_job, 1, job.identity ? jmamd::rgb_tiles(tw, th) : 0, job.identity ? 0 : jmamd::rgb_tiles(tw, th), st);
-    hipError_t e = hipGetLastError();
-    hipStreamSynchronize(st);
-    hipFree(d_job); if (tables) hipFree(tables);
-    return e == hipSuccess ? 0 : -(int)e;
+    const int r = run_one_job(job, stream, [&](const jmamd::RgbJob *d_job, hipStream_t st) {
+        jmamd::launch_rgb_pack(d_job, 1, job.identity ? jmamd::rgb_tiles(tw, th) : 0, job.identity ? 0 : jmamd::rgb_tiles(tw, th), st); });
+    if (tables) hipFree(tables);
+    return r;
 }
 
 __attribute__((visibility("default"))) long jm_amddec_feed_annexb(const unsigned char *buf, long len, int passes, unsigned char *out, int out_cap,

@@ -12,7 +12,9 @@
 //   int16 coef[]            raw (un-scaled) levels, 16 per CODED 4x4 block
 // packed into one pinned buffer so that a single hipMemcpyAsync uploads it.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+#include <vector>
 
 namespace jmamd {
 
@@ -177,5 +179,17 @@ struct DeintJob {                 // one display frame to deinterlace (k_deint, 
 // (job.dst_pitch / dst_chroma_offset describe it) and entry `index` of the ScaleJob / RgbJob list beside it reads that surface -- the engine sets
 // job.dst and that job's src when it launches the batch
 struct DeintReq { DeintJob job; int feeds, index; };
+
+// host side: the display frames a picture puts out on ONE side of its decode kernels (before them: frames that show earlier pictures; after them), in the
+// order the decoder queued them -- the jobs per kernel (a frame has one, a deinterlaced frame of a scaled / RGB handle two) and every frame's output slot
+struct OutSlot;
+struct OutSide {
+    std::vector<PackJob> plain;       // k_packout
+    std::vector<ScaleJob> scale;      // k_scale_pack: handles with scaled / cropped output
+    std::vector<RgbJob> rgb;          // k_rgb_pack: handles with RGB output
+    std::vector<DeintReq> deint;      // k_deint: frames that are deinterlaced first, or -- plain handles -- deinterlaced and packed
+    std::vector<OutSlot *> slots;
+    size_t frames() const { size_t n = plain.size() + scale.size() + rgb.size(); for (auto &r : deint) n += r.feeds == 0; return n; }
+};
 
 }  // namespace jmamd

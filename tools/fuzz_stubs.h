@@ -1,11 +1,18 @@
 // tools/fuzz_stubs.h -- stand-ins for the kernel launchers (never reached in parse-only mode), so that the host sources link without the device objects;
-// included by the sanitizer harnesses (fuzz_host.cpp, fuzz_pushpull.cpp)
+// included by the sanitizer harnesses (fuzz_host.cpp, fuzz_pushpull.cpp) and by host_bench.cpp
 #pragma once
+#include <cstdlib>
 #include "../jmcodec_amd/csrc/kernels.h"
 namespace jmamd {
 bool deblock_lds_supported(int, int) { return true; }
 bool intra_lds_supported(int, int) { return true; }
 void launch_packout(const PackJob *, int, int, int, ihipStream_t *) { abort(); }
+int scale_tiles(int, int) { return 1; }
+void launch_scale_pack(const ScaleJob *, int, int, ihipStream_t *) { abort(); }
+int rgb_tiles(int, int) { return 1; }
+void launch_rgb_pack(const RgbJob *, int, int, int, ihipStream_t *) { abort(); }
+int deint_items(int, int) { return 1; }
+void launch_deint(const DeintJob *, int, int, ihipStream_t *) { abort(); }
 void launch_recon_inter(const PicParams *, int, int, bool, bool, int *, ihipStream_t *) { abort(); }
 void launch_intra_lds(const PicParams *, int, int, int *, int *, ihipStream_t *) { abort(); }
 void launch_recon_intra(const PicParams *, int, ihipStream_t *) { abort(); }
