@@ -124,14 +124,24 @@ int  jm_amddec_scale_device(const void *d_src, int pitch, int chroma_offset, int
  *   "deinterlace_field": 0 the field that is first in time (the smaller field order count; top on a tie or when there is one count only), 1 top,
  *     2 bottom.  A frame of which only one field was decoded is always interpolated from that field (bob), whatever the mode;
  *   "deinterlace_threshold": T of mode 2, 1..255 (0 = 10).
- * One frame per picture (no field-rate output).  Stats: "deint_frames", "interlaced_sequence" (0 / 1, the active SPS), "display_field:<n>" (output
- * frame n: 0 not deinterlaced, 1 top kept, 2 bottom kept), and with option "profile" k_deint_ns / _n / _pics / _alg_bytes.
+ *   "deinterlace_rate": 0 one frame per picture; 1 field rate -- every frame chosen for D leaves as TWO consecutive output frames, D with the
+ *     field "deinterlace_field" picks kept, then D with the other field kept (a lone field: one frame).  No effect while "deinterlace" is 0.  Each
+ *     decode / poll call still hands out one frame; the second of a pair is the next one.
+ * Stats: "deint_frames" (output frames that went through D), "field_rate_pairs", "interlaced_sequence" (0 / 1, the active SPS), "display_field:<n>"
+ * (output frame n: 0 not deinterlaced, 1 top kept, 2 bottom kept), "display_picture:<n>" (the display picture, index of "display_poc:<k>", that output
+ * frame n shows), "out_fps_num" / "out_fps_den" (fps_num / fps_den, the numerator doubled while a field-rate handle deinterlaces the active sequence),
+ * and with option "profile" k_deint_ns / _n / _pics / _alg_bytes (k_deint and k_deint2 together; a pair counts 2 frames and 3 / 2 of a frame's bytes).
  *   jm_amddec_deinterlace_device: stand-alone D on one pitch-linear NV12 surface in device memory (luma rows at `pitch`, the UV rows from byte
  *     chroma_offset; w x h even, h >= 4) into a pitch-linear NV12 surface (dst_pitch = w and dst_chroma_offset = w * h give a tight NV12 frame).
  *     mode 1 / 2, keep_field 1 top / 2 bottom, threshold 1..255 (0 = 10).  Source and destination must not overlap.  stream: a hipStream_t or
  *     NULL.  Returns 0, -1 for invalid arguments, or a negative hipError. */
 int  jm_amddec_deinterlace_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int mode, int keep_field, int threshold,
                                   void *d_dst, int dst_pitch, int dst_chroma_offset, void *stream);
+/*   jm_amddec_deinterlace2_device: both fields of one surface in one pass (k_deint2) -- d_dst_first gets D with first_field (1 top / 2 bottom) kept,
+ *     d_dst_second D with the other field kept, both in the destination layout above.  Arguments and returns as jm_amddec_deinterlace_device; in
+ *     addition the two destinations must not overlap each other and neither may overlap the source (-1). */
+int  jm_amddec_deinterlace2_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int mode, int first_field, int threshold,
+                                   void *d_dst_first, void *d_dst_second, int dst_pitch, int dst_chroma_offset, void *stream);
 /* RGB output (INTEGRATION.md "RGB output" defines the conversion C exactly).  A handle with an RGB spec hands out every display frame as
  * C(R_G(F)): three samples per pixel of the target size, planar (CHW) or interleaved (HWC), R,G,B or B,G,R order, u8 / f32 / f16 / bf16
  * (f16 and bf16 as their 16-bit patterns), frame bytes 3 * w * h * sizeof(sample).  matrix 0 / range 0 = from the stream's VUI (matrix: the VUI

@@ -66,6 +66,7 @@ def lib():
     L.jm_amddec_scale_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, vp, vp]
     L.jm_amddec_deinterlace_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
+    L.jm_amddec_deinterlace2_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp]
     L.jm_amddec_feed_annexb.argtypes = [cp, C.c_long, C.c_int, C.POINTER(C.c_ubyte), C.c_int, vp]
     L.jm_amddec_feed_annexb.restype = C.c_long
     L.jm_amddec_poll_frame.argtypes = [ip, vp]
@@ -169,6 +170,16 @@ def deinterlace_device(src, pitch, chroma_offset, width, height, mode, keep_fiel
     dp = width if dst_pitch is None else dst_pitch
     return lib().jm_amddec_deinterlace_device(src, pitch, chroma_offset, width, height, mode, keep_field, threshold, dst, dp,
                                               dp * height if dst_chroma_offset is None else dst_chroma_offset, stream)
+
+
+def deinterlace2_device(src, pitch, chroma_offset, width, height, mode, first_field, dst_first, dst_second, dst_pitch=None, dst_chroma_offset=None,
+                        threshold=0, stream=None):
+    """jm_amddec_deinterlace2_device: field-rate deinterlacing of one pitch-linear NV12 surface in one pass -- dst_first gets D with first_field
+    (1 top / 2 bottom) kept, dst_second D with the other field kept; both in deinterlace_device's destination layout.  The destinations must not
+    overlap each other or the source.  Returns 0 or < 0."""
+    dp = width if dst_pitch is None else dst_pitch
+    return lib().jm_amddec_deinterlace2_device(src, pitch, chroma_offset, width, height, mode, first_field, threshold, dst_first, dst_second, dp,
+                                               dp * height if dst_chroma_offset is None else dst_chroma_offset, stream)
 
 
 def scale_device(src, pitch, chroma_offset, width, height, crop, target, out_fmt, dst, lone_field=0, stream=None):

@@ -158,6 +158,10 @@ int Decoder::set_option(const char *key, long long v) {
         if (inited_ || v < 0 || v > hi) return -1;
         (k == "deinterlace" ? deint_mode_ : k == "deinterlace_when" ? deint_when_ : k == "deinterlace_field" ? deint_field_ : deint_thr_) = (int)v;
     }
+    else if (k == "deinterlace_rate") {      // 1: field rate -- two frames per deinterlaced picture (no effect while deinterlace is 0)
+        if (inited_ || v < 0 || v > 1) return -1;
+        deint_rate_ = (int)v;
+    }
     else if (k == "profile") { profile_ = v != 0; if (engine_) engine_->set_profile(profile_); }
     else if (k.rfind("chain_", 0) == 0 || k == "debug_stall" || k == "debug_no_bi" || k == "early_intra_ahead") {    // engine-wide knobs (every handle of the device), after init
         if (!engine_ || !engine_->set_knob(k, v)) return -1;
@@ -183,6 +187,7 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "rgb_frames") return stat_rgb_;
     // deinterlaced output: frames that went through D, whether the active SPS allows field pictures, and (below) display_field:<n>
     if (k == "deint_frames") return stat_deint_;
+    if (k == "field_rate_pairs") return stat_pairs_;         // display pictures handed out as two frames (option deinterlace_rate)
     if (k == "interlaced_sequence") return codec_ == 0 && seq_active_ && !seq_.frame_mbs_only ? 1 : 0;
     if (k == "out_frame_bytes") { std::lock_guard<std::mutex> lk(const_cast<std::mutex &>(mtx_));
         return (long long)(cur_out_ ? cur_out_->fbytes : !ready_.empty() ? ready_.front()->fbytes : frame_bytes_); }
@@ -215,6 +220,10 @@ long long Decoder::get_stat(const char *key) const {
     // frame rate of the active sequence as a fraction (VUI timing information; 0 / 0 when the stream carries none): H.264 counts FIELD ticks (E.2.1)
     if (k == "fps_num") return codec_ == 1 ? (long long)hsps_.time_scale : (long long)seq_.time_scale;
     if (k == "fps_den") return codec_ == 1 ? (long long)hsps_.num_units_in_tick : 2ll * seq_.num_units_in_tick;
+    // ... of the frames handed out: the numerator doubles while a field-rate handle deinterlaces the active sequence's frames
+    if (k == "out_fps_num") { const bool chosen = deint_when_ == 1 || (codec_ == 0 && seq_active_ && !seq_.frame_mbs_only);
+        return (field_rate() && chosen ? 2 : 1) * get_stat("fps_num"); }
+    if (k == "out_fps_den") return get_stat("fps_den");
     // display frames decided and not yet made current by a decode / poll call (finished or still on the device)
     if (k == "frames_done_unfetched") return (long long)frames_done_unfetched();
     if (k == "frames_waiting") { std::lock_guard<std::mutex> lk(const_cast<std::mutex &>(mtx_)); return (long long)ready_.size(); }
@@ -278,6 +287,10 @@ long long Decoder::get_stat(const char *key) const {
     }
     if (k.rfind("display_field:", 0) == 0) { size_t i = (size_t)atoll(k.c_str() + 14);
         return i < display_fields_.size() ? display_fields_[i] : (i < display_pocs_.size() ? 0 : -1); }
+    // the display picture (index of display_poc) that output frame n shows: the identity unless the handle is at field rate
+    if (k.rfind("display_picture:", 0) == 0) { size_t i = (size_t)atoll(k.c_str() + 16);
+        if (field_rate()) return i < display_pics_.size() ? (long long)display_pics_[i] : -1;
+        return i < display_pocs_.size() ? (long long)i : -1; }
     if (k.rfind("display_poc:", 0) == 0) { size_t i = (size_t)atoll(k.c_str() + 12); return i < display_pocs_.size() ? display_pocs_[i] : -1; }
     return -1;
 }
@@ -595,7 +608,8 @@ bool Decoder::gpu_alloc_sequence() {
         // an RGB frame is 2-8x an NV12 one and the handle keeps n_jobs_ + 4 output slots: at most 1 GiB of them (device staging + page-locked), at least
         // 8 job slots
         const size_t copies = (size_t)((!device_output_ && out_route_ != 1 && out_route_ != 3) ? 1 : 0) + ((out_via_copy_engine_ || device_output_) ? 1 : 0);
-        const long long fit = (long long)((1ull << 30) / std::max<size_t>(1, frame_bytes_ * copies)) - 4;
+        // (a field-rate handle keeps twice the population, below)
+        const long long fit = (long long)((1ull << 30) / std::max<size_t>(1, frame_bytes_ * copies)) / (field_rate() ? 2 : 1) - 4;
         n_jobs_ = (int)std::max(8ll, std::min((long long)n_jobs_, fit));
         display_delay_ = std::min(display_delay_, n_jobs_ - 4);
     }
@@ -654,7 +668,8 @@ bool Decoder::gpu_alloc_sequence() {
     {
         std::lock_guard<std::mutex> lk(mtx_);
         std::vector<OutSlot *> tmp;
-        for (int i = 0; i < n_jobs_ + 4; i++) tmp.push_back(alloc_out_slot());
+        // (field rate: a picture may leave as two frames)
+        for (int i = 0; i < (n_jobs_ + 4) * (field_rate() ? 2 : 1); i++) tmp.push_back(alloc_out_slot());
         for (OutSlot *o : tmp) free_out_.push_back(o);
     }
     return !failed_;
@@ -1643,23 +1658,32 @@ void Decoder::submit_ready() {
 // has one count only (HEVC) -- unless the option names one; a frame of which one field was decoded keeps that one.
 int Decoder::display_entry(int slot) {
     const DpbPic &d = dpb_[slot];
-    int field = 0;
+    int field = 0, both = 0;
     if (deint_mode_) {
         if (d.deint) field = d.lone ? d.lone : (deint_field_ ? deint_field_ : (codec_ == 0 && d.fpoc[1] < d.fpoc[0] ? 2 : 1));
         display_fields_.push_back((uint8_t)field);
+        // field rate: the frame leaves twice, the other field second (a lone field has no other one); bit 26 of the entry says so
+        both = deint_rate_ && field && !d.lone;
+        if (both) display_fields_.push_back((uint8_t)(3 - field));
+        if (deint_rate_) display_pics_.insert(display_pics_.end(), both ? 2 : 1, display_count_);
     }
-    return slot | d.lone << 8 | d.color << 16 | field << 24;
+    display_count_++;
+    return slot | d.lone << 8 | d.color << 16 | field << 24 | both << 26;
 }
 
 // a display frame leaves the DPB: reserve an output slot (display order) and describe the pack-out for the engine
 void Decoder::enqueue_output(int entry, OutSide &out) {
     // display_entry: bits 8..15 = the one field that was decoded, if only one was; bits 16..23 = the matrix and range of the picture's sequence;
     // bits 24.. = the field the deinterlacer keeps (0: the frame is not deinterlaced)
-    const int slot = entry & 255, color = (entry >> 16) & 255, field = entry >> 24;
+    const int slot = entry & 255, color = (entry >> 16) & 255, field = (entry >> 24) & 3, both = (entry >> 26) & 1;
     int lone = (entry >> 8) & 255;
-    OutSlot *o;
-    { std::lock_guard<std::mutex> lk(mtx_); o = alloc_out_slot(); ready_.push_back(o); num_frames_++; }   // nv_dec.cpp:48 num_frames++
-    if (parse_only_ || failed_) { std::lock_guard<std::mutex> lk(mtx_); o->ready = true; done_unfetched_++; if (field) stat_deint_++; return; }
+    // (a field-rate pair: two slots in display order, the frame that keeps `field` first)
+    OutSlot *o, *o2 = nullptr;
+    { std::lock_guard<std::mutex> lk(mtx_); o = alloc_out_slot(); ready_.push_back(o); num_frames_++;   // nv_dec.cpp:48 num_frames++
+      if (both) { o2 = alloc_out_slot(); ready_.push_back(o2); num_frames_++; } }
+    if (both) stat_pairs_++;
+    if (parse_only_ || failed_) { std::lock_guard<std::mutex> lk(mtx_); o->ready = true; done_unfetched_++; if (field) stat_deint_++;
+        if (both) { o2->ready = true; done_unfetched_++; stat_deint_++; } return; }
     // k_packout packs the tight frame into device staging and a copy engine moves it to the pinned slot -- or, in direct mode,
     // the kernel stores straight into the pinned host slot (see Engine::launch for why the copy engine is the default)
     // (a frame of which only one field was decoded is shown with that field's lines repeated: PackJob.lone_field)
@@ -1667,35 +1691,40 @@ void Decoder::enqueue_output(int entry, OutSide &out) {
     // (an RGB handle: k_rgb_pack crops, resamples and converts with the matrix and range of the sequence the picture was decoded in)
     // (a deinterlaced frame: k_deint writes D(F) -- the tight frame itself, or for a scaled / RGB handle a surface in the batch's scratch that the
     //  ScaleJob / RgbJob then reads instead of the picture (DeintReq: the engine fills in both addresses).  A lone field is bob from that field.)
+    // (a field-rate pair: ONE DeintReq with both destinations (k_deint2) and, for a scaled / RGB handle, two jobs of the same geometry and colour)
+    auto dst_of = [](OutSlot *s) { return s->dev ? s->dev : s->host; };
     const uint8_t *src = surf_[slot]; int src_chroma = chroma_off_;
     if (field) {
         const int t = deint_thr_ ? deint_thr_ : 10;
-        DeintReq r{DeintJob{surf_[slot], o->dev ? o->dev : o->host, pitch_, chroma_off_, disp_w_, disp_h_, disp_w_, disp_w_ * disp_h_, out_fmt_, lone ? 1 : deint_mode_,
-                            field - 1, 4 * t * t}, 0, 0};
+        DeintReq r{DeintJob{surf_[slot], dst_of(o), pitch_, chroma_off_, disp_w_, disp_h_, disp_w_, disp_w_ * disp_h_, out_fmt_, lone ? 1 : deint_mode_,
+                            field - 1, 4 * t * t, both ? dst_of(o2) : nullptr}, 0, 0, 0};
         if (rgb_ || scaled_) {
-            r.feeds = rgb_ ? 2 : 1; r.index = (int)(rgb_ ? out.rgb.size() : out.scale.size());
-            r.job.dst = nullptr; r.job.dst_pitch = pitch_; r.job.dst_chroma_offset = src_chroma = pitch_ * disp_h_; r.job.out_fmt = 0;
+            r.feeds = rgb_ ? 2 : 1; r.index = (int)(rgb_ ? out.rgb.size() : out.scale.size()); r.index2 = both ? r.index + 1 : 0;
+            r.job.dst = r.job.dst2 = nullptr; r.job.dst_pitch = pitch_; r.job.dst_chroma_offset = src_chroma = pitch_ * disp_h_; r.job.out_fmt = 0;
             src = nullptr; lone = 0;
         }
-        out.deint.push_back(r); stat_deint_++;
+        out.deint.push_back(r); stat_deint_ += both ? 2 : 1;
     }
-    if (rgb_) {
-        RgbJob rj = {};
-        rj.s = ScaleJob{src, o->dev ? o->dev : o->host, pitch_, src_chroma, crop_[0], crop_[1], out_w_, out_h_, 0, lone, {}};
-        for (int a = 0; a < 4; a++) rj.s.ax[a] = scale_ax_[a];
-        rj.identity = scaled_ ? 0 : 1;
-        fill_rgb_color(rj, rgb_spec_, color & 15, (color >> 4) == 2);
-        out.rgb.push_back(rj); stat_rgb_++;
-        if (scaled_) stat_scaled_++;
-    } else if (scaled_) {
-        ScaleJob sj{src, o->dev ? o->dev : o->host, pitch_, src_chroma, crop_[0], crop_[1], out_w_, out_h_, out_fmt_, lone, {}};
-        for (int a = 0; a < 4; a++) sj.ax[a] = scale_ax_[a];
-        out.scale.push_back(sj); stat_scaled_++;
-    } else if (!field) out.plain.push_back(PackJob{surf_[slot], o->dev ? o->dev : o->host, pitch_, chroma_off_, disp_w_, disp_h_, out_fmt_, lone});
-    out.slots.push_back(o);
-    o->has_data = true;
-    // route of this frame (see Decoder::init): fetch when the device's synchronous-copy queue is idle right now
-    o->fetch = o->dev && (!o->host || (out_route_ == 0 && engine_ && engine_->fetchers() < fetch_limit_));
+    for (OutSlot *s : {o, o2}) {
+        if (!s) continue;
+        if (rgb_) {
+            RgbJob rj = {};
+            rj.s = ScaleJob{src, dst_of(s), pitch_, src_chroma, crop_[0], crop_[1], out_w_, out_h_, 0, lone, {}};
+            for (int a = 0; a < 4; a++) rj.s.ax[a] = scale_ax_[a];
+            rj.identity = scaled_ ? 0 : 1;
+            fill_rgb_color(rj, rgb_spec_, color & 15, (color >> 4) == 2);
+            out.rgb.push_back(rj); stat_rgb_++;
+            if (scaled_) stat_scaled_++;
+        } else if (scaled_) {
+            ScaleJob sj{src, dst_of(s), pitch_, src_chroma, crop_[0], crop_[1], out_w_, out_h_, out_fmt_, lone, {}};
+            for (int a = 0; a < 4; a++) sj.ax[a] = scale_ax_[a];
+            out.scale.push_back(sj); stat_scaled_++;
+        } else if (!field) out.plain.push_back(PackJob{surf_[slot], dst_of(s), pitch_, chroma_off_, disp_w_, disp_h_, out_fmt_, lone});
+        out.slots.push_back(s);
+        s->has_data = true;
+        // route of this frame (see Decoder::init): fetch when the device's synchronous-copy queue is idle right now
+        s->fetch = s->dev && (!s->host || (out_route_ == 0 && engine_ && engine_->fetchers() < fetch_limit_));
+    }
 }
 
 void Decoder::submit_task(PicTask *t) {
@@ -1877,8 +1906,8 @@ int Decoder::decode(const uint8_t *buf, int len, int *got_frame) {
                 snprintf(fmt, sizeof fmt, "%s %s %s", rgb_spec_.bgr ? "BGR" : "RGB", rgb_spec_.planar ? "planar" : "interleaved", dt[rgb_spec_.dtype & 3]); }
             else snprintf(fmt, sizeof fmt, "%s", out_fmt_ == 0 ? "NV12" : "YV12");
             char deint[96] = "";                             // (only with option deinterlace: the text is the reference's otherwise)
-            if (deint_mode_) snprintf(deint, sizeof deint, "Deinterlace:\t%s, %s, %lld frames\n", deint_mode_ == 1 ? "bob" : "comb-adaptive",
-                deint_when_ ? "always" : "auto", (long long)stat_deint_);
+            if (deint_mode_) snprintf(deint, sizeof deint, "Deinterlace:\t%s, %s%s, %lld frames\n", deint_mode_ == 1 ? "bob" : "comb-adaptive",
+                deint_when_ ? "always" : "auto", deint_rate_ ? ", field rate" : "", (long long)stat_deint_);
             snprintf(info_, sizeof info_,
                      "==========================================\n"
                      "Codec:\t\t%s\n"

@@ -157,6 +157,7 @@ public:
     int  stream_info(int *w, int *h) const;
     void set_eof(bool e) { eof_flag_ = e; }
     bool is_exit() const { return is_exit_; }
+    bool field_rate() const { return deint_mode_ && deint_rate_; }     // options deinterlace + deinterlace_rate: a picture may leave as two frames
     char *info() { return info_; }
     const char *last_error();
     int  set_option(const char *key, long long v);
@@ -258,7 +259,8 @@ private:
     std::atomic<long long> stat_rgb_{0};
     // deinterlaced output (options deinterlace*, before init): the frames chosen by deinterlace_when leave as C(R_G(D(F))), D through k_deint
     int deint_mode_ = 0, deint_when_ = 0, deint_field_ = 0, deint_thr_ = 0;      // (deint_thr_: T, 0 = 10)
-    std::atomic<long long> stat_deint_{0};
+    int deint_rate_ = 0;                       // option deinterlace_rate: 1 = field rate, a frame chosen for D leaves as D_f(F), D_f'(F) (k_deint2)
+    std::atomic<long long> stat_deint_{0}, stat_pairs_{0};
 
     // DPB / picture state (front end only)
     DpbPic dpb_[kMaxSurfaces];
@@ -334,6 +336,8 @@ private:
     long long stat_i_ = 0, stat_p_ = 0, stat_b_ = 0;
     std::vector<int> display_pocs_;            // diagnostic (get via stats)
     std::vector<uint8_t> display_fields_;      // per output frame: the kept field (display_entry); only filled with option deinterlace
+    std::vector<uint32_t> display_pics_;       // per output frame: the display picture it shows (display_entry); only filled at field rate
+    uint32_t display_count_ = 0;               // display pictures queued so far (display_entry calls)
     struct TraceRec { uint64_t seq; long long t_dispatch, t_parsed, t_submit0, t_submit1; int is_i; };
     std::vector<TraceRec> trace_; bool trace_on_ = false;
 };

@@ -152,6 +152,24 @@ __attribute__((visibility("default"))) int jm_amddec_deinterlace_device(const vo
     return run_one_job(job, stream, [&](const jmamd::DeintJob *d_job, hipStream_t st) { jmamd::launch_deint(d_job, 1, jmamd::deint_items(w, hgt), st); });
 }
 
+// both fields of one surface in one pass (k_deint2): D with first_field kept, then D with the other field kept
+__attribute__((visibility("default"))) int jm_amddec_deinterlace2_device(const void *src, int pitch, int chroma_offset, int w, int hgt, int mode, int first_field,
+    int threshold, void *dst_first, void *dst_second, int dst_pitch, int dst_chroma_offset, void *stream) {
+    if (!src || !dst_first || !dst_second || w <= 0 || hgt < 4 || ((w | hgt) & 1) || pitch < w || dst_pitch < w) return -1;
+    if ((mode != 1 && mode != 2) || (first_field != 1 && first_field != 2) || threshold < 0 || threshold > 255) return -1;
+    if (chroma_offset < 0 || dst_chroma_offset < 0) return -1;
+    {   // the two destinations must not overlap each other, and neither may overlap the source (every row is read after rows of both were written)
+        const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)chroma_offset + (size_t)pitch * (hgt / 2 - 1) + w;
+        const size_t dn = (size_t)dst_chroma_offset + (size_t)dst_pitch * (hgt / 2 - 1) + w;
+        const uintptr_t a0 = (uintptr_t)dst_first, a1 = a0 + dn, b0 = (uintptr_t)dst_second, b1 = b0 + dn;
+        if ((a0 < b1 && b0 < a1) || (a0 < s1 && s0 < a1) || (b0 < s1 && s0 < b1)) return -1;
+    }
+    const int t = threshold ? threshold : 10;
+    jmamd::DeintJob job{static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst_first), pitch, chroma_offset, w, hgt, dst_pitch, dst_chroma_offset, 0, mode,
+        first_field - 1, 4 * t * t, static_cast<uint8_t *>(dst_second)};
+    return run_one_job(job, stream, [&](const jmamd::DeintJob *d_job, hipStream_t st) { jmamd::launch_deint2(d_job, 1, jmamd::deint2_items(w, hgt), st); });
+}
+
 static_assert(sizeof(jm_amddec_rgb_spec) == sizeof(jmamd::RgbSpec) && offsetof(jm_amddec_rgb_spec, bias) == offsetof(jmamd::RgbSpec, bias),
               "RgbSpec restates jm_amddec_rgb_spec");
 __attribute__((visibility("default"))) int jm_amddec_set_rgb(jm_amddec_handle h, const jm_amddec_rgb_spec *spec) {
@@ -198,9 +216,11 @@ __attribute__((visibility("default"))) long jm_amddec_feed_annexb(const unsigned
             const long b = starts[k], e = k + 1 < starts.size() ? starts[k + 1] : len;
             int got = 0;
             if (guarded(h, [&] { return D(h)->decode(buf + b, (int)(e - b), &got); }) != 0) return -2;
-            if (got == 1) {
+            // (a field-rate handle puts out up to two frames per picture: one more look, so that finished frames do not pile up behind the input)
+            for (int take = 0; got == 1 && take < (D(h)->field_rate() ? 2 : 1); take++) {
                 if (out) { int n = out_cap; if (D(h)->output(out, &n) > 0) frames++; }
                 else { void *dev = nullptr; int n = 0; if (D(h)->output_device(&dev, &n) > 0) frames++; }
+                if (take == 0 && D(h)->field_rate() && guarded(h, [&] { return D(h)->poll(&got); }) != 0) return -2;
             }
         }
     return frames;

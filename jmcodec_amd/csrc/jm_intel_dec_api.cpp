@@ -155,7 +155,7 @@ JM_EXPORT char *jm_amdintel_info(jm_amdintel_handle h) { return h ? jm_amddec_sh
 JM_EXPORT int jm_amdintel_get_stream_info(int *w, int *hh, float *fps, jm_amdintel_handle h) {
     if (!h || !w || !hh) return -1;
     if (fps) {
-        const long long num = jm_amddec_get_stat(C(h)->dec, "fps_num"), den = jm_amddec_get_stat(C(h)->dec, "fps_den");
+        const long long num = jm_amddec_get_stat(C(h)->dec, "out_fps_num"), den = jm_amddec_get_stat(C(h)->dec, "out_fps_den");   // (of the frames handed out: field rate doubles it)
         *fps = num > 0 && den > 0 ? (float)((double)num / (double)den) : 0.0f;
     }
     return jm_amddec_stream_info(w, hh, C(h)->dec);

@@ -174,14 +174,17 @@ struct DeintJob {                 // one display frame to deinterlace (k_deint, 
     int mode;                     // 1 bob, 2 comb-adaptive (a lone field: 1)
     int parity;                   // the kept rows: 0 top field, 1 bottom field
     int thr;                      // 4 * T * T
+    uint8_t *dst2;                // field rate (k_deint2): D with the OTHER parity kept goes here, in dst's layout; nullptr = one output
 };
 // host side: a DeintJob on its way to the engine.  feeds 0: job.dst is the frame's output slot; 1 / 2: D(F) goes to a surface in the batch's scratch
 // (job.dst_pitch / dst_chroma_offset describe it) and entry `index` of the ScaleJob / RgbJob list beside it reads that surface -- the engine sets
-// job.dst and that job's src when it launches the batch
-struct DeintReq { DeintJob job; int feeds, index; };
+// job.dst and that job's src when it launches the batch.  A field-rate pair has two destinations: feeds 0: job.dst2 is the second frame's output slot;
+// 1 / 2: index2 (never 0: the second job follows the first) names the ScaleJob / RgbJob that reads the second scratch surface
+struct DeintReq { DeintJob job; int feeds, index, index2;
+    bool pair() const { return feeds ? index2 != 0 : job.dst2 != nullptr; } };
 
 // host side: the display frames a picture puts out on ONE side of its decode kernels (before them: frames that show earlier pictures; after them), in the
-// order the decoder queued them -- the jobs per kernel (a frame has one, a deinterlaced frame of a scaled / RGB handle two) and every frame's output slot
+// order the decoder queued them -- the jobs per kernel (a frame has one, a deinterlaced frame of a scaled / RGB handle two; a field-rate pair is two frames behind one k_deint job) and every frame's output slot
 struct OutSlot;
 struct OutSide {
     std::vector<PackJob> plain;       // k_packout
@@ -189,7 +192,7 @@ struct OutSide {
     std::vector<RgbJob> rgb;          // k_rgb_pack: handles with RGB output
     std::vector<DeintReq> deint;      // k_deint: frames that are deinterlaced first, or -- plain handles -- deinterlaced and packed
     std::vector<OutSlot *> slots;
-    size_t frames() const { size_t n = plain.size() + scale.size() + rgb.size(); for (auto &r : deint) n += r.feeds == 0; return n; }
+    size_t frames() const { size_t n = plain.size() + scale.size() + rgb.size(); for (auto &r : deint) if (r.feeds == 0) n += r.pair() ? 2 : 1; return n; }
 };
 
 }  // namespace jmamd

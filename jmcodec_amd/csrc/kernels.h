@@ -44,6 +44,10 @@ void launch_rgb_pack(const RgbJob *d_jobs, int n, int identity_tiles, int scaled
 // pitch-linear NV12 surface -> D(F), as NV12 at the job's pitch or as a tight I420 frame (k_deint); max_items: the largest deint_items() of the jobs
 int  deint_items(int w, int h);
 void launch_deint(const DeintJob *d_jobs, int n, int max_items, hipStream_t st);
+// the same table through k_deint2: jobs with a second destination (DeintJob::dst2) put out both parities in one pass, the others are k_deint's work;
+// max_items: the largest deint_items() / deint2_items() of the jobs
+int  deint2_items(int w, int h);
+void launch_deint2(const DeintJob *d_jobs, int n, int max_items, hipStream_t st);
 // tight I420 (fmt 1) / NV12 (fmt 0) frame in device memory -> ARGB32 in device memory
 void launch_frame_to_argb(const uint8_t *d_src, int w, int h, int fmt, uint8_t *d_dst, int dst_pitch, hipStream_t st);
 // tight I420 / NV12 -> pitch NV12 (encoder input)

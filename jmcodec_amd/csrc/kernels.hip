@@ -16,6 +16,7 @@
 #include "kernel_common.h"
 #include "recon_device.h"      // ResTile, mb_residual_to_lds, luma_sample, recon_inter_wave (shared with chain.hip)
 #include "deint_packed.h"      // deint_strip (k_deint)
+#include "deint2_packed.h"     // deint2_strip (k_deint2)
 
 namespace jmamd {
 
@@ -916,6 +917,31 @@ __global__ __launch_bounds__(256) void k_deint(const DeintJob *jobs) {
 int deint_items(int w, int h) { return dei::frame_items(w, h); }
 void launch_deint(const DeintJob *d_jobs, int n, int max_items, hipStream_t st) {
     if (n > 0 && max_items > 0) hipLaunchKernelGGL(k_deint, dim3((max_items + 255) / 256, n), dim3(256), 0, st, d_jobs);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_deint2: field-rate deinterlacing (option deinterlace_rate, deint2_packed.h).  A job with a second destination puts out D with its parity kept (dst)
+// AND D with the other parity kept (dst2) from one walk over the surface: a lane owns a 16-byte column chunk and 8 output rows, loads its 10 source rows
+// once and stores 16.  A job without a second destination is k_deint's work, item by item (the branch is uniform per workgroup), so one launch serves a
+// side that mixes both; a side without pairs is launched as k_deint.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_deint2(const DeintJob *jobs) {
+    const DeintJob jb = jobs[blockIdx.y];
+    const dei::gbyte *src = (const dei::gbyte *)jb.src; dei::gbyte *dst = (dei::gbyte *)jb.dst, *dst2 = (dei::gbyte *)jb.dst2;
+    if (!dst2) {
+        const int total = dei::frame_items(jb.width, jb.height);
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
+            dei::deint_item(src, dst, jb.pitch, jb.chroma_offset, jb.width, jb.height, jb.dst_pitch, jb.dst_chroma_offset, jb.out_fmt, jb.mode, jb.parity, jb.thr, i);
+        return;
+    }
+    const int total = dei::frame2_items(jb.width, jb.height);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
+        dei::deint2_item(src, jb.parity ? dst2 : dst, jb.parity ? dst : dst2, jb.pitch, jb.chroma_offset, jb.width, jb.height, jb.dst_pitch, jb.dst_chroma_offset,
+                         jb.out_fmt, jb.mode, jb.thr, i);
+}
+int deint2_items(int w, int h) { return dei::frame2_items(w, h); }
+void launch_deint2(const DeintJob *d_jobs, int n, int max_items, hipStream_t st) {
+    if (n > 0 && max_items > 0) hipLaunchKernelGGL(k_deint2, dim3((max_items + 255) / 256, n), dim3(256), 0, st, d_jobs);
 }
 
 void launch_packout(const PackJob *d_jobs, int n, int max_width, int max_height, hipStream_t st) {

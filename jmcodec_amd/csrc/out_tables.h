@@ -5,7 +5,9 @@
 // after side at 2 * kMaxBatch; entries are in picture order and, within a picture, in the order the decoder queued them.  The launch grids are maxima over
 // BOTH sides (one figure per kernel and batch).  A deinterlaced frame of a scaled / RGB handle passes through a surface in the batch's scratch: k_deint
 // writes it, the ScaleJob / RgbJob at DeintReq::index of the same picture and side reads it; surfaces are handed out in the order of the add() calls, each
-// rounded up to 256 bytes.
+// rounded up to 256 bytes.  A field-rate pair (DeintReq::pair) is ONE entry of k_deint's table with two destinations and, for a scaled / RGB handle, two
+// scratch surfaces (first field first) read by the jobs at DeintReq::index and index2; it counts as two frames.  pairs[side] says whether a side holds one
+// (the engine then launches the table through k_deint2).
 // Host code, header-only, no HIP: the tables' memory is the caller's.  tests/test_out_tables.py checks the layout against a restatement of these rules.
 #pragma once
 #include "jobs.h"
@@ -33,24 +35,24 @@ struct OutTables {
     JobTable<PackJob> plain; JobTable<ScaleJob> scale; JobTable<RgbJob> rgb; JobTable<DeintJob> deint;
     template <class F> void each(F &&f) { f(plain); f(scale); f(rgb); f(deint); }
     // grids: k_packout's frame size (over the pictures with a plain job), launch_scale_pack's tiles, launch_rgb_pack's (identity / resampled jobs), launch_deint's
-    int max_w = 0, max_h = 0, s_tiles = 0, r_tiles[2] = {0, 0}, d_items = 0;
+    int max_w = 0, max_h = 0, s_tiles = 0, r_tiles[2] = {0, 0}, d_items = 0, pairs[2] = {0, 0};
     // profiling sums: frames and their algorithmic bytes -- of every output kernel together, of k_rgb_pack alone, of k_deint alone
     long long alg_pack = 0, alg_rgb = 0, alg_deint = 0; int n_frames = 0, n_rgb = 0, n_deint = 0;
     uint8_t *scratch = nullptr; size_t scratch_used = 0;
 
     static size_t scratch_bytes(const DeintJob &j) { return ((size_t)j.dst_pitch * j.height * 3 / 2 + 255) & ~(size_t)255; }
     // scratch the frames of one side of a picture need (the caller adds up its batch and grows the allocation before reset())
-    static size_t bytes_needed(const OutSide &o) { size_t n = 0; for (auto &r : o.deint) if (r.feeds) n += scratch_bytes(r.job); return n; }
+    static size_t bytes_needed(const OutSide &o) { size_t n = 0; for (auto &r : o.deint) if (r.feeds) n += scratch_bytes(r.job) * (r.pair() ? 2 : 1); return n; }
     bool any(int side) const { return plain.n[side] || scale.n[side] || rgb.n[side] || deint.n[side]; }
 
     void reset(uint8_t *scratch_base) {
         each([](auto &t) { t.n[0] = t.n[1] = 0; });
-        max_w = max_h = s_tiles = r_tiles[0] = r_tiles[1] = d_items = 0;
+        max_w = max_h = s_tiles = r_tiles[0] = r_tiles[1] = d_items = pairs[0] = pairs[1] = 0;
         alg_pack = alg_rgb = alg_deint = 0; n_frames = n_rgb = n_deint = 0;
         scratch = scratch_base; scratch_used = 0;
     }
     // The frames of one side of one picture; pictures in batch order, a picture's before side first.  disp_w / disp_h: the picture's display size;
-    // pack_bytes / deint_bytes: algorithmic bytes of one of its frames in a pack kernel / in k_deint.  false: a frame needed scratch and there is none
+    // pack_bytes / deint_bytes: algorithmic bytes of one of its frames in a pack kernel / in k_deint (a pair: 3 / 2 of it).  false: a frame needed scratch and there is none
     // (scratch_base was null) -- its k_deint job is left out and its ScaleJob / RgbJob reads the picture's surface instead; the caller fails the handle.
     bool add(const OutSide &o, int side, int disp_w, int disp_h, long long pack_bytes, long long deint_bytes) {
         ScaleJob *s0 = scale.h(side) + scale.n[side]; RgbJob *r0 = rgb.h(side) + rgb.n[side];       // this picture's first entries
@@ -61,13 +63,19 @@ struct OutTables {
         bool ok = true;
         for (auto &r : o.deint) {
             DeintJob j = r.job;
+            const bool pair = r.pair();
             if (r.feeds) {
                 const uint8_t *&src = r.feeds == 1 ? s0[r.index].src : r0[r.index].s.src;
-                if (!scratch) { src = j.src; ok = false; continue; }
+                const uint8_t *&src2 = r.feeds == 1 ? s0[pair ? r.index2 : r.index].src : r0[pair ? r.index2 : r.index].s.src;
+                if (!scratch) { src = src2 = j.src; ok = false; continue; }
                 j.dst = scratch + scratch_used; src = j.dst; scratch_used += scratch_bytes(j);
+                if (pair) { j.dst2 = scratch + scratch_used; src2 = j.dst2; scratch_used += scratch_bytes(j); }
             }
-            deint.h(side)[deint.n[side]++] = j; d_items = std::max(d_items, deint_items(j.width, j.height));
-            alg_deint += deint_bytes; n_deint++;
+            deint.h(side)[deint.n[side]++] = j;
+            d_items = std::max(d_items, deint_items(j.width, j.height));        // (a pair has no more items than a frame: the grid covers it)
+            // (a pair reads the surface once and writes two frames: 3 S against a frame's 2 S)
+            if (pair) { pairs[side]++; alg_deint += deint_bytes * 3 / 2; n_deint += 2; }
+            else { alg_deint += deint_bytes; n_deint++; }
         }
         const int f = (int)o.frames(), nr = (int)o.rgb.size();
         alg_pack += pack_bytes * f; n_frames += f; alg_rgb += pack_bytes * nr; n_rgb += nr;

@@ -4,7 +4,11 @@ the twins is identical: the streams are progressive), the twins alternated in on
 `hbm` frames left in device memory, `scaled` 960x540 fetched, `rgb` planar u8 RGB fetched.  One JSON line per leg, twin and round -- with the
 engine's profile counters: k_deint and all pack-out kernels, microseconds per frame and GB/s -- then a summary line per leg.
 
-    python tools/deint_output_bench.py [--streams 32] [--frames 60] [--passes 2] [--rounds 3] [--mode 2] [--legs host,hbm,scaled,rgb]
+    python tools/deint_output_bench.py [--streams 32] [--frames 60] [--passes 2] [--rounds 3] [--mode 2] [--rate 0] [--legs host,hbm,scaled,rgb]
+
+--rate 1 compares field rate with frame rate instead: the twins are deinterlace = MODE with deinterlace_rate = 0 and with deinterlace_rate = 1.
+Frames per second count OUTPUT frames (a field-rate handle puts out two per picture; `pictures_per_s` is the decode rate), and the pair counters
+are printed: `field_rate_pairs` and k_deint's microseconds per pair.
 
 The twin's k_packout time per frame is its `pack_us_per_frame` on the `host` / `hbm` legs (k_packout is the only pack-out kernel there); launch
 counts: run one leg under rocprofv3 --kernel-trace --stats."""
@@ -26,7 +30,7 @@ LEGS = {"host": dict(), "hbm": dict(device=True), "scaled": dict(target=(960, 54
 COUNTERS = ("k_deint_ns", "k_deint_pics", "k_deint_alg_bytes", "k_deint_n", "k_packout_ns", "k_packout_pics", "k_packout_n")
 
 
-def run_leg(L, datas, leg, mode, passes, parse_only=False):
+def run_leg(L, datas, leg, mode, passes, parse_only=False, rate=0):
     """One twin of one leg: fresh handles, one warm-up pass, then `passes` timed passes of every stream on its own thread."""
     S = len(datas)
     cfg = LEGS[leg]
@@ -43,7 +47,7 @@ def run_leg(L, datas, leg, mode, passes, parse_only=False):
         if cfg.get("target"):
             opts.update(target_width=tw, target_height=th)
         if mode:
-            opts.update(deinterlace=mode, deinterlace_when=1)
+            opts.update(deinterlace=mode, deinterlace_when=1, deinterlace_rate=rate)
         for k, v in opts.items():
             assert L.jm_amddec_set_option(h, k.encode(), v) == 0, k
         if cfg.get("rgb"):
@@ -63,7 +67,7 @@ def run_leg(L, datas, leg, mode, passes, parse_only=False):
         if k < 0:
             raise SystemExit("feed failed: " + L.jm_amddec_last_error(hs[i]).decode())
         # drain as bench.py does: access-unit delimiters close the last picture, then take what is finished
-        for step in range(66):
+        for step in range(66 * (2 if rate else 1)):
             if step == 2:
                 L.jm_amddec_set_option(hs[i], b"wait_idle", 1)
             L.jm_amddec_decode_frame(C.cast(C.c_char_p(aud), C.c_void_p), len(aud), C.byref(got), hs[i])
@@ -95,16 +99,23 @@ def run_leg(L, datas, leg, mode, passes, parse_only=False):
     dt = time.perf_counter() - t0
     c1 = counters()
     d = {k: c1[k] - c0[k] for k in COUNTERS}
-    deint_frames = 0
+    deint_frames = pairs = 0
     for h in hs:
         assert L.jm_amddec_get_stat(h, b"errors") == 0
         deint_frames += L.jm_amddec_get_stat(h, b"deint_frames")
+        pairs += max(0, L.jm_amddec_get_stat(h, b"field_rate_pairs"))
         api.jm_nvdec_deinit(h)
     n = sum(counts)
-    res = {"leg": leg, "deinterlace": mode, "frames": n, "seconds": round(dt, 3), "frames_per_s": round(n / dt, 1), "deint_frames": deint_frames}
+    res = {"leg": leg, "deinterlace": mode, "rate": rate, "frames": n, "seconds": round(dt, 3), "frames_per_s": round(n / dt, 1),
+           "deint_frames": deint_frames, "field_rate_pairs": pairs}
+    if rate:
+        # (the handles' counters include the warm-up pass; the timed passes hold passes / (passes + 1) of the pairs)
+        res["pictures_per_s"] = round(n / 2 / dt, 1)
     if d["k_deint_pics"] > 0:
         res.update(deint_us_per_frame=round(d["k_deint_ns"] / 1e3 / d["k_deint_pics"], 3), deint_launches=d["k_deint_n"],
                    deint_gb_per_s=round(d["k_deint_alg_bytes"] / max(1, d["k_deint_ns"]), 1))
+        if rate:
+            res["deint_us_per_pair"] = round(2 * d["k_deint_ns"] / 1e3 / d["k_deint_pics"], 3)       # (k_deint_pics counts a pair as two frames)
     if d["k_packout_pics"] > 0:
         # (every pack-out kernel of the launch points, k_deint included when it runs there)
         res.update(pack_us_per_frame=round(d["k_packout_ns"] / 1e3 / d["k_packout_pics"], 3), pack_launches=d["k_packout_n"])
@@ -118,6 +129,7 @@ def main():
     ap.add_argument("--passes", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--mode", type=int, default=2, choices=[1, 2])
+    ap.add_argument("--rate", type=int, default=0, choices=[0, 1], help="1: the twins are frame rate and field rate of the same mode")
     ap.add_argument("--legs", default="host,hbm,scaled,rgb")
     ap.add_argument("--parse-only", action="store_true", help="host half only (no GPU): checks the tool itself, the numbers mean nothing")
     args = ap.parse_args()
@@ -126,24 +138,33 @@ def main():
     L = api.lib()
     with ThreadPoolExecutor(16) as ex:
         datas = list(ex.map(lambda i: streams.generate(**streams.config_c1(stream_id=i, frames=args.frames)), range(args.streams)))
-    fps = {(l, m): [] for l in legs for m in (0, args.mode)}
+    # the twins of a leg as (deinterlace, deinterlace_rate): plain against deinterlaced, or -- --rate 1 -- frame rate against field rate
+    twins = [(args.mode, 0), (args.mode, 1)] if args.rate else [(0, 0), (args.mode, 0)]
+    fps = {(l, t): [] for l in legs for t in twins}
     last = {}
     for r in range(args.rounds):
         for leg in legs:
-            for mode in (0, args.mode):
-                res = run_leg(L, datas, leg, mode, args.passes, args.parse_only)
+            for t in twins:
+                res = run_leg(L, datas, leg, t[0], args.passes, args.parse_only, t[1])
                 res["round"] = r
-                fps[(leg, mode)].append(res["frames_per_s"])
-                last[(leg, mode)] = res
+                fps[(leg, t)].append(res["frames_per_s"])
+                last[(leg, t)] = res
                 print(json.dumps(res), flush=True)
     for leg in legs:
-        med = {m: sorted(fps[(leg, m)])[len(fps[(leg, m)]) // 2] for m in (0, args.mode)}
-        out = {"summary": True, "leg": leg, "streams": args.streams, "median_plain_fps": med[0], "median_deint_fps": med[args.mode],
-               "ratio": round(med[args.mode] / med[0], 3) if med[0] else None}
-        a, b = last[(leg, args.mode)], last[(leg, 0)]
-        if "deint_us_per_frame" in a and "pack_us_per_frame" in b:
-            out.update(deint_us_per_frame=a["deint_us_per_frame"], twin_pack_us_per_frame=b["pack_us_per_frame"],
-                       deint_over_twin_pack=round(a["deint_us_per_frame"] / b["pack_us_per_frame"], 3))
+        med = {t: sorted(fps[(leg, t)])[len(fps[(leg, t)]) // 2] for t in twins}
+        b, a = last[(leg, twins[0])], last[(leg, twins[1])]
+        if args.rate:
+            out = {"summary": True, "leg": leg, "streams": args.streams, "median_frame_rate_fps": med[twins[0]], "median_field_rate_fps": med[twins[1]],
+                   "ratio": round(med[twins[1]] / med[twins[0]], 3) if med[twins[0]] else None}
+            if "deint_us_per_pair" in a and "deint_us_per_frame" in b:
+                out.update(deint_us_per_pair=a["deint_us_per_pair"], twin_deint_us_per_frame=b["deint_us_per_frame"],
+                           pair_over_two_frames=round(a["deint_us_per_pair"] / (2 * b["deint_us_per_frame"]), 3))
+        else:
+            out = {"summary": True, "leg": leg, "streams": args.streams, "median_plain_fps": med[twins[0]], "median_deint_fps": med[twins[1]],
+                   "ratio": round(med[twins[1]] / med[twins[0]], 3) if med[twins[0]] else None}
+            if "deint_us_per_frame" in a and "pack_us_per_frame" in b:
+                out.update(deint_us_per_frame=a["deint_us_per_frame"], twin_pack_us_per_frame=b["pack_us_per_frame"],
+                           deint_over_twin_pack=round(a["deint_us_per_frame"] / b["pack_us_per_frame"], 3))
         print(json.dumps(out), flush=True)
 
 
