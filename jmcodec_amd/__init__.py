@@ -22,4 +22,5 @@ from .api import (  # noqa: F401
     lib,
     lib_path,
     split_nalus,
+    split_jpegs,
 )

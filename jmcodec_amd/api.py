@@ -278,6 +278,53 @@ def split_nalus(data):
     return out
 
 
+def split_jpegs(data):
+    """Split a byte stream of concatenated JPEG pictures (MJPEG, codec_type 2) into one chunk per picture, SOI .. EOI.  Segments are walked by their
+    length fields, so an APPn segment that embeds a thumbnail's SOI / EOI stays inside its picture; entropy-coded data ends at the first marker that
+    is neither a stuffed FF 00 nor RSTn.  Bytes between pictures go with the picture in front of them; a last picture without EOI is its own chunk.
+    (The decoder itself accepts any chunking: this is a convenience for callers that want one picture per call.)"""
+    data = bytes(data)
+    n, cuts, o = len(data), [], data.find(b"\xff\xd8")
+    while 0 <= o < n:
+        cuts.append(o)
+        o += 2
+        while o < n:                                        # one picture: marker segments, then entropy-coded data, until EOI
+            if data[o] != 0xFF:
+                o += 1
+                continue
+            while o < n and data[o] == 0xFF:
+                o += 1
+            if o >= n:
+                break
+            m = data[o]
+            o += 1
+            if m == 0xD9:
+                break
+            if m == 0xD8:                                   # a picture that never ended
+                o -= 2
+                break
+            if m == 0 or m == 1 or 0xD0 <= m <= 0xD7 or o + 2 > n:
+                continue
+            ln = data[o] << 8 | data[o + 1]
+            if ln < 2:
+                continue
+            o += ln
+            if m == 0xDA:
+                while o < n:
+                    o = data.find(b"\xff", o)
+                    if o < 0 or o + 1 >= n:
+                        o = n
+                    elif data[o + 1] == 0 or 0xD0 <= data[o + 1] <= 0xD7:
+                        o += 2
+                        continue
+                    break
+        o = data.find(b"\xff\xd8", o)
+    if not cuts:
+        return [data] if data else []
+    cuts[0] = 0
+    return [data[a:b] for a, b in zip(cuts, cuts[1:] + [n])]
+
+
 def annexb_to_avcc(data, length_size=4):
     """(avcC record, [length-prefixed packets]) of an Annex-B stream: what a demuxer hands test_player for an MP4 source when no
     h264_mp4toannexb filter is in the way (test_player.cpp:221-226).  One packet per access unit (split before each first slice)."""

@@ -204,6 +204,10 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "job_regrown") return stat_job_regrown_;          // job slots grown on demand (a few per handle, then none)
     if (k == "job_slot_bytes") { long long n = 0; for (auto &j : jobs_) n += (long long)j.cap; return n; }   // page-locked job memory of this handle right now
     if (k == "errors") return stat_errors_;
+    // MJPEG: pictures dispatched, the active sequence's sampling (0x22 / 0x21 / 0x11, 0x10 = grey), pictures that came with a restart interval
+    if (k == "jpeg_pictures") return stat_jpeg_pics_;
+    if (k == "jpeg_sampling") return codec_ == 2 && seq_active_ ? j_sampling_ : 0;
+    if (k == "jpeg_restart_intervals") return stat_jpeg_ri_;
     if (k == "copy_engines") return copier_ ? (long long)copier_->engine_mask() : 0;      // SDMA engines the direct route uses (bit mask)
     if (k == "direct_frames") return stat_direct_;
     // ... and the time their callers spent waiting for them // frames that went out by the "direct" route (one DMA into the caller's registered buffer)
@@ -241,7 +245,7 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "wait_slot_ns") return stat_wait_slot_ns_;
     if (k == "parse_ns_p") return stat_parse_ns_p_;
     if (k.rfind("k_", 0) == 0 || k.rfind("eng_", 0) == 0) {          // engine-wide (all handles on this device), profile option
-        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint"};
+        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg"};
         if (!engine_) return 0;
         EngineStats es = engine_->stats();
         for (int i = 0; i < kKernelClasses; i++) {
@@ -299,7 +303,7 @@ long long Decoder::get_stat(const char *key) const {
 // MI355X-class device can be opened, because silently continuing would mean a CPU fallback.
 int Decoder::init(int codec_type, int out_fmt, const uint8_t *extra, int len) {
     codec_ = codec_type; out_fmt_ = out_fmt ? 1 : 0;
-    if (codec_type != 0 && codec_type != 1) { fail("only codec_type 0 (H.264) and 1 (HEVC) are implemented"); return -1; }
+    if (codec_type != 0 && codec_type != 1 && codec_type != 2) { fail("only codec_type 0 (H.264), 1 (HEVC) and 2 (MJPEG) are implemented"); return -1; }
     if (getenv("JM_AMD_DEC_SYNC")) sync_mode_ = true;
     if (const char *js = getenv("JM_AMD_DEC_JOB_SLOTS")) { n_jobs_ = std::max(8, std::min(atoi(js), kMaxJobSlots)); n_jobs_set_ = true; }
     if (const char *dd = getenv("JM_AMD_DEC_DISPLAY_DELAY")) display_delay_ = std::max(0, std::min(atoi(dd), n_jobs_ - 4));
@@ -603,7 +607,8 @@ bool Decoder::gpu_alloc_sequence() {
     job_cap_ = std::min(job_cap_max_, n_mbs * (sizeof(MbRec) + per_mb) + 256 * (sizeof(SliceRec) + 452) + 4096);
     if (getenv("JM_AMD_DEC_JOB_WORST_CASE")) job_cap_ = job_cap_max_;
     if (codec_ == 1) job_cap_ = n_mbs * 128 + (1u << 20);            // HEVC job lists vary a lot in size: start small, grow on demand (ensure_job_cap)
-    if (!n_jobs_set_) n_jobs_ = codec_ == 0 && n_mbs <= 8704 ? kJobSlotsSmall : kJobSlots;      // (decoder.h)
+    if (codec_ == 2) job_cap_ = n_mbs * 160 + (1u << 16);            // MJPEG: 6 block records per macroblock + a typical share of levels; grown on demand too
+    if (!n_jobs_set_) n_jobs_ = codec_ == 2 ? kJpegJobSlots : codec_ == 0 && n_mbs <= 8704 ? kJobSlotsSmall : kJobSlots;      // (decoder.h)
     if (!n_jobs_set_ && rgb_ && !parse_only_) {
         // an RGB frame is 2-8x an NV12 one and the handle keeps n_jobs_ + 4 output slots: at most 1 GiB of them (device staging + page-locked), at least
         // 8 job slots
@@ -703,6 +708,7 @@ OutSlot *Decoder::alloc_out_slot() {   // mtx_ held
 // front end: Annex-B splitting (replaces the NAL scanning half of cuvidParseVideoData, nv_dec.cpp:394)
 // =============================================================================================
 void Decoder::feed(const uint8_t *buf, size_t len) {
+    if (codec_ == 2) { jpeg_feed(buf, len); return; }      // concatenated JPEG pictures, cut anywhere (jpeg_decoder.cpp)
     if (avcc_len_size_ && !have_start_ && in_.empty()) {
         // avcC mode: a packet is a whole number of length-prefixed NAL units -- unless it starts with a start code (already converted)
         // (a 4-byte length of 256..511 reads 00 00 01 xx, so the first bytes alone cannot tell the two forms apart: the packet is
@@ -756,6 +762,7 @@ void Decoder::feed(const uint8_t *buf, size_t len) {
 
 // ENDOFSTREAM packet (nv_dec.cpp:389-392)
 void Decoder::flush_stream() {
+    if (codec_ == 2) jpeg_flush();
     if (have_start_) {
         size_t end = in_.size();
         while (end > nal_start_ && in_[end - 1] == 0) end--;
@@ -903,6 +910,7 @@ int Decoder::compute_poc(const SliceHeader &sh, DpbPic &store) {
 }
 
 void Decoder::flush_dpb(std::vector<int> &out) {
+    if (codec_ == 2) return;                       // (a JPEG picture is displayed by its own task: nothing waits)
     if (codec_ == 1) { for (int i = 0; i < n_surf_; i++) if (i != cur_) dpb_[i].ref = 0; hevc_bump(out, true, true);
         for (int i = 0; i < n_surf_; i++) if (i != cur_ && !dpb_[i].wait_output) dpb_[i].in_use = false; return; }
     if (pending_first_ >= 0) { const int pf = pending_first_; pending_first_ = -1; dpb_[pf].waiting_second = false; store_done(pf, out); }
@@ -1485,6 +1493,7 @@ void Decoder::push_task(std::unique_ptr<PicTask> t) {
 // =============================================================================================
 void Decoder::parse_task(PicTask *t, ParseScratch &scratch) {
     if (t->hevc) { hevc_parse_task(t); return; }
+    if (t->jpeg) { jpeg_parse_task(t); return; }
     auto pt0 = std::chrono::steady_clock::now();
     JobSlot &js = jobs_[t->job_slot];
     const int n_mbs = t->sps.mb_w * t->sps.mb_h;
@@ -1735,6 +1744,7 @@ void Decoder::submit_task(PicTask *t) {
     for (int s : t->out_before) { enqueue_output(s, ep.out[kBefore]); ep.out_mask |= 1u << (s & 255); }
     memset(&ep.pp, 0, sizeof ep.pp);
     if (ep.has_picture && t->hevc) hevc_fill_engine_pic(t, ep);
+    else if (ep.has_picture && t->jpeg) jpeg_fill_engine_pic(t, ep);
     else if (ep.has_picture) {
         JobSlot &js = jobs_[t->job_slot];
         const int n_mbs = t->sps.mb_w * t->sps.mb_h;
@@ -1918,7 +1928,7 @@ int Decoder::decode(const uint8_t *buf, int len, int *got_frame) {
                      "Elapsed Time:\t%d ms\n"
                      "Decode FPS:\t%f fps\n"
                      "==========================================\n",
-                     codec_ == 0 ? "H.264" : "H.265", out_w_, out_h_, fmt, deint, (int)num_frames_,
+                     codec_ == 0 ? "H.264" : (codec_ == 1 ? "H.265" : "MJPEG"), out_w_, out_h_, fmt, deint, (int)num_frames_,
                      (int)elapsed_ms_, elapsed_ms_ > 0 ? (double)num_frames_ * 1000.0 / elapsed_ms_ : 0.0);
         }
     }

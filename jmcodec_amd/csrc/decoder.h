@@ -10,6 +10,7 @@
 #include "h264_cavlc.h"
 #include "h264_syntax.h"
 #include "hevc_slice.h"
+#include "jpeg_syntax.h"
 #include "jobs.h"
 #include <atomic>
 #include <chrono>
@@ -30,6 +31,9 @@ constexpr int kJobSlots = 24;   // pictures in flight per handle (parse + device
 // costs ~0.85 ms plus ~0.1 ms per picture, so n decides its rate: 24 slots -> 6.8 pictures per launch, 4.5 k frames/s; 40 slots (and chains of up to 16) ->
 // 14.6 per launch, 6.6 k (profiles/r06_single_stream_slots.txt).  1.3 MB of page-locked memory per slot at 1080p Baseline
 constexpr int kJobSlotsSmall = 40;
+// MJPEG: pictures are independent and of one size, nothing like an I picture's parse has to hide behind a GOP; its surfaces are dealt round robin over
+// kJpegSurfaces > kJpegJobSlots (jpeg_decoder.cpp), so a handle never runs more job slots than this, whatever "job_slots" asks for
+constexpr int kJpegJobSlots = 16, kJpegSurfaces = 18;
 
 struct DpbPic {                                // one frame store (C.4.5): a frame, or the one or two field pictures of a frame
     bool in_use = false;
@@ -75,6 +79,9 @@ struct HevcTask {
     int n_pus = 0, n_tbs = 0, n_itbs = 0; bool any_sao = false, any_deblock = false;
 };
 
+// MJPEG picture (codec_type 2): its headers' snapshot, its entropy-coded bytes, and where the packed job list sits in the job buffer
+struct JpegTask { JpegPic pic; std::vector<uint8_t> data; size_t off_first = 0, off_count = 0, off_entries = 0; int n_entries = 0; };
+
 struct PicTask {
     uint64_t seq = 0;
     bool has_picture = false;
@@ -84,6 +91,7 @@ struct PicTask {
     SeqParams sps; PicParamSet pps;
     std::vector<SliceTask> slices;
     std::unique_ptr<HevcTask> hevc;            // codec_type 1
+    std::unique_ptr<JpegTask> jpeg;            // codec_type 2
     std::vector<int> out_before, out_after;    // frames to display before / after this picture (Decoder::display_entry)
     bool wait_prev_pack = false;               // current surface was displayed by the previous picture (no cooling slack)
     // written by the parse worker
@@ -220,6 +228,13 @@ private:
     void hevc_parse_task(PicTask *t);
     void hevc_fill_engine_pic(PicTask *t, struct EnginePic &ep);
     bool ensure_job_cap(JobSlot &js, size_t bytes, size_t keep = 0);
+    // ---- MJPEG front end (jpeg_decoder.cpp) ----
+    void jpeg_feed(const uint8_t *buf, size_t len);
+    void jpeg_flush();
+    void jpeg_handle_picture(const uint8_t *p, size_t n, bool truncated);
+    bool jpeg_activate(const JpegPic &pic);
+    void jpeg_parse_task(PicTask *t);
+    void jpeg_fill_engine_pic(PicTask *t, struct EnginePic &ep);
     void gpu_close();
     void submit_ready();
     void submit_task(PicTask *t);
@@ -338,6 +353,10 @@ private:
     std::vector<uint8_t> display_fields_;      // per output frame: the kept field (display_entry); only filled with option deinterlace
     std::vector<uint32_t> display_pics_;       // per output frame: the display picture it shows (display_entry); only filled at field rate
     uint32_t display_count_ = 0;               // display pictures queued so far (display_entry calls)
+    // MJPEG state (front end only unless noted)
+    JpegSplitter jsplit_; JpegTables jtab_;
+    int j_w_ = 0, j_h_ = 0, j_sampling_ = 0; unsigned j_surf_rr_ = 0;
+    std::atomic<long long> stat_jpeg_pics_{0}, stat_jpeg_ri_{0};
     struct TraceRec { uint64_t seq; long long t_dispatch, t_parsed, t_submit0, t_submit1; int is_i; };
     std::vector<TraceRec> trace_; bool trace_on_ = false;
 };

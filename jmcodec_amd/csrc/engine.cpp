@@ -446,7 +446,7 @@ bool Engine::form(Lane &ln, int lane_idx, Batch &b) {
             EngineDecoderState &es = d->engine_state();
             while (es.in_batch < kHevcWorkSets && (int)b.pics.size() < kMaxBatch) {
                 auto it = std::find_if(pending_.begin(), pending_.end(), [&](const EnginePic &p) { return p.dec == d; });
-                if (it == pending_.end() || !it->has_picture || it->codec != 1 || it->lane(false) != lane_idx || !it->before_empty() ||
+                if (it == pending_.end() || !it->has_picture || it->codec == 0 || it->lane(false) != lane_idx || !it->before_empty() ||
                     it->wait_prev_pack) break;
                 if ((it->ref_mask & es.batch_written) || ((1u << it->hp.cur) & (es.batch_written | es.batch_read)) ||
                     n_post + it->out[kAfter].frames() > (size_t)kOutSideCap) break;
@@ -475,7 +475,18 @@ void Engine::launch(Lane &ln, Batch &b) {
     }
     LANE_TRACE("launch lane %d batch %llu pics %d\n", li, b.serial, n);
     int max_mbs = 0, max_mb_h = 0, max_mb_w = 0, stages = 0;
-    bool wait_pack = false, any_hevc = false;
+    bool wait_pack = false, any_hevc = false, any_jpeg = false; int max_jpeg_items = 0;
+    for (auto &p : b.pics) any_jpeg |= p.codec == 2 && p.has_picture;
+    if (any_jpeg && !b.h_jpics) {       // first MJPEG picture this slot of the ring sees: its parameter table (the batch's earlier launch has retired)
+        if (hipHostMalloc((void **)&b.h_jpics, sizeof(JpegPicParams) * kMaxBatch, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc((void **)&b.d_jpics, sizeof(JpegPicParams) * kMaxBatch) != hipSuccess) {
+            (void)hipGetLastError();
+            if (b.h_jpics) hipHostFree(b.h_jpics);
+            b.h_jpics = nullptr; b.d_jpics = nullptr; any_jpeg = false;
+            for (auto &p : b.pics) if (p.codec == 2 && p.has_picture) { p.has_picture = false; p.dec->on_engine_error("hipMalloc(MJPEG parameter table) failed"); }
+        }
+    }
+    if (any_jpeg && profile_ && !b.jev[0]) for (auto &e : b.jev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
     HevcBatchDims hd;
     const EnginePic *last_upload[4] = {nullptr, nullptr, nullptr, nullptr};      // per copy stream (upload k went to stream k % n_copy_)
     b.pmask = 0;
@@ -492,8 +503,12 @@ void Engine::launch(Lane &ln, Batch &b) {
     b.out.reset(b.deint_scratch);
     for (int i = 0; i < n; i++) {
         EnginePic &p = b.pics[i];
-        const bool hevc = p.codec == 1;
+        const bool hevc = p.codec != 0;            // (an MJPEG picture sits in an HEVC batch as an entry without stages)
         if (hevc) { b.h_hpics[i] = p.hp; if (!p.has_picture) b.h_hpics[i].stages = 0; any_hevc = true; }
+        if (any_jpeg) {
+            if (p.codec == 2 && p.has_picture) { b.h_jpics[i] = p.jp; max_jpeg_items = std::max(max_jpeg_items, p.jp.n_items); b.alg[7] += p.jpeg_alg_bytes; b.npics[7]++; }
+            else b.h_jpics[i].n_items = 0;
+        }
         b.h_pics[i] = p.pp;
         if (!p.has_picture || hevc) b.h_pics[i].stages = 0;
         else if (b.any_chain && (p.chain_ok || p.chain_intra)) {
@@ -571,6 +586,7 @@ void Engine::launch(Lane &ln, Batch &b) {
         } }
     if (any_hevc) hipMemcpyAsync(b.d_hpics, b.h_hpics, sizeof(HevcPicParams) * n, hipMemcpyHostToDevice, ps);
     else hipMemcpyAsync(b.d_pics, b.h_pics, sizeof(PicParams) * n, hipMemcpyHostToDevice, ps);
+    if (any_jpeg) hipMemcpyAsync(b.d_jpics, b.h_jpics, sizeof(JpegPicParams) * n, hipMemcpyHostToDevice, ps);
     b.out.each([&](auto &t) { for (int side : {kBefore, kAfter}) if (t.n[side])
         hipMemcpyAsync(t.dev + side * kOutSideCap, t.h(side), sizeof(*t.host) * t.n[side], hipMemcpyHostToDevice, ps); });
     // job lists were copied on the (in-order) copy stream when the pictures were parsed: waiting for the most recently
@@ -599,6 +615,12 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (hd.any_intra) b.pmask |= 4;
         if (hd.any_deblock || hd.any_sao) b.pmask |= 8;
         b.last_ev = 4;
+    }
+    if (any_jpeg && max_jpeg_items > 0) {        // MJPEG pictures of the batch: independent of everything else in it
+        const bool timed = profile_ && b.jev[0] && b.jev[1];
+        if (timed) hipEventRecord(b.jev[0], st);
+        launch_jpeg_recon(b.d_jpics, n, max_jpeg_items, st);
+        if (timed) { hipEventRecord(b.jev[1], st); b.pmask |= 1024; }
     }
     b.any_bipred = b.any_field = false;
     for (auto &p : b.pics) { b.any_bipred |= p.has_picture && p.codec == 0 && p.bipred; b.any_field |= p.has_picture && p.codec == 0 && p.pp.field != 0; }
@@ -875,6 +897,7 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
         add(3, 0, 1, b.pmask & 1); add(0, 1, 2, b.pmask & 2); add(1, 2, 3, b.pmask & 4); add(2, 3, 4, b.pmask & 8); add(3, 5, 6, b.pmask & 16);
         add(4, 4, 7, b.pmask & 32); add(5, 10, 11, b.pmask & 64); add(5, 12, 13, b.pmask & 128);
         add(6, 14, 15, b.pmask & 256); add(6, 16, 17, b.pmask & 512);
+        if (b.pmask & 1024) { float ms = 0; if (hipEventElapsedTime(&ms, b.jev[0], b.jev[1]) == hipSuccess) { st_.ns[7] += ms * 1e6; st_.launches[7]++; } }
         for (int k = 0; k < kKernelClasses; k++) { st_.pics[k] += b.npics[k]; st_.alg_bytes[k] += b.alg[k]; }
         st_.batches++; st_.batch_pics += (long long)b.pics.size();
         // the lane's time line: how long this batch's kernels held the lane's stream, and how long the stream sat idle since the previous batch's last kernel

@@ -1,0 +1,140 @@
+// jmcodec_amd/csrc/jpeg_decoder.cpp -- the MJPEG half of jmamd::Decoder (codec_type 2 = NV_CODEC_MJPEG, nv_dec/nv_dec.h:37-46 of the reference).
+//
+// The input is any chunking of a byte stream of concatenated JPEG interchange pictures.  The caller thread reassembles pictures (JpegSplitter), reads
+// their headers (what is accepted, what fails the handle: INTEGRATION.md "MJPEG") and picks a surface; a parse worker runs the Huffman decode into the
+// sparse job list (jpeg_jobs.h); the engine runs k_jpeg_recon on the HEVC lane and packs the picture out behind it.  A picture has no references:
+// frames leave in decode order.  Job slots, output slots and the hand-over to the engine are shared with the other codecs (decoder.cpp).
+#include "decoder.h"
+#include "engine.h"
+#include "jpeg_jobs.h"
+#include <hip/hip_runtime_api.h>
+#include <algorithm>
+#include <cstring>
+
+namespace jmamd {
+
+// A surface is written by k_jpeg_recon and read by the pack-out behind it; the picture holds its job slot until both are done, pictures of a handle
+// complete in order (one lane), and at most kJpegJobSlots are in flight -- so handing surfaces out round robin over more of them than that never
+// meets one that is still in use.
+// (kJpegJobSlots = 16, kJpegSurfaces = 18: decoder.h)
+
+void Decoder::jpeg_feed(const uint8_t *buf, size_t len) {
+    jsplit_.feed(buf, len, [&](const uint8_t *p, size_t n, bool truncated) { if (!failed_) jpeg_handle_picture(p, n, truncated); });
+}
+
+// end of stream: a picture whose scan had begun is decoded as far as it goes (errors counts it)
+void Decoder::jpeg_flush() {
+    const bool dropped = jsplit_.flush([&](const uint8_t *p, size_t n, bool truncated) { if (!failed_) jpeg_handle_picture(p, n, truncated); });
+    if (dropped) { stat_errors_++; note_error("MJPEG: the stream ends inside a picture's headers"); }
+}
+
+bool Decoder::jpeg_activate(const JpegPic &pic) {
+    const bool changed = !seq_active_ || pic.width != j_w_ || pic.height != j_h_ || pic.sampling != j_sampling_;
+    // JFIF: BT.601 coefficients, full range
+    { const int vui[4] = {1, -1, -1, 6}; resolve_color(vui, pic.disp_h()); }
+    if (!changed) return true;
+    if (seq_active_) {
+        // a new size or sampling starts a new sequence, like an SPS change: drain everything that still refers to the old surfaces
+        auto t = std::make_unique<PicTask>();
+        t->out_before = std::move(carry_out_); carry_out_.clear();
+        push_task(std::move(t));
+        { std::unique_lock<std::mutex> lk(mtx_); cv_.wait(lk, [&] { return outstanding_ == 0 && parse_pending_ == 0; }); }
+        if (gpu_open_) { hipSetDevice(device_); free_surfaces(); free_job_buffers(); free_out_slots(false); }
+        else free_job_buffers();
+    }
+    j_w_ = pic.width; j_h_ = pic.height; j_sampling_ = pic.sampling;
+    disp_w_ = pic.disp_w(); disp_h_ = pic.disp_h();
+    mb_w_ = (disp_w_ + 15) / 16; mb_h_ = (disp_h_ + 15) / 16;
+    n_surf_ = kJpegSurfaces; extra_surf_ = 0; j_surf_rr_ = 0;
+    for (auto &d : dpb_) d = DpbPic();
+    // job slots: the caller's choice up to kJpegJobSlots, else gpu_alloc_sequence's (kJpegJobSlots, fewer where RGB output slots would pass 1 GiB)
+    if (n_jobs_set_) n_jobs_ = std::min(n_jobs_, kJpegJobSlots);
+    // (the surfaces are filled with 128 when they are allocated: a grey sequence never writes its chroma)
+    if (!gpu_alloc_sequence()) return false;
+    display_delay_ = std::min(display_delay_, n_jobs_ - 4);
+    seq_active_ = true;
+    if (!timer_started_) { t0_ = std::chrono::steady_clock::now(); timer_started_ = true; }
+    return true;
+}
+
+void Decoder::jpeg_handle_picture(const uint8_t *p, size_t n, bool truncated) {
+    auto jt = std::make_unique<JpegTask>();
+    bool refuse = false;
+    const std::string e = jpeg_parse_picture(p, n, jtab_, jt->pic, &refuse);
+    if (!e.empty()) { stat_errors_++; if (refuse) fail(e); else note_error(e); return; }
+    if (truncated) { stat_errors_++; note_error("MJPEG: the stream ends inside a picture"); }
+    if (!jpeg_activate(jt->pic)) return;
+    jt->data.assign(p + jt->pic.scan_off, p + jt->pic.scan_end);
+    jt->pic.scan_end -= jt->pic.scan_off; jt->pic.scan_off = 0;
+    const int slot = (int)(j_surf_rr_++ % (unsigned)n_surf_);
+    DpbPic &c = dpb_[slot];
+    c = DpbPic(); c.decode_idx = decode_count_; c.poc = decode_count_;
+    c.color = color_matrix_ | color_range_ << 4;
+    c.deint = deint_when_ == 1;                          // (a JPEG picture says nothing about interlace: deinterlaced only on request)
+    auto t = std::make_unique<PicTask>();
+    t->has_picture = true; t->cur_slot = slot;
+    t->out_before = std::move(carry_out_); carry_out_.clear();
+    t->out_after.push_back(display_entry(slot)); display_pocs_.push_back(decode_count_);
+    c.out_at = decode_count_;
+    decode_count_++;
+    stat_i_++; stat_jpeg_pics_++;
+    if (jt->pic.restart_interval) stat_jpeg_ri_++;
+    t->jpeg = std::move(jt);
+    first_sh_ = SliceHeader(); first_sh_.type = SL_I;
+    t->job_slot = acquire_job_slot();
+    push_task(std::move(t));
+}
+
+// worker: Huffman-decode one picture and pack its job list
+void Decoder::jpeg_parse_task(PicTask *t) {
+    auto pt0 = std::chrono::steady_clock::now();
+    JpegTask &jt = *t->jpeg;
+    JobSlot &js = jobs_[t->job_slot];
+    static thread_local JpegJobs jobs;
+    const std::string e = jpeg_decode_scan(jt.pic, jt.data.data(), jt.data.size(), jobs);
+    if (!e.empty()) { t->error = e; stat_errors_++; note_error(e); }
+    std::vector<uint8_t>().swap(jt.data);
+    size_t off = 0;
+    auto place = [&](size_t bytes) { size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
+    jt.off_first = place(jobs.first.size() * 4); jt.off_count = place(jobs.count.size()); jt.off_entries = place(jobs.entries.size() * 4);
+    jt.n_entries = (int)jobs.entries.size();
+    t->n_slices = 1;
+    if (!ensure_job_cap(js, off + 64)) fail("job buffer allocation failed");
+    else {
+        if (!jobs.first.empty()) memcpy(js.host + jt.off_first, jobs.first.data(), jobs.first.size() * 4);
+        if (!jobs.count.empty()) memcpy(js.host + jt.off_count, jobs.count.data(), jobs.count.size());
+        if (!jobs.entries.empty()) memcpy(js.host + jt.off_entries, jobs.entries.data(), jobs.entries.size() * 4);
+        t->upload_bytes = off;
+        if (want_job_digest_) { uint64_t h = job_digest_; for (size_t i = 0; i < off; i++) { h ^= js.host[i]; h *= 1099511628211ull; } job_digest_ = h; }
+        stat_pictures_++; stat_job_bytes_ += (long long)off; stat_coef_ += (long long)jobs.entries.size();
+        if (!parse_only_ && !failed_) t->upload_seq = engine_->upload(js.dev, js.host, off, js.uploaded, false);
+    }
+    stat_parse_ns_i_ += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - pt0).count();
+    t->state.store(1, std::memory_order_release);
+    submit_ready();
+    { std::lock_guard<std::mutex> lk(mtx_); parse_pending_--; cv_.notify_all(); }
+}
+
+// describe the picture to the device engine (called by submit_task)
+void Decoder::jpeg_fill_engine_pic(PicTask *t, EnginePic &ep) {
+    const JpegTask &jt = *t->jpeg;
+    JobSlot &js = jobs_[t->job_slot];
+    ep.codec = 2; ep.uploaded = js.uploaded; ep.upload_seq = t->upload_seq;
+    memset(&ep.hp, 0, sizeof ep.hp);
+    ep.hp.cur = t->cur_slot;                             // (the engine's surface bookkeeping reads the slot here for every codec but H.264)
+    JpegPicParams &jp = ep.jp;
+    memset(&jp, 0, sizeof jp);
+    jp.surf = surf_[t->cur_slot]; jp.pitch = pitch_; jp.chroma_offset = chroma_off_;
+    jp.coded_w = mb_w_ * 16; jp.coded_h = mb_h_ * 16;
+    jp.sampling = jt.pic.sampling;
+    jp.y_bw = jt.pic.y_bw; jp.y_bh = jt.pic.y_bh; jp.c_bw = jt.pic.c_bw; jp.c_bh = jt.pic.c_bh;
+    jp.n_items_y = ((jp.y_bw + 7) / 8) * jp.y_bh;
+    jp.n_items = jp.n_items_y + ((jp.c_bw + 3) / 4) * jp.c_bh;
+    jp.n_blocks = jt.pic.n_blocks(); jp.n_entries = jt.n_entries;
+    jp.first = (const uint32_t *)(js.dev + jt.off_first); jp.count = js.dev + jt.off_count; jp.entries = (const uint32_t *)(js.dev + jt.off_entries);
+    memcpy(jp.q, jt.pic.q, sizeof jp.q);
+    // algorithmic bytes: the job list in, 1.5 W H out
+    ep.jpeg_alg_bytes = (long long)t->upload_bytes + (long long)disp_w_ * disp_h_ * 3 / 2;
+}
+
+}  // namespace jmamd

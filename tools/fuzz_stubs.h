@@ -34,7 +34,9 @@ void launch_deblock(const PicParams *, int, ihipStream_t *) { abort(); }
 namespace jmamd { void launch_frame_to_argb(const uint8_t *, int, int, int, uint8_t *, int, ihipStream_t *) { abort(); }
 void launch_frame_to_nv12_pitch(const uint8_t *, int, int, int, uint8_t *, int, ihipStream_t *) { abort(); } }
 #include "../jmcodec_amd/csrc/hevc_kernels.h"
+#include "../jmcodec_amd/csrc/jpeg_jobs.h"
 namespace jmamd {
 void launch_hevc_picture_batch(const HevcPicParams *, int, const HevcBatchDims &, int *, ihipStream_t *, ihipEvent_t **) { abort(); }
+void launch_jpeg_recon(const JpegPicParams *, int, int, ihipStream_t *) { abort(); }
 void hevc_kernels_init() {}
 }
