@@ -454,34 +454,6 @@ void Decoder::gpu_close() {
 }
 
 // ---- scaled / cropped output (INTEGRATION.md "Scaled and cropped output": the resampler R_G) ----
-int build_scale_taps(int S, int D, std::vector<int32_t> &first, std::vector<int16_t> &w) {
-    if (S <= 0 || D <= 0 || (long long)S > 8ll * D || (long long)D > 4ll * S) return -1;
-    const long long s = S, d = D;
-    int taps = 2;                                         // D >= S: bilinear, half-sample centres
-    if (D < S) { taps = 0; for (long long j = 0; j < d; j++) taps = std::max(taps, (int)(((j + 1) * s + d - 1) / d - j * s / d)); }    // area average
-    first.assign((size_t)D, 0);
-    w.assign((size_t)D * taps, 0);
-    for (long long j = 0; j < d; j++) {
-        int16_t *wj = &w[(size_t)j * taps];
-        if (D >= S) {
-            const long long num = (2 * j + 1) * s - d, d2 = 2 * d;
-            const long long i0 = num >= 0 ? num / d2 : -((-num + d2 - 1) / d2);     // floor division
-            const long long w1 = ((num - d2 * i0) * 16384 + d) / d2;
-            first[j] = (int32_t)i0; wj[0] = (int16_t)(16384 - w1); wj[1] = (int16_t)w1;
-        } else {
-            const long long lo = j * s / d, hi = ((j + 1) * s + d - 1) / d;          // source samples lo .. hi - 1 overlap output j
-            long long sum = 0, best = 0; int bk = 0;
-            for (long long i = lo; i < hi; i++) {
-                const long long a = std::min((i + 1) * d, (j + 1) * s) - std::max(i * d, j * s);   // overlap; they sum to S
-                wj[i - lo] = (int16_t)(a * 16384 / s); sum += wj[i - lo];
-                if (a > best) { best = a; bk = (int)(i - lo); }
-            }
-            first[j] = (int32_t)lo; wj[bk] = (int16_t)(wj[bk] + 16384 - sum);      // the rounding remainder to the first largest overlap
-        }
-    }
-    return taps;
-}
-
 bool upload_scale_tables(int w, int h, int tw, int th, uint8_t **dev, ScaleAxis ax[4]) {
     const int S[4] = {w, h, w / 2, h / 2}, D[4] = {tw, th, tw / 2, th / 2};
     std::vector<int32_t> first[4]; std::vector<int16_t> wt[4];

@@ -12,6 +12,7 @@
 #include "hevc_slice.h"
 #include "jpeg_syntax.h"
 #include "jobs.h"
+#include "scale_packed.h"    // build_scale_taps
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -132,10 +133,7 @@ struct OutSlot {                       // one display frame in pinned host memor
 
 class HostCopier;
 
-// Scaled / cropped output: the tap table of one axis of the resampler R_G, S source samples -> D output samples.
-// first[j] = first source index of output j (not clamped), w[j * taps + k] = weight of source index first[j] + k (1/16384; they sum to 16384).
-// Returns taps (the same for every output; unused taps weigh 0), or -1 when S, D are not positive or the ratio is outside 1/8 .. 4.
-int build_scale_taps(int S, int D, std::vector<int32_t> &first, std::vector<int16_t> &w);
+// Scaled / cropped output: build_scale_taps (scale_packed.h) makes the tap table of one axis of the resampler R_G;
 // the four tables of a geometry (crop w x h -> target tw x th: luma x, luma y, chroma x, chroma y) in ONE device allocation *dev (the caller
 // frees it); ax[] points into it.  Synchronous (activation time).  false: invalid sizes or a failed allocation.
 bool upload_scale_tables(int w, int h, int tw, int th, uint8_t **dev, ScaleAxis ax[4]);

@@ -1,4 +1,4 @@
-// jmcodec_amd/csrc/deint2_packed.h -- field-rate deinterlacing: D_0(F) and D_1(F) of one surface in one pass (k_deint2, kernels.hip).
+// jmcodec_amd/csrc/deint2_packed.h -- field-rate deinterlacing: D_0(F) and D_1(F) of one surface in one pass (k_deint2, out_kernels.hip).
 //
 // With option deinterlace_rate = 1 a display frame F leaves as two frames, D with the top rows kept and D with the bottom rows kept (INTEGRATION.md
 // "Deinterlaced output").  Every row of F is a kept row of one of them and a missing row of the other, so both come out of ONE walk over the plane:

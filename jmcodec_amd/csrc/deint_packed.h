@@ -1,4 +1,4 @@
-// jmcodec_amd/csrc/deint_packed.h -- the deinterlacer D of INTEGRATION.md "Deinterlaced output" on 16-byte column chunks (k_deint, kernels.hip).
+// jmcodec_amd/csrc/deint_packed.h -- the deinterlacer D of INTEGRATION.md "Deinterlaced output" on 16-byte column chunks (k_deint, out_kernels.hip).
 //
 // D keeps the rows of one parity and rebuilds the others, plane by plane: mode 1 (bob) writes the rounded average i of the kept rows above and below,
 // mode 2 (comb-adaptive) writes i only where the woven sample is combed, M = s[x-1] + 2 s[x] + s[x+1] > 4 T^2 with s = (up - cur) * (dn - cur).

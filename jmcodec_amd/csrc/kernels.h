@@ -1,4 +1,4 @@
-// jmcodec_amd/csrc/kernels.h -- host-callable launchers of the gfx950 kernels (kernels.hip, intra_lds.hip, deblock_lds.hip).
+// jmcodec_amd/csrc/kernels.h -- host-callable launchers of the gfx950 kernels (kernels.hip, out_kernels.hip, intra_lds.hip, deblock_lds.hip).
 // Every launch processes a BATCH: d_pics / d_jobs are device arrays, blockIdx.y selects the picture; a picture takes part in a
 // kernel only if the matching PS_* bit is set in PicParams::stages.
 #pragma once

@@ -1,22 +1,17 @@
-// jmcodec_amd/csrc/kernels.hip -- gfx950 reconstruction kernels of the jm_amd_dec backend.
+// jmcodec_amd/csrc/kernels.hip -- gfx950 reconstruction kernels of the jm_amd_dec backend (H.264, one launch per stage).
 //
 // Together these kernels are the device half of what the reference delegates to the NVDEC ASIC
-// through cuvidDecodePicture (/root/reference/nv_dec/nv_dec.cpp:33-41) plus the host repack of
-// jm_nvdec_output_frame (nv_dec.cpp:750-828):
+// through cuvidDecodePicture (/root/reference/nv_dec/nv_dec.cpp:33-41):
 //   k_recon_inter   sub-pel motion compensation + dequant/inverse transform + I_PCM   (fully parallel)
 //   k_recon_intra   Intra4x4 / Intra16x16 / chroma intra prediction + residual        (MB wavefront)
 //   k_deblock       in-loop deblocking filter, clause 8.7 order                        (MB wavefront)
-//   k_packout       pitch NV12 surface -> tight NV12 / I420 display frame              (fully parallel)
-//   k_scale_pack    ... cropped and resampled;  k_rgb_pack  ... and converted to RGB   (fully parallel)
-// All arithmetic is 8-bit integer pixel work: HBM/LDS bound, no MFMA.
+// All arithmetic is 8-bit integer pixel work: HBM/LDS bound, no MFMA.  The output kernels (k_packout and what follows it) are in out_kernels.hip.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "jobs.h"
 #include "kernels.h"
 #include "kernel_common.h"
 #include "recon_device.h"      // ResTile, mb_residual_to_lds, luma_sample, recon_inter_wave (shared with chain.hip)
-#include "deint_packed.h"      // deint_strip (k_deint)
-#include "deint2_packed.h"     // deint2_strip (k_deint2)
 
 namespace jmamd {
 
@@ -509,50 +504,6 @@ __global__ __launch_bounds__(kWaves * 64) void k_deblock(const PicParams *pics) 
 }
 
 // ------------------------------------------------------------------------------------------
-// k_packout: restates jm_nvdec_output_frame (nv_dec.cpp:782-820) on the device.
-// out_fmt 0: tight NV12; out_fmt 1: Y plane, U plane, V plane ("YV12" in the reference's words, I420 order).
-// One thread moves 16 source bytes.
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_packout(const PackJob *jobs) {
-    const PackJob jb = jobs[blockIdx.y];
-    const uint8_t *src = jb.src; uint8_t *dst = jb.dst;
-    const int pitch = jb.pitch, chroma_offset = jb.chroma_offset, width = jb.width, height = jb.height, out_fmt = jb.out_fmt;
-    int chunks_per_row = (width + 15) >> 4;
-    int luma_chunks = chunks_per_row * height;
-    int h2 = height >> 1, w2 = width >> 1;
-    int total = luma_chunks + chunks_per_row * h2;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        bool chroma = i >= luma_chunks;
-        int j = chroma ? i - luma_chunks : i;
-        int row = j / chunks_per_row, x = (j % chunks_per_row) * 16;
-        // (a frame of which only one field was decoded: every row shows the line of that parity of its line pair)
-        const int srow = jb.lone_field ? ((row & ~1) | (jb.lone_field - 1)) : row;
-        const uint8_t *s = src + (chroma ? chroma_offset : 0) + (size_t)srow * pitch + x;
-        int n = width - x < 16 ? width - x : 16;
-        if (!chroma || out_fmt == 0) {
-            uint8_t *d = dst + (chroma ? (size_t)width * height : 0) + (size_t)row * width + x;
-            if (n == 16 && ((((uintptr_t)d) & 15) == 0)) *(uint4 *)d = *(const uint4 *)s;
-            else for (int k = 0; k < n; k++) d[k] = s[k];
-        } else {
-            uint8_t *du = dst + (size_t)width * height + (size_t)row * w2 + (x >> 1);
-            uint8_t *dv = du + (size_t)w2 * h2;
-            if (n == 16 && ((((uintptr_t)du) & 7) == 0) && ((((uintptr_t)dv) & 7) == 0)) {
-                uint4 v = *(const uint4 *)s;
-                uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                uint32_t u[2], vv[2];
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    uint32_t a = w[2 * k], b = w[2 * k + 1];
-                    u[k] = (a & 0xff) | ((a >> 8) & 0xff00) | ((b & 0xff) << 16) | ((b << 8) & 0xff000000u);
-                    vv[k] = ((a >> 8) & 0xff) | ((a >> 16) & 0xff00) | ((b << 8) & 0xff0000) | (b & 0xff000000u);
-                }
-                *(uint2 *)du = make_uint2(u[0], u[1]); *(uint2 *)dv = make_uint2(vv[0], vv[1]);
-            } else for (int k = 0; k < n / 2; k++) { du[k] = s[2 * k]; dv[k] = s[2 * k + 1]; }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
 // launchers: d_pics / d_jobs are device arrays of n entries; max_* size the grid for the largest picture
 // ------------------------------------------------------------------------------------------
 void launch_recon_inter(const PicParams *d_pics, int n, int max_mbs, bool any_bipred, bool any_field, int *d_err, hipStream_t st) {
@@ -567,393 +518,5 @@ void launch_recon_inter(const PicParams *d_pics, int n, int max_mbs, bool any_bi
 void launch_recon_intra(const PicParams *d_pics, int n, hipStream_t st) { hipLaunchKernelGGL(k_recon_intra, dim3(1, n), dim3(kIntraWaves * 64), 0, st, d_pics);
     }
 void launch_deblock(const PicParams *d_pics, int n, hipStream_t st) { hipLaunchKernelGGL(k_deblock, dim3(1, n), dim3(kWaves * 64), 0, st, d_pics); }
-// Tight I420 / NV12 frame -> 32-bit ARGB (bytes B, G, R, A), BT.601 limited range, the conversion the reference left behind
-// "#if 0" (nv_dec.h:98-107, nv_dec.cpp:244-265).  One thread per pixel pair.
-__global__ __launch_bounds__(256) void k_frame_to_argb(const uint8_t *src, int w, int h, int fmt, uint8_t *dst, int dst_pitch) {
-    int x2 = (blockIdx.x * 256 + threadIdx.x) * 2, y = blockIdx.y;
-    if (x2 >= w || y >= h) return;
-    const uint8_t *Y = src + (size_t)y * w + x2;
-    int u, v;
-    if (fmt == 0) { const uint8_t *c = src + (size_t)w * h + (size_t)(y >> 1) * w + (x2 & ~1); u = c[0]; v = c[1]; }
-    else { int cw = w >> 1; const uint8_t *pu = src + (size_t)w * h + (size_t)(y >> 1) * cw + (x2 >> 1); u = pu[0]; v = pu[(size_t)cw * (h >> 1)]; }
-    int d = u - 128, e = v - 128;
-    uint32_t *o = (uint32_t *)(dst + (size_t)y * dst_pitch) + x2;
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        if (x2 + k >= w) break;
-        int c = 298 * (Y[k] - 16) + 128;
-        int r = clip1((c + 409 * e) >> 8), g = clip1((c - 100 * d - 208 * e) >> 8), b = clip1((c + 516 * d) >> 8);
-        o[k] = 0xFF000000u | ((uint32_t)r << 16) | ((uint32_t)g << 8) | (uint32_t)b;
-    }
-}
-void launch_frame_to_argb(const uint8_t *d_src, int w, int h, int fmt, uint8_t *d_dst, int dst_pitch, hipStream_t st) {
-    hipLaunchKernelGGL(k_frame_to_argb, dim3((w / 2 + 255) / 256, h), dim3(256), 0, st, d_src, w, h, fmt, d_dst, dst_pitch);
-}
-
-// SURVEY 8f f4 -- the encoder-side pre-processing of the reference as a HIP kernel: tight I420 (or tight NV12) frame -> pitch-linear NV12
-// surface, i.e. the cuMemcpy2D of the luma plane plus the "InterleaveUV" kernel of /root/reference/nv_enc/nv_enc.cpp:1022-1079 (arguments
-// U, V, dst chroma, chroma width / height, source strides, dst stride) in one launch, device to device.  It is the inverse of k_packout.
-// One thread per 4 output bytes of a row (luma rows first, then the h/2 interleaved chroma rows).
-__global__ __launch_bounds__(256) void k_frame_to_nv12_pitch(const uint8_t *src, int w, int h, int fmt, uint8_t *dst, int pitch) {
-    const int x = (blockIdx.x * 256 + threadIdx.x) * 4, row = blockIdx.y;
-    if (x >= w) return;
-    uint8_t *o = dst + (size_t)row * pitch + x;
-    uint8_t v[4];
-    if (row < h || fmt == 0) {                                   // luma row, or an already interleaved chroma row: plain copy
-        const uint8_t *i = src + (size_t)row * w + x;
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = x + k < w ? i[k] : 0;
-    } else {                                                     // chroma row r: bytes 2c, 2c+1 = U[r][c], V[r][c]
-        const int cw = w >> 1, r = row - h;
-        const uint8_t *pu = src + (size_t)w * h + (size_t)r * cw, *pv = pu + (size_t)cw * (h >> 1);
-#pragma unroll
-        for (int k = 0; k < 4; k++) { const int c = (x + k) >> 1; v[k] = x + k < w ? (((x + k) & 1) ? pv[c] : pu[c]) : 0; }
-    }
-    if (x + 4 <= w && !(pitch & 3)) *(uint32_t *)o = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
-    else for (int k = 0; k < 4 && x + k < w; k++) o[k] = v[k];
-}
-void launch_frame_to_nv12_pitch(const uint8_t *d_src, int w, int h, int fmt, uint8_t *d_dst, int pitch, hipStream_t st) {
-    hipLaunchKernelGGL(k_frame_to_nv12_pitch, dim3(((w + 3) / 4 + 255) / 256, h + h / 2), dim3(256), 0, st, d_src, w, h, fmt, d_dst, pitch);
-}
-
-// ------------------------------------------------------------------------------------------
-// k_scale_pack: k_packout with a crop rectangle and a resampler (options crop_* / target_*, INTEGRATION.md "Scaled and cropped output").
-// Output = R_G(F), F = the frame k_packout would produce (lone-field row mapping included): separable fixed-point filter, horizontal pass
-// h = (sum wx * p + 64) >> 7 (int16), vertical pass out = min(255, (sum wy * h + 2^20) >> 21), taps from the handle's tables (ScaleAxis).
-// One workgroup per output tile: 64 luma columns x 16 rows, or 32 chroma columns (both channels) x 16 chroma rows; luma tiles first, then
-// chroma tiles.  The horizontal pass writes the tile's filtered source rows (every row its vertical taps reach) into LDS as int16, the
-// vertical pass writes 4 output bytes per lane.
-// ------------------------------------------------------------------------------------------
-constexpr int kScaleTileW = 64, kScaleTileH = 16;
-// source rows one tile can reach: 15 output rows of at most 8 source rows each + 1 (floor), + kScaleMaxTaps - 1, + 1; with slack
-constexpr int kScaleMaxRows = 136;
-__device__ __forceinline__ int clamp_to(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-
-__global__ __launch_bounds__(256) void k_scale_pack(const ScaleJob *jobs) {
-    __shared__ int16_t hbuf[kScaleMaxRows * kScaleTileW];   // [source row][64 columns]: luma, or 32 chroma columns x (U, V)
-    const ScaleJob &jb = jobs[blockIdx.y];
-    const int tw = jb.tw, th = jb.th, cw = tw >> 1, ch = th >> 1;
-    const int txl = (tw + kScaleTileW - 1) / kScaleTileW, nl = txl * ((th + kScaleTileH - 1) / kScaleTileH);
-    const int txc = (cw + kScaleTileW / 2 - 1) / (kScaleTileW / 2), nc = txc * ((ch + kScaleTileH - 1) / kScaleTileH);
-    int t = blockIdx.x;
-    if (t >= nl + nc) return;
-    const bool chroma = t >= nl;
-    if (chroma) t -= nl;
-    const int ntx = chroma ? txc : txl, cols = chroma ? kScaleTileW / 2 : kScaleTileW;
-    const int ow = chroma ? cw : tw, oh = chroma ? ch : th;
-    const int j0 = (t % ntx) * cols, i0 = (t / ntx) * kScaleTileH;
-    const int jn = min(cols, ow - j0), in = min(kScaleTileH, oh - i0);
-    const ScaleAxis ax = jb.ax[chroma ? 2 : 0], ay = jb.ax[chroma ? 3 : 1];
-    const int Sx = ax.src_len, Sy = ay.src_len;
-    // the source rows the tile's vertical taps reach (clamping is monotonic: every tap of the tile lies in [r0, r1])
-    const int r0 = clamp_to(ay.first[i0], Sy), r1 = clamp_to(ay.first[i0 + in - 1] + ay.taps - 1, Sy);
-    const int nrows = r1 - r0 + 1;
-    if (nrows > kScaleMaxRows) return;                       // (cannot happen within the validated ratios: S <= 8 D)
-    const uint8_t *plane = jb.src + (chroma ? jb.chroma_offset : 0);
-    const int ox = chroma ? jb.crop_x >> 1 : jb.crop_x, oy = chroma ? jb.crop_y >> 1 : jb.crop_y;
-    const int pitch = jb.pitch, lone = jb.lone_field;
-
-    // horizontal pass: lane column c = output column (luma) or output chroma column c / 2, channel c & 1; rows threadIdx.x / 64, + 4, ...
-    {
-        const int c = threadIdx.x & (kScaleTileW - 1);
-        const int jj = chroma ? c >> 1 : c;
-        if (jj < jn) {
-            const int j = j0 + jj, f = ax.first[j], T = ax.taps;
-            int xs[kScaleMaxTaps], wv[kScaleMaxTaps];
-#pragma unroll
-            for (int k = 0; k < kScaleMaxTaps; k++) {
-                const int x = ox + clamp_to(f + k, Sx);
-                xs[k] = chroma ? 2 * x + (c & 1) : x;
-                wv[k] = k < T ? ax.w[j * T + k] : 0;
-            }
-            for (int r = threadIdx.x >> 6; r < nrows; r += 4) {
-                const int sy = oy + r0 + r;                  // row of the display frame F ...
-                const uint8_t *p = plane + (size_t)(lone ? ((sy & ~1) | (lone - 1)) : sy) * pitch;    // ... and of the surface (k_packout's mapping)
-                int acc = 64;
-#pragma unroll
-                for (int k = 0; k < kScaleMaxTaps; k++) if (k < T) acc += wv[k] * p[xs[k]];
-                hbuf[r * kScaleTileW + c] = (int16_t)(acc >> 7);
-            }
-        }
-    }
-    __syncthreads();
-
-    // vertical pass: 16 lanes per output row, 4 output bytes each (luma / NV12 chroma: bytes 4q..4q+3 of the tile's row = hbuf columns 4q..4q+3;
-    // I420 chroma: lanes q < 8 write U columns 4q.., lanes q >= 8 V columns 4(q-8).., i.e. hbuf columns 2 * column + channel)
-    const int r = threadIdx.x >> 4, q = threadIdx.x & 15;
-    if (r >= in) return;
-    const int i = i0 + r, fy = ay.first[i], Ty = ay.taps;
-    const bool planar = chroma && jb.out_fmt == 1;
-    int col[4], n_valid = 0;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        const int b = planar ? 4 * (q & 7) + e : 4 * q + e;          // output byte of the tile's row (planar: in its U or V row)
-        col[e] = planar ? 2 * b + (q >> 3) : b;
-        if ((planar ? b : (chroma ? b >> 1 : b)) < jn) n_valid = e + 1;
-    }
-    int acc[4] = {1 << 20, 1 << 20, 1 << 20, 1 << 20};
-#pragma unroll
-    for (int k = 0; k < kScaleMaxTaps; k++) {
-        if (k >= Ty) break;
-        const int w = ay.w[i * Ty + k];
-        const int16_t *hr = hbuf + (clamp_to(fy + k, Sy) - r0) * kScaleTileW;
-#pragma unroll
-        for (int e = 0; e < 4; e++) acc[e] += w * hr[col[e]];
-    }
-    uint32_t v = 0;
-#pragma unroll
-    for (int e = 0; e < 4; e++) v |= (uint32_t)min(255, acc[e] >> 21) << (8 * e);
-    uint8_t *d;
-    if (!chroma) d = jb.dst + (size_t)i * tw + j0 + 4 * q;
-    else if (!planar) d = jb.dst + (size_t)tw * th + (size_t)i * tw + 2 * j0 + 4 * q;
-    else d = jb.dst + (size_t)tw * th + (size_t)(q >> 3) * cw * ch + (size_t)i * cw + j0 + 4 * (q & 7);
-    if (n_valid == 4 && !(((uintptr_t)d) & 3)) *(uint32_t *)d = v;
-    else for (int e = 0; e < n_valid; e++) d[e] = (uint8_t)(v >> (8 * e));
-}
-
-int scale_tiles(int tw, int th) {
-    return ((tw + kScaleTileW - 1) / kScaleTileW) * ((th + kScaleTileH - 1) / kScaleTileH) +
-           ((tw / 2 + kScaleTileW / 2 - 1) / (kScaleTileW / 2)) * ((th / 2 + kScaleTileH - 1) / kScaleTileH);
-}
-void launch_scale_pack(const ScaleJob *d_jobs, int n, int max_tiles, hipStream_t st) {
-    if (n > 0 && max_tiles > 0) hipLaunchKernelGGL(k_scale_pack, dim3(max_tiles, n), dim3(256), 0, st, d_jobs);
-}
-
-// ------------------------------------------------------------------------------------------
-// k_rgb_pack: output C(R_G(F)) -- k_scale_pack's crop and resampler followed by the colour conversion C (INTEGRATION.md "RGB output").
-// One workgroup per output tile of 64 x 16 pixels.  C needs luma AND chroma of the same pixels, so a scaled job resamples both in one workgroup:
-// the tile's luma (64 x 16) and its chroma (32 x 8, both channels) go through k_scale_pack's horizontal pass into LDS, the vertical chroma results
-// into LDS again (the integer steps are k_scale_pack's, so G is bit-identical), then every lane filters 4 luma samples of one row.  An identity job
-// (target size == crop size) reads the surface directly, no tap tables.  Then every lane converts its 4 pixels and stores 3 x 4 samples.
-// ------------------------------------------------------------------------------------------
-constexpr int kRgbTileW = 64, kRgbTileH = 16;
-
-__device__ __forceinline__ uint32_t rgb_u8(int a) { const int v = (a + 8192) >> 14; return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
-__device__ __forceinline__ float rgb_f32(int a, float k, float b) {
-#pragma clang fp contract(off)
-    const int c = a < 0 ? 0 : (a > 255 * 16384 ? 255 * 16384 : a);        // exact in fp32 (< 2^24)
-    const float m = (float)c * k;                                           // two roundings, never an FMA: numpy float32 restates them
-    return m + b;
-}
-__device__ __forceinline__ uint32_t f32_to_bf16(float f) {                 // round to nearest even
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;        // NaN stays a (quiet) NaN
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ uint32_t f32_to_f16(float f) { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f); }
-
-// 4 consecutive samples of sz bytes (their bit patterns in s[]), n of them valid: one vector store when all are and the address allows it
-__device__ __forceinline__ void store4(uint8_t *d, int sz, const uint32_t s[4], int n) {
-    if (n <= 0) return;
-    const uintptr_t a = (uintptr_t)d;
-    if (sz == 1) {
-        if (n >= 4 && !(a & 3)) *(uint32_t *)d = s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
-        else for (int k = 0; k < 4; k++) { if (k < n) d[k] = (uint8_t)s[k]; }
-    } else if (sz == 2) {
-        if (n >= 4 && !(a & 7)) *(uint2 *)d = make_uint2(s[0] | (s[1] << 16), s[2] | (s[3] << 16));
-        else for (int k = 0; k < 4; k++) { if (k < n) ((uint16_t *)d)[k] = (uint16_t)s[k]; }
-    } else {
-        if (n >= 4 && !(a & 15)) *(uint4 *)d = make_uint4(s[0], s[1], s[2], s[3]);
-        else for (int k = 0; k < 4; k++) { if (k < n) ((uint32_t *)d)[k] = s[k]; }
-    }
-}
-
-// Two instantiations over the same job table, each for the jobs of its kind: SCALED = false (identity jobs) uses no LDS, so its occupancy is set by
-// registers alone; SCALED = true holds the two passes' LDS buffers.
-template <bool SCALED>
-__global__ __launch_bounds__(256) void k_rgb_pack(const RgbJob *jobs) {
-    const RgbJob &jb = jobs[blockIdx.y];
-    if (jb.identity == (SCALED ? 1 : 0)) return;             // (a job of the other instantiation)
-    const ScaleJob &sj = jb.s;
-    const int tw = sj.tw, th = sj.th;
-    const int ntx = (tw + kRgbTileW - 1) / kRgbTileW, t = blockIdx.x;
-    if (t >= ntx * ((th + kRgbTileH - 1) / kRgbTileH)) return;
-    const int j0 = (t % ntx) * kRgbTileW, i0 = (t / ntx) * kRgbTileH;
-    const int jn = min(kRgbTileW, tw - j0), in = min(kRgbTileH, th - i0);      // (both even: tw, th are)
-    const int pitch = sj.pitch, lone = sj.lone_field;
-    const uint8_t *luma = sj.src, *chroma = sj.src + sj.chroma_offset;
-    const int r = threadIdx.x >> 4, q = threadIdx.x & 15;   // the lane's row of the tile and its columns 4q .. 4q + 3
-    const int i = i0 + r;
-    int Y[4] = {0, 0, 0, 0}, U[2] = {128, 128}, V[2] = {128, 128};
-    if constexpr (SCALED) {
-        __shared__ int16_t hy[kScaleMaxRows * kRgbTileW];    // luma source rows after the horizontal pass
-        __shared__ int16_t hc[kScaleMaxRows * kRgbTileW];    // chroma source rows after the horizontal pass: 32 columns x (U, V)
-        __shared__ uint8_t gc[kRgbTileH / 2][kRgbTileW];     // the tile's chroma of G: 8 rows x 32 columns x (U, V)
-        const ScaleAxis ax = sj.ax[0], ay = sj.ax[1], cax = sj.ax[2], cay = sj.ax[3];
-        const int Sx = ax.src_len, Sy = ay.src_len, Sxc = cax.src_len, Syc = cay.src_len;
-        const int ic0 = i0 >> 1, icn = in >> 1, jc0 = j0 >> 1, jcn = jn >> 1;
-        // the source rows the tile's vertical taps reach, luma and chroma (clamping is monotonic)
-        const int r0 = clamp_to(ay.first[i0], Sy), nrows = clamp_to(ay.first[i0 + in - 1] + ay.taps - 1, Sy) - r0 + 1;
-        const int cr0 = clamp_to(cay.first[ic0], Syc), ncrows = clamp_to(cay.first[ic0 + icn - 1] + cay.taps - 1, Syc) - cr0 + 1;
-        if (nrows > kScaleMaxRows || ncrows > kScaleMaxRows) return;      // (cannot happen within the validated ratios: S <= 8 D)
-        const int cx = sj.crop_x, cy = sj.crop_y;
-        // horizontal passes (k_scale_pack's): lane column c = output luma column, and output chroma column c / 2, channel c & 1
-        {
-            const int c = threadIdx.x & (kRgbTileW - 1);
-            int xs[kScaleMaxTaps], wv[kScaleMaxTaps];
-            if (c < jn) {
-                const int j = j0 + c, f = ax.first[j], T = ax.taps;
-#pragma unroll
-                for (int k = 0; k < kScaleMaxTaps; k++) { xs[k] = cx + clamp_to(f + k, Sx); wv[k] = k < T ? ax.w[j * T + k] : 0; }
-                for (int rr = threadIdx.x >> 6; rr < nrows; rr += 4) {
-                    const int sy = cy + r0 + rr;
-                    const uint8_t *p = luma + (size_t)(lone ? ((sy & ~1) | (lone - 1)) : sy) * pitch;
-                    int acc = 64;
-#pragma unroll
-                    for (int k = 0; k < kScaleMaxTaps; k++) if (k < T) acc += wv[k] * p[xs[k]];
-                    hy[rr * kRgbTileW + c] = (int16_t)(acc >> 7);
-                }
-            }
-            if ((c >> 1) < jcn) {
-                const int j = jc0 + (c >> 1), f = cax.first[j], T = cax.taps;
-#pragma unroll
-                for (int k = 0; k < kScaleMaxTaps; k++) { xs[k] = 2 * ((cx >> 1) + clamp_to(f + k, Sxc)) + (c & 1); wv[k] = k < T ? cax.w[j * T + k] : 0; }
-                for (int rr = threadIdx.x >> 6; rr < ncrows; rr += 4) {
-                    const int sy = (cy >> 1) + cr0 + rr;
-                    const uint8_t *p = chroma + (size_t)(lone ? ((sy & ~1) | (lone - 1)) : sy) * pitch;
-                    int acc = 64;
-#pragma unroll
-                    for (int k = 0; k < kScaleMaxTaps; k++) if (k < T) acc += wv[k] * p[xs[k]];
-                    hc[rr * kRgbTileW + c] = (int16_t)(acc >> 7);
-                }
-            }
-        }
-        __syncthreads();
-        // vertical chroma pass: the tile's 8 x 64 chroma values of G
-        for (int e = threadIdx.x; e < (kRgbTileH / 2) * kRgbTileW; e += 256) {
-            const int rr = e / kRgbTileW, c = e % kRgbTileW;
-            if (rr < icn && (c >> 1) < jcn) {
-                const int ic = ic0 + rr, fy = cay.first[ic], Ty = cay.taps;
-                int acc = 1 << 20;
-#pragma unroll
-                for (int k = 0; k < kScaleMaxTaps; k++) if (k < Ty) acc += cay.w[ic * Ty + k] * hc[(clamp_to(fy + k, Syc) - cr0) * kRgbTileW + c];
-                gc[rr][c] = (uint8_t)min(255, acc >> 21);
-            }
-        }
-        // vertical luma pass: the lane's 4 samples
-        if (r < in) {
-            const int fy = ay.first[i], Ty = ay.taps;
-            int acc[4] = {1 << 20, 1 << 20, 1 << 20, 1 << 20};
-#pragma unroll
-            for (int k = 0; k < kScaleMaxTaps; k++) {
-                if (k >= Ty) break;
-                const int w = ay.w[i * Ty + k];
-                const int16_t *hr = hy + (clamp_to(fy + k, Sy) - r0) * kRgbTileW + 4 * q;
-#pragma unroll
-                for (int e = 0; e < 4; e++) acc[e] += w * hr[e];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; e++) Y[e] = min(255, acc[e] >> 21);
-        }
-        __syncthreads();
-        if (r < in) {
-#pragma unroll
-            for (int k = 0; k < 2; k++) { U[k] = gc[r >> 1][2 * (2 * q + k)]; V[k] = gc[r >> 1][2 * (2 * q + k) + 1]; }
-        }
-    } else if (r < in && 4 * q < jn) {
-        // identity geometry: Y = F_Y[crop_y + i][crop_x + j], chroma of F row (crop_y / 2 + i / 2), byte pair crop_x + 2 * (j / 2) (k_packout's row mapping)
-        const int sy = sj.crop_y + i, sc = (sj.crop_y >> 1) + (i >> 1);
-        const uint8_t *py = luma + (size_t)(lone ? ((sy & ~1) | (lone - 1)) : sy) * pitch + sj.crop_x + j0 + 4 * q;
-        const uint8_t *pc = chroma + (size_t)(lone ? ((sc & ~1) | (lone - 1)) : sc) * pitch + sj.crop_x + j0 + 4 * q;
-#pragma unroll
-        for (int e = 0; e < 4; e++) if (4 * q + e < jn) Y[e] = py[e];
-#pragma unroll
-        for (int k = 0; k < 2; k++) if (4 * q + 2 * k < jn) { U[k] = pc[2 * k]; V[k] = pc[2 * k + 1]; }
-    }
-    if (r >= in) return;
-    const int n = min(4, jn - 4 * q);
-    if (n <= 0) return;
-    // C: 14-bit fixed-point accumulators, then the sample type of the job
-    uint32_t s[3][4];
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        const int yv = jb.cy * (Y[e] - jb.yo), d = U[e >> 1] - 128, f = V[e >> 1] - 128;
-        const int aR = yv + jb.crv * f, aG = yv - jb.cgu * d - jb.cgv * f, aB = yv + jb.cbu * d;
-        const int a[3] = {jb.bgr ? aB : aR, aG, jb.bgr ? aR : aB};          // storage positions
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            if (jb.dtype == RGB_U8) s[c][e] = rgb_u8(a[c]);
-            else {
-                const float v = rgb_f32(a[c], jb.k[c], jb.b[c]);
-                s[c][e] = jb.dtype == RGB_F32 ? __float_as_uint(v) : jb.dtype == RGB_F16 ? f32_to_f16(v) : f32_to_bf16(v);
-            }
-        }
-    }
-    const int sz = jb.dtype == RGB_U8 ? 1 : (jb.dtype == RGB_F32 ? 4 : 2);
-    const size_t px = (size_t)i * tw + j0 + 4 * q;
-    if (jb.planar) {
-        const size_t P = (size_t)tw * th;
-#pragma unroll
-        for (int c = 0; c < 3; c++) store4(sj.dst + (c * P + px) * sz, sz, s[c], n);
-    } else {
-        uint32_t v[12];
-#pragma unroll
-        for (int e = 0; e < 4; e++) for (int c = 0; c < 3; c++) v[3 * e + c] = s[c][e];
-        uint8_t *d = sj.dst + 3 * px * sz;
-#pragma unroll
-        for (int g = 0; g < 3; g++) store4(d + 4 * g * sz, sz, v + 4 * g, 3 * n - 4 * g);
-    }
-}
-
-int rgb_tiles(int tw, int th) { return ((tw + kRgbTileW - 1) / kRgbTileW) * ((th + kRgbTileH - 1) / kRgbTileH); }
-void launch_rgb_pack(const RgbJob *d_jobs, int n, int identity_tiles, int scaled_tiles, hipStream_t st) {
-    if (n > 0 && identity_tiles > 0) hipLaunchKernelGGL(k_rgb_pack<false>, dim3(identity_tiles, n), dim3(256), 0, st, d_jobs);
-    if (n > 0 && scaled_tiles > 0) hipLaunchKernelGGL(k_rgb_pack<true>, dim3(scaled_tiles, n), dim3(256), 0, st, d_jobs);
-}
-
-// ------------------------------------------------------------------------------------------
-// k_deint: the deinterlacer D (option deinterlace, INTEGRATION.md "Deinterlaced output") -- k_packout with a vertical stencil.  A pure streaming kernel:
-// a lane owns a 16-byte column chunk of one plane and walks a strip of 8 rows with a window of 9 in registers (deint_packed.h: deint_strip), so consecutive lanes read and write
-// consecutive 16 bytes of the same rows.  All loads of a strip are issued before the first store; no LDS.  Work items: the luma strips row-major
-// (chunk fastest), then the strips of the interleaved chroma plane.  The job's mode and parity are uniform per workgroup (blockIdx.y = job).
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_deint(const DeintJob *jobs) {
-    const DeintJob jb = jobs[blockIdx.y];
-    const dei::gbyte *src = (const dei::gbyte *)jb.src; dei::gbyte *dst = (dei::gbyte *)jb.dst;
-    const int total = dei::frame_items(jb.width, jb.height);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
-        dei::deint_item(src, dst, jb.pitch, jb.chroma_offset, jb.width, jb.height, jb.dst_pitch, jb.dst_chroma_offset, jb.out_fmt, jb.mode, jb.parity, jb.thr, i);
-}
-int deint_items(int w, int h) { return dei::frame_items(w, h); }
-void launch_deint(const DeintJob *d_jobs, int n, int max_items, hipStream_t st) {
-    if (n > 0 && max_items > 0) hipLaunchKernelGGL(k_deint, dim3((max_items + 255) / 256, n), dim3(256), 0, st, d_jobs);
-}
-
-// ------------------------------------------------------------------------------------------
-// k_deint2: field-rate deinterlacing (option deinterlace_rate, deint2_packed.h).  A job with a second destination puts out D with its parity kept (dst)
-// AND D with the other parity kept (dst2) from one walk over the surface: a lane owns a 16-byte column chunk and 8 output rows, loads its 10 source rows
-// once and stores 16.  A job without a second destination is k_deint's work, item by item (the branch is uniform per workgroup), so one launch serves a
-// side that mixes both; a side without pairs is launched as k_deint.
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_deint2(const DeintJob *jobs) {
-    const DeintJob jb = jobs[blockIdx.y];
-    const dei::gbyte *src = (const dei::gbyte *)jb.src; dei::gbyte *dst = (dei::gbyte *)jb.dst, *dst2 = (dei::gbyte *)jb.dst2;
-    if (!dst2) {
-        const int total = dei::frame_items(jb.width, jb.height);
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
-            dei::deint_item(src, dst, jb.pitch, jb.chroma_offset, jb.width, jb.height, jb.dst_pitch, jb.dst_chroma_offset, jb.out_fmt, jb.mode, jb.parity, jb.thr, i);
-        return;
-    }
-    const int total = dei::frame2_items(jb.width, jb.height);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
-        dei::deint2_item(src, jb.parity ? dst2 : dst, jb.parity ? dst : dst2, jb.pitch, jb.chroma_offset, jb.width, jb.height, jb.dst_pitch, jb.dst_chroma_offset,
-                         jb.out_fmt, jb.mode, jb.thr, i);
-}
-int deint2_items(int w, int h) { return dei::frame2_items(w, h); }
-void launch_deint2(const DeintJob *d_jobs, int n, int max_items, hipStream_t st) {
-    if (n > 0 && max_items > 0) hipLaunchKernelGGL(k_deint2, dim3((max_items + 255) / 256, n), dim3(256), 0, st, d_jobs);
-}
-
-void launch_packout(const PackJob *d_jobs, int n, int max_width, int max_height, hipStream_t st) {
-    int chunks = ((max_width + 15) >> 4) * (max_height + (max_height >> 1));
-    int blocks = (chunks + 255) / 256;
-    // The destination is pinned HOST memory: the kernel is PCIe-bound (~55 GB/s), not CU-bound.  A small grid is enough to
-    // keep the link full and leaves the CUs to the decode kernels of the next batch that run concurrently.
-    const int total = 160;
-    int cap = total / (n > 0 ? n : 1);
-    if (cap < 1) cap = 1;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(k_packout, dim3(blocks, n), dim3(256), 0, st, d_jobs);
-}
 
 }  // namespace jmamd

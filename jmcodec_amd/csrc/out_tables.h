@@ -19,7 +19,7 @@ constexpr int kMaxBatch = 64;                       // pictures of one launch
 constexpr int kOutSideCap = 2 * kMaxBatch;          // table entries of one side: Engine::form keeps a batch's frames per side within it
 enum : int { kBefore = 0, kAfter = 1 };             // the sides
 
-// the grid a job needs, defined beside its kernel (kernels.hip)
+// the grid a job needs, defined beside its kernel (out_kernels.hip)
 int scale_tiles(int tw, int th);
 int rgb_tiles(int tw, int th);
 int deint_items(int w, int h);

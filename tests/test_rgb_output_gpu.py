@@ -3,7 +3,6 @@ oracle's frames (the oracle decodes the same stream without its colour descripti
 seeded random cases, both codecs end to end, every output route, the device and push / pull interfaces, a stream whose sequences change matrix
 and size, RGB handles in the same batches as scaled and plain ones, and the 1 GiB rule of the output slots."""
 import ctypes as C
-import random
 import threading
 
 import numpy as np
@@ -11,54 +10,22 @@ import pytest
 
 from jmcodec_amd import api
 from tools import streams
-from test_rgb_output_host import MATRICES, rgb_frame
-from test_scaled_output_gpu import _hip, _packout_ref
+from test_rgb_output_host import IMAGENET, rgb_device_cases, rgb_frame
+from test_scaled_output_gpu import _hip
+from test_scaled_output_host import _packout_ref
 
 pytestmark = pytest.mark.gpu
-IMAGENET = dict(mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225))
-
-
-def _case_spec(n, rng):
-    """Case n of 192 covers every dtype x layout x order x matrix x range once; floats get the defaults, ImageNet or a random scale / bias."""
-    dtype, planar, bgr, matrix, rng_ = n % 4, (n // 4) % 2, (n // 8) % 2, MATRICES[(n // 16) % 6], 1 + (n // 96) % 2
-    kind = rng.randrange(3)
-    if dtype == 0 or kind == 0:
-        return api.rgb_spec(dtype, planar, bgr, matrix, rng_)
-    if kind == 1:
-        return api.rgb_spec(dtype, planar, bgr, matrix, rng_, **IMAGENET)
-    return api.rgb_spec(dtype, planar, bgr, matrix, rng_, scale=[rng.uniform(-2, 2) for _ in range(3)], bias=[rng.uniform(-100, 100) for _ in range(3)])
-
-
-def _case_geometry(n, rng):
-    W, H = rng.randrange(2, 240, 2), rng.randrange(2, 180, 2)
-    cw, ch = rng.randrange(2, W + 1, 2), rng.randrange(2, H + 1, 2)
-    cx, cy = rng.randrange(0, W - cw + 1, 2), rng.randrange(0, H - ch + 1, 2)
-    kind = n % 5                                            # identity, the 8:1 and 1:4 limits, random
-
-    def dst(s):
-        lo, hi = -(-s // 8), 4 * s
-        lo += lo & 1
-        return s if kind == 0 else lo if kind == 1 else hi if kind == 2 else rng.randrange(lo, hi + 1, 2)
-    return W, H, (cx, cy, cw, ch), (dst(cw), dst(ch))
 
 
 def test_rgb_device_random_cases():
     """jm_amddec_rgb_device alone: 200 seeded cases (sizes that are no multiples of 16, crops, identity / 8:1 / 1:4 / random targets, lone_field
     0 / 1 / 2, every sample type, layout, order, matrix and range, random surface bytes with 0 and 255) against C(R_G(F))."""
     hip = _hip()
-    rng = random.Random(0xC0105)
     d_src, d_dst = C.c_void_p(), C.c_void_p()
     src_cap, dst_cap = 400 * 200 * 3 // 2, 3 * 960 * 720 * 4
     assert hip.hipMalloc(C.byref(d_src), src_cap) == 0 and hip.hipMalloc(C.byref(d_dst), dst_cap) == 0
     try:
-        for n in range(200):
-            spec = _case_spec(n % 192, rng)
-            W, H, crop, target = _case_geometry(n, rng)
-            pitch = W + rng.choice([0, 2, 14, 128 - W % 128])
-            lone = rng.randrange(3)
-            hs = H + (16 if lone and H % 4 else rng.choice([0, 16]))
-            src = np.random.default_rng(n).integers(0, 256, pitch * hs * 3 // 2, dtype=np.uint8)
-            src[::7], src[3::11] = 0, 255
+        for n, spec, W, H, crop, target, pitch, lone, hs, src in rgb_device_cases():
             out_n = 3 * target[0] * target[1] * api.RGB_SAMPLE_BYTES[spec.dtype]
             assert src.size <= src_cap and out_n <= dst_cap
             assert hip.hipMemcpy(d_src, src.ctypes.data_as(C.c_void_p), src.size, 1) == 0

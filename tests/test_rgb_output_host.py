@@ -1,6 +1,11 @@
 """RGB output, host side (no GPU): the colour coefficients against an exact rational computation, a numpy restatement of the conversion C
-(INTEGRATION.md "RGB output") and its closed forms, the colour description of both parsers, and the RGB spec of parse-only handles.  The
-restatement here is what the GPU tests (test_rgb_output_gpu.py) compare the device output with."""
+(INTEGRATION.md "RGB output") and its closed forms, the lane routines of both k_rgb_pack instantiations (jmcodec_amd/csrc/rgb_packed.h) walked over
+whole frames on the CPU, the colour description of both parsers, and the RGB spec of parse-only handles.  The restatement and the case list here are
+what the GPU tests (test_rgb_output_gpu.py) compare the device output with."""
+import ctypes as C
+import os
+import random
+import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -8,9 +13,12 @@ import pytest
 
 from jmcodec_amd import api
 from tools import streams
-from test_scaled_output_host import scale_frame, split_frame
+from test_scaled_output_host import _packout_ref, build_native, load_scale_check, scale_device_cases, scale_frame, scale_walk, split_frame
 
 MATRICES = (1, 4, 5, 6, 7, 9)
+IMAGENET = dict(mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225))
+HIPCC = "/opt/rocm/bin/hipcc"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KRKB = {1: ("0.2126", "0.0722"), 4: ("0.30", "0.11"), 5: ("0.299", "0.114"), 6: ("0.299", "0.114"), 7: ("0.212", "0.087"), 9: ("0.2627", "0.0593")}
 
 
@@ -61,6 +69,138 @@ def rgb_frame(F, W, H, fmt, crop, target, spec, matrix, full):
     G = scale_frame(F, W, H, fmt, crop, target)
     Y, U, V = split_frame(G, target[0], target[1], fmt)
     return convert(Y, U, V, spec.dtype, spec.planar, spec.bgr, matrix, full, tuple(spec.scale), tuple(spec.bias))
+
+
+# ---- the cases of the stand-alone kernel tests (CPU walk here, the device in test_rgb_output_gpu.py) ------------------------------------
+def _case_spec(n, rng):
+    """Case n of 192 covers every dtype x layout x order x matrix x range once; floats get the defaults, ImageNet or a random scale / bias."""
+    dtype, planar, bgr, matrix, rng_ = n % 4, (n // 4) % 2, (n // 8) % 2, MATRICES[(n // 16) % 6], 1 + (n // 96) % 2
+    kind = rng.randrange(3)
+    if dtype == 0 or kind == 0:
+        return api.rgb_spec(dtype, planar, bgr, matrix, rng_)
+    if kind == 1:
+        return api.rgb_spec(dtype, planar, bgr, matrix, rng_, **IMAGENET)
+    return api.rgb_spec(dtype, planar, bgr, matrix, rng_, scale=[rng.uniform(-2, 2) for _ in range(3)], bias=[rng.uniform(-100, 100) for _ in range(3)])
+
+
+def _case_geometry(n, rng):
+    W, H = rng.randrange(2, 240, 2), rng.randrange(2, 180, 2)
+    cw, ch = rng.randrange(2, W + 1, 2), rng.randrange(2, H + 1, 2)
+    cx, cy = rng.randrange(0, W - cw + 1, 2), rng.randrange(0, H - ch + 1, 2)
+    kind = n % 5                                            # identity, the 8:1 and 1:4 limits, random
+
+    def dst(s):
+        lo, hi = -(-s // 8), 4 * s
+        lo += lo & 1
+        return s if kind == 0 else lo if kind == 1 else hi if kind == 2 else rng.randrange(lo, hi + 1, 2)
+    return W, H, (cx, cy, cw, ch), (dst(cw), dst(ch))
+
+
+def rgb_device_cases():
+    """200 seeded cases (sizes that are no multiples of 16, crops, identity / 8:1 / 1:4 / random targets, lone_field 0 / 1 / 2, every sample type,
+    layout, order, matrix and range, random surface bytes with 0 and 255); yields (n, spec, W, H, crop, target, pitch, lone, hs, src)."""
+    rng = random.Random(0xC0105)
+    for n in range(200):
+        spec = _case_spec(n % 192, rng)
+        W, H, crop, target = _case_geometry(n, rng)
+        pitch = W + rng.choice([0, 2, 14, 128 - W % 128])
+        lone = rng.randrange(3)
+        hs = H + (16 if lone and H % 4 else rng.choice([0, 16]))
+        src = np.random.default_rng(n).integers(0, 256, pitch * hs * 3 // 2, dtype=np.uint8)
+        src[::7], src[3::11] = 0, 255
+        yield n, spec, W, H, crop, target, pitch, lone, hs, src
+
+
+# ---- rgb_packed.h: k_rgb_pack's lanes on the CPU ------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc: the f16 samples need its clang (_Float16)")
+    l = build_native("rgb_packed_check", [HIPCC, "-x", "c++"], ("scale_packed.h", "rgb_packed.h", "mc_packed.h", "jobs.h"),
+                     ("scale_packed_walk.h", "rgb_packed_walk.h"))
+    l.rgbp_frame.argtypes = [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3
+    return l
+
+
+@pytest.fixture(scope="module")
+def scale_lib():
+    return load_scale_check()
+
+
+def rgb_walk(lib, src, pitch, hs, crop, target, spec, lone, coefs=None, misalign=0, guard=64):
+    """k_rgb_pack's lanes (the instantiation of the job's kind) over one job on the CPU.  The frame starts `misalign` samples behind a 16-byte boundary
+    and has `guard` bytes of 0xA5 before and behind it, which must stay."""
+    src = np.ascontiguousarray(src)
+    sz = api.RGB_SAMPLE_BYTES[spec.dtype]
+    out_n = 3 * target[0] * target[1] * sz
+    raw = np.full(out_n + 2 * guard + 16 + misalign * sz, 0xA5, np.uint8)
+    off = guard + (-(raw.ctypes.data + guard)) % 16 + misalign * sz
+    coefs = (C.c_int * 5)(*(coefs or api.color_coefs(spec.matrix, spec.range == 2)))
+    scale, bias = (C.c_float * 3)(*spec.scale), (C.c_float * 3)(*spec.bias)
+    rc = lib.rgbp_frame(src.ctypes.data, pitch, pitch * hs, lone, *crop, *target, coefs, int(spec.range == 2), spec.dtype, spec.planar, spec.bgr, scale, bias,
+                        raw.ctypes.data + off)
+    assert rc == 0, rc
+    assert (raw[:off] == 0xA5).all() and (raw[off + out_n:] == 0xA5).all(), "bytes outside the frame were written"
+    return raw[off:off + out_n].tobytes()
+
+
+def _describe(n, W, H, crop, target, lone, spec):
+    return (f"case {n}: {W}x{H} crop {crop} -> {target} lone {lone} dtype {spec.dtype} planar {spec.planar} bgr {spec.bgr} matrix {spec.matrix} "
+            f"range {spec.range}")
+
+
+def test_rgb_packed_walk_equals_the_restatement(lib):
+    """Every tile of every one of the device test's 200 cases (every dtype, layout, order, matrix and range; identity and scaled jobs), 256 lanes per
+    tile in the kernel's order, byte for byte against C(R_G(F))."""
+    kinds = set()
+    for n, spec, W, H, crop, target, pitch, lone, hs, src in rgb_device_cases():
+        got = rgb_walk(lib, src, pitch, hs, crop, target, spec, lone)
+        want = rgb_frame(_packout_ref(src, pitch, hs, W, H, lone, 1), W, H, 1, crop, target, spec, spec.matrix, spec.range == 2)
+        assert got == want, _describe(n, W, H, crop, target, lone, spec)
+        kinds.add((spec.dtype, target == crop[2:]))
+    assert len(kinds) == 8                                  # each dtype through both instantiations
+
+
+@pytest.mark.parametrize("dtype", [0, 1, 2, 3])
+def test_rgb_packed_walk_with_a_misaligned_destination(lib, dtype):
+    """A frame that starts one sample behind a 16-byte boundary: no vector store of a planar row start is aligned, store4's scalar tails run."""
+    rng = np.random.default_rng(0xA11 + dtype)
+    W, H, pitch = 70, 22, 72
+    src = rng.integers(0, 256, pitch * H * 3 // 2, dtype=np.uint8)
+    for planar in (1, 0):
+        for crop, target in (((0, 0, W, H), (W, H)), ((2, 2, 66, 18), (50, 26))):
+            spec = api.rgb_spec(dtype, planar, 0, 1, 1, **({} if dtype == 0 else IMAGENET))
+            got = rgb_walk(lib, src, pitch, H, crop, target, spec, 0, misalign=1)
+            want = rgb_frame(_packout_ref(src, pitch, H, W, H, 0, 1), W, H, 1, crop, target, spec, 1, False)
+            assert got == want, (dtype, planar, crop, target)
+
+
+def test_rgb_luma_of_a_scaled_tile_is_k_scale_packs(lib, scale_lib):
+    """G is shared: with cy = 1, no chroma terms, full range and u8, k_rgb_pack's R = G = B = the luma of G, which must be k_scale_pack's output for
+    the same geometry (both go through the same lane routines)."""
+    spec = api.rgb_spec(0, 1, 0, 1, 2)
+    seen = 0
+    for n, W, H, crop, target, pitch, lone, fmt, hs, src in scale_device_cases():
+        if n % 8 or target == crop[2:]:
+            continue
+        rgb = rgb_walk(lib, src, pitch, hs, crop, target, spec, lone, coefs=(16384, 0, 0, 0, 0))
+        Y = scale_walk(scale_lib, src, pitch, hs, crop, target, fmt, lone)[:target[0] * target[1]]
+        assert rgb == Y * 3, f"case {n}"
+        seen += 1
+    assert seen >= 25
+
+
+def test_out_packed_asan_builds_and_runs_clean(tmp_path):
+    """tools/out_packed_asan.cpp: both walks over edge geometries under AddressSanitizer / UBSan, every buffer of the exact size."""
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc: the program is built with its clang")
+    out = tmp_path / "out"
+    r = subprocess.run(["make", "-C", os.path.join(ROOT, "tools"), "out_packed_asan", f"OUT={out}"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout[-4000:]
+    r = subprocess.run([str(out / "out_packed_asan")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-4000:]
+    assert "ok: 198 walks" in r.stdout
+    assert "Sanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-4000:]
 
 
 # ---- coefficients ----------------------------------------------------------------------------------------------------------------

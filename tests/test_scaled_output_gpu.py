@@ -2,7 +2,6 @@
 oracle's unscaled frames (test_scaled_output_host.py): the stand-alone kernel, both codecs end to end, every output route, a resolution
 change under a fixed target, and scaled handles in the same batches as unscaled ones."""
 import ctypes as C
-import random
 import threading
 
 import numpy as np
@@ -10,7 +9,7 @@ import pytest
 
 from jmcodec_amd import api
 from tools import streams
-from test_scaled_output_host import scale_frame, scale_frames, split_frame
+from test_scaled_output_host import _packout_ref, scale_device_cases, scale_frame, scale_frames, split_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -24,56 +23,15 @@ def _hip():
     return hip
 
 
-def _packout_ref(src, pitch, hs, w, h, lone, fmt):
-    """The frame F k_packout makes of a pitch-linear NV12 surface of hs rows (lone-field row mapping included)."""
-    rows = np.arange(h)
-    rows_c = np.arange(h // 2)
-    if lone:
-        rows, rows_c = (rows & ~1) | (lone - 1), (rows_c & ~1) | (lone - 1)
-    Y = src[:pitch * hs].reshape(hs, pitch)[rows, :w]
-    uv = src[pitch * hs:pitch * hs + pitch * (hs // 2)].reshape(hs // 2, pitch)[rows_c, :w]
-    U, V = uv[:, 0::2], uv[:, 1::2]
-    return Y.tobytes() + (np.stack([U, V], 2).tobytes() if fmt == 0 else U.tobytes() + V.tobytes())
-
-
-def _random_geometry(rng, limit=None):
-    W = rng.randrange(2, 400, 2)
-    H = rng.randrange(2, 300, 2)
-    cw = rng.randrange(2, W + 1, 2)
-    ch = rng.randrange(2, H + 1, 2)
-    cx = rng.randrange(0, W - cw + 1, 2)
-    cy = rng.randrange(0, H - ch + 1, 2)
-
-    def dst(s):
-        lo, hi = -(-s // 8), 4 * s
-        lo += lo & 1
-        if limit == "down":
-            return lo
-        if limit == "up":
-            return hi
-        return rng.randrange(lo, hi + 1, 2)
-    return W, H, (cx, cy, cw, ch), (dst(cw), dst(ch))
-
-
 def test_scale_device_random_geometries():
     """jm_amddec_scale_device alone: 240 seeded random geometries (sizes that are no multiples of 16, both formats, lone_field 0 / 1 / 2, the
     ratio limits 8:1 and 1:4) against R_G of the k_packout restatement."""
     hip = _hip()
-    rng = random.Random(0x5CA1ED)
-    cases = [_random_geometry(rng) for _ in range(200)] + [_random_geometry(rng, "down") for _ in range(20)] + \
-            [_random_geometry(rng, "up") for _ in range(20)]
-    cases.append((1920, 1080, (0, 0, 1920, 1080), (240, 136)))
-    cases.append((180, 100, (0, 0, 180, 100), (720, 400)))
     d_src, d_dst = C.c_void_p(), C.c_void_p()
     src_cap, dst_cap = 2048 * 1200 * 3 // 2, 1920 * 1088 * 3 // 2
     assert hip.hipMalloc(C.byref(d_src), src_cap) == 0 and hip.hipMalloc(C.byref(d_dst), dst_cap) == 0
     try:
-        for n, (W, H, crop, target) in enumerate(cases):
-            pitch = W + rng.choice([0, 2, 14, 128 - W % 128])
-            lone, fmt = n % 3, (n // 3) % 2
-            # surface rows (the coded height): a lone field of a frame with an odd number of chroma rows reads the surface's next one
-            hs = H + (16 if lone and H % 4 else rng.choice([0, 16]))
-            src = np.random.default_rng(n).integers(0, 256, pitch * hs * 3 // 2, dtype=np.uint8)
+        for n, W, H, crop, target, pitch, lone, fmt, hs, src in scale_device_cases():
             assert src.size <= src_cap
             out_n = target[0] * target[1] * 3 // 2
             assert out_n <= dst_cap

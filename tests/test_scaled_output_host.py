@@ -1,13 +1,19 @@
 """Scaled and cropped output, host side (no GPU): the tap builder against a numpy restatement of the resampler R_G (INTEGRATION.md
-"Scaled and cropped output"), the closed forms R_G must satisfy, and the geometry options of parse-only handles.  The restatement here is
-what the GPU tests (test_scaled_output_gpu.py) compare the device output with."""
+"Scaled and cropped output"), the closed forms R_G must satisfy, the lane routines of k_scale_pack (jmcodec_amd/csrc/scale_packed.h) walked over
+whole frames on the CPU, and the geometry options of parse-only handles.  The restatement and the case list here are what the GPU tests
+(test_scaled_output_gpu.py) compare the device output with."""
+import ctypes as C
+import os
 import random
+import subprocess
 
 import numpy as np
 import pytest
 
 from jmcodec_amd import api
 from tools import streams
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- R_G restated ---------------------------------------------------------------------------------------------------------
@@ -92,6 +98,103 @@ def scale_frame(F, W, H, fmt, crop, target):
 def scale_frames(blob, n, W, H, fmt, crop, target):
     fs = W * H * 3 // 2
     return [scale_frame(blob[i * fs:(i + 1) * fs], W, H, fmt, crop, target) for i in range(n)]
+
+
+# ---- the cases of the stand-alone kernel tests (CPU walk here, the device in test_scaled_output_gpu.py) ---------------------------------
+def _packout_ref(src, pitch, hs, w, h, lone, fmt):
+    """The frame F k_packout makes of a pitch-linear NV12 surface of hs rows (lone-field row mapping included)."""
+    rows = np.arange(h)
+    rows_c = np.arange(h // 2)
+    if lone:
+        rows, rows_c = (rows & ~1) | (lone - 1), (rows_c & ~1) | (lone - 1)
+    Y = src[:pitch * hs].reshape(hs, pitch)[rows, :w]
+    uv = src[pitch * hs:pitch * hs + pitch * (hs // 2)].reshape(hs // 2, pitch)[rows_c, :w]
+    U, V = uv[:, 0::2], uv[:, 1::2]
+    return Y.tobytes() + (np.stack([U, V], 2).tobytes() if fmt == 0 else U.tobytes() + V.tobytes())
+
+
+def _random_geometry(rng, limit=None):
+    W = rng.randrange(2, 400, 2)
+    H = rng.randrange(2, 300, 2)
+    cw = rng.randrange(2, W + 1, 2)
+    ch = rng.randrange(2, H + 1, 2)
+    cx = rng.randrange(0, W - cw + 1, 2)
+    cy = rng.randrange(0, H - ch + 1, 2)
+
+    def dst(s):
+        lo, hi = -(-s // 8), 4 * s
+        lo += lo & 1
+        if limit == "down":
+            return lo
+        if limit == "up":
+            return hi
+        return rng.randrange(lo, hi + 1, 2)
+    return W, H, (cx, cy, cw, ch), (dst(cw), dst(ch))
+
+
+def scale_device_cases():
+    """240 seeded random geometries (sizes that are no multiples of 16, both formats, lone_field 0 / 1 / 2, the ratio limits 8:1 and 1:4) and two
+    fixed ones; yields (n, W, H, crop, target, pitch, lone, fmt, hs, src): src a surface of hs rows (the coded height) at the given pitch."""
+    rng = random.Random(0x5CA1ED)
+    cases = [_random_geometry(rng) for _ in range(200)] + [_random_geometry(rng, "down") for _ in range(20)] + \
+            [_random_geometry(rng, "up") for _ in range(20)]
+    cases.append((1920, 1080, (0, 0, 1920, 1080), (240, 136)))
+    cases.append((180, 100, (0, 0, 180, 100), (720, 400)))
+    for n, (W, H, crop, target) in enumerate(cases):
+        pitch = W + rng.choice([0, 2, 14, 128 - W % 128])
+        lone, fmt = n % 3, (n // 3) % 2
+        # surface rows (the coded height): a lone field of a frame with an odd number of chroma rows reads the surface's next one
+        hs = H + (16 if lone and H % 4 else rng.choice([0, 16]))
+        src = np.random.default_rng(n).integers(0, 256, pitch * hs * 3 // 2, dtype=np.uint8)
+        yield n, W, H, crop, target, pitch, lone, fmt, hs, src
+
+
+# ---- scale_packed.h: k_scale_pack's lanes on the CPU ------------------------------------------------------------------------------------
+def build_native(name, compiler, hdrs, walks=("scale_packed_walk.h",)):
+    """tests/native/<name>.cpp as a shared library under tests/_build (rebuilt when the source or one of the headers is newer)."""
+    out = os.path.join(ROOT, "tests", "_build")
+    os.makedirs(out, exist_ok=True)
+    so = os.path.join(out, f"lib{name}.so")
+    src = os.path.join(ROOT, "tests", "native", name + ".cpp")
+    deps = [src] + [os.path.join(ROOT, "tests", "native", h) for h in walks] + [os.path.join(ROOT, "jmcodec_amd", "csrc", h) for h in hdrs]
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in deps):
+        subprocess.check_call(compiler + ["-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-o", so, src])
+    return C.CDLL(so)
+
+
+def load_scale_check():
+    l = build_native("scale_packed_check", ["g++"], ("scale_packed.h", "mc_packed.h", "jobs.h"))
+    l.scl_frame.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p]
+    return l
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return load_scale_check()
+
+
+def scale_walk(lib, src, pitch, hs, crop, target, fmt, lone, guard=64):
+    """k_scale_pack's lanes over one job on the CPU.  The surface is a heap copy of exactly its size; the frame has `guard` bytes of 0xA5 behind it,
+    which must stay."""
+    src = np.ascontiguousarray(src)
+    out_n = target[0] * target[1] * 3 // 2
+    out = np.full(out_n + guard, 0xA5, np.uint8)
+    rc = lib.scl_frame(src.ctypes.data, pitch, pitch * hs, lone, *crop, *target, fmt, out.ctypes.data)
+    assert rc == 0, rc
+    assert (out[out_n:] == 0xA5).all(), "bytes behind the frame were written"
+    return out[:out_n].tobytes()
+
+
+def test_scale_packed_walk_equals_the_restatement(lib):
+    """Every tile of every one of the device test's 242 cases, 256 lanes per tile, horizontal pass then vertical pass, byte for byte against R_G of
+    the k_packout restatement: tile edges, the clamp of the row range, the I420 lane mapping and the tail stores run here without a GPU."""
+    count = 0
+    for n, W, H, crop, target, pitch, lone, fmt, hs, src in scale_device_cases():
+        got = scale_walk(lib, src, pitch, hs, crop, target, fmt, lone)
+        want = scale_frame(_packout_ref(src, pitch, hs, W, H, lone, fmt), W, H, fmt, crop, target)
+        assert got == want, f"case {n}: {W}x{H} crop {crop} -> {target} lone {lone} fmt {fmt}"
+        count += 1
+    assert count == 242
 
 
 # ---- the library's tap builder ---------------------------------------------------------------------------------------------
