@@ -65,6 +65,7 @@ int  jm_amddec_is_hw_support(void);
  *       "chain_lag", "chain_streams", "debug_stall" (DESIGN.md 4b); before init: "job_slots" (pictures in flight per handle, 8..64; default 40 for H.264 up
  *       to 1080p, else 24);
  *       "crop_x" / "crop_y" / "crop_w" / "crop_h" / "target_width" / "target_height" (before init: scaled and cropped output, see below);
+ *       "verify_hash" (before init, HEVC: 1 / 2 = check the decoded picture hash SEI on the device, see below);
  *       tests only: "fast_parse" (0 = every macroblock through the general parser path), "job_digest" (1 = digest of the job lists; implies sync) */
 /* like jm_amddec_decode_frame without input: *got_frame = 1 when a display-order frame became ready (never signals end of stream) */
 int  jm_amddec_poll_frame(int *got_frame, jm_amddec_handle h);
@@ -80,10 +81,11 @@ int  jm_amddec_push_eos(jm_amddec_handle h);
 int  jm_amddec_set_option(jm_amddec_handle h, const char *key, long long value);
 /* keys: "frames", "pictures", "job_bytes", "errors", "intra_mbs", "coef_int16", "syntax_digest",
  *       "digest_mbs", "i_pictures", "p_pictures", "coded_width", "coded_height", "pitch", "device",
- *       "threads", "elapsed_us", "display_poc:<n>", "fps_num" / "fps_den" (frame rate from the VUI timing information, 0 / 0 = not transmitted),
+ *       "threads", "elapsed_us", "failed" (1: the handle has failed, jm_amddec_last_error says why), "display_poc:<n>", "fps_num" / "fps_den" (frame rate from the VUI timing information, 0 / 0 = not transmitted),
  *       "frames_waiting" (display frames decided and not yet made current by a decode / poll call), "frames_done_unfetched" (those of them whose samples are there), "device_wait_errors", "direct_frames" / "direct_ns" (frames that left by one copy-engine
  *       transfer into the caller's buffer, and the time their callers waited), "copy_engines" (SDMA engines used for that, bit mask),
- *       "job_digest", "eng_*" / "k_*" (engine and per-kernel counters, bench.py), "out_width" / "out_height" / "scaled_frames" (see below) */
+ *       "job_digest", "eng_*" / "k_*" (engine and per-kernel counters, bench.py), "out_width" / "out_height" / "scaled_frames" (see below),
+ *       "hash_*" (picture hash verification, see below) */
 long long jm_amddec_get_stat(jm_amddec_handle h, const char *key);
 const char *jm_amddec_last_error(jm_amddec_handle h);
 
@@ -171,6 +173,21 @@ int  jm_amddec_set_rgb(jm_amddec_handle h, const jm_amddec_rgb_spec *spec);
 int  jm_amddec_color_coefs(int matrix, int full_range, int coefs[5]);
 int  jm_amddec_rgb_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int lone_field, int crop_x, int crop_y, int crop_w,
                           int crop_h, int tw, int th, const jm_amddec_rgb_spec *spec, void *d_dst, void *stream);
+/* Picture hash verification (INTEGRATION.md "Picture hash" defines both hashes exactly).  An HEVC stream may say what every decoded picture hashes to:
+ * the decoded picture hash SEI message (payload type 132) in a suffix SEI NAL unit (type 40) holds an MD5, a CRC or a checksum per colour component of
+ * the picture at its coded size.  Option "verify_hash", before init (set_option returns -1 after init and for other values):
+ *   0 (default) off: suffix SEI is not looked at and nothing changes;  1: the CRC or the checksum is computed on the device behind the picture's last
+ *   kernel (k_hevc_pichash) and compared, mismatches are counted;  2: the first mismatch also fails the handle, jm_amddec_last_error then reads
+ *   "picture hash mismatch: POC <n>, component <Y|Cb|Cr>, <crc|checksum> expected 0x... got 0x...".
+ * MD5 messages are counted and never compared.  A hash in a prefix SEI is ignored; a malformed message counts in "errors" and is ignored.
+ * Stats: "hash_pictures" (pictures that carried a hash message), "hash_checked", "hash_mismatch", "hash_unchecked" (their batch failed, or the handle
+ * had), "hash_md5", "hash_first_bad_poc" (-2^31: none), "hash_last_crc:<c>" / "hash_last_checksum:<c>" (c = 0..2: the device's values of the most
+ * recently completed hashed picture), "hash_sei_poc:<n>" / "hash_sei_type:<n>" / "hash_sei_value:<n>:<c>" (the n-th hash message in decode order as
+ * parsed; works on a parse_only handle), and with option "profile" k_pichash_ns / _n / _pics / _alg_bytes.
+ *   jm_amddec_picture_hash_device: stand-alone, both hashes of one pitch-linear NV12 surface in device memory (luma rows at `pitch`, the UV rows from
+ *     byte chroma_offset; w x h even, 2..16384): crc[c] and checksum[c] of Y, Cb, Cr.  stream: a hipStream_t or NULL; synchronised before returning.
+ *     Returns 0, -1 for invalid arguments, or a negative hipError. */
+int  jm_amddec_picture_hash_device(const void *d_src, int pitch, int chroma_offset, int w, int h, unsigned crc[3], unsigned checksum[3], void *stream);
 /* SURVEY 8f f4 -- the encoder-side pre-processing of the reference (/root/reference/nv_enc/nv_enc.cpp:1022-1079: cuMemcpy2D of the luma plane +
  * the InterleaveUV kernel; the CPU loop of intel_enc.cpp:316-387) as one HIP kernel, device to device: a tight frame (src_fmt 1 = I420
  * planar Y,U,V; 0 = tight NV12) becomes a pitch-linear NV12 surface (luma rows at `pitch`, interleaved UV rows from row `height`), the layout an

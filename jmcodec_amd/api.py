@@ -94,6 +94,7 @@ def lib():
     L.jm_amddec_color_coefs.argtypes = [C.c_int, C.c_int, ip]
     L.jm_amddec_rgb_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(RgbSpec), vp, vp]
+    L.jm_amddec_picture_hash_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), vp]
     _LIB = L
     return L
 
@@ -185,6 +186,15 @@ def deinterlace2_device(src, pitch, chroma_offset, width, height, mode, first_fi
 def scale_device(src, pitch, chroma_offset, width, height, crop, target, out_fmt, dst, lone_field=0, stream=None):
     """jm_amddec_scale_device: crop = (x, y, w, h), target = (tw, th); src / dst device addresses.  Returns 0 or < 0."""
     return lib().jm_amddec_scale_device(src, pitch, chroma_offset, width, height, lone_field, *crop, *target, out_fmt, dst, stream)
+
+
+# ---- picture hash (include/jm_amd_dec.h; both hashes are defined in INTEGRATION.md "Picture hash") ----------
+def picture_hash_device(src, pitch, chroma_offset, width, height, stream=None):
+    """jm_amddec_picture_hash_device: the CRC and the checksum of the decoded picture hash SEI (H.265 D.3.19) of one pitch-linear NV12 surface in
+    device memory, per component.  Returns (rc, [crc Y, Cb, Cr], [checksum Y, Cb, Cr]); rc 0 or < 0."""
+    crc, chk = (C.c_uint * 3)(), (C.c_uint * 3)()
+    rc = lib().jm_amddec_picture_hash_device(src, pitch, chroma_offset, width, height, crc, chk, stream)
+    return rc, list(crc), list(chk)
 
 
 # ---- RGB output (include/jm_amd_dec.h; the conversion C is defined in INTEGRATION.md "RGB output") ----------
@@ -553,6 +563,8 @@ def intel_push_pull(data, codec_type=0, out_fmt=1, callback=False, max_push=None
                     sinfo = jm_intel_get_stream_info(h)
         if sinfo is None:
             sinfo = jm_intel_get_stream_info(h)
+        if lib().jm_amddec_get_stat(lib().jm_amdintel_decoder(h), b"failed") == 1:
+            raise RuntimeError(lib().jm_amddec_last_error(lib().jm_amdintel_decoder(h)).decode())
         return frames, jm_intel_dec_info(h), sinfo, biggest
     finally:
         jm_intel_dec_deinit(h)

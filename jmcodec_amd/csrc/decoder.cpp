@@ -162,6 +162,10 @@ int Decoder::set_option(const char *key, long long v) {
         if (inited_ || v < 0 || v > 1) return -1;
         deint_rate_ = (int)v;
     }
+    else if (k == "verify_hash") {           // HEVC: check the decoded picture hash SEI (CRC, checksum) on the device; 2: a mismatch fails the handle
+        if (inited_ || v < 0 || v > 2) return -1;
+        verify_hash_ = (int)v;
+    }
     else if (k == "profile") { profile_ = v != 0; if (engine_) engine_->set_profile(profile_); }
     else if (k.rfind("chain_", 0) == 0 || k == "debug_stall" || k == "debug_no_bi" || k == "early_intra_ahead") {    // engine-wide knobs (every handle of the device), after init
         if (!engine_ || !engine_->set_knob(k, v)) return -1;
@@ -200,10 +204,32 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "color_matrix") return color_matrix_;
     if (k == "color_range") return color_range_;
     if (k == "pictures") return stat_pictures_;
+    // option verify_hash: pictures that carried a hash message / compared / differing / not compared (failed batch) / carrying MD5 (never compared)
+    if (k == "hash_pictures") return stat_hash_pics_;
+    if (k == "hash_checked") return stat_hash_checked_;
+    if (k == "hash_mismatch") return stat_hash_mismatch_;
+    if (k == "hash_unchecked") return stat_hash_unchecked_;
+    if (k == "hash_md5") return stat_hash_md5_;
+    if (k == "hash_first_bad_poc") return stat_hash_bad_poc_;
+    if (k.rfind("hash_last_crc:", 0) == 0 || k.rfind("hash_last_checksum:", 0) == 0) {
+        const bool crc = k[10] == 'c' && k[11] == 'r'; const int c = atoi(k.c_str() + (crc ? 14 : 19));
+        return c >= 0 && c < 3 ? (long long)hash_last_[(crc ? 0 : 3) + c].load() : -1; }
+    // ... and the messages themselves, in decode order (tests): hash_sei_poc:<n>, hash_sei_type:<n>, hash_sei_value:<n>:<component>
+    if (k.rfind("hash_sei_", 0) == 0) {
+        const size_t colon = k.find(':'); if (colon == std::string::npos) return -1;
+        const size_t i = (size_t)atoll(k.c_str() + colon + 1); if (i >= hash_seen_.size()) return -1;
+        if (k.compare(0, colon, "hash_sei_poc") == 0) return hash_seen_[i].poc;
+        if (k.compare(0, colon, "hash_sei_type") == 0) return hash_seen_[i].h.type;
+        const size_t c2 = k.find(':', colon + 1);
+        if (k.compare(0, colon, "hash_sei_value") == 0 && c2 != std::string::npos) { const int c = atoi(k.c_str() + c2 + 1);
+            return c >= 0 && c < 3 ? (long long)hash_seen_[i].h.v[c] : -1; }
+        return -1;
+    }
     if (k == "job_bytes") return stat_job_bytes_;
     if (k == "job_regrown") return stat_job_regrown_;          // job slots grown on demand (a few per handle, then none)
     if (k == "job_slot_bytes") { long long n = 0; for (auto &j : jobs_) n += (long long)j.cap; return n; }   // page-locked job memory of this handle right now
     if (k == "errors") return stat_errors_;
+    if (k == "failed") return failed_ ? 1 : 0;                 // the handle has failed (jm_amddec_last_error says why): every call returns an error from now on
     // MJPEG: pictures dispatched, the active sequence's sampling (0x22 / 0x21 / 0x11, 0x10 = grey), pictures that came with a restart interval
     if (k == "jpeg_pictures") return stat_jpeg_pics_;
     if (k == "jpeg_sampling") return codec_ == 2 && seq_active_ ? j_sampling_ : 0;
@@ -245,7 +271,7 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "wait_slot_ns") return stat_wait_slot_ns_;
     if (k == "parse_ns_p") return stat_parse_ns_p_;
     if (k.rfind("k_", 0) == 0 || k.rfind("eng_", 0) == 0) {          // engine-wide (all handles on this device), profile option
-        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg"};
+        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash"};
         if (!engine_) return 0;
         EngineStats es = engine_->stats();
         for (int i = 0; i < kKernelClasses; i++) {
@@ -1716,6 +1742,7 @@ void Decoder::submit_task(PicTask *t) {
     for (int s : t->out_before) { enqueue_output(s, ep.out[kBefore]); ep.out_mask |= 1u << (s & 255); }
     memset(&ep.pp, 0, sizeof ep.pp);
     if (ep.has_picture && t->hevc) hevc_fill_engine_pic(t, ep);
+    else if (t->hevc && t->hevc->hash.type > 0 && !parse_only_) stat_hash_unchecked_++;      // (a failed handle's picture is not decoded: nothing to compare)
     else if (ep.has_picture && t->jpeg) jpeg_fill_engine_pic(t, ep);
     else if (ep.has_picture) {
         JobSlot &js = jobs_[t->job_slot];
@@ -1791,6 +1818,20 @@ void Decoder::on_device_wait_error(int code) {
     stat_errors_++; stat_wait_errors_++;
     if (code & 64) note_error("device: a kernel met a motion record it was compiled without (code " + std::to_string(code) + "): the picture is damaged");
     else note_error("device: a wait between workgroups timed out (code " + std::to_string(code) + "): the picture may be damaged");
+}
+
+// engine thread: the picture's hashes as the device computed them (Engine::complete compared them with the SEI's values)
+void Decoder::on_picture_hash(const EnginePic &p, const uint32_t *words, int bad) {
+    if (!words) { stat_hash_unchecked_++; return; }
+    for (int k = 0; k < 6; k++) hash_last_[k] = words[k];
+    stat_hash_checked_++;
+    if (bad < 0) return;
+    if (stat_hash_mismatch_++ == 0) stat_hash_bad_poc_ = p.hash_poc;
+    static const char *const comp[3] = {"Y", "Cb", "Cr"};
+    char msg[160];
+    snprintf(msg, sizeof msg, "picture hash mismatch: POC %d, component %s, %s expected 0x%x got 0x%x", p.hash_poc, comp[bad],
+             p.hash_type == 1 ? "crc" : "checksum", p.hash_want[bad], words[(p.hash_type == 1 ? 0 : 3) + bad]);
+    if (verify_hash_ == 2) fail(msg); else note_error(msg);
 }
 
 // called by the engine thread when the batch containing this picture has finished on the device

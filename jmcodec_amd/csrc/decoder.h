@@ -10,6 +10,7 @@
 #include "h264_cavlc.h"
 #include "h264_syntax.h"
 #include "hevc_slice.h"
+#include "hevc_sei.h"
 #include "jpeg_syntax.h"
 #include "jobs.h"
 #include "scale_packed.h"    // build_scale_taps
@@ -78,6 +79,7 @@ struct HevcTask {
     std::shared_ptr<HevcColMotion> col_out;
     size_t off_ctbs = 0, off_qp8 = 0, off_pus = 0, off_tbs = 0, off_itbs = 0, off_coefs = 0, off_wps = 0;
     int n_pus = 0, n_tbs = 0, n_itbs = 0; bool any_sao = false, any_deblock = false;
+    HevcPicHash hash;                          // option verify_hash: what the picture's suffix SEI says its samples hash to (type -1: nothing)
 };
 
 // MJPEG picture (codec_type 2): its headers' snapshot, its entropy-coded bytes, and where the packed job list sits in the job buffer
@@ -180,6 +182,9 @@ public:
     void on_engine_done(const struct EnginePic &p, bool failed = false);
     void on_engine_error(const std::string &msg) { fail(msg); }     // engine: a resource this handle's frames need could not be had
     void on_device_wait_error(int code);       // engine: a kernel's bounded wait gave up while this handle's picture was decoded
+    // engine: the device's hashes of a picture that carried a CRC / checksum SEI (words: CRC of Y, Cb, Cr, then their checksums; nullptr = the picture's
+    // batch failed or was recovered, nothing to compare); bad: -1, or the first component whose value differs from the SEI's
+    void on_picture_hash(const struct EnginePic &p, const uint32_t *words, int bad);
     struct EngineDecoderState &engine_state() { return *eng_state_; }
     // display frames that are decoded and packed and that the caller has not fetched yet (the engine asks: is this handle's next picture urgent?)
     int frames_done_unfetched() const { return done_unfetched_.load(std::memory_order_relaxed); }
@@ -222,6 +227,7 @@ private:
     bool hevc_activate(const HevcSps &sps);
     bool hevc_build_refs(const HevcSliceHeader &sh, HevcSliceRefs &refs);
     void hevc_dispatch_pending();
+    void hevc_handle_suffix_sei(const uint8_t *nal, size_t len);
     void hevc_bump(std::vector<int> &out, bool all, bool use_fullness);
     void hevc_parse_task(PicTask *t);
     void hevc_fill_engine_pic(PicTask *t, struct EnginePic &ep);
@@ -348,6 +354,13 @@ private:
     HevcDigest hdigest_;                       // written by the parse worker (sync option)
     long long stat_i_ = 0, stat_p_ = 0, stat_b_ = 0;
     std::vector<int> display_pocs_;            // diagnostic (get via stats)
+    // option verify_hash (before init): 0 off -- suffix SEI is not looked at; 1 verify and count; 2 a mismatch fails the handle
+    int verify_hash_ = 0;
+    std::atomic<long long> stat_hash_pics_{0}, stat_hash_checked_{0}, stat_hash_mismatch_{0}, stat_hash_unchecked_{0}, stat_hash_md5_{0};
+    std::atomic<long long> stat_hash_bad_poc_{-2147483648ll};
+    std::atomic<uint32_t> hash_last_[6] = {};  // the device's words of the most recently completed hashed picture (engine thread writes)
+    struct HashSeen { int poc; HevcPicHash h; };
+    std::vector<HashSeen> hash_seen_;          // diagnostic (stats hash_sei_*): the hash messages in decode order, the first 65536
     std::vector<uint8_t> display_fields_;      // per output frame: the kept field (display_entry); only filled with option deinterlace
     std::vector<uint32_t> display_pics_;       // per output frame: the display picture it shows (display_entry); only filled at field rate
     uint32_t display_count_ = 0;               // display pictures queued so far (display_entry calls)

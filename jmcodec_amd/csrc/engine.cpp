@@ -487,6 +487,18 @@ void Engine::launch(Lane &ln, Batch &b) {
         }
     }
     if (any_jpeg && profile_ && !b.jev[0]) for (auto &e : b.jev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
+    // pictures to verify (option verify_hash): the result words, when the batch first holds one.  Without them the pictures go unverified, and say so
+    b.any_hash = false;
+    for (auto &p : b.pics) b.any_hash |= p.codec == 1 && p.has_picture && p.hp.hash_mode != 0;
+    if (b.any_hash && !b.d_hash) {
+        const size_t bytes = sizeof(uint32_t) * kMaxBatch * kHashStride;
+        if (hipMalloc((void **)&b.d_hash, bytes) != hipSuccess || hipHostMalloc((void **)&b.h_hash, bytes, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            if (b.d_hash) hipFree(b.d_hash);
+            b.d_hash = nullptr; b.h_hash = nullptr; b.any_hash = false;
+            for (auto &p : b.pics) p.hp.hash_mode = 0;
+        }
+    }
     HevcBatchDims hd;
     const EnginePic *last_upload[4] = {nullptr, nullptr, nullptr, nullptr};      // per copy stream (upload k went to stream k % n_copy_)
     b.pmask = 0;
@@ -543,6 +555,7 @@ void Engine::launch(Lane &ln, Batch &b) {
             hd.max_ctb_w = std::max(hd.max_ctb_w, h.ctb_w); hd.max_ctb_h = std::max(hd.max_ctb_h, h.ctb_h);
             hd.max_w = std::max(hd.max_w, h.w); hd.max_h = std::max(hd.max_h, h.h); hd.any_intra |= (h.stages & HPS_INTRA) != 0;
             hd.any_deblock |= (h.stages & HPS_DEBLOCK) != 0; hd.any_sao |= (h.stages & HPS_SAO) != 0;
+            if (h.hash_mode) { hd.any_hash = true; b.alg[8] += (long long)h.w * h.h * 3 / 2; b.npics[8]++; }
         }
         if (p.has_picture) {
             max_mbs = std::max(max_mbs, p.mb_w * p.mb_h); max_mb_h = std::max(max_mb_h, p.mb_h);
@@ -609,12 +622,14 @@ void Engine::launch(Lane &ln, Batch &b) {
     run_side(b, kBefore, st, true);
     if (any_hevc && (hd.max_pus || hd.max_tbs || hd.any_intra || hd.any_deblock || hd.any_sao)) {
         // HEVC batch (its own lane, so never mixed with H.264 pictures): MC + residual | intra diagonals | deblocking + SAO
-        hipEvent_t ev[4] = {b.pev[1], b.pev[2], b.pev[3], b.pev[4]};
-        launch_hevc_picture_batch(b.d_hpics, n, hd, b.d_progress, st, profile_ ? ev : nullptr);
+        hipEvent_t ev[5] = {b.pev[1], b.pev[2], b.pev[3], b.pev[4], b.pev[18]};
+        launch_hevc_picture_batch(b.d_hpics, n, hd, b.d_progress, st, profile_ ? ev : nullptr, b.d_hash);
         if (hd.max_pus || hd.max_tbs) b.pmask |= 2;
         if (hd.any_intra) b.pmask |= 4;
         if (hd.any_deblock || hd.any_sao) b.pmask |= 8;
         b.last_ev = 4;
+        // the hashes of the finished pictures, to the host behind the kernel (Engine::complete compares them)
+        if (hd.any_hash) { hipMemcpyAsync(b.h_hash, b.d_hash, sizeof(uint32_t) * (size_t)n * kHashStride, hipMemcpyDeviceToHost, st); b.pmask |= 2048; b.last_ev = 18; }
     }
     if (any_jpeg && max_jpeg_items > 0) {        // MJPEG pictures of the batch: independent of everything else in it
         const bool timed = profile_ && b.jev[0] && b.jev[1];
@@ -896,7 +911,7 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
         };
         add(3, 0, 1, b.pmask & 1); add(0, 1, 2, b.pmask & 2); add(1, 2, 3, b.pmask & 4); add(2, 3, 4, b.pmask & 8); add(3, 5, 6, b.pmask & 16);
         add(4, 4, 7, b.pmask & 32); add(5, 10, 11, b.pmask & 64); add(5, 12, 13, b.pmask & 128);
-        add(6, 14, 15, b.pmask & 256); add(6, 16, 17, b.pmask & 512);
+        add(6, 14, 15, b.pmask & 256); add(6, 16, 17, b.pmask & 512); add(8, 4, 18, b.pmask & 2048);
         if (b.pmask & 1024) { float ms = 0; if (hipEventElapsedTime(&ms, b.jev[0], b.jev[1]) == hipSuccess) { st_.ns[7] += ms * 1e6; st_.launches[7]++; } }
         for (int k = 0; k < kKernelClasses; k++) { st_.pics[k] += b.npics[k]; st_.alg_bytes[k] += b.alg[k]; }
         st_.batches++; st_.batch_pics += (long long)b.pics.size();
@@ -942,6 +957,17 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
     // a kernel whose bounded wait gave up (damaged hand-over between workgroups) left a code in the picture's error word: the handle reports it
     for (size_t i = 0; i < b.pics.size(); i++) if (b.h_err[i]) { b.pics[i].dec->on_device_wait_error(b.h_err[i]); b.h_err[i] = 0;
         std::lock_guard<std::mutex> lk(sm_); st_.wait_errors++; }
+    // option verify_hash: what the device computed against what the picture's SEI says.  A picture of a failed or recovered batch, or one whose hashes
+    // could not be computed, is reported as not compared
+    for (size_t i = 0; i < b.pics.size(); i++) {
+        const EnginePic &p = b.pics[i];
+        if (p.codec != 1 || p.hash_type <= 0) continue;
+        if (failed || b.redo || !p.has_picture || !p.hp.hash_mode || !b.h_hash) { p.dec->on_picture_hash(p, nullptr, -1); continue; }
+        const uint32_t *words = b.h_hash + i * kHashStride, *got = words + (p.hash_type == 1 ? 0 : 3);
+        int bad = -1;
+        for (int c = 2; c >= 0; c--) if (got[c] != p.hash_want[c]) bad = c;
+        p.dec->on_picture_hash(p, words, bad);
+    }
     for (auto &p : b.pics) p.dec->on_engine_done(p, failed);
     b.pics.clear();
 }

@@ -76,6 +76,8 @@ struct EnginePic {
     int reach_cols = 0;                             // ... and how many macroblocks further right (both space the pictures of a chain launch, Engine::launch)
     long long alg_bytes[5] = {0, 0, 0, 0, 0};       // algorithmic bytes of this picture per kernel class (recon, intra, deblock, packout, deint)
     unsigned long long seq = 0;                     // position in its decoder's decode order (Engine::submit)
+    // HEVC, option verify_hash: the picture's SEI carries a CRC (1) or a checksum (2) of Y, Cb, Cr (0: nothing to verify); hp.hash_mode asks for k_hevc_pichash
+    int hash_type = 0, hash_poc = 0; uint32_t hash_want[3] = {0, 0, 0};
     // chaining: the engine currently forms chain launches -- an intra picture that can join one stays on the ordinary lane
     int lane(bool chaining = false) const {
         // MJPEG pictures ride the HEVC lane: its batches run everything on the lane's stream, with no pre-stream and no chain logic
@@ -86,8 +88,9 @@ struct EnginePic {
 };
 
 // per kernel class: 0 recon_inter, 1 intra, 2 deblock (prep+lds), 3 packout (every pack-out kernel), 4 chain (k_chain: recon + deblock),
-// 5 rgb_pack (k_rgb_pack alone: its frames are counted in class 3 too), 6 deint (k_deint alone, likewise), 7 jpeg (k_jpeg_recon)
-constexpr int kKernelClasses = 8;
+// 5 rgb_pack (k_rgb_pack alone: its frames are counted in class 3 too), 6 deint (k_deint alone, likewise), 7 jpeg (k_jpeg_recon),
+// 8 pichash (k_hevc_pichash: pictures hashed, 1.5 w h bytes each)
+constexpr int kKernelClasses = 9;
 struct EngineStats {
     double ns[kKernelClasses] = {}; long long launches[kKernelClasses] = {}, pics[kKernelClasses] = {}, alg_bytes[kKernelClasses] = {};
     long long batches = 0, batch_pics = 0, chain_batches = 0, chain_pics = 0, wait_errors = 0, chain_recoveries = 0;
@@ -156,6 +159,9 @@ private:
         int *d_progress = nullptr;                            // CTB row progress counters of k_hevc_intra
         int *d_ctl = nullptr;                                 // H.264: kMaxBatch control blocks (chain_common.h), cleared once per batch
         int *h_err = nullptr, *d_err = nullptr;               // error words, one per picture: pinned host memory and its device address
+        // result words of k_hevc_pichash, kHashStride per picture: device memory and the pinned copy behind the kernel; allocated when the batch first
+        // holds a picture to verify (Engine::launch)
+        uint32_t *d_hash = nullptr, *h_hash = nullptr; bool any_hash = false;
         // redo: an earlier batch of the lane was recovered, this one read its (then damaged) output
         bool any_chain = false, chain_with_intra = false, redo = false; int max_depth = 1;
         int max_mbs = 0, max_mb_h = 0; bool any_bipred = false, any_field = false;
@@ -166,8 +172,9 @@ private:
         // OutTables hands out its surfaces
         uint8_t *deint_scratch = nullptr; size_t deint_cap = 0;
         // packed: surfaces were read by k_packout (before the copies)
-        // (profile events 10 / 11 and 12 / 13 bracket the k_rgb_pack launches before / after the decode kernels, 14 / 15 and 16 / 17 k_deint's)
-        ihipEvent_t *done = nullptr, *kdone = nullptr, *packed = nullptr, *pre_done = nullptr, *pev[18] = {nullptr};
+        // (profile events 10 / 11 and 12 / 13 bracket the k_rgb_pack launches before / after the decode kernels, 14 / 15 and 16 / 17 k_deint's;
+        // 18 is recorded behind k_hevc_pichash)
+        ihipEvent_t *done = nullptr, *kdone = nullptr, *packed = nullptr, *pre_done = nullptr, *pev[19] = {nullptr};
         std::vector<EnginePic> pics;
         unsigned pmask = 0;
         long long alg[kKernelClasses] = {}; int npics[kKernelClasses] = {};

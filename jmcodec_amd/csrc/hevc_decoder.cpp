@@ -38,6 +38,8 @@ void Decoder::hevc_handle_nal(const uint8_t *nal, size_t len) {
     if (layer != 0 || tid < 0) return;
     const bool is_slice = type <= 9 || (type >= 16 && type <= 21);
     if (!is_slice && type != 33 && type != 34) {
+        // suffix SEI belongs to the picture in front of it: it never ends an access unit.  (A hash in a prefix SEI, type 39, is not looked at.)
+        if (type == 40) { if (verify_hash_) hevc_handle_suffix_sei(nal, len); return; }
         if (type == 32 || type == 35 || type == 39) hevc_dispatch_pending();            // VPS, AUD, prefix SEI: a new access unit starts
         if (type == 36 || type == 37) {                                              // end of sequence / bitstream: everything decoded so far is output
             hevc_dispatch_pending(); h_seen_eos_ = true;
@@ -240,9 +242,25 @@ bool Decoder::hevc_build_refs(const HevcSliceHeader &sh, HevcSliceRefs &rf) {
     return true;
 }
 
+// option verify_hash: the decoded picture hash of a suffix SEI NAL goes with the picture being collected; without one (a dropped RASL picture, or before
+// the first IRAP picture) it is ignored.  A second message for the same picture replaces the first.
+void Decoder::hevc_handle_suffix_sei(const uint8_t *nal, size_t len) {
+    std::vector<uint8_t> rbsp(len + Rbsp::kSlack);
+    const size_t n = Rbsp::unescape(nal + 2, len - 2, rbsp.data());
+    HevcPicHash h; bool found = false;
+    const int bad = parse_sei_picture_hash(rbsp.data(), n, h, found);
+    if (bad) { stat_errors_ += bad; note_error("malformed SEI message in a suffix SEI NAL unit: ignored"); }
+    if (found && pending_ && pending_->hevc) pending_->hevc->hash = h;
+}
+
 void Decoder::hevc_dispatch_pending() {
     if (!pending_) return;
     std::unique_ptr<PicTask> t = std::move(pending_);
+    if (t->hevc && t->hevc->hash.type >= 0) {
+        stat_hash_pics_++;
+        if (t->hevc->hash.type == 0) stat_hash_md5_++;           // counted, never compared: DESIGN.md 7
+        if (hash_seen_.size() < 65536) hash_seen_.push_back({t->hevc->poc, t->hevc->hash});
+    }
     dpb_[cur_].ref = 1;                            // "used for short-term reference" after decoding (8.3.2 decides later)
     const int done = cur_;
     cur_ = -1;
@@ -331,6 +349,7 @@ void Decoder::hevc_fill_engine_pic(PicTask *t, EnginePic &ep) {
     hp.pus = (const HevcPu *)(js.dev + ht.off_pus); hp.n_pus = ht.n_pus; hp.tbs = (const HevcTb *)(js.dev + ht.off_tbs); hp.n_tbs = ht.n_tbs;
     hp.itbs = (const HevcIntraTb *)(js.dev + ht.off_itbs); hp.n_itbs = ht.n_itbs; hp.coefs = (const uint32_t *)(js.dev + ht.off_coefs);
     hp.wps = (const HevcWp *)(js.dev + ht.off_wps); hp.resid = (int16_t *)(resid_ + (size_t)ht.work_slot * ((size_t)mb_w_ * mb_h_ * 768));
+    if (ht.hash.type > 0) { hp.hash_mode = 1; ep.hash_type = ht.hash.type; ep.hash_poc = ht.poc; for (int c = 0; c < 3; c++) ep.hash_want[c] = ht.hash.v[c]; }
     hp.stages = (ht.n_pus ? HPS_MC : 0) | (ht.n_tbs ? HPS_RESID : 0) | (ht.n_itbs ? HPS_INTRA : 0) | (ht.any_deblock ? HPS_DEBLOCK : 0) |
         (ht.any_sao ? HPS_SAO : 0);
     // which surfaces the picture reads: lets the engine put INDEPENDENT pictures of this handle (the B pictures of one pyramid level) into one batch

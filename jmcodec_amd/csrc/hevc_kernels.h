@@ -5,11 +5,17 @@
 
 namespace jmamd {
 struct HevcBatchDims { int max_pus = 0, max_tbs = 0, max_itbs = 0, max_ctb_w = 0, max_ctb_h = 0, max_w = 0, max_h = 0;
-    bool any_intra = false, any_deblock = false, any_sao = false; };
+    bool any_intra = false, any_deblock = false, any_sao = false;
+    bool any_hash = false; };        // some picture asks for its hashes (HevcPicParams::hash_mode): k_hevc_pichash runs behind the last filter
 // marks (optional, 4 events): before MC, after residual, after intra, after the loop filters
 constexpr int kHevcIntraSegs = 8;             // workgroups per CTB row in k_hevc_intra (each walks a run of consecutive CTBs)
 constexpr int kHevcProgressStride = 544 * kHevcIntraSegs;   // progress counters per picture: one per CTB row (8192 / 16 + slack) and segment
 // progress: device array of n * kHevcProgressStride ints (row progress counters of k_hevc_intra, cleared by this call)
-void launch_hevc_picture_batch(const HevcPicParams *d_pics, int n, const HevcBatchDims &m, int *progress, hipStream_t st, hipEvent_t *marks);
+// hash: the batch's result words (kHashStride per picture), needed when m.any_hash; marks then has a fifth event, recorded behind k_hevc_pichash
+void launch_hevc_picture_batch(const HevcPicParams *d_pics, int n, const HevcBatchDims &m, int *progress, hipStream_t st, hipEvent_t *marks, uint32_t *hash);
+// k_hevc_pichash (pichash.hip) alone: clears n * kHashStride words of d_hash on st, then per picture with hash_mode != 0 words 0..2 = the CRC of Y, Cb, Cr
+// of surf[cur] (coded size w x h), words 3..5 = their checksums (INTEGRATION.md "Picture hash")
+constexpr int kHashStride = 32;               // words per picture: the six results and padding to a cache line of their own (they are atomics' targets)
+void launch_hevc_pichash(const HevcPicParams *d_pics, int n, int max_h, uint32_t *d_hash, hipStream_t st);
 void hevc_kernels_init();
 }  // namespace jmamd

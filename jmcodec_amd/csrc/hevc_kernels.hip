@@ -971,7 +971,7 @@ static void upload_tables() {
 }
 void hevc_kernels_init() { upload_tables(); }
 
-void launch_hevc_picture_batch(const HevcPicParams *d_pics, int n, const HevcBatchDims &m, int *progress, hipStream_t st, hipEvent_t *marks) {
+void launch_hevc_picture_batch(const HevcPicParams *d_pics, int n, const HevcBatchDims &m, int *progress, hipStream_t st, hipEvent_t *marks, uint32_t *hash) {
     upload_tables();
     if (marks) hipEventRecord(marks[0], st);
     if (m.max_pus > 0) hipLaunchKernelGGL(k_hevc_mc, dim3(((m.max_pus + kMcWaves - 1) / kMcWaves + 7) & ~7, n), dim3(64 * kMcWaves), 0, st, d_pics);
@@ -997,6 +997,8 @@ void launch_hevc_picture_batch(const HevcPicParams *d_pics, int n, const HevcBat
     }
     if (m.any_sao) hipLaunchKernelGGL(k_hevc_sao, dim3((m.max_w / 4 + 63) / 64, n, (m.max_h + m.max_h / 2 + 3) / 4), dim3(256), 0, st, d_pics);
     if (marks) hipEventRecord(marks[3], st);
+    // the picture hashes read the finished surface: behind SAO, or deblocking, or reconstruction, whichever ran last
+    if (m.any_hash && hash) { launch_hevc_pichash(d_pics, n, m.max_h, hash, st); if (marks) hipEventRecord(marks[4], st); }
 }
 
 }  // namespace jmamd

@@ -2,6 +2,7 @@
 #include "../../include/jm_amd_dec.h"
 #include "decoder.h"
 #include "kernels.h"
+#include "hevc_kernels.h"
 #include <hip/hip_runtime_api.h>
 #include <cstddef>
 #include <cstdio>
@@ -168,6 +169,23 @@ __attribute__((visibility("default"))) int jm_amddec_deinterlace2_device(const v
     jmamd::DeintJob job{static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst_first), pitch, chroma_offset, w, hgt, dst_pitch, dst_chroma_offset, 0, mode,
         first_field - 1, 4 * t * t, static_cast<uint8_t *>(dst_second)};
     return run_one_job(job, stream, [&](const jmamd::DeintJob *d_job, hipStream_t st) { jmamd::launch_deint2(d_job, 1, jmamd::deint2_items(w, hgt), st); });
+}
+
+// the two parallel picture hashes of one surface: the kernel the decoder runs behind a picture with a hash SEI, on a one-picture batch
+__attribute__((visibility("default"))) int jm_amddec_picture_hash_device(const void *src, int pitch, int chroma_offset, int w, int hgt, unsigned crc[3],
+    unsigned checksum[3], void *stream) {
+    if (!src || !crc || !checksum || w < 2 || hgt < 2 || ((w | hgt) & 1) || w > 16384 || hgt > 16384 || pitch < w || chroma_offset < 0) return -1;
+    jmamd::HevcPicParams pp = {};
+    pp.w = w; pp.h = hgt; pp.pitch = pitch; pp.chroma_offset = chroma_offset; pp.cur = 0; pp.hash_mode = 1;
+    pp.surf[0] = static_cast<uint8_t *>(const_cast<void *>(src));
+    uint32_t *d_hash = nullptr, words[6] = {0, 0, 0, 0, 0, 0};
+    if (hipMalloc((void **)&d_hash, sizeof(uint32_t) * jmamd::kHashStride) != hipSuccess) return -1;
+    int r = run_one_job(pp, stream, [&](const jmamd::HevcPicParams *d_pp, hipStream_t st) {
+        jmamd::launch_hevc_pichash(d_pp, 1, hgt, d_hash, st);
+        hipMemcpyAsync(words, d_hash, sizeof words, hipMemcpyDeviceToHost, st); });
+    hipFree(d_hash);
+    if (r == 0) for (int c = 0; c < 3; c++) { crc[c] = words[c]; checksum[c] = words[3 + c]; }
+    return r;
 }
 
 static_assert(sizeof(jm_amddec_rgb_spec) == sizeof(jmamd::RgbSpec) && offsetof(jm_amddec_rgb_spec, bias) == offsetof(jmamd::RgbSpec, bias),

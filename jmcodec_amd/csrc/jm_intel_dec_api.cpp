@@ -177,6 +177,8 @@ JM_EXPORT int jm_amdintel_is_exit(jm_amdintel_handle h) {
     if (!c->eof) return 0;
     if (c->cb) c->deliver();
     else if (!c->have && c->flushed && !jm_amddec_is_exit(c->dec)) c->take(0);   // the drain call that finds the queue empty is what ends the decoder (nv_dec.cpp:460-466)
+    // (a handle that failed -- option verify_hash 2 met a wrong picture, say -- never drains: the loop of the reference's harness ends here all the same)
+    if (!c->have && c->flushed && jm_amddec_get_stat(c->dec, "failed") == 1) return 1;
     return !c->have && c->flushed && jm_amddec_is_exit(c->dec);
 }
 JM_EXPORT int jm_amdintel_is_hw_support(void) { return jm_amddec_is_hw_support(); }
