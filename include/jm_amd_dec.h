@@ -65,7 +65,8 @@ int  jm_amddec_is_hw_support(void);
  *       "chain_lag", "chain_streams", "debug_stall" (DESIGN.md 4b); before init: "job_slots" (pictures in flight per handle, 8..64; default 40 for H.264 up
  *       to 1080p, else 24);
  *       "crop_x" / "crop_y" / "crop_w" / "crop_h" / "target_width" / "target_height" (before init: scaled and cropped output, see below);
- *       "verify_hash" (before init, HEVC: 1 / 2 = check the decoded picture hash SEI on the device, see below);
+ *       "verify_hash" (before init, HEVC: 1 / 2 = check the decoded picture hash SEI on the device, see below); "verify_md5" (before init, 0 / 1:
+ *       with verify_hash, MD5 messages are verified too, see below);
  *       tests only: "fast_parse" (0 = every macroblock through the general parser path), "job_digest" (1 = digest of the job lists; implies sync) */
 /* like jm_amddec_decode_frame without input: *got_frame = 1 when a display-order frame became ready (never signals end of stream) */
 int  jm_amddec_poll_frame(int *got_frame, jm_amddec_handle h);
@@ -179,15 +180,24 @@ int  jm_amddec_rgb_device(const void *d_src, int pitch, int chroma_offset, int w
  *   0 (default) off: suffix SEI is not looked at and nothing changes;  1: the CRC or the checksum is computed on the device behind the picture's last
  *   kernel (k_hevc_pichash) and compared, mismatches are counted;  2: the first mismatch also fails the handle, jm_amddec_last_error then reads
  *   "picture hash mismatch: POC <n>, component <Y|Cb|Cr>, <crc|checksum> expected 0x... got 0x...".
- * MD5 messages are counted and never compared.  A hash in a prefix SEI is ignored; a malformed message counts in "errors" and is ignored.
+ * Option "verify_md5", before init (0 default, 1; set_option returns -1 after init and for other values), takes effect only with verify_hash 1 or 2:
+ *   0: MD5 messages (hash_type 0) are counted in "hash_md5" and never compared -- no kernel, table or allocation appears;  1: the three MD5 digests
+ *   (RFC 1321, of each component's samples as a raster byte array of the coded size) are computed behind the picture's last kernel (k_hevc_md5) and
+ *   compared; the picture counts in "hash_checked" like a CRC picture, and the error text reads "picture hash mismatch: POC <n>, component <Y|Cb|Cr>,
+ *   md5 expected <32 hex digits> got <32 hex digits>".  An MD5 chain is serial: about 20 ms per 1080p picture, and the batch waits for it.
+ * A hash in a prefix SEI is ignored; a malformed message counts in "errors" and is ignored.
  * Stats: "hash_pictures" (pictures that carried a hash message), "hash_checked", "hash_mismatch", "hash_unchecked" (their batch failed, or the handle
- * had), "hash_md5", "hash_first_bad_poc" (-2^31: none), "hash_last_crc:<c>" / "hash_last_checksum:<c>" (c = 0..2: the device's values of the most
+ * had), "hash_md5" (pictures that carried MD5), "hash_first_bad_poc" (-2^31: none), "hash_last_crc:<c>" / "hash_last_checksum:<c>" (c = 0..2: the device's values of the most
  * recently completed hashed picture), "hash_sei_poc:<n>" / "hash_sei_type:<n>" / "hash_sei_value:<n>:<c>" (the n-th hash message in decode order as
- * parsed; works on a parse_only handle), and with option "profile" k_pichash_ns / _n / _pics / _alg_bytes.
+ * parsed; works on a parse_only handle), "hash_last_md5:<c>:<k>" (the device's digest of the most recent MD5-verified picture; k = 0..3: bytes
+ * 4k .. 4k+3 of the 16 read big-endian, so four words printed %08x give the usual hex string), "hash_sei_md5:<n>:<c>:<k>" (the same view of the n-th
+ * parsed message), and with option "profile" k_pichash_ns / _n / _pics / _alg_bytes and k_md5_ns / _n / _pics / _alg_bytes.
  *   jm_amddec_picture_hash_device: stand-alone, both hashes of one pitch-linear NV12 surface in device memory (luma rows at `pitch`, the UV rows from
  *     byte chroma_offset; w x h even, 2..16384): crc[c] and checksum[c] of Y, Cb, Cr.  stream: a hipStream_t or NULL; synchronised before returning.
  *     Returns 0, -1 for invalid arguments, or a negative hipError. */
 int  jm_amddec_picture_hash_device(const void *d_src, int pitch, int chroma_offset, int w, int h, unsigned crc[3], unsigned checksum[3], void *stream);
+/*   jm_amddec_picture_md5_device: its counterpart for MD5, same argument rules and return codes: md5[c] = the 16 digest bytes, RFC order, of Y, Cb, Cr. */
+int  jm_amddec_picture_md5_device(const void *d_src, int pitch, int chroma_offset, int w, int h, unsigned char md5[3][16], void *stream);
 /* SURVEY 8f f4 -- the encoder-side pre-processing of the reference (/root/reference/nv_enc/nv_enc.cpp:1022-1079: cuMemcpy2D of the luma plane +
  * the InterleaveUV kernel; the CPU loop of intel_enc.cpp:316-387) as one HIP kernel, device to device: a tight frame (src_fmt 1 = I420
  * planar Y,U,V; 0 = tight NV12) becomes a pitch-linear NV12 surface (luma rows at `pitch`, interleaved UV rows from row `height`), the layout an

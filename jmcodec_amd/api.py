@@ -95,6 +95,7 @@ def lib():
     L.jm_amddec_rgb_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(RgbSpec), vp, vp]
     L.jm_amddec_picture_hash_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), vp]
+    L.jm_amddec_picture_md5_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte * 16), vp]
     _LIB = L
     return L
 
@@ -195,6 +196,14 @@ def picture_hash_device(src, pitch, chroma_offset, width, height, stream=None):
     crc, chk = (C.c_uint * 3)(), (C.c_uint * 3)()
     rc = lib().jm_amddec_picture_hash_device(src, pitch, chroma_offset, width, height, crc, chk, stream)
     return rc, list(crc), list(chk)
+
+
+def picture_md5_device(src, pitch, chroma_offset, width, height, stream=None):
+    """jm_amddec_picture_md5_device: the MD5 (RFC 1321; hash_type 0 of the same SEI message) of each component of one pitch-linear NV12 surface in
+    device memory.  Returns (rc, [digest of Y, Cb, Cr: 16 bytes each]); rc 0 or < 0."""
+    md5 = ((C.c_ubyte * 16) * 3)()
+    rc = lib().jm_amddec_picture_md5_device(src, pitch, chroma_offset, width, height, md5, stream)
+    return rc, [bytes(md5[c]) for c in range(3)]
 
 
 # ---- RGB output (include/jm_amd_dec.h; the conversion C is defined in INTEGRATION.md "RGB output") ----------

@@ -166,6 +166,10 @@ int Decoder::set_option(const char *key, long long v) {
         if (inited_ || v < 0 || v > 2) return -1;
         verify_hash_ = (int)v;
     }
+    else if (k == "verify_md5") {            // ... and the MD5 too (k_hevc_md5: three serial chains per picture; takes effect with verify_hash 1 or 2)
+        if (inited_ || v < 0 || v > 1) return -1;
+        verify_md5_ = (int)v;
+    }
     else if (k == "profile") { profile_ = v != 0; if (engine_) engine_->set_profile(profile_); }
     else if (k.rfind("chain_", 0) == 0 || k == "debug_stall" || k == "debug_no_bi" || k == "early_intra_ahead") {    // engine-wide knobs (every handle of the device), after init
         if (!engine_ || !engine_->set_knob(k, v)) return -1;
@@ -214,10 +218,25 @@ long long Decoder::get_stat(const char *key) const {
     if (k.rfind("hash_last_crc:", 0) == 0 || k.rfind("hash_last_checksum:", 0) == 0) {
         const bool crc = k[10] == 'c' && k[11] == 'r'; const int c = atoi(k.c_str() + (crc ? 14 : 19));
         return c >= 0 && c < 3 ? (long long)hash_last_[(crc ? 0 : 3) + c].load() : -1; }
-    // ... and the messages themselves, in decode order (tests): hash_sei_poc:<n>, hash_sei_type:<n>, hash_sei_value:<n>:<component>
+    // hash_last_md5:<c>:<k>: bytes 4 k .. 4 k + 3 of component c's digest, read big-endian (four of them printed %08x give the usual hex string)
+    if (k.rfind("hash_last_md5:", 0) == 0) {
+        const size_t c2 = k.find(':', 14); if (c2 == std::string::npos) return -1;
+        const int c = atoi(k.c_str() + 14), w = atoi(k.c_str() + c2 + 1);
+        return c >= 0 && c < 3 && w >= 0 && w < 4 ? (long long)hash_last_md5_[4 * c + w].load() : -1;
+    }
+    // ... and the messages themselves, in decode order (tests): hash_sei_poc:<n>, hash_sei_type:<n>, hash_sei_value:<n>:<component>,
+    // hash_sei_md5:<n>:<component>:<k> (the same view of an MD5 message's digest)
     if (k.rfind("hash_sei_", 0) == 0) {
         const size_t colon = k.find(':'); if (colon == std::string::npos) return -1;
         const size_t i = (size_t)atoll(k.c_str() + colon + 1); if (i >= hash_seen_.size()) return -1;
+        if (k.compare(0, colon, "hash_sei_md5") == 0) {
+            const size_t c2 = k.find(':', colon + 1), c3 = c2 == std::string::npos ? c2 : k.find(':', c2 + 1);
+            if (c3 == std::string::npos) return -1;
+            const int c = atoi(k.c_str() + c2 + 1), w = atoi(k.c_str() + c3 + 1);
+            if (c < 0 || c > 2 || w < 0 || w > 3) return -1;
+            const uint8_t *d = hash_seen_[i].h.md5[c] + 4 * w;
+            return (long long)((uint32_t)d[0] << 24 | (uint32_t)d[1] << 16 | (uint32_t)d[2] << 8 | d[3]);
+        }
         if (k.compare(0, colon, "hash_sei_poc") == 0) return hash_seen_[i].poc;
         if (k.compare(0, colon, "hash_sei_type") == 0) return hash_seen_[i].h.type;
         const size_t c2 = k.find(':', colon + 1);
@@ -271,7 +290,7 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "wait_slot_ns") return stat_wait_slot_ns_;
     if (k == "parse_ns_p") return stat_parse_ns_p_;
     if (k.rfind("k_", 0) == 0 || k.rfind("eng_", 0) == 0) {          // engine-wide (all handles on this device), profile option
-        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash"};
+        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5"};
         if (!engine_) return 0;
         EngineStats es = engine_->stats();
         for (int i = 0; i < kKernelClasses; i++) {
@@ -1742,7 +1761,7 @@ void Decoder::submit_task(PicTask *t) {
     for (int s : t->out_before) { enqueue_output(s, ep.out[kBefore]); ep.out_mask |= 1u << (s & 255); }
     memset(&ep.pp, 0, sizeof ep.pp);
     if (ep.has_picture && t->hevc) hevc_fill_engine_pic(t, ep);
-    else if (t->hevc && t->hevc->hash.type > 0 && !parse_only_) stat_hash_unchecked_++;      // (a failed handle's picture is not decoded: nothing to compare)
+    else if (t->hevc && (t->hevc->hash.type > 0 || (t->hevc->hash.type == 0 && verify_md5_)) && !parse_only_) stat_hash_unchecked_++;      // (a failed handle's picture is not decoded: nothing to compare)
     else if (ep.has_picture && t->jpeg) jpeg_fill_engine_pic(t, ep);
     else if (ep.has_picture) {
         JobSlot &js = jobs_[t->job_slot];
@@ -1831,6 +1850,19 @@ void Decoder::on_picture_hash(const EnginePic &p, const uint32_t *words, int bad
     char msg[160];
     snprintf(msg, sizeof msg, "picture hash mismatch: POC %d, component %s, %s expected 0x%x got 0x%x", p.hash_poc, comp[bad],
              p.hash_type == 1 ? "crc" : "checksum", p.hash_want[bad], words[(p.hash_type == 1 ? 0 : 3) + bad]);
+    if (verify_hash_ == 2) fail(msg); else note_error(msg);
+}
+
+// ... and its MD5s (option verify_md5): three digests of 16 bytes
+void Decoder::on_picture_md5(const EnginePic &p, const uint8_t *digests, int bad) {
+    for (int k = 0; k < 12; k++) { const uint8_t *d = digests + 4 * k; hash_last_md5_[k] = (uint32_t)d[0] << 24 | (uint32_t)d[1] << 16 | (uint32_t)d[2] << 8 | d[3]; }
+    stat_hash_checked_++;
+    if (bad < 0) return;
+    if (stat_hash_mismatch_++ == 0) stat_hash_bad_poc_ = p.hash_poc;
+    static const char *const comp[3] = {"Y", "Cb", "Cr"};
+    char want[33], got[33], msg[192];
+    for (int k = 0; k < 16; k++) { snprintf(want + 2 * k, 3, "%02x", p.md5_want[bad][k]); snprintf(got + 2 * k, 3, "%02x", digests[16 * bad + k]); }
+    snprintf(msg, sizeof msg, "picture hash mismatch: POC %d, component %s, md5 expected %s got %s", p.hash_poc, comp[bad], want, got);
     if (verify_hash_ == 2) fail(msg); else note_error(msg);
 }
 

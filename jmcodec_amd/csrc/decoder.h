@@ -185,6 +185,8 @@ public:
     // engine: the device's hashes of a picture that carried a CRC / checksum SEI (words: CRC of Y, Cb, Cr, then their checksums; nullptr = the picture's
     // batch failed or was recovered, nothing to compare); bad: -1, or the first component whose value differs from the SEI's
     void on_picture_hash(const struct EnginePic &p, const uint32_t *words, int bad);
+    // ... and of a picture that carried an MD5 SEI (option verify_md5): digests = 3 x 16 bytes, Y, Cb, Cr; bad as above
+    void on_picture_md5(const struct EnginePic &p, const uint8_t *digests, int bad);
     struct EngineDecoderState &engine_state() { return *eng_state_; }
     // display frames that are decoded and packed and that the caller has not fetched yet (the engine asks: is this handle's next picture urgent?)
     int frames_done_unfetched() const { return done_unfetched_.load(std::memory_order_relaxed); }
@@ -356,6 +358,8 @@ private:
     std::vector<int> display_pocs_;            // diagnostic (get via stats)
     // option verify_hash (before init): 0 off -- suffix SEI is not looked at; 1 verify and count; 2 a mismatch fails the handle
     int verify_hash_ = 0;
+    int verify_md5_ = 0;                       // option verify_md5 (before init): 1 = MD5 messages are compared too (only with verify_hash 1 or 2)
+    std::atomic<uint32_t> hash_last_md5_[12] = {};      // the device's digests of the most recent MD5-verified picture: per component four big-endian words
     std::atomic<long long> stat_hash_pics_{0}, stat_hash_checked_{0}, stat_hash_mismatch_{0}, stat_hash_unchecked_{0}, stat_hash_md5_{0};
     std::atomic<long long> stat_hash_bad_poc_{-2147483648ll};
     std::atomic<uint32_t> hash_last_[6] = {};  // the device's words of the most recently completed hashed picture (engine thread writes)

@@ -499,6 +499,12 @@ void Engine::launch(Lane &ln, Batch &b) {
             for (auto &p : b.pics) p.hp.hash_mode = 0;
         }
     }
+    // ... and, with option profile, the two events around k_hevc_md5 when the batch first holds a picture whose MD5 is wanted (option verify_md5)
+    if (b.any_hash && profile_ && !b.mev[0]) {
+        bool any_md5 = false;
+        for (auto &p : b.pics) any_md5 |= p.codec == 1 && p.has_picture && (p.hp.hash_mode & 2) != 0;
+        if (any_md5) for (auto &e : b.mev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
+    }
     HevcBatchDims hd;
     const EnginePic *last_upload[4] = {nullptr, nullptr, nullptr, nullptr};      // per copy stream (upload k went to stream k % n_copy_)
     b.pmask = 0;
@@ -555,7 +561,8 @@ void Engine::launch(Lane &ln, Batch &b) {
             hd.max_ctb_w = std::max(hd.max_ctb_w, h.ctb_w); hd.max_ctb_h = std::max(hd.max_ctb_h, h.ctb_h);
             hd.max_w = std::max(hd.max_w, h.w); hd.max_h = std::max(hd.max_h, h.h); hd.any_intra |= (h.stages & HPS_INTRA) != 0;
             hd.any_deblock |= (h.stages & HPS_DEBLOCK) != 0; hd.any_sao |= (h.stages & HPS_SAO) != 0;
-            if (h.hash_mode) { hd.any_hash = true; b.alg[8] += (long long)h.w * h.h * 3 / 2; b.npics[8]++; }
+            if (h.hash_mode & 1) { hd.any_hash = true; b.alg[8] += (long long)h.w * h.h * 3 / 2; b.npics[8]++; }
+            if (h.hash_mode & 2) { hd.any_md5 = true; b.alg[9] += (long long)h.w * h.h * 3 / 2; b.npics[9]++; }
         }
         if (p.has_picture) {
             max_mbs = std::max(max_mbs, p.mb_w * p.mb_h); max_mb_h = std::max(max_mb_h, p.mb_h);
@@ -629,7 +636,16 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (hd.any_deblock || hd.any_sao) b.pmask |= 8;
         b.last_ev = 4;
         // the hashes of the finished pictures, to the host behind the kernel (Engine::complete compares them)
-        if (hd.any_hash) { hipMemcpyAsync(b.h_hash, b.d_hash, sizeof(uint32_t) * (size_t)n * kHashStride, hipMemcpyDeviceToHost, st); b.pmask |= 2048; b.last_ev = 18; }
+        // (MD5, option verify_md5: three serial chains per picture on this same stream, behind whatever ran last -- the batch waits for its slowest
+        // chain.  The surfaces are protected from reuse by this stream's order alone, so the kernel gets no stream of its own; lane_busy ends in front of it)
+        if (hd.any_md5 && b.d_hash) {
+            const bool timed = profile_ && b.mev[0] && b.mev[1];
+            if (timed) hipEventRecord(b.mev[0], st);
+            launch_hevc_md5(b.d_hpics, n, b.d_hash, st);
+            if (timed) { hipEventRecord(b.mev[1], st); b.pmask |= 4096; }
+        }
+        if (hd.any_hash || (hd.any_md5 && b.d_hash)) hipMemcpyAsync(b.h_hash, b.d_hash, sizeof(uint32_t) * (size_t)n * kHashStride, hipMemcpyDeviceToHost, st);
+        if (hd.any_hash) { b.pmask |= 2048; b.last_ev = 18; }
     }
     if (any_jpeg && max_jpeg_items > 0) {        // MJPEG pictures of the batch: independent of everything else in it
         const bool timed = profile_ && b.jev[0] && b.jev[1];
@@ -913,6 +929,7 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
         add(4, 4, 7, b.pmask & 32); add(5, 10, 11, b.pmask & 64); add(5, 12, 13, b.pmask & 128);
         add(6, 14, 15, b.pmask & 256); add(6, 16, 17, b.pmask & 512); add(8, 4, 18, b.pmask & 2048);
         if (b.pmask & 1024) { float ms = 0; if (hipEventElapsedTime(&ms, b.jev[0], b.jev[1]) == hipSuccess) { st_.ns[7] += ms * 1e6; st_.launches[7]++; } }
+        if (b.pmask & 4096) { float ms = 0; if (hipEventElapsedTime(&ms, b.mev[0], b.mev[1]) == hipSuccess) { st_.ns[9] += ms * 1e6; st_.launches[9]++; } }
         for (int k = 0; k < kKernelClasses; k++) { st_.pics[k] += b.npics[k]; st_.alg_bytes[k] += b.alg[k]; }
         st_.batches++; st_.batch_pics += (long long)b.pics.size();
         // the lane's time line: how long this batch's kernels held the lane's stream, and how long the stream sat idle since the previous batch's last kernel
@@ -961,8 +978,15 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
     // could not be computed, is reported as not compared
     for (size_t i = 0; i < b.pics.size(); i++) {
         const EnginePic &p = b.pics[i];
-        if (p.codec != 1 || p.hash_type <= 0) continue;
+        if (p.codec != 1 || (p.hash_type <= 0 && !p.hash_md5)) continue;
         if (failed || b.redo || !p.has_picture || !p.hp.hash_mode || !b.h_hash) { p.dec->on_picture_hash(p, nullptr, -1); continue; }
+        if (p.hash_md5) {           // 16 bytes per component, as k_hevc_md5 stored its state words
+            const uint8_t *digests = (const uint8_t *)(b.h_hash + i * kHashStride + kMd5Word);
+            int bad = -1;
+            for (int c = 2; c >= 0; c--) if (memcmp(digests + 16 * c, p.md5_want[c], 16) != 0) bad = c;
+            p.dec->on_picture_md5(p, digests, bad);
+            continue;
+        }
         const uint32_t *words = b.h_hash + i * kHashStride, *got = words + (p.hash_type == 1 ? 0 : 3);
         int bad = -1;
         for (int c = 2; c >= 0; c--) if (got[c] != p.hash_want[c]) bad = c;

@@ -78,6 +78,8 @@ struct EnginePic {
     unsigned long long seq = 0;                     // position in its decoder's decode order (Engine::submit)
     // HEVC, option verify_hash: the picture's SEI carries a CRC (1) or a checksum (2) of Y, Cb, Cr (0: nothing to verify); hp.hash_mode asks for k_hevc_pichash
     int hash_type = 0, hash_poc = 0; uint32_t hash_want[3] = {0, 0, 0};
+    // ... or, with option verify_md5, an MD5 (hash_type stays 0): the three digests to expect; hp.hash_mode bit 1 asks for k_hevc_md5
+    bool hash_md5 = false; uint8_t md5_want[3][16] = {};
     // chaining: the engine currently forms chain launches -- an intra picture that can join one stays on the ordinary lane
     int lane(bool chaining = false) const {
         // MJPEG pictures ride the HEVC lane: its batches run everything on the lane's stream, with no pre-stream and no chain logic
@@ -89,8 +91,8 @@ struct EnginePic {
 
 // per kernel class: 0 recon_inter, 1 intra, 2 deblock (prep+lds), 3 packout (every pack-out kernel), 4 chain (k_chain: recon + deblock),
 // 5 rgb_pack (k_rgb_pack alone: its frames are counted in class 3 too), 6 deint (k_deint alone, likewise), 7 jpeg (k_jpeg_recon),
-// 8 pichash (k_hevc_pichash: pictures hashed, 1.5 w h bytes each)
-constexpr int kKernelClasses = 9;
+// 8 pichash (k_hevc_pichash: pictures hashed, 1.5 w h bytes each), 9 md5 (k_hevc_md5, likewise)
+constexpr int kKernelClasses = 10;
 struct EngineStats {
     double ns[kKernelClasses] = {}; long long launches[kKernelClasses] = {}, pics[kKernelClasses] = {}, alg_bytes[kKernelClasses] = {};
     long long batches = 0, batch_pics = 0, chain_batches = 0, chain_pics = 0, wait_errors = 0, chain_recoveries = 0;
@@ -162,6 +164,7 @@ private:
         // result words of k_hevc_pichash, kHashStride per picture: device memory and the pinned copy behind the kernel; allocated when the batch first
         // holds a picture to verify (Engine::launch)
         uint32_t *d_hash = nullptr, *h_hash = nullptr; bool any_hash = false;
+        ihipEvent_t *mev[2] = {nullptr, nullptr};             // option profile: around k_hevc_md5, created when the batch first holds an MD5 picture
         // redo: an earlier batch of the lane was recovered, this one read its (then damaged) output
         bool any_chain = false, chain_with_intra = false, redo = false; int max_depth = 1;
         int max_mbs = 0, max_mb_h = 0; bool any_bipred = false, any_field = false;

@@ -258,7 +258,7 @@ void Decoder::hevc_dispatch_pending() {
     std::unique_ptr<PicTask> t = std::move(pending_);
     if (t->hevc && t->hevc->hash.type >= 0) {
         stat_hash_pics_++;
-        if (t->hevc->hash.type == 0) stat_hash_md5_++;           // counted, never compared: DESIGN.md 7
+        if (t->hevc->hash.type == 0) stat_hash_md5_++;           // carried MD5: compared only with option verify_md5
         if (hash_seen_.size() < 65536) hash_seen_.push_back({t->hevc->poc, t->hevc->hash});
     }
     dpb_[cur_].ref = 1;                            // "used for short-term reference" after decoding (8.3.2 decides later)
@@ -349,7 +349,9 @@ void Decoder::hevc_fill_engine_pic(PicTask *t, EnginePic &ep) {
     hp.pus = (const HevcPu *)(js.dev + ht.off_pus); hp.n_pus = ht.n_pus; hp.tbs = (const HevcTb *)(js.dev + ht.off_tbs); hp.n_tbs = ht.n_tbs;
     hp.itbs = (const HevcIntraTb *)(js.dev + ht.off_itbs); hp.n_itbs = ht.n_itbs; hp.coefs = (const uint32_t *)(js.dev + ht.off_coefs);
     hp.wps = (const HevcWp *)(js.dev + ht.off_wps); hp.resid = (int16_t *)(resid_ + (size_t)ht.work_slot * ((size_t)mb_w_ * mb_h_ * 768));
+    // hash_mode: bit 0 = the CRC / checksum kernel, bit 1 = the MD5 kernel
     if (ht.hash.type > 0) { hp.hash_mode = 1; ep.hash_type = ht.hash.type; ep.hash_poc = ht.poc; for (int c = 0; c < 3; c++) ep.hash_want[c] = ht.hash.v[c]; }
+    else if (ht.hash.type == 0 && verify_md5_) { hp.hash_mode = 2; ep.hash_md5 = true; ep.hash_poc = ht.poc; memcpy(ep.md5_want, ht.hash.md5, sizeof ep.md5_want); }
     hp.stages = (ht.n_pus ? HPS_MC : 0) | (ht.n_tbs ? HPS_RESID : 0) | (ht.n_itbs ? HPS_INTRA : 0) | (ht.any_deblock ? HPS_DEBLOCK : 0) |
         (ht.any_sao ? HPS_SAO : 0);
     // which surfaces the picture reads: lets the engine put INDEPENDENT pictures of this handle (the B pictures of one pyramid level) into one batch

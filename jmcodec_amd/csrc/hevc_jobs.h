@@ -96,7 +96,8 @@ struct HevcPicParams {
     const uint32_t *coefs;
     const HevcWp *wps;
     int16_t *resid;               // per-handle scratch: residual of the intra blocks, planar (Y w x h, Cb, Cr), written by k_hevc_iresid
-    int hash_mode;                // != 0: k_hevc_pichash computes the picture's CRCs and checksums (option verify_hash and a hash SEI for the picture)
+    int hash_mode;                // bit 0: k_hevc_pichash computes the picture's CRCs and checksums (option verify_hash and a hash SEI for the picture);
+                                  // bit 1: k_hevc_md5 computes its MD5s (option verify_md5 too, and an MD5 SEI)
 };
 
 }  // namespace jmamd

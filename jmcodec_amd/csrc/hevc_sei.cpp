@@ -1,6 +1,7 @@
 // jmcodec_amd/csrc/hevc_sei.cpp -- see hevc_sei.h.  The syntax is written from memory of H.265 7.3.5 (sei_message: 0xFF-extended payload type and size
 // bytes) and D.2.19 (hash_type u(8), then per component 16 bytes, u(16) or u(32)): no copy of the standard is at hand.
 #include "hevc_sei.h"
+#include <string.h>
 
 namespace jmamd {
 
@@ -27,6 +28,7 @@ int parse_sei_picture_hash(const uint8_t *b, size_t n, HevcPicHash &out, bool &f
             else if (ht <= 2) {
                 HevcPicHash h;
                 h.type = ht;
+                for (int c = 0; c < 3 && ht == 0; c++) memcpy(h.md5[c], p + 1 + 16 * c, 16);       // (size - 1 == 48 was checked)
                 for (int c = 0; c < 3 && ht > 0; c++) {
                     const uint8_t *q = p + 1 + (ht == 1 ? 2 : 4) * c;
                     h.v[c] = ht == 1 ? (uint32_t)q[0] << 8 | q[1] : (uint32_t)q[0] << 24 | (uint32_t)q[1] << 16 | (uint32_t)q[2] << 8 | q[3];

@@ -9,7 +9,8 @@ namespace jmamd {
 
 struct HevcPicHash {
     int type = -1;                 // hash_type: 0 MD5, 1 CRC, 2 checksum; -1 = the picture carries none
-    uint32_t v[3] = {0, 0, 0};     // Y, Cb, Cr (CRC: 16 bits; MD5: not kept, it is never compared)
+    uint32_t v[3] = {0, 0, 0};     // Y, Cb, Cr of a CRC (16 bits) or a checksum
+    uint8_t md5[3][16] = {};       // Y, Cb, Cr of an MD5: the 16 bytes as MD5 emits them (RFC 1321 order), compared with option verify_md5
 };
 
 // Walks every sei_message of an unescaped SEI RBSP (the bytes behind the two-byte NAL header).  A type-132 message of 4:2:0 content (three

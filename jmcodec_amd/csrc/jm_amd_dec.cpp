@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <exception>
 #include <vector>
 
@@ -185,6 +186,23 @@ __attribute__((visibility("default"))) int jm_amddec_picture_hash_device(const v
         hipMemcpyAsync(words, d_hash, sizeof words, hipMemcpyDeviceToHost, st); });
     hipFree(d_hash);
     if (r == 0) for (int c = 0; c < 3; c++) { crc[c] = words[c]; checksum[c] = words[3 + c]; }
+    return r;
+}
+
+// ... and its three MD5s: k_hevc_md5 on a one-picture batch
+__attribute__((visibility("default"))) int jm_amddec_picture_md5_device(const void *src, int pitch, int chroma_offset, int w, int hgt, unsigned char md5[3][16],
+    void *stream) {
+    if (!src || !md5 || w < 2 || hgt < 2 || ((w | hgt) & 1) || w > 16384 || hgt > 16384 || pitch < w || chroma_offset < 0) return -1;
+    jmamd::HevcPicParams pp = {};
+    pp.w = w; pp.h = hgt; pp.pitch = pitch; pp.chroma_offset = chroma_offset; pp.cur = 0; pp.hash_mode = 2;
+    pp.surf[0] = static_cast<uint8_t *>(const_cast<void *>(src));
+    uint32_t *d_hash = nullptr, words[12] = {};
+    if (hipMalloc((void **)&d_hash, sizeof(uint32_t) * jmamd::kHashStride) != hipSuccess) return -1;
+    int r = run_one_job(pp, stream, [&](const jmamd::HevcPicParams *d_pp, hipStream_t st) {
+        jmamd::launch_hevc_md5(d_pp, 1, d_hash, st);
+        hipMemcpyAsync(words, d_hash + jmamd::kMd5Word, sizeof words, hipMemcpyDeviceToHost, st); });
+    hipFree(d_hash);
+    if (r == 0) memcpy(md5, words, 48);
     return r;
 }
 

@@ -2,7 +2,8 @@
 // mode (no GPU work) so that it can be run under AddressSanitizer / UBSan on the CPU build:
 //   make -C tools fuzz_host_asan && tools/_build/fuzz_host_asan stream.h264 [seed] [trials] [codec_type: 0 H.264, 1 HEVC]
 // HEVC trials also run with option verify_hash = 1 and suffix SEI NAL units put between the stream's NAL units: decoded picture hash messages of
-// every hash_type, random payload types, sizes that lie, runs of 0xFF, several messages per unit (hevc_sei.cpp)
+// every hash_type (a quarter of them MD5, whose 48 digest bytes the parser keeps), random payload types, sizes that lie, runs of 0xFF, several
+// messages per unit (hevc_sei.cpp); a third of the trials also set verify_md5
 #include "../include/jm_amd_dec.h"
 #include <cstdio>
 #include <cstdlib>
@@ -65,6 +66,7 @@ int main(int argc, char **argv) {
         void *h = jm_amddec_create_handle();
         jm_amddec_set_option(h, "parse_only", 1);
         if (codec == 1 && t % 4 != 1) jm_amddec_set_option(h, "verify_hash", 1 + t % 2);
+        if (codec == 1 && t % 3 == 0) jm_amddec_set_option(h, "verify_md5", 1);       // (with and without verify_hash: alone it must change nothing)
         if (t % 2) jm_amddec_set_option(h, "digest", 1);
         jm_amddec_init(codec, 1, nullptr, 0, h);
         size_t pos = 0; int got = 0;

@@ -38,6 +38,7 @@ void launch_frame_to_nv12_pitch(const uint8_t *, int, int, int, uint8_t *, int, 
 namespace jmamd {
 void launch_hevc_picture_batch(const HevcPicParams *, int, const HevcBatchDims &, int *, ihipStream_t *, ihipEvent_t **, uint32_t *) { abort(); }
 void launch_hevc_pichash(const HevcPicParams *, int, int, uint32_t *, ihipStream_t *) { abort(); }
+void launch_hevc_md5(const HevcPicParams *, int, uint32_t *, ihipStream_t *) { abort(); }
 void launch_jpeg_recon(const JpegPicParams *, int, int, ihipStream_t *) { abort(); }
 void hevc_kernels_init() {}
 }
