@@ -7,6 +7,7 @@
 #include "kernels.h"
 #include "kernel_common.h"
 #include "chain_common.h"
+#include "deblock_packed.h"
 
 namespace jmamd {
 
@@ -20,74 +21,9 @@ struct DbRec {                 // 96 bytes per macroblock: 48 for the luma workg
 };
 static_assert(sizeof(DbRec) == 96, "DbRec must be 96 bytes");
 
-// ------------------------------------------------------------------------------------------
-// sample filters on register arrays
-// ------------------------------------------------------------------------------------------
-// s[0..7] = p3 p2 p1 p0 q0 q1 q2 q3; bsw = bS | tC0 << 3.  Written without divergent branches: the two filters of 8.7.2.3 / 8.7.2.4
-// are computed for every lane and selected, and the only branches are wave-uniform (nothing to filter / no lane with bS = 4).  The
-// branchy form cost ~10 exec-mask regions and, in the horizontal pass, ~110 register copies at the joins per edge.
-// |a - b| of two samples (0..255, upper bytes zero): one v_sad_u8 instead of sub / neg / max
-__device__ __forceinline__ int adiff(int a, int b) { return (int)__builtin_amdgcn_sad_u8((unsigned)a, (unsigned)b, 0u); }
-__device__ __forceinline__ int sel(bool c, int a, int b) { return c ? a : b; }      // operands are evaluated by the caller: a v_cndmask, never a branch
-// ---- the luma edge filter on PACKED 16-bit pairs (round 3) ----
-// One 32-bit register holds the sample i of the p side in its low half and the sample i of the q side in its high half: A = (p0 | q0 << 16),
-// B = (p1 | q1), C = (p2 | q2), D = (p3 | q3).  The two sides of 8.7.2.3 / 8.7.2.4 are mirror images, so every side-wise quantity (|p1 - p0| and
-// |q1 - q0|, ap and aq, p1' and q1', the strong filter's three outputs per side) is ONE v_pk_* instruction instead of two scalar ones, conditions
-// become masks ((x - limit) >> 15 per half) and selects become bitwise blends: ~60 vector instructions for the normal filter where the scalar
-// form needed ~100, and no int <-> bool conversions.  Same arithmetic, value for value (tests: every deblocking case against the oracle).
-typedef short s2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ s2 as_s2(uint32_t v) { return __builtin_bit_cast(s2, v); }
-__device__ __forceinline__ uint32_t as_u(s2 v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ s2 splat(int v) { return as_s2((uint32_t)v | ((uint32_t)v << 16)); }      // 0 <= v < 65536
-__device__ __forceinline__ s2 swp(s2 v) { const uint32_t u = as_u(v); return as_s2(__builtin_amdgcn_alignbit(u, u, 16)); }
-__device__ __forceinline__ s2 pabs(s2 v) { return __builtin_elementwise_max(v, -v); }
-__device__ __forceinline__ s2 pmin(s2 a, s2 b) { return __builtin_elementwise_min(a, b); }
-__device__ __forceinline__ s2 pmax(s2 a, s2 b) { return __builtin_elementwise_max(a, b); }
-__device__ __forceinline__ s2 blend(uint32_t m, s2 a, s2 b) { return as_s2((as_u(a) & m) | (as_u(b) & ~m)); }      // m: all ones / all zeros per half
+// the edge filters (flt_luma on packed 16-bit pairs, flt_chroma) live in deblock_packed.h, where a host build checks them against the clause
 // v_perm_b32: byte k of the result = byte sel[k] of {hi, lo} (0..3 = lo, 4..7 = hi, 0x0c = zero)
 __device__ __forceinline__ uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
-// A, B, C are updated in place (D = p3 | q3 is only read); bsw = bS | tC0 << 3
-__device__ __forceinline__ void flt_luma(s2 &A, s2 &B, s2 &C, const s2 D, int bsw, int alpha, int beta) {
-    const int bS = bsw & 7, tc0 = bsw >> 3;
-    const s2 As = swp(A), Bs = swp(B);
-    const s2 beta2 = splat(beta);
-    const s2 d10 = pabs(B - A), dpq = pabs(As - A);                       // (|p1 - p0| , |q1 - q0|), |p0 - q0| in both halves
-    const s2 m10 = (d10 - beta2) >> 15, mpq = (dpq - splat(alpha)) >> 15;
-    const uint32_t on = as_u(m10) & as_u(swp(m10)) & as_u(mpq) & (bS ? 0xffffffffu : 0u);      // filterSamplesFlag, the same in both halves
-    if (!__builtin_amdgcn_ballot_w64(on != 0)) return;
-    const s2 m20 = (pabs(C - A) - beta2) >> 15;                           // (ap , aq) as masks
-    const int tc = tc0 + (int)(as_u(m20) & 1u) + (int)(as_u(m20) >> 31);
-    const s2 t = ((As - A) << 2) + (B - Bs) + splat(4);                    // low half: ((q0 - p0) << 2) + (p1 - q1) + 4
-    const int dl = clip3(-tc, tc, (int)(short)(as_u(t) & 0xffffu) >> 3);
-    const s2 dd = as_s2(((uint32_t)dl & 0xffffu) | ((uint32_t)(-dl) << 16));       // (+delta , -delta)
-    const s2 nA = pmin(pmax(A + dd, splat(0)), splat(255));
-    const s2 avg = as_s2((as_u(A + As + splat(1)) >> 1) & 0x7fff7fffu);     // (p0 + q0 + 1) >> 1 in both halves
-    const s2 tcs = splat(tc0);
-    const s2 tt = pmin(pmax((C + avg - (B << 1)) >> 1, -tcs), tcs);
-    const s2 nB = B + as_s2(as_u(tt) & as_u(m20));                        // p1' only with ap, q1' only with aq
-    const uint32_t nrm = on & (bS < 4 ? 0xffffffffu : 0u);
-    s2 rA = blend(nrm, nA, A), rB = blend(nrm, nB, B), rC = C;
-    const uint32_t st = on & (bS >= 4 ? 0xffffffffu : 0u);
-    if (__builtin_amdgcn_ballot_w64(st != 0)) {
-        const s2 msg = (dpq - splat((alpha >> 2) + 2)) >> 15;
-        const uint32_t sm = st & as_u(m20) & as_u(msg);                    // the strong filter, per side
-        const s2 S0 = (C + ((B + A + As) << 1) + Bs + splat(4)) >> 3;
-        const s2 S1 = (C + B + A + As + splat(2)) >> 2;
-        const s2 S2 = ((D << 1) + C + (C << 1) + B + A + As + splat(4)) >> 3;
-        const s2 W0 = ((B << 1) + A + Bs + splat(2)) >> 2;
-        rA = blend(sm, S0, blend(st, W0, rA)); rB = blend(sm, S1, rB); rC = blend(sm, S2, rC);
-    }
-    A = rA; B = rB; C = rC;
-}
-// chroma: p1 p0 q0 q1 by reference
-__device__ __forceinline__ void flt_chroma(int p1, int &p0, int &q0, int q1, int bsw, int alpha, int beta) {
-    const int bS = bsw & 7, tc = (bsw >> 3) + 1;
-    const bool on = ((int)(bS != 0) & (int)(adiff(p0, q0) < alpha) & (int)(adiff(p1, p0) < beta) & (int)(adiff(q1, q0) < beta)) != 0;
-    const int delta = clip3(-tc, tc, (((q0 - p0) << 2) + (p1 - q1) + 4) >> 3);
-    const int n_p0 = clip1(p0 + delta), n_q0 = clip1(q0 - delta), w_p0 = (2 * p1 + p0 + q1 + 2) >> 2, w_q0 = (2 * q1 + q0 + p1 + 2) >> 2;
-    p0 = sel(on, sel(bS < 4, n_p0, w_p0), p0); q0 = sel(on, sel(bS < 4, n_q0, w_q0), q0);
-}
-
 
 // LDS layout (dynamic): per macroblock row
 //   lumaTile  [2][16][16]   = 512 B        chromaTile [2][8][16] = 256 B

@@ -655,7 +655,8 @@ bool Decoder::gpu_alloc_sequence() {
         for (size_t i = 0; i < n; i++) surf_[i] = surf_block_ + i * stride;
     }
     // the banded LDS wavefronts hold pictures of up to 512 macroblock rows (16 rows x 32 bands); the one-workgroup spin-wait kernels k_deblock / k_recon_intra
-    // remain for taller ones (a legal H.264 picture may have up to 1,055 rows), k_recon_intra also for P / B pictures with a few scattered intra macroblocks
+    // remain for taller ones (a legal H.264 picture may have up to 1,055 rows; activate() refuses more than kMaxMbRows), k_recon_intra also for P / B
+    // pictures with a few scattered intra macroblocks
     use_lds_deblock_ = deblock_lds_supported(mb_w_, mb_h_);
     use_lds_intra_ = intra_lds_supported(mb_w_, mb_h_);
     lds_intra8_ = true;
@@ -841,6 +842,10 @@ bool Decoder::activate(const SeqParams &sps) {
     // a new coded video sequence needs new device resources when the coded size changes, and new output slots / stream_info when only the
     // cropping does (hevc_activate compares the display size too); job buffers are sized for every profile, so a Baseline -> High switch
     // at the same size needs nothing
+    // k_deblock / k_recon_intra (the only kernels for pictures above 512 macroblock rows) keep a progress word per row in LDS: kMaxMbRows of them
+    static_assert(kMaxMbRows == 1056, "the text below names the limit");
+    if (sps.mb_h > kMaxMbRows) { stat_errors_++;
+        fail("picture of more than 1056 macroblock rows: not supported (the wavefront kernels keep one progress word per macroblock row in LDS)"); return false; }
     bool changed = !seq_active_ || sps.mb_w != mb_w_ || sps.mb_h != mb_h_ || sps.disp_w() != disp_w_ || sps.disp_h() != disp_h_;
     // (the colour of every sequence, size change or not: pictures decoded before keep theirs in DpbPic::color)
     { const int vui[4] = {sps.vui_full_range, sps.vui_primaries, sps.vui_transfer, sps.vui_matrix}; resolve_color(vui, sps.disp_h()); }

@@ -9,6 +9,11 @@ namespace jmamd {
 void launch_recon_inter(const PicParams *d_pics, int n, int max_mbs, bool any_bipred, bool any_field, int *d_err, hipStream_t st);
 void launch_recon_intra(const PicParams *d_pics, int n, hipStream_t st);          // spin-wait wavefront (sparse intra, any height)
 void launch_deblock(const PicParams *d_pics, int n, hipStream_t st);              // spin-wait wavefront (any height)
+// The tallest picture the spin-wait kernels take, in macroblock rows: they keep one progress word per row in LDS (kernels.hip: progress[kMaxMbRows]), and a
+// row beyond the array would read and write whatever follows it.  1056 covers every legal picture (A.3.1: a frame is at most Sqrt(8 * MaxFS) = 1055
+// macroblocks high at level 6.2); the parser lets frames of a field stream through up to 2048 rows, and Decoder::activate refuses what is taller than
+// this with a text that names the limit.
+constexpr int kMaxMbRows = 1056;
 bool intra_lds_supported(int mb_w, int mb_h);
 // ctl: the batch's control buffer, n * kChainStride ints (chain_common.h), cleared once per batch by the caller; err: the batch's error words
 // (one int per picture, host-pinned and device-visible): a kernel whose bounded wait gives up writes a non-zero code there

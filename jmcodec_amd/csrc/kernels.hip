@@ -11,6 +11,7 @@
 #include "jobs.h"
 #include "kernels.h"
 #include "kernel_common.h"
+#include "deblock_packed.h"    // filter_luma, filter_chroma of k_deblock
 #include "recon_device.h"      // ResTile, mb_residual_to_lds, luma_sample, recon_inter_wave (shared with chain.hip)
 
 namespace jmamd {
@@ -46,7 +47,10 @@ constexpr int kWaves = 16;
 // k_recon_intra runs eight: a workgroup of 16 waves is four per SIMD, i.e. 128 registers each, and the kernel then spilled 63 of them (368 bytes of scratch);
 // with two waves per SIMD it keeps everything in registers.  It only sees pictures with a few scattered intra macroblocks (decoder.cpp).
 constexpr int kIntraWaves = 8;
-constexpr int kMaxRows = 512;
+// one progress word per macroblock row of the tallest picture the decoder launches (kernels.h; Decoder::activate refuses taller ones): these two kernels
+// are the only route above the 512 rows of the banded kernels
+constexpr int kMaxRows = kMaxMbRows;
+static_assert(kMaxRows == kMaxMbRows && kMaxRows * sizeof(int) <= 8192, "progress[] must hold every row activate() lets through");
 
 __device__ __forceinline__ void wait_row(volatile int *progress, int row, int need) {
     if (row < 0) return;
@@ -319,38 +323,7 @@ __global__ __launch_bounds__(kIntraWaves * 64) void k_recon_intra(const PicParam
 // ------------------------------------------------------------------------------------------
 // k_deblock
 // ------------------------------------------------------------------------------------------
-// filter one line across an edge; s[0..7] = p3 p2 p1 p0 q0 q1 q2 q3 (luma) in registers
-__device__ __forceinline__ void filter_luma(int *s, int bS, int alpha, int beta, const uint8_t *tc0_row) {
-    int p3 = s[0], p2 = s[1], p1 = s[2], p0 = s[3], q0 = s[4], q1 = s[5], q2 = s[6], q3 = s[7];
-    if (!(iabs(p0 - q0) < alpha && iabs(p1 - p0) < beta && iabs(q1 - q0) < beta)) return;
-    int ap = iabs(p2 - p0) < beta, aq = iabs(q2 - q0) < beta;
-    if (bS < 4) {
-        int tc0 = tc0_row[bS - 1], tc = tc0 + ap + aq;
-        int delta = clip3(-tc, tc, (((q0 - p0) << 2) + (p1 - q1) + 4) >> 3);
-        s[3] = clip1(p0 + delta); s[4] = clip1(q0 - delta);
-        if (ap) s[2] = p1 + clip3(-tc0, tc0, (p2 + ((p0 + q0 + 1) >> 1) - (p1 << 1)) >> 1);
-        if (aq) s[5] = q1 + clip3(-tc0, tc0, (q2 + ((p0 + q0 + 1) >> 1) - (q1 << 1)) >> 1);
-    } else {
-        bool strong = iabs(p0 - q0) < ((alpha >> 2) + 2);
-        if (ap && strong) { s[3] = (p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3; s[2] = (p2 + p1 + p0 + q0 + 2) >> 2;
-            s[1] = (2 * p3 + 3 * p2 + p1 + p0 + q0 + 4) >> 3; }
-        else s[3] = (2 * p1 + p0 + q1 + 2) >> 2;
-        if (aq && strong) { s[4] = (p1 + 2 * p0 + 2 * q0 + 2 * q1 + q2 + 4) >> 3; s[5] = (p0 + q0 + q1 + q2 + 2) >> 2;
-            s[6] = (2 * q3 + 3 * q2 + q1 + q0 + p0 + 4) >> 3; }
-        else s[4] = (2 * q1 + q0 + p1 + 2) >> 2;
-    }
-}
-// chroma: s[0..3] = p1 p0 q0 q1
-__device__ __forceinline__ void filter_chroma(int *s, int bS, int alpha, int beta, const uint8_t *tc0_row) {
-    int p1 = s[0], p0 = s[1], q0 = s[2], q1 = s[3];
-    if (!(iabs(p0 - q0) < alpha && iabs(p1 - p0) < beta && iabs(q1 - q0) < beta)) return;
-    if (bS < 4) {
-        int tc = tc0_row[bS - 1] + 1;
-        int delta = clip3(-tc, tc, (((q0 - p0) << 2) + (p1 - q1) + 4) >> 3);
-        s[1] = clip1(p0 + delta); s[2] = clip1(q0 - delta);
-    } else { s[1] = (2 * p1 + p0 + q1 + 2) >> 2; s[2] = (2 * q1 + q0 + p1 + 2) >> 2; }
-}
-
+// the scalar edge filters filter_luma / filter_chroma: deblock_packed.h (checked against the clause on the host)
 struct DbTables { uint8_t alpha[52], beta[52], tc0[52][3]; };   // LDS copy of Tables 8-16 / 8-17
 struct DbTile {
     uint8_t y[20][24];      // rows -4..15, cols -4..15 (+pad)

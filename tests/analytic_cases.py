@@ -1,7 +1,7 @@
 """The scripted H.264 known-answer cases: name -> builder(width, height) -> (seq, pics).
 
 Every case is a script for tests/scripted_h264.py; its expected frames come from tests/analytic_expect.py.  All randomness is seeded: two calls give the
-same script.  Sizes: 96x80 and 90x70 (cropped from 96x80: the cropped-away samples are still reference samples).
+same script.  Sizes: 96x80 and 90x70 (cropped from 96x80: the cropped-away samples are still reference samples); the deblock_filters_* cases also 48x288.
 """
 import numpy as np
 
@@ -386,6 +386,225 @@ def with_filter_on(pics, qp=12):
     macroblocks count qP 0), alpha(indexA) = 0 (Table 8-16), so no edge is filtered and the expected pictures are those of the script as it was -- but
     the decoder now runs its deblocking stage (and, on the GPU, may run the pictures inside chain launches, which need that stage)."""
     return [dict(p, deblock=(0, 0, 0), qp=qp) for p in pics]
+
+
+# -- deblocking where it filters ------------------------------------------------------------------------------------------------------------------
+# Content on which the filters fire: smooth, not noise -- a level per macroblock and plane that steps from neighbour to neighbour by amounts spread
+# below and above alpha (Table 8-16: 4 .. 255), plus seeded noise whose amplitude is chosen per picture from 1, 4, 12, 40, so that ap / aq (and the
+# |p1 - p0| / |q1 - q0| tests) fall on both sides of beta (2 .. 18).  Levels visit 0 and 255, where Clip1 acts.  tests/deblock_ref.py computes what the
+# filter does; tests/test_analytic_host.py asserts from its counters that every path of 8.7.2 was taken, vertically and horizontally.
+SIZES_FILTER = SIZES + [(48, 288)]          # 3 x 18 macroblocks: rows 16, 17 lie in the second deblocking band of the band kernels
+STEPS = [1, 2, 3, 4, 6, 9, 13, 18, 25, 35, 50, 70, 100]
+AMPS = [4, 12, 1, 40]
+
+
+def stepped_planes(rng, mbw, mbh, amp):
+    out = []
+    for s in (16, 8, 8):
+        lv = np.zeros((mbh, mbw), np.int64)
+        for y in range(mbh):
+            for x in range(mbw):
+                prev = int(lv[y, x - 1]) if x else (int(lv[y - 1, 0]) if y else int(rng.integers(60, 200)))
+                v = prev + int(rng.choice(STEPS)) * int(rng.choice([-1, 1]))
+                if v < 0 or v > 255:
+                    v = 2 * prev - v                                # step the other way instead
+                lv[y, x] = min(255, max(0, v)) if rng.integers(0, 5) else int(rng.choice([0, 1, 254, 255]))
+                if (y * mbw + x) % 5 == 2:
+                    lv[y, x] = (0, 255)[((y * mbw + x) // 5) & 1]        # both ends in every picture, whatever the seed
+        up = np.kron(lv, np.ones((s, s), np.int64))
+        # At the two ends of the range a texture of period 4 takes the place of the noise: 0 7 1 0 along x and along y (255 - that at the top end).  Across
+        # an edge at a multiple of 4 it reads p2 p1 p0 | q0 q1 q2 = 7 1 0 | 0 7 1: ((q0 - p0) << 2) + (p1 - q1) + 4 = -2, delta = -1, and p0 + delta = -1 is
+        # what Clip1 is for (beta > 7 provided; 8.7.2.3); the mirror image gives 256.  An inter macroblock with an integer vector carries it to its edges.
+        tex = np.maximum.outer(np.array([0, 7, 1, 0])[np.arange(mbh * s) % 4], np.array([0, 7, 1, 0])[np.arange(mbw * s) % 4])
+        pl = np.where(up < 2, tex, np.where(up > 253, 255 - tex, up + rng.integers(-amp, amp + 1, up.shape)))
+        out.append(np.clip(pl, 0, 255).astype(np.uint8))
+    return out
+
+
+def stepped_pcm(rng, mbw, mbh, amp):
+    return pcm_from_planes(*stepped_planes(rng, mbw, mbh, amp), mbw, mbh)
+
+
+def dqp_to(pred, target):
+    """mb_qp_delta that takes QPY,PRED to target (7.4.5: (pred + delta + 52) % 52, delta in -26 .. 25): through the wrap where the straight way is too far"""
+    d = target - pred
+    return d - 52 if d > 25 else (d + 52 if d < -26 else d)
+
+
+def intra_filter_pic(rng, mbw, mbh, kind, poc, layout, deblock, amp, qp, k, walk=(16, 36)):
+    """Intra16x16 macroblocks (the modes their neighbours allow; mb_qp_delta walks QPY through 16 .. 51) beside I_PCM ones (qPp 0 in the filter)."""
+    pcm = stepped_pcm(rng, mbw, mbh, amp)
+    step = {"row": mbw, "pic": mbw * mbh}[layout]
+    mbs, n, pred = [], k, qp
+    for a in range(mbw * mbh):
+        x, y = a % mbw, a // mbw
+        if a % step == 0:
+            pred = qp
+        al, at = x > 0 and a - 1 >= a - a % step, y > 0 and a - mbw >= a - a % step
+        if (x + 2 * y + k) % 3 == 0:
+            mbs.append(pcm[a])                                      # (QPY,PRED passes through an I_PCM macroblock unchanged)
+            continue
+        ok_l = [m for m in (2, 0, 1, 3) if (m != 0 or at) and (m != 1 or al) and (m != 3 or (al and at))]
+        ok_c = [m for m in (0, 2, 1, 3) if (m != 2 or at) and (m != 1 or al) and (m != 3 or (al and at))]
+        target = walk[0] + (n * 7) % walk[1]
+        mbs.append(dict(t="i16", mode=ok_l[n % len(ok_l)], cmode=ok_c[(n // 2) % len(ok_c)], dqp=dqp_to(pred, target)))
+        pred = target
+        n += 1
+    return dict(kind=kind, poc=poc, layout=layout, deblock=deblock, qp=qp, mbs=mbs)
+
+
+def deblock_filters_intra(w, h):
+    """I and P pictures of Intra16x16 macroblocks (bS 3 inside, 4 at macroblock edges) beside I_PCM; one slice per picture and one per row; offsets that
+    clip indexA / indexB at 51 (+12 at QP above 39) and at 0 (-12 between two I_PCM macroblocks); disable_deblocking_filter_idc 0 and 2."""
+    rng = np.random.default_rng(0xA201)
+    mbw, mbh = dims(w, h)
+    spec = [("I", "pic", (0, 0, 0), 26, 4), ("P", "pic", (0, 6, 6), 40, 40), ("P", "row", (0, -3, 3), 30, 1), ("P", "row", (0, 3, -2), 51, 4),
+            ("P", "pic", (2, 1, 2), 20, 12)]
+    # (with a slice per row only DC and horizontal prediction remain, and idc 2 filters no horizontal macroblock edge there; the QPs of those two pictures
+    # stay in 40 .. 51 so that what is left still changes most macroblocks; indexA / indexB below 0 come from the inner edges of their I_PCM macroblocks)
+    pics = [intra_filter_pic(rng, mbw, mbh, kind, 2 * k, layout, db, amp, qp, k, (40, 12) if layout == "row" else (16, 36))
+            for k, (kind, layout, db, qp, amp) in enumerate(spec)]
+    return dict(width=w, height=h, chroma_qp_off=-3), pics
+
+
+def mb_slice_fields(x, y, k):
+    """QP and deblocking fields of a one-macroblock slice: left, top and own QP all different (the three edge classes get different alpha / beta), idc 0,
+    1 and 2 mixed, offsets that differ across most edges"""
+    return dict(qp=16 + (7 * x + 13 * y + 5 * k) % 36, deblock=((0, 0, 2, 0, 1, 0, 0)[(x + 3 * y + k) % 7], (-3, 0, 2, 6)[(x + y) % 4], (0, -2, 3, 6)[(2 * x + y + k) % 4]))
+
+
+def deblock_filters_inter(w, h):
+    """One slice per macroblock.  16x16 macroblocks whose vectors differ from their neighbours' by exactly 3 or exactly 4 in one component (bS 0 / bS 1),
+    different reference pictures (bS 1), 16x8 / 8x16 with halves that differ (inner edges), I_PCM and Intra16x16 macroblocks in between (bS 4 / 3)."""
+    rng = np.random.default_rng(0xA202)
+    mbw, mbh = dims(w, h)
+    pics = [intra_filter_pic(rng, mbw, mbh, "I", 0, "pic", (0, 6, 6), 4, 44, 0), intra_filter_pic(rng, mbw, mbh, "P", 2, "pic", (0, 3, 3), 12, 40, 1)]
+    incx, incy = [3, 4, 0, 4, 3, 12], [4, 3, 3, 0, 4, 8]
+    for k in range(3):
+        pcm = stepped_pcm(rng, mbw, mbh, AMPS[(k + 2) % 4])
+        mbs = []
+        for a in range(mbw * mbh):
+            x, y = a % mbw, a // mbw
+            mv = (-20 + 8 * k + sum(incx[i % 6] for i in range(x)), 10 - 4 * k + sum(incy[(i + k) % 6] for i in range(y)))
+            t = (x + 3 * y + k) % 8
+            ref = int((x // 2 + y + k) % 3 == 0)
+            if t == 0:
+                m = dict(pcm[a])
+            elif t == 1:
+                m = dict(t="i16", mode=2, cmode=0)
+            elif t in (2, 3):
+                second = [(ref, (mv[0] + 4, mv[1])), (1 - ref, mv), (ref, (mv[0], mv[1] - 3)), (ref, (mv[0] - 3, mv[1] + 4))][(a + k) % 4]
+                m = dict(t=("16x8", "8x16")[t - 2], parts=[(ref, mv), second])
+            else:
+                m = l0(ref, *mv)
+            m.update(mb_slice_fields(x, y, k))
+            if (x > 0 and (x - 1 + 3 * y + k) % 8 == 0) or (y > 0 and (x + 3 * (y - 1) + k) % 8 == 0):
+                m["qp"] = 51                                        # beside or below an I_PCM macroblock (QPY 0): the widest qPav there is
+            mbs.append(m)
+        pics.append(p_pic(4 + 2 * k, mbs, is_ref=False, num_ref=(2, 1)))
+    return dict(width=w, height=h, num_ref_frames=2, chroma_qp_off=4), pics
+
+
+def deblock_filters_b(w, h):
+    """B pictures of 16x16 macroblocks: L0-only, L1-only and bi-predicted neighbours; pairs of (picture, vector) that are equal crosswise (bS 0), equal in
+    pictures but not in vectors, and both vectors on ONE picture (which is in both lists) -- 8.7.2.1 compares reference pictures, not indices or lists."""
+    rng = np.random.default_rng(0xA203)
+    mbw, mbh = dims(w, h)
+    seq = dict(width=w, height=h, num_ref_frames=2, profile=77, chroma_qp_off=-2)
+    pics = [intra_filter_pic(rng, mbw, mbh, "I", 0, "pic", (0, 6, 6), 4, 44, 2), intra_filter_pic(rng, mbw, mbh, "P", 8, "pic", (0, 4, 2), 12, 40, 3)]
+    A, B = (12, -8), (-16, 20)
+    for k, poc in enumerate((4, 12, 6)):
+        mbs = []
+        for a in range(mbw * mbh):
+            x, y = a % mbw, a // mbw
+            A2, B2 = (A[0] + 3 + (y & 1), A[1]), (B[0], B[1] - 4 + (x & 1))
+            m = [dict(t="16x16", l0=(0, A)), dict(t="16x16", l1=(1, B)), dict(t="16x16", l0=(0, A), l1=(1, B)), dict(t="16x16", l0=(1, B), l1=(0, A)),
+                 dict(t="16x16", l0=(0, A2), l1=(1, B)), dict(t="16x16", l0=(0, A), l1=(0, B)), dict(t="16x16", l0=(0, B2), l1=(0, A)),
+                 dict(t="16x16", l0=(1, B), l1=(1, B2)), dict(t="16x16", l0=(0, A), l1=(1, B))][(x + 4 * y + k) % 9]
+            m.update(mb_slice_fields(x, y, k))
+            mbs.append(m)
+        pics.append(dict(kind="B", poc=poc, mbs=mbs, num_ref=(2, 2)))
+    return seq, pics
+
+
+def deblock_filters_coeff(w, h):
+    """P macroblocks with ONE coded coefficient (the DC of one 4x4 luma block, +-1): bS 2 on that block's edges -- inner 4x4 edges and macroblock edges,
+    from the p side and from the q side -- beside neighbours with bS 1 (vector or reference differs) and bS 0."""
+    rng = np.random.default_rng(0xA204)
+    mbw, mbh = dims(w, h)
+    pics = [intra_filter_pic(rng, mbw, mbh, "I", 0, "pic", (0, 6, 6), 4, 44, 4)]
+    for k in range(3):
+        mbs = []
+        for a in range(mbw * mbh):
+            x, y = a % mbw, a // mbw
+            mv = (4 * (k - 1) + (4, 0, 0, 3)[(x + y) % 4], -16 + (0, 0, 4, 0, 3)[(x + 2 * y) % 5])
+            t = (2 * x + y + k) % 5
+            m = l0(0, *mv) if t < 3 else dict(t=("16x8", "8x16")[t - 3], parts=[(0, mv), (0, (mv[0], mv[1] + (4 if a % 2 else 0)))])
+            if (x + y + k) % 3 != 2:
+                m["resid"] = ((0, 5, 10, 15, 3, 12, 6, 9)[(a + 3 * k) % 8], (1, -1)[(a + k) & 1])
+            m.update(mb_slice_fields(x, y, k))
+            m["deblock"] = (0,) + m["deblock"][1:]
+            mbs.append(m)
+        pics.append(p_pic(2 + 2 * k, mbs, is_ref=False))
+    return dict(width=w, height=h), pics
+
+
+def deblock_filters_refs(w, h):
+    """An intra picture, then four P pictures in a row, each the reference of the next, vectors up to +-24 samples, filtering at every edge: every
+    expected picture depends on the previous one having been filtered BEFORE it was read (asserted in the host test).  A decoder that lets the
+    reconstruction of picture n + 1 read a reference window before the deblocking of picture n has made it final fails here, and nowhere before."""
+    rng = np.random.default_rng(0xA205)
+    mbw, mbh = dims(w, h)
+    pics = [intra_filter_pic(rng, mbw, mbh, "I", 0, "pic", (0, 6, 6), 12, 44, 1)]
+    for k in range(4):
+        mbs = []
+        for a in range(mbw * mbh):
+            x, y = a % mbw, a // mbw
+            m = l0(k, 4 * int(rng.integers(-24, 25)) + int(rng.integers(0, 4)), 4 * int(rng.integers(-24, 25)) + int(rng.integers(0, 4)))
+            m.update(qp=28 + (5 * x + 11 * y + 3 * k) % 24, deblock=(0, (0, 2, 4)[(x + k) % 3], (0, 3)[(y + k) % 2]))
+            mbs.append(m)
+        pics.append(p_pic(2 + 2 * k, mbs))
+    return dict(width=w, height=h), pics
+
+
+# the cases on which the deblocking filter changes samples; they also run at 48x288 (case_sizes) and, as scripted, through chain launches on the GPU
+H264_FILTER_CASES = ["deblock_filters_intra", "deblock_filters_inter", "deblock_filters_b", "deblock_filters_coeff", "deblock_filters_refs"]
+H264_CASES.update({n: globals()[n] for n in H264_FILTER_CASES})
+
+
+def case_sizes(name):
+    return SIZES_FILTER if name in H264_FILTER_CASES else SIZES
+
+
+def tall_filter_script(w=16, h=8208):
+    """1 x 513 macroblocks: taller than the 512 rows of the banded kernels, so the GPU decoder takes its spin-wait kernels (k_deblock, and k_recon_intra
+    for the Intra16x16 macroblocks).  Two pictures in the manner of deblock_filters_intra, then two P pictures of one slice each: runs of 16x16
+    macroblocks with the picture's one vector between Intra16x16 and I_PCM ones (bS 4 at their edges, 3 inside), each predicted from the picture
+    before -- filtered.  One slice per picture: 513 slices would be beyond the 255 a picture may have."""
+    rng = np.random.default_rng(0xA206)
+    mbw, mbh = dims(w, h)
+    pics = [intra_filter_pic(rng, mbw, mbh, "I", 0, "pic", (0, 6, 6), 4, 40, 0), intra_filter_pic(rng, mbw, mbh, "P", 2, "pic", (0, 2, 3), 12, 30, 1)]
+    for k in (2, 3):
+        base = intra_filter_pic(rng, mbw, mbh, "P", 2 * k, "pic", (0, (4, -1)[k - 2], (3, 5)[k - 2]), (4, 1)[k - 2], 34 + 6 * (k - 2), k)
+        mv = l0(k - 1, (6, -9)[k - 2], (-37, 50)[k - 2])
+        pred, mbs = base["qp"], []
+        for a, m in enumerate(base["mbs"]):
+            if a % 5 in (1, 2, 3) or a == 0:
+                mbs.append(mv)                                      # (no mb_qp_delta: QPY,PRED passes through)
+            elif m["t"] == "i16":
+                target = 20 + (a * 5) % 32
+                mbs.append(dict(m, mode=(2, 0)[a & 1] if mbs[a - 1] is not None else 2, dqp=dqp_to(pred, target)))
+                pred = target
+            else:
+                mbs.append(m)
+        pics.append(dict(base, mbs=mbs))
+    return dict(width=w, height=h, chroma_qp_off=2), pics
+
+
+def too_tall_stream(rows=1058):
+    """A frame of `rows` macroblock rows in a stream with frame_mbs_only_flag = 0 (the only way past the 1024 map-unit rows of the parser)."""
+    seq = dict(width=16, height=16 * rows, frame_mbs_only=0)
+    return seq, [dict(kind="I", poc=0, layout="pic", mbs=[dict(t="i16", mode=2, cmode=0) for _ in range(rows)])]
 
 
 def full_hd_rows(w=1920, h=1080):

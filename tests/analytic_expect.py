@@ -3,12 +3,15 @@
 Sample interpolation is the literal restatement of 8.4.2.2.1 in tests/test_mc_packed.py (``luma_literal``), vectorised here (``mc_luma``; the host test
 checks the vectorised form against the scalar one), and the chroma formula 8-270; weighted prediction is 8.4.2.3 typed out; Intra16x16 / chroma
 prediction are 8.3.3 / 8.3.4 typed out.  The closed forms (ramps, half-sample chroma, flat fields) live beside them and are checked against these
-restatements in tests/test_analytic_host.py before any stream relies on them.  Deblocking is never computed: the cases choose streams on which the
-filter, when on, must be the identity.
+restatements in tests/test_analytic_host.py before any stream relies on them.  Deblocking is clause 8.7 typed out in tests/deblock_ref.py, applied to
+every finished picture before it serves as a reference (the identity cases choose streams on which it changes nothing; the deblock_filters_* cases
+streams on which it changes most macroblocks).  The one residual a script can carry -- a single DC coefficient of +-1 -- is ``dc_only_residual``.
 """
 import numpy as np
 
+import deblock_ref
 import scripted_h264 as sw
+from spec_tables_h264 import NORM_ADJUST_4x4
 
 
 def clip1(a):
@@ -135,6 +138,17 @@ def intra_chroma(C, x0, y0, mode, al, at):
     return clip1((a + b * (xx - 3) + c * (yy - 3) + 16) >> 5)
 
 
+def dc_only_residual(qp, level):
+    """What every sample of a 4x4 luma block gains when its only coefficient is c00 = level, flat scaling matrices, no transform bypass.
+    8.5.12.1: LevelScale4x4(qP % 6, 0, 0) = 16 * normAdjust4x4(qP % 6, 0, 0) (8.5.9, Flat_4x4_16); d00 = (c00 * LevelScale) << (qP / 6 - 4) for qP >= 24,
+    else (c00 * LevelScale + 2^(3 - qP / 6)) >> (4 - qP / 6).  8.5.12.2 with d00 alone: each one-dimensional transform of (d, 0, 0, 0) is (d, d, d, d)
+    -- e0 = e1 = d, e2 = e3 = 0, f = (e0 + e3, e1 + e2, e1 - e2, e0 - e3) -- horizontally, then vertically on every column: h_ij = d00 everywhere, and
+    r_ij = (h_ij + 32) >> 6 (8-354)."""
+    ls = 16 * NORM_ADJUST_4x4[qp % 6][0]
+    d = (level * ls) << (qp // 6 - 4) if qp >= 24 else (level * ls + (1 << (3 - qp // 6))) >> (4 - qp // 6)
+    return (d + 32) >> 6
+
+
 def partitions(m):
     """(x, y, w, h, l0, l1) of every partition of an inter macroblock of the script."""
     if m["t"] == "16x16":
@@ -143,13 +157,17 @@ def partitions(m):
     return [(0, 0, 16, 8, a, None), (0, 8, 16, 8, b, None)] if m["t"] == "16x8" else [(0, 0, 8, 16, a, None), (8, 0, 8, 16, b, None)]
 
 
-def expect_h264(seq, pics):
-    """[(Y, Cb, Cr)] per picture in DECODE order, coded size (multiples of 16), uint8."""
+def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None):
+    """[(Y, Cb, Cr)] per picture in DECODE order, coded size (multiples of 16), uint8.  stats: counters of deblock_ref; unfiltered: a list that receives
+    each picture as reconstructed, before 8.7; stale_ref_of = k: picture k alone is predicted from the UNFILTERED picture k - 1 (what a decoder computes
+    that reads its reference too early; the host test shows that this is visible)."""
     mbw, mbh = (seq["width"] + 15) // 16, (seq["height"] + 15) // 16
     pl = sw.plan(seq, pics)
-    out = []
+    out, raw = [], []
     for k, p in enumerate(pics):
         kind = p["kind"]
+        qps = sw.mb_qps(seq, p)
+        refs = out if stale_ref_of != k else out[:k - 1] + [raw[k - 1]]
         planes = [np.zeros((mbh * 16, mbw * 16), np.uint8), np.zeros((mbh * 8, mbw * 8), np.uint8), np.zeros((mbh * 8, mbw * 8), np.uint8)]
         step = {"mb": 1, "row": mbw, "pic": mbw * mbh}[p.get("layout", "mb" if kind != "I" else "pic")]
         mode = 0
@@ -182,7 +200,7 @@ def expect_h264(seq, pics):
                         for l, q in enumerate((l0, l1)):
                             if q is None:
                                 continue
-                            R = out[q[0]][c]
+                            R = refs[q[0]][c]
                             pr[l] = mc_luma(R, X, Yy, W, Hh, q[1]) if c == 0 else mc_chroma(R, X, Yy, W, Hh, q[1])
                             if mode == 1:
                                 wp = p["wp"]
@@ -199,7 +217,14 @@ def expect_h264(seq, pics):
                             w0, w1 = implicit_weights(p["poc"], pics[l0[0]]["poc"], pics[l1[0]]["poc"])
                             ent = [(w0, 0), (w1, 0)]
                         planes[c][Yy:Yy + Hh, X:X + W] = weighted(pr[0], pr[1], mode, logwd, ent[0], ent[1])
-        out.append(tuple(planes))
+                if "resid" in m:
+                    bx, by = sw.BLK_XY[m["resid"][0]]
+                    blk = planes[0][y * 16 + by:y * 16 + by + 4, x * 16 + bx:x * 16 + bx + 4]
+                    blk[:] = clip1(blk.astype(np.int64) + dc_only_residual(qps[a], m["resid"][1]))      # 8.5.14: Clip1(pred + r)
+        raw.append(tuple(planes))
+        out.append(deblock_ref.deblock_picture(seq, pics, pl, k, tuple(planes), stats))
+    if unfiltered is not None:
+        unfiltered[:] = raw
     return out
 
 

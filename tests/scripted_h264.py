@@ -5,7 +5,7 @@ ever coded, so the decoded picture follows from the script by arithmetic alone (
 7.3.3, 7.3.4, 7.3.5, 9.1, 9.2.1) -- not from tools/h264gen.c, the oracle or the product: a fourth typing of the syntax is part of the value.
 
 The script
-    seq  = dict(width, height, num_ref_frames=1, profile=66 | 77, weighted_pred=0, weighted_bipred=0, init_qp=26)
+    seq  = dict(width, height, num_ref_frames=1, profile=66 | 77, weighted_pred=0, weighted_bipred=0, init_qp=26, chroma_qp_off=0)
     pics = [dict(kind="I" | "P" | "B", poc=even int, layout="mb" | "row" | "pic", mbs=[...], and optionally
                  is_ref (default: kind != "B"), qp (slice QP, default init_qp), deblock=(disable_idc, alpha_div2, beta_div2) (default (1, 0, 0)),
                  num_ref=(n0, n1) (active entries, sent with num_ref_idx_active_override), wp=dict(ld_y, ld_c, l0=[entry..], l1=[entry..]) with
@@ -16,13 +16,22 @@ The script
         dict(t="skip")                                             P_Skip
         dict(t="16x16", l0=(pic, (mvx, mvy)) | None, l1=(pic, (mvx, mvy)) | None)      pic = index into pics (decode order), vectors in quarter samples
         dict(t="16x8" | "8x16", parts=[(pic, mv), (pic, mv)])      P only
+    and, for the streams on which the deblocking filter has to filter (tests/deblock_ref.py computes what it does):
+        qp=.., deblock=(idc, a, b) on any macroblock of layout "mb": the macroblock is a slice, so slice_qp_delta and the three deblocking fields carry them
+        dqp=.. on t="i16": mb_qp_delta, accumulated per 7.4.5 within the slice (``mb_qps``); layouts "row" / "pic"
+        resid=(blkIdx, +1 | -1) on a P 16x16 / 16x8 / 8x16 macroblock of layout "mb": ONE coded coefficient, the DC of luma block blkIdx (6.4.3 order), level
+        +-1 -- coded_block_pattern has the luma bit of that block's 8x8 and nothing else, mb_qp_delta is 0; the block's sixteen samples move by one constant
+        (analytic_expect.dc_only_residual)
 layout "mb": one slice per macroblock (no neighbour is available: every vector predictor is (0, 0), mvd = the vector); "row" / "pic": one slice per
 macroblock row / per picture -- inter macroblocks of such a slice must be 16x16 with ONE vector and reference per list throughout the slice (the
-predictor is then that vector as soon as a neighbour exists, whichever of 8.4.1.3's branches applies) and may not be P_Skip.
+predictor is then that vector as soon as a neighbour exists, whichever of 8.4.1.3's branches applies) and may not be P_Skip; intra macroblocks may sit
+between them only in a picture one macroblock wide.  seq may carry frame_mbs_only=0 (frame pictures of a stream that could hold fields).
 """
 import re
 
 import numpy as np
+
+from spec_tables_h264 import CBP_OF_CODENUM, COEFF_TOKEN, TOTAL_ZEROS_4x4, parse_code_table
 
 
 class Bits:
@@ -94,12 +103,16 @@ def sps(seq):
     b.ue(LOG2_MAX_POC_LSB - 4)
     b.ue(seq.get("num_ref_frames", 1))
     b.u(1, 0)                                                       # gaps_in_frame_num_value_allowed_flag
+    fmo = seq.get("frame_mbs_only", 1)                              # 0: the stream may hold field pictures (the scripts' pictures are all frames)
+    assert fmo or mbh % 2 == 0
     b.ue(mbw - 1)
-    b.ue(mbh - 1)
-    b.u(1, 1)                                                       # frame_mbs_only_flag
+    b.ue((mbh if fmo else mbh // 2) - 1)                            # pic_height_in_map_units_minus1: field macroblock rows when frame_mbs_only_flag = 0
+    b.u(1, fmo)                                                     # frame_mbs_only_flag
+    if not fmo:
+        b.u(1, 0)                                                   # mb_adaptive_frame_field_flag
     b.u(1, 1)                                                       # direct_8x8_inference_flag
     cr, cb_ = mbw * 16 - w, mbh * 16 - h
-    assert cr % 2 == 0 and cb_ % 2 == 0
+    assert cr % 2 == 0 and cb_ % 2 == 0 and (fmo or cb_ == 0)
     if cr or cb_:
         b.u(1, 1)
         b.ue(0); b.ue(cr // 2); b.ue(0); b.ue(cb_ // 2)             # crop units: two luma samples (4:2:0 frames)
@@ -122,7 +135,7 @@ def pps(seq):
     b.u(2, seq.get("weighted_bipred", 0))
     b.se(seq.get("init_qp", 26) - 26)
     b.se(0)                                                         # pic_init_qs_minus26
-    b.se(0)                                                         # chroma_qp_index_offset
+    b.se(seq.get("chroma_qp_off", 0))                               # chroma_qp_index_offset
     b.u(1, 1)                                                       # deblocking_filter_control_present_flag
     b.u(1, 0)                                                       # constrained_intra_pred_flag
     b.u(1, 0)                                                       # redundant_pic_cnt_present_flag
@@ -167,12 +180,71 @@ def plan(seq, pics):
     return out
 
 
+def slice_fields(seq, p, step, m):
+    """(SliceQPY, (disable_deblocking_filter_idc, alpha_div2, beta_div2)) of the slice that starts at macroblock m: layout "mb" lets the macroblock say"""
+    qp, db = p.get("qp", seq.get("init_qp", 26)), p.get("deblock", (1, 0, 0))
+    if step == 1:
+        qp, db = m.get("qp", qp), m.get("deblock", db)
+    else:
+        assert "qp" not in m and "deblock" not in m, "per-macroblock qp / deblock need layout mb"
+    return qp, db
+
+
+def layout_step(seq, p):
+    mbw, mbh = (seq["width"] + 15) // 16, (seq["height"] + 15) // 16
+    return {"mb": 1, "row": mbw, "pic": mbw * mbh}[p.get("layout", "mb" if p["kind"] != "I" else "pic")]
+
+
+def mb_qps(seq, p):
+    """QPY of every macroblock (7.4.5): QPY,PRED is the QPY of the previous macroblock of the slice in decoding order, SliceQPY for the first; a
+    macroblock without mb_qp_delta (I_PCM included: the value is inferred to be 0) keeps QPY,PRED.  That the deblocking filter takes qPp = 0 for an I_PCM
+    macroblock is a rule of 8.7.2.2 alone (tests/deblock_ref.py) and does not touch this chain."""
+    step, out = layout_step(seq, p), []
+    for a, m in enumerate(p["mbs"]):
+        if a % step == 0:
+            pred = slice_fields(seq, p, step, m)[0]
+        qp = (pred + m.get("dqp", 0) + 52) % 52
+        assert 0 <= pred <= 51 and -26 <= m.get("dqp", 0) <= 25
+        out.append(qp)
+        pred = qp
+    return out
+
+
+BLK_XY = [(((k >> 2) & 1) * 8 + (k & 1) * 4, ((k >> 3) & 1) * 8 + ((k >> 1) & 1) * 4) for k in range(16)]      # 6.4.3: luma4x4BlkIdx -> (x, y)
+_COEFF_TOKEN = parse_code_table(COEFF_TOKEN, 5)
+_TOTAL_ZEROS = parse_code_table(TOTAL_ZEROS_4x4, 15)
+
+
+def one_dc_coefficient(b, blk, sign):
+    """coded_block_pattern, mb_qp_delta and residual_luma of an Inter macroblock whose only coefficient is level `sign` at scan position 0 of block blk."""
+    b8 = blk >> 2
+    b.ue([c[1] for c in CBP_OF_CODENUM].index(1 << b8))               # me(v), Table 9-4, Inter column
+    b.se(0)                                                         # mb_qp_delta
+    total = {blk: 1}                                                # total_coeff of the blocks coded so far (others: 0)
+    at = {xy: k for k, xy in enumerate(BLK_XY)}
+    for k in range(4 * b8, 4 * b8 + 4):
+        x, y = BLK_XY[k]
+        # 9.2.1: blkA / blkB inside this macroblock are available (in an 8x8 without coded coefficients: total_coeff 0); outside it lies another slice
+        na = total.get(at[(x - 4, y)], 0) if x > 0 else None
+        nb = total.get(at[(x, y - 4)], 0) if y > 0 else None
+        nc = (na + nb + 1) >> 1 if na is not None and nb is not None else (na if na is not None else (nb if nb is not None else 0))
+        assert nc in (0, 1), nc
+        ln, val = _COEFF_TOKEN[(1, 1) if k == blk else (0, 0)][0]       # column 0 <= nC < 2
+        b.u(ln, val)
+        if k == blk:
+            b.u(1, 0 if sign > 0 else 1)                            # trailing_ones_sign_flag
+            ln, val = _TOTAL_ZEROS[(0,)][0]                         # total_zeros 0, tzVlcIndex 1: the coefficient sits at scan position 0, the DC
+            b.u(ln, val)
+
+
 def slice_header(b, seq, p, pl, first_mb):
     kind = p["kind"]
     b.ue(first_mb)
     b.ue({"P": 0, "B": 1, "I": 2}[kind])
     b.ue(0)                                                         # pic_parameter_set_id
     b.u(LOG2_MAX_FRAME_NUM, pl["frame_num"])
+    if not seq.get("frame_mbs_only", 1):
+        b.u(1, 0)                                                   # field_pic_flag
     if pl["idr"]:
         b.ue(0)                                                     # idr_pic_id
     b.u(LOG2_MAX_POC_LSB, p["poc"] % (1 << LOG2_MAX_POC_LSB))
@@ -233,10 +305,12 @@ def write(seq, pics):
     for k, (p, pl) in enumerate(zip(pics, plan(seq, pics))):
         kind, mbs = p["kind"], p["mbs"]
         assert len(mbs) == n_mbs
-        step = {"mb": 1, "row": mbw, "pic": n_mbs}[p.get("layout", "mb" if kind != "I" else "pic")]
+        step = layout_step(seq, p)
+        mb_qps(seq, p)                                              # its assertions
         for first in range(0, n_mbs, step):
             b = Bits()
-            slice_header(b, seq, p, pl, first)
+            qp, db = slice_fields(seq, p, step, mbs[first])
+            slice_header(b, seq, dict(p, qp=qp, deblock=db), pl, first)
             skip_run = 0
             for a in range(first, min(first + step, n_mbs)):
                 m = mbs[a]
@@ -256,7 +330,7 @@ def write(seq, pics):
                 elif t == "i16":
                     b.ue(intra_base + 1 + m["mode"])                # I_16x16_<mode>_0_0
                     b.ue(m["cmode"])                                # intra_chroma_pred_mode
-                    b.se(0)                                         # mb_qp_delta
+                    b.se(m.get("dqp", 0))                           # mb_qp_delta
                     # Intra16x16DCLevel, blkIdx 0: nC from the total_coeff of the blocks left of and above it (9.2.1): 16 in an I_PCM macroblock,
                     # 0 in every other macroblock a script can hold; a neighbour in another slice is not available
                     x, y = a % mbw, a // mbw
@@ -294,10 +368,22 @@ def write(seq, pics):
                             else:
                                 # every macroblock of this slice is the same 16x16 block: as soon as one neighbour exists, every available neighbour holds
                                 # this vector and reference, and each branch of 8.4.1.3 (one neighbour, one matching reference, median) returns it
-                                assert m == mbs[first], "a slice of several macroblocks repeats one 16x16 inter macroblock"
-                                mvp = (0, 0) if a == first else mv
+                                inter = [q_ for q_ in mbs[first:min(first + step, n_mbs)] if q_["t"] == "16x16"]
+                                assert all(q_ == inter[0] for q_ in inter), "a slice of several macroblocks repeats one 16x16 inter macroblock"
+                                if len(inter) == min(first + step, n_mbs) - first:
+                                    mvp = (0, 0) if a == first else mv
+                                else:
+                                    # intra macroblocks in between, pictures ONE macroblock wide only: A, C and D lie outside the picture, B is the
+                                    # macroblock above -- inter in this slice: the one neighbour whose reference matches, the predictor is its vector
+                                    # (this vector); intra or in another slice: no reference matches, median(0, 0, 0)
+                                    assert mbw == 1
+                                    mvp = mv if a > first and mbs[a - 1]["t"] == "16x16" else (0, 0)
                             b.se(mv[0] - mvp[0]); b.se(mv[1] - mvp[1])
-                    b.ue(0)                                         # coded_block_pattern 0 (Table 9-4, Inter, codeNum 0)
+                    if "resid" in m:
+                        assert kind == "P" and step == 1
+                        one_dc_coefficient(b, *m["resid"])
+                    else:
+                        b.ue(0)                                     # coded_block_pattern 0 (Table 9-4, Inter, codeNum 0)
             if skip_run:
                 b.ue(skip_run)
             b.trailing()

@@ -1,6 +1,8 @@
 """Analytic known-answer streams on the GPU (-m gpu): every scripted stream of tests/analytic_cases.py through the C ABI, I420 and NV12, against the
 ANALYTIC expectation of tests/analytic_expect.py -- not the oracle's output.  A kernel that is wrong in the same way as the oracle passes the parity
 tests; it does not pass these.  tests/test_analytic_host.py checks the expectations themselves (closed forms, restatements, the CPU oracle)."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -14,7 +16,7 @@ from test_gpu_parity import _chains_must_have_formed, _wait_until_the_gpu_is_our
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(n, s) for n in sorted(ac.H264_CASES) for s in ac.SIZES]
+CASES = [(n, s) for n in sorted(ac.H264_CASES) for s in ac.case_sizes(n)]     # the deblock_filters_* cases also at 48x288: two deblocking bands
 IDS = [f"{n}-{s[0]}x{s[1]}" for n, s in CASES]
 
 
@@ -31,12 +33,19 @@ def decode(data, fmt, chunks=None, codec=0, **opts):
         return frames, chained
 
 
+@functools.lru_cache(maxsize=None)
+def scripted(name, size):
+    """(seq, pics, stream, expected planes) of a case: computed once for both output formats and for the chain test, never modified"""
+    seq, pics = ac.H264_CASES[name](*size)
+    return seq, pics, sw.write(seq, pics), ae.expect_h264(seq, pics)
+
+
 @pytest.mark.parametrize("fmt", [1, 0], ids=["i420", "nv12"])
 @pytest.mark.parametrize("name,size", CASES, ids=IDS)
 def test_gpu_decodes_the_analytic_expectation(name, size, fmt):
-    seq, pics = ac.H264_CASES[name](*size)
-    frames, _ = decode(sw.write(seq, pics), fmt)
-    diff = ae.first_difference(seq, pics, frames, fmt)
+    seq, pics, data, planes = scripted(name, size)
+    frames, _ = decode(data, fmt)
+    diff = ae.first_difference(seq, pics, frames, fmt, planes)
     assert diff is None, f"{name} {size} format {fmt}: {diff}"
 
 
@@ -48,6 +57,24 @@ def test_chain_launches_decode_the_analytic_expectation(name):
     pics = ac.with_filter_on(pics)
     data = sw.write(seq, pics)
     planes = ae.expect_h264(seq, pics)
+    ours = _wait_until_the_gpu_is_ours()
+    for depth in (1, 8):
+        frames, chained = decode(None, 1, chunks=[data], chain_depth=depth, chain_lag=24)
+        diff = ae.first_difference(seq, pics, frames, 1, planes)
+        assert diff is None, f"{name} chain depth {depth}: {diff}"
+        assert chained == 0 or depth > 1, (name, depth, chained)
+        assert chained > 0 or depth == 1 or not ours, f"{name}: depth {depth}: no picture ran inside a chain launch on a GPU the engine owns"
+    _chains_must_have_formed(ours, name)
+
+
+@pytest.mark.parametrize("name", ac.H264_FILTER_CASES)
+def test_chain_launches_decode_the_filtering_cases(name):
+    """The deblock_filters_* cases AS SCRIPTED -- the filter changes most macroblocks of every picture (tests/deblock_ref.py) -- all pictures fed in one
+    call, chain depth 1 (k_deblock_band) and 8 (the deblocking role of k_chain, write-through stores): both equal the analytic expectation.  With the
+    identity filter of the test above, a reconstruction group of k_chain that read its reference window before the deblocking band had made those
+    samples final read the same bytes either way; here it does not (deblock_filters_refs: the host test shows that every P picture differs from what
+    the unfiltered reference gives).  Chains really formed on a GPU the engine owns, else a visible skip."""
+    seq, pics, data, planes = scripted(name, (96, 80))
     ours = _wait_until_the_gpu_is_ours()
     for depth in (1, 8):
         frames, chained = decode(None, 1, chunks=[data], chain_depth=depth, chain_lag=24)
@@ -81,6 +108,18 @@ def test_255_slices_decode_exactly_and_256_fail_the_handle():
         with pytest.raises(RuntimeError, match="255 slices"):
             d.decode_stream(sw.write(seq, pics))
         assert d.stat("errors") >= 1 and "255 slices" in api.lib().jm_amddec_last_error(d.h).decode()
+
+
+def test_tall_picture_through_the_spin_wait_kernels():
+    """16x8208 (1 x 513 macroblocks): above 512 macroblock rows the decoder launches k_deblock and, for the Intra16x16 macroblocks, k_recon_intra -- the
+    kernels with a progress word per macroblock row in LDS (kMaxMbRows, kernels.h); rows 512 and up used to index past that array.  Against the numpy
+    expectation (tests/deblock_ref.py); tests/test_analytic_host.py holds the CPU oracle to the same script."""
+    from test_analytic_host import tall_script
+    seq, pics, data, planes = tall_script()
+    frames, chained = decode(data, 1)
+    diff = ae.first_difference(seq, pics, frames, 1, planes)
+    assert diff is None, diff
+    assert chained == 0
 
 
 # ---- H.265 -------------------------------------------------------------------------------------------------------------------------------------

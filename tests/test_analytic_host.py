@@ -6,16 +6,19 @@ Three layers, each resting on the one before:
   2. every scripted stream through the CPU oracle, both output formats: frames == the analytic expectation, byte for byte;
   3. every scripted stream through a parse_only product handle: the host parser accepts a typing of the syntax that is not the generator's.
 The GPU half is tests/test_analytic_gpu.py."""
+import functools
+
 import numpy as np
 import pytest
 
 import analytic_cases as ac
 import analytic_expect as ae
+import deblock_ref
 import scripted_h264 as sw
 from jmcodec_amd import api
 from test_mc_packed import luma_literal
 
-CASES = [(n, s) for n in sorted(ac.H264_CASES) for s in ac.SIZES]
+CASES = [(n, s) for n in sorted(ac.H264_CASES) for s in ac.case_sizes(n)]
 IDS = [f"{n}-{s[0]}x{s[1]}" for n, s in CASES]
 
 
@@ -148,6 +151,65 @@ def test_noise_case_visits_every_fractional_position():
     assert len(set(mvs)) == len(mvs) and any(abs(x) > 800 or abs(y) > 800 for x, y in mvs)
 
 
+# ---- deblocking where it filters: the restatement's own pins, and the conditions that keep the filtering cases from passing vacuously ---------------
+@functools.lru_cache(maxsize=None)
+def filter_case(name, size):
+    """(seq, pics, expected planes, counters of deblock_ref, the pictures before 8.7) of a deblock_filters_* case: computed once, never modified"""
+    seq, pics = ac.H264_CASES[name](*size)
+    stats, raw = {}, []
+    planes = ae.expect_h264(seq, pics, stats, raw)
+    return seq, pics, planes, stats, raw
+
+
+def test_dc_only_residual_and_bs_of_vector_pairs_worked_by_hand():
+    # 8.5.12.1: qP 16: (-1 * 16 * 16 + 2) >> 2 = -64, (-64 + 32) >> 6 = -1;  qP 30: (16 * 10) << 1 = 320, 352 >> 6 = 5;  qP 51: (16 * 14) << 4 = 3584, 3616 >> 6 = 56
+    # qP 23: (16 * 18 + 1) >> 1 = 144, 176 >> 6 = 2;  qP 24, level -1: -160 << 0, -128 >> 6 = -2
+    assert [ae.dc_only_residual(q, s) for q, s in ((16, -1), (16, 1), (30, 1), (51, 1), (51, -1), (23, 1), (24, -1))] == [-1, 1, 5, 56, -56, 2, -2]
+    A, B, C = (4, -8), (-16, 20), (7, -8)
+    bs = deblock_ref.motion_bs
+    assert bs([(0, A)], [(0, C)]) == 0 and bs([(0, A)], [(0, (8, -8))]) == 1 and bs([(0, A)], [(1, A)]) == 1            # |4 - 7| = 3; |4 - 8| = 4; pictures
+    assert bs([(0, A)], [(0, A), (1, B)]) == 1                                                                          # number of vectors
+    assert bs([(0, A), (1, B)], [(1, B), (0, A)]) == 0 and bs([(0, A), (1, B)], [(1, B), (0, (8, -8))]) == 1            # crosswise equal; same pictures, far vector
+    assert bs([(0, A), (0, B)], [(0, B), (0, A)]) == 0 and bs([(0, A), (0, B)], [(0, A), (0, A)]) == 1                  # one picture twice: both pairings tried
+    assert bs([(0, A), (0, B)], [(0, A), (1, B)]) == 1                                                                  # {0, 0} against {0, 1}
+
+
+REQUIRED_PER_DIRECTION = (
+    ["Y%s:on_bS1", "Y%s:on_bS2", "Y%s:on_bS3", "Y%s:on_bS4", "Y%s:off_alpha_only", "Y%s:off_beta_p_only", "Y%s:off_beta_q_only", "Y%s:ap0_aq0", "Y%s:ap0_aq1",
+     "Y%s:ap1_aq0", "Y%s:ap1_aq1", "Y%s:delta_clip_pos", "Y%s:delta_clip_neg", "Y%s:delta_unclipped", "Y%s:clip1_at_0", "Y%s:clip1_at_255", "Y%s:strong_both",
+     "Y%s:strong_p", "Y%s:strong_q", "Y%s:strong_neither", "C%s:on_lt4", "C%s:on_4", "C%s:off_lt4", "C%s:off_4", "%s:indexA_clipped_at_0",
+     "%s:indexB_clipped_at_0", "%s:indexA_clipped_at_51", "%s:indexB_clipped_at_51", "%s:qPav_of_unequal_QPs", "%s:qPav_of_I_PCM_and_51",
+     "%s:chroma_qp_from_table_with_offset", "%s:idc2_slice_edge_left_alone", "%s:idc0_slice_edge_filtered_with_q_offsets",
+     "%s:mb_edge_vectors_differ_by_3_bS0", "%s:mb_edge_vectors_differ_by_4_bS1"])
+
+
+@pytest.mark.parametrize("size", ac.SIZES_FILTER, ids=lambda s: "%dx%d" % s)
+def test_filter_cases_take_every_path_of_the_clause_in_both_directions(size):
+    """Conditions, not measurements: over the five deblock_filters_* cases at this size, the restatement's own counters show every path of 8.7.2 taken by
+    at least one line across a vertical edge and one across a horizontal edge (luma_mb moves data differently for the two); every picture has a changed
+    sample in at least half of its macroblocks; and in deblock_filters_refs every P picture differs from what it would be had its reference been read
+    before that reference was filtered."""
+    total = {}
+    for name in ac.H264_FILTER_CASES:
+        seq, pics, planes, stats, raw = filter_case(name, size)
+        for k, v in stats.items():
+            total[k] = total.get(k, 0) + v
+        mbw, mbh = ac.dims(*size)
+        for k, (o, r) in enumerate(zip(planes, raw)):
+            changed = np.zeros((mbh, mbw), bool)
+            for c, s in ((0, 16), (1, 8), (2, 8)):
+                changed |= (o[c] != r[c]).reshape(mbh, s, mbw, s).any(axis=(1, 3))
+            assert changed.mean() >= 0.5, f"{name} {size} picture {k}: the filter changes {changed.mean():.2f} of the macroblocks"
+    missed = [key % d for d in "VH" for key in REQUIRED_PER_DIRECTION if total.get(key % d, 0) == 0]
+    assert not missed, f"{size}: paths of 8.7 that no filtering case takes: {missed}"
+    seq, pics, planes, stats, raw = filter_case("deblock_filters_refs", size)
+    assert [p["kind"] for p in pics] == ["I", "P", "P", "P", "P"]
+    for k in range(1, 5):
+        assert all(m["l0"][0] == k - 1 for m in pics[k]["mbs"])
+        stale = ae.expect_h264(seq, pics[:k + 1], stale_ref_of=k)[k]
+        assert any(not np.array_equal(a, b) for a, b in zip(stale, planes[k])), f"{size} picture {k}: reading the unfiltered reference would not show"
+
+
 # ---- 2. / 3. the streams through the CPU oracle and the host parser -----------------------------------------------------------------------------
 @pytest.mark.parametrize("name,size", CASES, ids=IDS)
 def test_scripted_stream_writer_is_deterministic(name, size):
@@ -159,7 +221,7 @@ def test_scripted_stream_writer_is_deterministic(name, size):
 def test_oracle_decodes_the_analytic_expectation(oracle, name, size):
     seq, pics = ac.H264_CASES[name](*size)
     data = sw.write(seq, pics)
-    planes = ae.expect_h264(seq, pics)
+    planes = filter_case(name, size)[2] if name in ac.H264_FILTER_CASES else ae.expect_h264(seq, pics)
     for fmt in (1, 0):
         got, n, w, h = oracle.decode(data, fmt)
         assert (n, w, h) == (len(pics), size[0], size[1])
@@ -227,6 +289,35 @@ def test_255_slices_per_picture_decode_and_256_are_refused_loudly(oracle):
     assert ae.first_difference(seq, pics, [got[i * fs:(i + 1) * fs] for i in range(n)], 1) is None
     n, errors, info, err, failed = parse_only(data)
     assert failed is not None and "255 slices" in failed and "255 slices" in err and errors >= 1, (n, errors, err, failed)
+
+
+# ---- pictures taller than the banded kernels -----------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def tall_script():
+    seq, pics = ac.tall_filter_script()
+    return seq, pics, sw.write(seq, pics), ae.expect_h264(seq, pics)
+
+
+def test_tall_picture_decodes_on_the_cpu_and_one_beyond_the_limit_is_refused_loudly(oracle):
+    """16x8208 is 1 x 513 macroblocks: above the 512 rows of the banded kernels the GPU decoder runs k_deblock and k_recon_intra, which keep a progress
+    word per macroblock row in LDS -- kMaxMbRows = 1056 of them (kernels.h).  The CPU oracle decodes the script to the numpy expectation (the GPU test
+    compares the same script).  A frame of 1058 rows (the next height a stream can have past 1056: frame_mbs_only_flag = 0 counts field rows) fails a
+    parse_only handle at activation with a text that names the limit; 1056 rows are accepted."""
+    seq, pics, data, planes = tall_script()
+    assert ac.dims(seq["width"], seq["height"]) == (1, 513)
+    got, n, w, h = oracle.decode(data, 1)
+    fs = w * h * 3 // 2
+    diff = ae.first_difference(seq, pics, [got[i * fs:(i + 1) * fs] for i in range(n)], 1, planes)
+    assert (n, w, h) == (4, 16, 8208) and diff is None, diff
+    raw = []
+    ae.expect_h264(seq, pics[:1], None, raw)
+    assert not np.array_equal(raw[0][0], planes[0][0])              # it filters
+    n, errors, info, err, failed = parse_only(data)
+    assert (n, errors, info, failed, err) == (4, 0, (16, 8208), None, "")
+    n, errors, info, err, failed = parse_only(sw.write(*ac.too_tall_stream(1058)))
+    assert failed is not None and "1056 macroblock rows" in failed and "1056 macroblock rows" in err and errors >= 1, (n, errors, err, failed)
+    n, errors, info, err, failed = parse_only(sw.write(*ac.too_tall_stream(1056)))
+    assert (n, errors, info, failed, err) == (1, 0, (16, 16896), None, "")
 
 
 # ---- H.265 -------------------------------------------------------------------------------------------------------------------------------------
