@@ -121,6 +121,24 @@ int  jm_amddec_packout_device(const void *d_src, int pitch, int width, int heigh
 int  jm_amddec_scale_taps(int src_len, int dst_len, int *first, short *weights, int max_taps);
 int  jm_amddec_scale_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int lone_field, int crop_x, int crop_y, int crop_w,
                             int crop_h, int tw, int th, int out_fmt, void *d_dst, void *stream);
+/* Placed output (INTEGRATION.md "Placed output"): the resampled picture fills a rectangle inside the target, every sample outside it is a constant
+ * colour; the frame handed out keeps the target size, and the one launch that writes it writes every byte once.  Options, before init (set_option
+ * returns -1 after init and for odd, negative or out-of-range values):
+ *   "rect_x", "rect_y", "rect_w", "rect_h": the rectangle inside the target, even values (w / h 0 = up to the target's right / bottom edge);
+ *   "fit": 0 stretch (default), 1 letterbox -- the aspect ratio kept, centred --, 2 letterbox at the top left; needs both target sizes and excludes rect_*;
+ *   "fit_sar": 1 = the letterbox honours the sequence's sample aspect ratio where the VUI transmits one (aspect_ratio_idc 1..16, 255);
+ *   "fill": -1 (default: Y'CbCr 16, 128, 128; RGB 0, 0, 0) or 0xAABBCC = Y, Cb, Cr of a Y'CbCr handle, R, G, B of an RGB handle.
+ * The rectangle is checked or computed when a sequence starts (again at every resolution change); the ratio limits 8:1 down and 1:4 up then apply
+ * to crop -> rectangle.  A geometry that does not fit fails the handle, jm_amddec_last_error says why.  Stats: "rect_x", "rect_y", "rect_w", "rect_h"
+ * (the rectangle in use: map model boxes back to the picture with it), "placed_frames", "sar_num", "sar_den" (as transmitted, 0 / 0 = absent).
+ *   jm_amddec_fit_rect: the letterbox rectangle of a cw x ch picture with sample aspect ratio sar_num : sar_den (0 / 0: square) in a tw x th target,
+ *     fit 1 or 2 (host only); rect = x, y, w, h.  Returns 0, -1 for invalid arguments.
+ *   jm_amddec_scale_rect_device: jm_amddec_scale_device with a placement (rect_w / rect_h 0: to the target's edge; all 0: no placement) and a fill
+ *     (-1 or 0xYYUUVV); same validation and return codes. */
+int  jm_amddec_fit_rect(int cw, int ch, int sar_num, int sar_den, int tw, int th, int fit, int rect[4]);
+int  jm_amddec_scale_rect_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int lone_field, int crop_x, int crop_y, int crop_w,
+                                 int crop_h, int tw, int th, int out_fmt, void *d_dst, void *stream, int rect_x, int rect_y, int rect_w, int rect_h,
+                                 int fill);
 /* Deinterlaced output (INTEGRATION.md "Deinterlaced output" defines the function D exactly).  With option "deinterlace" a handle hands out
  * C(R_G(D(F))): every display frame chosen by "deinterlace_when" keeps the lines of one field and rebuilds the others, before the resampler and
  * the colour conversion.  Options, before init (set_option returns -1 after init and for values out of range), all default 0:
@@ -174,6 +192,11 @@ int  jm_amddec_set_rgb(jm_amddec_handle h, const jm_amddec_rgb_spec *spec);
 int  jm_amddec_color_coefs(int matrix, int full_range, int coefs[5]);
 int  jm_amddec_rgb_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int lone_field, int crop_x, int crop_y, int crop_w,
                           int crop_h, int tw, int th, const jm_amddec_rgb_spec *spec, void *d_dst, void *stream);
+/* ... with a placement and a fill (-1 or 0xRRGGBB), as jm_amddec_scale_rect_device: the fill goes through the sample step of the storage position
+ * its colour lands in */
+int  jm_amddec_rgb_rect_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int lone_field, int crop_x, int crop_y, int crop_w,
+                               int crop_h, int tw, int th, const jm_amddec_rgb_spec *spec, void *d_dst, void *stream, int rect_x, int rect_y,
+                               int rect_w, int rect_h, int fill);
 /* Picture hash verification (INTEGRATION.md "Picture hash" defines both hashes exactly).  An HEVC stream may say what every decoded picture hashes to:
  * the decoded picture hash SEI message (payload type 132) in a suffix SEI NAL unit (type 40) holds an MD5, a CRC or a checksum per colour component of
  * the picture at its coded size.  Option "verify_hash", before init (set_option returns -1 after init and for other values):

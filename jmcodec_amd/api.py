@@ -65,6 +65,8 @@ def lib():
     L.jm_amddec_scale_taps.argtypes = [C.c_int, C.c_int, ip, C.POINTER(C.c_short), C.c_int]
     L.jm_amddec_scale_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, vp, vp]
+    L.jm_amddec_scale_rect_device.argtypes = L.jm_amddec_scale_device.argtypes + [C.c_int] * 5
+    L.jm_amddec_fit_rect.argtypes = [C.c_int] * 7 + [ip]
     L.jm_amddec_deinterlace_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
     L.jm_amddec_deinterlace2_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp]
     L.jm_amddec_feed_annexb.argtypes = [cp, C.c_long, C.c_int, C.POINTER(C.c_ubyte), C.c_int, vp]
@@ -94,6 +96,7 @@ def lib():
     L.jm_amddec_color_coefs.argtypes = [C.c_int, C.c_int, ip]
     L.jm_amddec_rgb_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(RgbSpec), vp, vp]
+    L.jm_amddec_rgb_rect_device.argtypes = L.jm_amddec_rgb_device.argtypes + [C.c_int] * 5
     L.jm_amddec_picture_hash_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), vp]
     L.jm_amddec_picture_md5_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte * 16), vp]
     _LIB = L
@@ -187,6 +190,28 @@ def deinterlace2_device(src, pitch, chroma_offset, width, height, mode, first_fi
 def scale_device(src, pitch, chroma_offset, width, height, crop, target, out_fmt, dst, lone_field=0, stream=None):
     """jm_amddec_scale_device: crop = (x, y, w, h), target = (tw, th); src / dst device addresses.  Returns 0 or < 0."""
     return lib().jm_amddec_scale_device(src, pitch, chroma_offset, width, height, lone_field, *crop, *target, out_fmt, dst, stream)
+
+
+# ---- placed output (include/jm_amd_dec.h; INTEGRATION.md "Placed output") ----------
+def fit_rect(cw, ch, tw, th, fit=1, sar=(0, 0)):
+    """jm_amddec_fit_rect: the letterbox rectangle (x, y, w, h) of a cw x ch picture with sample aspect ratio sar = (num, den) ((0, 0): square
+    samples) inside a tw x th target; fit 1 centred, 2 at the top left.  None for invalid arguments."""
+    r = (C.c_int * 4)()
+    if lib().jm_amddec_fit_rect(cw, ch, sar[0], sar[1], tw, th, fit, r) != 0:
+        return None
+    return tuple(r)
+
+
+def scale_rect_device(src, pitch, chroma_offset, width, height, crop, target, out_fmt, dst, rect, fill=-1, lone_field=0, stream=None):
+    """jm_amddec_scale_rect_device: scale_device with the picture placed at rect = (x, y, w, h) of the target (w / h 0: to the target's edge) and
+    the rest filled (fill -1: Y'CbCr 16, 128, 128, else 0xYYUUVV).  Returns 0 or < 0."""
+    return lib().jm_amddec_scale_rect_device(src, pitch, chroma_offset, width, height, lone_field, *crop, *target, out_fmt, dst, stream, *rect, fill)
+
+
+def rgb_rect_device(src, pitch, chroma_offset, width, height, crop, target, spec, dst, rect, fill=-1, lone_field=0, stream=None):
+    """jm_amddec_rgb_rect_device: rgb_device with the picture placed at rect = (x, y, w, h) of the target and the rest filled (fill -1: black, else
+    0xRRGGBB).  Returns 0 or < 0."""
+    return lib().jm_amddec_rgb_rect_device(src, pitch, chroma_offset, width, height, lone_field, *crop, *target, C.byref(spec), dst, stream, *rect, fill)
 
 
 # ---- picture hash (include/jm_amd_dec.h; both hashes are defined in INTEGRATION.md "Picture hash") ----------

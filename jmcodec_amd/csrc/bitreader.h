@@ -91,6 +91,16 @@ private:
     bool error_ = false;
 };
 
+// VUI aspect_ratio_idc (H.264 Table E-1, H.265 Table E.1) -> sample aspect ratio num : den.  idc 255 (Extended_SAR) takes the transmitted sar_width /
+// sar_height; idc 0, a reserved value or a zero term is "unspecified", 0 : 0.
+inline void sample_aspect_ratio(int idc, int sar_w, int sar_h, int &num, int &den) {
+    static const uint8_t kSar[17][2] = {{0, 0}, {1, 1}, {12, 11}, {10, 11}, {16, 11}, {40, 33}, {24, 11}, {20, 11}, {32, 11}, {80, 33}, {18, 11}, {15, 11},
+                                        {64, 33}, {160, 99}, {4, 3}, {3, 2}, {2, 1}};
+    num = den = 0;
+    if (idc >= 1 && idc <= 16) { num = kSar[idc][0]; den = kSar[idc][1]; }
+    else if (idc == 255 && sar_w > 0 && sar_h > 0) { num = sar_w; den = sar_h; }
+}
+
 // Emulation-prevention removal (7.4.1).  out must hold len + kSlack bytes.
 struct Rbsp {
     static constexpr size_t kSlack = 16;

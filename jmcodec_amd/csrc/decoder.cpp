@@ -152,6 +152,13 @@ int Decoder::set_option(const char *key, long long v) {
         static const char *const keys[6] = {"crop_x", "crop_y", "crop_w", "crop_h", "target_width", "target_height"};
         for (int i = 0; i < 6; i++) if (k == keys[i]) geo_[i] = (int)v;
     }
+    else if (k == "rect_x" || k == "rect_y" || k == "rect_w" || k == "rect_h") {      // placed output: fixed at init, even like the rest of the geometry
+        if (inited_ || v < 0 || v > 32768 || (v & 1)) return -1;
+        rect_opt_[k[5] == 'x' ? 0 : k[5] == 'y' ? 1 : k[5] == 'w' ? 2 : 3] = (int)v;
+    }
+    else if (k == "fit") { if (inited_ || v < 0 || v > 2) return -1; fit_ = (int)v; }                  // 0 stretch, 1 letterbox centred, 2 at the top left
+    else if (k == "fit_sar") { if (inited_ || v < 0 || v > 1) return -1; fit_sar_ = (int)v; }          // 1: the letterbox honours the sample aspect ratio
+    else if (k == "fill") { if (inited_ || v < -1 || v > 0xFFFFFF) return -1; fill_ = v; }             // -1 default; 0xAABBCC = Y, Cb, Cr or R, G, B
     else if (k == "deinterlace" || k == "deinterlace_when" || k == "deinterlace_field" || k == "deinterlace_threshold") {
         // deinterlaced output: fixed at init, like the geometry
         const long long hi = k == "deinterlace" || k == "deinterlace_field" ? 2 : (k == "deinterlace_when" ? 1 : 255);
@@ -190,6 +197,14 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "frames") return num_frames_;
     if (k == "out_width") return out_w_;              // size of the frames handed out (the target size of a scaled handle)
     if (k == "out_height") return out_h_;
+    // placed output: the picture's rectangle inside the target (the whole target unless placed), frames that were placed, the sample aspect ratio
+    if (k == "rect_x") return place_[0];
+    if (k == "rect_y") return place_[1];
+    if (k == "rect_w") return place_[2];
+    if (k == "rect_h") return place_[3];
+    if (k == "placed_frames") return stat_placed_;
+    if (k == "sar_num") return sar_[0];
+    if (k == "sar_den") return sar_[1];
     if (k == "scaled_frames") return stat_scaled_;    // display frames that went through the resampler (k_scale_pack, or k_rgb_pack with a geometry)
     // RGB output: frames converted, bytes of the frame current or about to be fetched, the colour description and what is in use
     if (k == "rgb_frames") return stat_rgb_;
@@ -572,12 +587,29 @@ void Decoder::resolve_color(const int vui[4], int disp_h) {
     color_matrix_ = m; color_range_ = r;
 }
 
+// the letterbox rectangle in 64-bit integers: W' = cw * sn, H' = ch * sd; the axis that fills the target is the one whose ratio is larger
+bool fit_rect(int cw, int ch, int sar_num, int sar_den, int tw, int th, int fit, int rect[4]) {
+    if (!rect || cw <= 0 || ch <= 0 || tw < 2 || th < 2 || ((tw | th) & 1) || sar_num < 0 || sar_den < 0 || (fit != 1 && fit != 2)) return false;
+    if (cw > 32768 || ch > 32768 || tw > 32768 || th > 32768 || sar_num > 65535 || sar_den > 65535) return false;
+    const long long sn = sar_num && sar_den ? sar_num : 1, sd = sar_num && sar_den ? sar_den : 1;
+    const long long Wp = cw * sn, Hp = ch * sd, TW = tw, TH = th;
+    auto clampll = [](long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); };
+    long long rw, rh;
+    if (Wp * TH >= Hp * TW) { rw = TW; rh = clampll(2 * ((TW * Hp + Wp) / (2 * Wp)), 2, TH); }
+    else { rh = TH; rw = clampll(2 * ((TH * Wp + Hp) / (2 * Hp)), 2, TW); }
+    rect[0] = fit == 1 ? (int)(2 * ((TW - rw) / 4)) : 0; rect[1] = fit == 1 ? (int)(2 * ((TH - rh) / 4)) : 0;
+    rect[2] = (int)rw; rect[3] = (int)rh;
+    return true;
+}
+
 // the geometry options against the display area of the sequence being activated (the crop rectangle is checked again at every new sequence; the
 // target stays what it was at init)
 bool Decoder::resolve_geometry() {
     const int W = disp_w_, H = disp_h_;
     out_w_ = W; out_h_ = H; crop_[0] = crop_[1] = 0; crop_[2] = W; crop_[3] = H; scaled_ = false;
-    if (!(geo_[0] | geo_[1] | geo_[2] | geo_[3] | geo_[4] | geo_[5])) return true;
+    place_[0] = place_[1] = 0; place_[2] = W; place_[3] = H; placed_ = false; rgb_identity_ = true;
+    const bool rect_set = (rect_opt_[0] | rect_opt_[1] | rect_opt_[2] | rect_opt_[3]) != 0;
+    if (!(geo_[0] | geo_[1] | geo_[2] | geo_[3] | geo_[4] | geo_[5]) && !rect_set && !fit_) return true;
     const int cx = geo_[0], cy = geo_[1], cw = geo_[2] ? geo_[2] : W - cx, ch = geo_[3] ? geo_[3] : H - cy;
     const int tw = geo_[4] ? geo_[4] : cw, th = geo_[5] ? geo_[5] : ch;
     char msg[256];
@@ -589,12 +621,29 @@ bool Decoder::resolve_geometry() {
         snprintf(msg, sizeof msg, "output geometry: the crop size %dx%d (display area %dx%d) is odd", cw, ch, W, H);
         fail(msg); return false;
     }
-    if (cw > 8 * tw || ch > 8 * th || tw > 4 * cw || th > 4 * ch) {
-        snprintf(msg, sizeof msg, "output geometry: the scaling ratio %dx%d -> %dx%d is out of range (per axis at most 8:1 down and 1:4 up)", cw, ch, tw, th);
+    // placed output: the rectangle the picture is resampled into (the whole target unless fit / rect_* say otherwise); the ratio limits apply to it
+    int rc[4] = {0, 0, tw, th};
+    if (fit_) {
+        if (!geo_[4] || !geo_[5]) { fail("output geometry: fit needs both target_width and target_height"); return false; }
+        if (rect_set) { fail("output geometry: fit and rect_x / rect_y / rect_w / rect_h exclude each other"); return false; }
+        if (!fit_rect(cw, ch, fit_sar_ ? sar_[0] : 0, fit_sar_ ? sar_[1] : 0, tw, th, fit_, rc)) { fail("output geometry: fit: no rectangle for this target"); return false; }
+    } else if (rect_set) {
+        rc[0] = rect_opt_[0]; rc[1] = rect_opt_[1]; rc[2] = rect_opt_[2] ? rect_opt_[2] : tw - rc[0]; rc[3] = rect_opt_[3] ? rect_opt_[3] : th - rc[1];
+        if (rc[2] <= 0 || rc[3] <= 0 || rc[0] + rc[2] > tw || rc[1] + rc[3] > th) {
+            snprintf(msg, sizeof msg, "output geometry: the placement rectangle %dx%d at (%d, %d) does not lie inside the target %dx%d", rc[2], rc[3], rc[0], rc[1], tw, th);
+            fail(msg); return false;
+        }
+    }
+    if (cw > 8 * rc[2] || ch > 8 * rc[3] || rc[2] > 4 * cw || rc[3] > 4 * ch) {
+        snprintf(msg, sizeof msg, "output geometry: the scaling ratio %dx%d -> %dx%d is out of range (per axis at most 8:1 down and 1:4 up)", cw, ch, rc[2], rc[3]);
         fail(msg); return false;
     }
     crop_[0] = cx; crop_[1] = cy; crop_[2] = cw; crop_[3] = ch; out_w_ = tw; out_h_ = th;
-    scaled_ = !(cx == 0 && cy == 0 && cw == W && ch == H && tw == cw && th == ch);     // the identity geometry keeps k_packout
+    for (int i = 0; i < 4; i++) place_[i] = rc[i];
+    placed_ = !(rc[0] == 0 && rc[1] == 0 && rc[2] == tw && rc[3] == th);
+    scaled_ = placed_ || !(cx == 0 && cy == 0 && cw == W && ch == H && tw == cw && th == ch);     // the identity geometry keeps k_packout
+    // (unplaced: any geometry goes through the tables, as before; placed: pure padding reads the surface directly)
+    rgb_identity_ = placed_ ? rc[2] == cw && rc[3] == ch : !scaled_;
     return true;
 }
 
@@ -644,7 +693,7 @@ bool Decoder::gpu_alloc_sequence() {
     hipSetDevice(device_);
     // (re-activation: nothing is in flight any more, activate() drained the handle)
     if (scale_dev_) { hipFree(scale_dev_); scale_dev_ = nullptr; }
-    if (scaled_ && !upload_scale_tables(crop_[2], crop_[3], out_w_, out_h_, &scale_dev_, scale_ax_)) { fail("scale table allocation failed"); return false; }
+    if (scaled_ && !upload_scale_tables(crop_[2], crop_[3], place_[2], place_[3], &scale_dev_, scale_ax_)) { fail("scale table allocation failed"); return false; }
     pitch_ = (mb_w_ * 16 + 127) & ~127;
     chroma_off_ = pitch_ * mb_h_ * 16;
     surf_bytes_ = (size_t)pitch_ * mb_h_ * 16 * 3 / 2;
@@ -849,6 +898,9 @@ bool Decoder::activate(const SeqParams &sps) {
     bool changed = !seq_active_ || sps.mb_w != mb_w_ || sps.mb_h != mb_h_ || sps.disp_w() != disp_w_ || sps.disp_h() != disp_h_;
     // (the colour of every sequence, size change or not: pictures decoded before keep theirs in DpbPic::color)
     { const int vui[4] = {sps.vui_full_range, sps.vui_primaries, sps.vui_transfer, sps.vui_matrix}; resolve_color(vui, sps.disp_h()); }
+    // (a letterbox that honours the sample aspect ratio is computed again when the ratio changes)
+    if (fit_ && fit_sar_ && (sps.sar_num != sar_[0] || sps.sar_den != sar_[1])) changed = true;
+    sar_[0] = sps.sar_num; sar_[1] = sps.sar_den;
     seq_ = sps;
     dpb_size_ = sps.dpb_frames();
     // display order == decode order when POC type 2 (8.2.1.3): no bumping delay needed
@@ -1713,6 +1765,7 @@ void Decoder::enqueue_output(int entry, OutSide &out) {
     { std::lock_guard<std::mutex> lk(mtx_); o = alloc_out_slot(); ready_.push_back(o); num_frames_++;   // nv_dec.cpp:48 num_frames++
       if (both) { o2 = alloc_out_slot(); ready_.push_back(o2); num_frames_++; } }
     if (both) stat_pairs_++;
+    if (placed_ && !failed_) stat_placed_ += both ? 2 : 1;
     if (parse_only_ || failed_) { std::lock_guard<std::mutex> lk(mtx_); o->ready = true; done_unfetched_++; if (field) stat_deint_++;
         if (both) { o2->ready = true; done_unfetched_++; stat_deint_++; } return; }
     // k_packout packs the tight frame into device staging and a copy engine moves it to the pinned slot -- or, in direct mode,
@@ -1742,13 +1795,15 @@ void Decoder::enqueue_output(int entry, OutSide &out) {
             RgbJob rj = {};
             rj.s = ScaleJob{src, dst_of(s), pitch_, src_chroma, crop_[0], crop_[1], out_w_, out_h_, 0, lone, {}};
             for (int a = 0; a < 4; a++) rj.s.ax[a] = scale_ax_[a];
-            rj.identity = scaled_ ? 0 : 1;
+            rj.identity = rgb_identity_ ? 1 : 0;
+            if (placed_) { rj.s.rx = place_[0]; rj.s.ry = place_[1]; rj.s.rw = place_[2]; rj.s.rh = place_[3]; rj.fill = fill_ < 0 ? 0 : (int)fill_; }
             fill_rgb_color(rj, rgb_spec_, color & 15, (color >> 4) == 2);
             out.rgb.push_back(rj); stat_rgb_++;
-            if (scaled_) stat_scaled_++;
+            if (scaled_ && !rgb_identity_) stat_scaled_++;          // (pure padding reads the surface directly: no resampler)
         } else if (scaled_) {
             ScaleJob sj{src, dst_of(s), pitch_, src_chroma, crop_[0], crop_[1], out_w_, out_h_, out_fmt_, lone, {}};
             for (int a = 0; a < 4; a++) sj.ax[a] = scale_ax_[a];
+            if (placed_) { sj.rx = place_[0]; sj.ry = place_[1]; sj.rw = place_[2]; sj.rh = place_[3]; sj.fill = fill_ < 0 ? 0x108080 : (int)fill_; }
             out.scale.push_back(sj); stat_scaled_++;
         } else if (!field) out.plain.push_back(PackJob{surf_[slot], dst_of(s), pitch_, chroma_off_, disp_w_, disp_h_, out_fmt_, lone});
         out.slots.push_back(s);
@@ -1968,17 +2023,19 @@ int Decoder::decode(const uint8_t *buf, int len, int *got_frame) {
             char deint[96] = "";                             // (only with option deinterlace: the text is the reference's otherwise)
             if (deint_mode_) snprintf(deint, sizeof deint, "Deinterlace:\t%s, %s%s, %lld frames\n", deint_mode_ == 1 ? "bob" : "comb-adaptive",
                 deint_when_ ? "always" : "auto", deint_rate_ ? ", field rate" : "", (long long)stat_deint_);
+            char place[64] = "";                             // (only when frames are placed)
+            if (placed_) snprintf(place, sizeof place, "Placement:\t%d,%d %dx%d\n", place_[0], place_[1], place_[2], place_[3]);
             snprintf(info_, sizeof info_,
                      "==========================================\n"
                      "Codec:\t\t%s\n"
                      "Display:\t%d x %d\n"
                      "Pixel Format:\t%s\n"
-                     "%s"
+                     "%s%s"
                      "Frame Count:\t%d\n"
                      "Elapsed Time:\t%d ms\n"
                      "Decode FPS:\t%f fps\n"
                      "==========================================\n",
-                     codec_ == 0 ? "H.264" : (codec_ == 1 ? "H.265" : "MJPEG"), out_w_, out_h_, fmt, deint, (int)num_frames_,
+                     codec_ == 0 ? "H.264" : (codec_ == 1 ? "H.265" : "MJPEG"), out_w_, out_h_, fmt, deint, place, (int)num_frames_,
                      (int)elapsed_ms_, elapsed_ms_ > 0 ? (double)num_frames_ * 1000.0 / elapsed_ms_ : 0.0);
         }
     }

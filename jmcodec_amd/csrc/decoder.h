@@ -139,6 +139,9 @@ class HostCopier;
 // the four tables of a geometry (crop w x h -> target tw x th: luma x, luma y, chroma x, chroma y) in ONE device allocation *dev (the caller
 // frees it); ax[] points into it.  Synchronous (activation time).  false: invalid sizes or a failed allocation.
 bool upload_scale_tables(int w, int h, int tw, int th, uint8_t **dev, ScaleAxis ax[4]);
+// Placed output (INTEGRATION.md "Placed output"): the letterbox rectangle of a cw x ch picture with sample aspect ratio sar_num : sar_den (a zero term:
+// square samples) inside a tw x th target; fit 1 centred, 2 at the top left.  rect = x, y, w, h, all even.  false: invalid arguments.
+bool fit_rect(int cw, int ch, int sar_num, int sar_den, int tw, int th, int fit, int rect[4]);
 
 // RGB output (INTEGRATION.md "RGB output"): the spec of jm_amddec_set_rgb (same layout as jm_amddec_rgb_spec)
 struct RgbSpec { int dtype, planar, bgr, matrix, range; float scale[3], bias[3]; };
@@ -272,6 +275,13 @@ private:
     // ... resolved per sequence (resolve_geometry): the size of the frames handed out, the crop rectangle; scaled_ = not the identity
     int out_w_ = 0, out_h_ = 0, crop_[4] = {0, 0, 0, 0}; bool scaled_ = false;
     uint8_t *scale_dev_ = nullptr; ScaleAxis scale_ax_[4] = {};     // the sequence's tap tables on the device (k_scale_pack)
+    // placed output (options before init): rect_x, rect_y, rect_w, rect_h (w / h 0: to the target's edge), fit, fit_sar, fill (-1: the default colour)
+    int rect_opt_[4] = {0, 0, 0, 0}, fit_ = 0, fit_sar_ = 0; long long fill_ = -1;
+    // ... resolved per sequence (resolve_geometry): the picture's rectangle inside the target; placed_ = it is not the whole target (then scaled_ is set
+    // and the tap tables are those of crop -> rectangle); rgb_identity_: k_rgb_pack reads the surface directly
+    int place_[4] = {0, 0, 0, 0}; bool placed_ = false, rgb_identity_ = false;
+    int sar_[2] = {0, 0};                      // the active sequence's sample aspect ratio as transmitted, 0 : 0 = absent
+    std::atomic<long long> stat_placed_{0};
     std::atomic<long long> stat_scaled_{0};
     // RGB output (jm_amddec_set_rgb, before init): every display frame leaves as C(R_G(F)) through k_rgb_pack
     bool rgb_ = false; RgbSpec rgb_spec_ = {};

@@ -118,7 +118,9 @@ std::string ParamSets::parse_sps(BitReader &br) {
         s.crop_l = (int)c[0]; s.crop_r = (int)c[1]; s.crop_t = (int)c[2] * vy; s.crop_b = (int)c[3] * vy;
     }
     if (br.u1()) {   // VUI (E.1.1): the bitstream restriction sizes the DPB; the timing information is what jm_intel_get_stream_info reports
-        if (br.u1()) { if (br.u(8) == 255) { br.u(16); br.u(16); } }
+        if (br.u1()) { const int idc = (int)br.u(8); int sw = 0, sh = 0;                            // aspect_ratio_info
+            if (idc == 255) { sw = (int)br.u(16); sh = (int)br.u(16); }
+            sample_aspect_ratio(idc, sw, sh, s.sar_num, s.sar_den); }
         if (br.u1()) br.u1();
         if (br.u1()) { br.u(3); s.vui_full_range = (int)br.u1();                                   // video_signal_type
             if (br.u1()) { s.vui_primaries = (int)br.u(8); s.vui_transfer = (int)br.u(8); s.vui_matrix = (int)br.u(8); } }

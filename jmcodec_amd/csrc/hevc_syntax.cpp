@@ -172,7 +172,10 @@ std::string HevcParamSets::parse_sps(BitReader &br) {
     // runs off the end of the NAL unit leaves the rate and the colour description unknown and the SPS valid.
     if (br.u1()) {
         int vst[4] = {-1, -1, -1, -1};                                                          // full range, primaries, transfer, matrix
-        if (br.u1()) { if (br.u(8) == 255) { br.u(16); br.u(16); } }                             // aspect ratio
+        int sar[2] = {0, 0};
+        if (br.u1()) { const int idc = (int)br.u(8); int sw = 0, sh = 0;                        // aspect ratio
+            if (idc == 255) { sw = (int)br.u(16); sh = (int)br.u(16); }
+            sample_aspect_ratio(idc, sw, sh, sar[0], sar[1]); }
         if (br.u1()) br.u1();                                                                   // overscan
         if (br.u1()) { br.u(3); vst[0] = (int)br.u1();                                          // video signal type
             if (br.u1()) { vst[1] = (int)br.u(8); vst[2] = (int)br.u(8); vst[3] = (int)br.u(8); } }
@@ -180,7 +183,7 @@ std::string HevcParamSets::parse_sps(BitReader &br) {
         br.u1(); br.u1(); br.u1();                                                              // neutral chroma, field_seq, frame_field_info
         if (br.u1()) { br.ue(); br.ue(); br.ue(); br.ue(); }                                    // default display window
         if (br.u1()) { const uint32_t tick = br.u(32), scale = br.u(32); if (!br.overrun()) { s.num_units_in_tick = tick; s.time_scale = scale; } }
-        if (!br.overrun()) { s.vui_full_range = vst[0]; s.vui_primaries = vst[1]; s.vui_transfer = vst[2]; s.vui_matrix = vst[3]; }
+        if (!br.overrun()) { s.sar_num = sar[0]; s.sar_den = sar[1]; s.vui_full_range = vst[0]; s.vui_primaries = vst[1]; s.vui_transfer = vst[2]; s.vui_matrix = vst[3]; }
     }
     sps[id] = s;
     return "";

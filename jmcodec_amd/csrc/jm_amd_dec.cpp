@@ -54,6 +54,17 @@ template <class Job, class Launch> static int run_one_job(const Job &job, void *
     return e == hipSuccess ? 0 : -(int)e;
 }
 
+// The placement arguments of the *_rect_device calls against the target: rect[] = x, y, w, h in use (w / h 0: to the target's edge); true: the picture
+// is placed (the rectangle is not the whole target).  -1 in *bad: odd, negative or outside the target, or a fill outside -1 .. 0xFFFFFF
+static bool resolve_rect(int tw, int th, int rx, int ry, int rw, int rh, long long fill, int rect[4], bool *bad) {
+    *bad = true;
+    if (((rx | ry | rw | rh) & 1) || rx < 0 || ry < 0 || rw < 0 || rh < 0 || fill < -1 || fill > 0xFFFFFF) return false;
+    rect[0] = rx; rect[1] = ry; rect[2] = rw ? rw : tw - rx; rect[3] = rh ? rh : th - ry;
+    if (rect[2] <= 0 || rect[3] <= 0 || rx + rect[2] > tw || ry + rect[3] > th) return false;
+    *bad = false;
+    return !(rx == 0 && ry == 0 && rect[2] == tw && rect[3] == th);
+}
+
 extern "C" {
 
 __attribute__((visibility("default"))) jm_amddec_handle jm_amddec_create_handle(void) { return new Decoder(); }
@@ -128,15 +139,27 @@ __attribute__((visibility("default"))) int jm_amddec_scale_taps(int src_len, int
     }
     return taps;
 }
+__attribute__((visibility("default"))) int jm_amddec_fit_rect(int cw, int ch, int sar_num, int sar_den, int tw, int th, int fit, int rect[4]) {
+    return jmamd::fit_rect(cw, ch, sar_num, sar_den, tw, th, fit, rect) ? 0 : -1;
+}
 __attribute__((visibility("default"))) int jm_amddec_scale_device(const void *src, int pitch, int chroma_offset, int w, int hgt, int lone_field, int crop_x,
     int crop_y, int crop_w, int crop_h, int tw, int th, int out_fmt, void *dst, void *stream) {
+    return jm_amddec_scale_rect_device(src, pitch, chroma_offset, w, hgt, lone_field, crop_x, crop_y, crop_w, crop_h, tw, th, out_fmt, dst, stream, 0, 0, 0, 0, -1);
+}
+// ... with the picture placed in the target (INTEGRATION.md "Placed output"); the ratio limits apply to the rectangle
+__attribute__((visibility("default"))) int jm_amddec_scale_rect_device(const void *src, int pitch, int chroma_offset, int w, int hgt, int lone_field, int crop_x,
+    int crop_y, int crop_w, int crop_h, int tw, int th, int out_fmt, void *dst, void *stream, int rect_x, int rect_y, int rect_w, int rect_h, int fill) {
     if (!src || !dst || w <= 0 || hgt <= 0 || pitch < w || lone_field < 0 || lone_field > 2 || (out_fmt != 0 && out_fmt != 1)) return -1;
     if ((crop_x | crop_y | crop_w | crop_h | tw | th) & 1) return -1;
     if (crop_x < 0 || crop_y < 0 || crop_w <= 0 || crop_h <= 0 || crop_x + crop_w > w || crop_y + crop_h > hgt || tw <= 0 || th <= 0) return -1;
-    if (crop_w > 8 * tw || crop_h > 8 * th || tw > 4 * crop_w || th > 4 * crop_h) return -1;
+    int rc[4]; bool bad;
+    const bool placed = resolve_rect(tw, th, rect_x, rect_y, rect_w, rect_h, fill, rc, &bad);
+    if (bad) return -1;
+    if (crop_w > 8 * rc[2] || crop_h > 8 * rc[3] || rc[2] > 4 * crop_w || rc[3] > 4 * crop_h) return -1;
     jmamd::ScaleJob job{static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), pitch, chroma_offset, crop_x, crop_y, tw, th, out_fmt, lone_field, {}};
+    if (placed) { job.rx = rc[0]; job.ry = rc[1]; job.rw = rc[2]; job.rh = rc[3]; job.fill = fill < 0 ? 0x108080 : (int)fill; }
     uint8_t *tables = nullptr;
-    if (!jmamd::upload_scale_tables(crop_w, crop_h, tw, th, &tables, job.ax)) return -1;
+    if (!jmamd::upload_scale_tables(crop_w, crop_h, rc[2], rc[3], &tables, job.ax)) return -1;
     const int r = run_one_job(job, stream, [&](const jmamd::ScaleJob *d_job, hipStream_t st) {
         jmamd::launch_scale_pack(d_job, 1, jmamd::scale_tiles(tw, th), st); });
     hipFree(tables);
@@ -220,18 +243,28 @@ __attribute__((visibility("default"))) int jm_amddec_color_coefs(int matrix, int
 }
 __attribute__((visibility("default"))) int jm_amddec_rgb_device(const void *src, int pitch, int chroma_offset, int w, int hgt, int lone_field, int crop_x,
     int crop_y, int crop_w, int crop_h, int tw, int th, const jm_amddec_rgb_spec *spec, void *dst, void *stream) {
+    return jm_amddec_rgb_rect_device(src, pitch, chroma_offset, w, hgt, lone_field, crop_x, crop_y, crop_w, crop_h, tw, th, spec, dst, stream, 0, 0, 0, 0, -1);
+}
+// ... with the picture placed in the target; a placed job whose rectangle has the crop's size (pure padding) reads the surface directly
+__attribute__((visibility("default"))) int jm_amddec_rgb_rect_device(const void *src, int pitch, int chroma_offset, int w, int hgt, int lone_field, int crop_x,
+    int crop_y, int crop_w, int crop_h, int tw, int th, const jm_amddec_rgb_spec *spec, void *dst, void *stream, int rect_x, int rect_y, int rect_w, int rect_h,
+    int fill) {
     if (!src || !dst || !spec || w <= 0 || hgt <= 0 || pitch < w || lone_field < 0 || lone_field > 2) return -1;
     const jmamd::RgbSpec &s = *reinterpret_cast<const jmamd::RgbSpec *>(spec);
     if (!jmamd::rgb_spec_valid(s, true) || ((uintptr_t)dst % (uintptr_t)jmamd::rgb_sample_bytes(s.dtype))) return -1;
     if ((crop_x | crop_y | crop_w | crop_h | tw | th) & 1) return -1;
     if (crop_x < 0 || crop_y < 0 || crop_w <= 0 || crop_h <= 0 || crop_x + crop_w > w || crop_y + crop_h > hgt || tw <= 0 || th <= 0) return -1;
-    if (crop_w > 8 * tw || crop_h > 8 * th || tw > 4 * crop_w || th > 4 * crop_h) return -1;
+    int rc[4]; bool bad;
+    const bool placed = resolve_rect(tw, th, rect_x, rect_y, rect_w, rect_h, fill, rc, &bad);
+    if (bad) return -1;
+    if (crop_w > 8 * rc[2] || crop_h > 8 * rc[3] || rc[2] > 4 * crop_w || rc[3] > 4 * crop_h) return -1;
     jmamd::RgbJob job = {};
     job.s = jmamd::ScaleJob{static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), pitch, chroma_offset, crop_x, crop_y, tw, th, 0, lone_field, {}};
-    job.identity = tw == crop_w && th == crop_h;
+    if (placed) { job.s.rx = rc[0]; job.s.ry = rc[1]; job.s.rw = rc[2]; job.s.rh = rc[3]; job.fill = fill < 0 ? 0 : (int)fill; }
+    job.identity = rc[2] == crop_w && rc[3] == crop_h;
     jmamd::fill_rgb_color(job, s, s.matrix, s.range == 2);
     uint8_t *tables = nullptr;
-    if (!job.identity && !jmamd::upload_scale_tables(crop_w, crop_h, tw, th, &tables, job.s.ax)) return -1;
+    if (!job.identity && !jmamd::upload_scale_tables(crop_w, crop_h, rc[2], rc[3], &tables, job.s.ax)) return -1;
     const int r = run_one_job(job, stream, [&](const jmamd::RgbJob *d_job, hipStream_t st) {
         jmamd::launch_rgb_pack(d_job, 1, job.identity ? jmamd::rgb_tiles(tw, th) : 0, job.identity ? 0 : jmamd::rgb_tiles(tw, th), st); });
     if (tables) hipFree(tables);

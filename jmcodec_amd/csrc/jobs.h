@@ -150,17 +150,23 @@ struct ScaleJob {                 // one display frame to crop + resample + pack
     int tw, th, out_fmt;          // target size (even), 0 = tight NV12, 1 = I420
     int lone_field;               // as PackJob::lone_field
     ScaleAxis ax[4];              // luma x, luma y, chroma x, chroma y (device pointers into the handle's tap tables)
+    // Placed output (INTEGRATION.md "Placed output"): the resampled picture fills the rectangle rw x rh at (rx, ry) of the target (luma samples, even,
+    // inside the target), every sample outside it is the fill.  rw == 0: no placement, the picture is the whole target (and the other four are 0).
+    // The tap tables of a placed job are those of crop -> rw / rh.
+    int rx, ry, rw, rh;
+    int fill;                     // k_scale_pack: Y << 16 | Cb << 8 | Cr (an RgbJob's fill is its own)
 };
 
 // RGB output (k_rgb_pack; the conversion C of INTEGRATION.md "RGB output" applied to R_G(F)).  The geometry fields are ScaleJob's; out_fmt is unused.
 enum : int { RGB_U8 = 0, RGB_F32 = 1, RGB_F16 = 2, RGB_BF16 = 3 };
 struct RgbJob {                   // one display frame to crop + resample + convert (k_rgb_pack, blockIdx.y = job)
-    ScaleJob s;                   // identity geometry (target size == crop size): s.ax[] is not read
-    int identity;                 // 1: no resampling -- the kernel reads the surface directly
+    ScaleJob s;                   // identity geometry (picture size == crop size): s.ax[] is not read
+    int identity;                 // 1: no resampling -- the kernel reads the surface directly (a placed identity job pads the picture with the fill)
     int cy, crv, cgu, cgv, cbu;   // 14-bit coefficients (jm_amddec_color_coefs)
     int yo;                       // luma offset: 16 limited, 0 full range
     int dtype, planar, bgr;       // RGB_*; 1 CHW, 0 HWC; 1 B,G,R order
     float k[3], b[3];             // float samples: fl32(fl32(v * k[c]) + b[c]), c = storage position (k = scale / 16384)
+    int fill;                     // placed jobs: R << 16 | G << 8 | B outside the rectangle (each colour's accumulator is fill << 14)
 };
 
 // Deinterlaced output (k_deint; the function D of INTEGRATION.md "Deinterlaced output").  The source is a pitch-linear NV12 surface; the destination is

@@ -125,16 +125,23 @@ void launch_frame_to_nv12_pitch(const uint8_t *d_src, int w, int h, int fmt, uin
 // ------------------------------------------------------------------------------------------
 // k_scale_pack: k_packout with a crop rectangle and a resampler (options crop_* / target_*, INTEGRATION.md "Scaled and cropped output").
 // One workgroup per output tile of one plane (scale_packed.h), luma tiles first, then chroma tiles: the horizontal pass writes the tile's filtered
-// source rows into LDS as int16, the vertical pass writes 4 output bytes per lane.
+// source rows into LDS as int16, the vertical pass writes 4 output bytes per lane.  A placed job (INTEGRATION.md "Placed output") runs the same two
+// calls: the tile's share of the picture's rectangle goes through the passes, the rest of the tile is stored as fill by the same lanes.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_scale_pack(const ScaleJob *jobs) {
     __shared__ int16_t hbuf[scl::kScaleMaxRows * scl::kScaleTileW];   // [source row][64 columns]: luma, or 32 chroma columns x (U, V)
     const ScaleJob &jb = jobs[blockIdx.y];
     scl::PlaneTile t;
     if (!scl::scale_tile(jb, blockIdx.x, t)) return;
-    scl::hpass_lane(t, threadIdx.x, hbuf);
-    __syncthreads();
-    scl::vpass_store_lane(jb, t, threadIdx.x, hbuf);
+    if (!t.placed) {                                          // (uniform per workgroup: an unplaced job runs the passes without the placement arithmetic)
+        scl::hpass_lane_t<false>(t, threadIdx.x, hbuf);
+        __syncthreads();
+        scl::vpass_store_lane_t<false>(jb, t, threadIdx.x, hbuf);
+    } else {
+        scl::hpass_lane_t<true>(t, threadIdx.x, hbuf);
+        __syncthreads();
+        scl::vpass_store_lane_t<true>(jb, t, threadIdx.x, hbuf);
+    }
 }
 
 int scale_tiles(int tw, int th) { return scl::tiles(tw, th); }
@@ -145,7 +152,8 @@ void launch_scale_pack(const ScaleJob *d_jobs, int n, int max_tiles, hipStream_t
 // ------------------------------------------------------------------------------------------
 // k_rgb_pack: output C(R_G(F)) -- k_scale_pack's crop and resampler followed by the colour conversion C (INTEGRATION.md "RGB output", rgb_packed.h).
 // One workgroup per output tile of 64 x 16 pixels.  Two instantiations over the same job table, each for the jobs of its kind: SCALED = false
-// (identity jobs) uses no LDS, so its occupancy is set by registers alone; SCALED = true holds the two passes' LDS buffers.
+// (identity jobs: the picture's size is the crop's, placed or not) uses no LDS, so its occupancy is set by registers alone; SCALED = true holds the two
+// passes' LDS buffers.  Pixels outside a placed job's rectangle leave as its fill colour through the same sample step and the same stores.
 // ------------------------------------------------------------------------------------------
 template <bool SCALED>
 __global__ __launch_bounds__(256) void k_rgb_pack(const RgbJob *jobs) {
@@ -170,11 +178,15 @@ __global__ __launch_bounds__(256) void k_rgb_pack(const RgbJob *jobs) {
         if (r < t.in) rgbp::vpass_luma_lane(ly, tid, hy, Y);
         __syncthreads();
         if (r < t.in) rgbp::chroma_lane(tid, gc, U, V);
-    } else if (r < t.in) rgbp::fetch_identity(sj, t.i0 + r, t.j0 + 4 * q, t.jn - 4 * q, Y, U, V);
+    } else if (r < t.in) {
+        if (!sj.rw) rgbp::fetch_identity(sj, t.i0 + r, t.j0 + 4 * q, t.jn - 4 * q, Y, U, V);                 // (uniform per workgroup)
+        else rgbp::fetch_placed(sj, t.i0 + r, t.j0 + 4 * q, rgbp::inside_mask(sj, t.i0 + r, t.j0 + 4 * q), Y, U, V);
+    }
     if (r >= t.in) return;
     const int n = min(4, t.jn - 4 * q);
     if (n <= 0) return;
-    rgbp::convert_store(jb, Y, U, V, (size_t)(t.i0 + r) * sj.tw + t.j0 + 4 * q, n);
+    // (a placed job: the pixels outside the picture's rectangle are the fill colour)
+    rgbp::convert_store_masked(jb, Y, U, V, (size_t)(t.i0 + r) * sj.tw + t.j0 + 4 * q, n, rgbp::inside_mask(sj, t.i0 + r, t.j0 + 4 * q));
 }
 
 int rgb_tiles(int tw, int th) { return scl::rgb_tiles(tw, th); }

@@ -4,8 +4,10 @@
 // 4 q .. 4 q + 3, q = tid & 15.  C needs luma AND chroma of the same pixels, so a scaled job resamples both in one workgroup: the tile's luma (64 x 16)
 // and its chroma (32 x 8, both channels) go through the resampler's horizontal pass (scale_packed.h) into two row buffers, the vertical chroma results
 // into a third (gc), then every lane filters 4 luma samples of its row -- the passes are k_scale_pack's own functions, so G is bit-identical.  An
-// identity job (target size == crop size) reads the surface directly, no tap tables.  Then every lane converts its 4 pixels -- 14-bit fixed-point
+// identity job (picture size == crop size) reads the surface directly, no tap tables.  Then every lane converts its 4 pixels -- 14-bit fixed-point
 // accumulators, then the sample type of the job -- and stores 3 x 4 samples.
+// A placed job (ScaleJob::rw != 0): pixels outside the picture's rectangle are the job's fill colour, selected per pixel in front of the sample step
+// (inside_mask, convert_store_masked); pure padding is an identity job (fetch_placed).
 // __host__ __device__ like scale_packed.h: tests/test_rgb_output_host.py walks whole frames through these routines on the CPU
 // (tests/native/rgb_packed_check.cpp, built with clang: _Float16) against the numpy restatement of C(R_G(F)).
 #pragma once
@@ -74,13 +76,19 @@ JM_HD bool tile(const ScaleJob &sj, int t, Tile &o) {
 JM_HD void vpass_chroma_lane(const scl::PlaneTile &c, int tid, const int16_t *hc, uint8_t (*gc)[kRgbTileW]) {
     for (int e = tid; e < (kRgbTileH / 2) * kRgbTileW; e += 256) {
         const int rr = e / kRgbTileW, col = e % kRgbTileW;
-        if (rr < c.in && (col >> 1) < c.jn) { int v; scl::vpass<1>(c, c.i0 + rr, hc, &col, &v); gc[rr][col] = (uint8_t)v; }
+        const int i = c.i0 + rr, j = c.j0 + (col >> 1);          // (the tile's share of the picture: the whole tile unless the job is placed)
+        if (i >= c.ia && i < c.ib && j >= c.ja && j < c.jb) { int v; scl::vpass<1>(c, c.i0 + rr, hc, &col, &v); gc[rr][col] = (uint8_t)v; }
     }
 }
 // ... and the vertical luma pass: the 4 samples of lane tid (y: the luma tile; the lane's row must be one of the tile's)
 JM_HD void vpass_luma_lane(const scl::PlaneTile &y, int tid, const int16_t *hy, int Y[4]) {
     const int r = tid >> 4, q = tid & 15;
-    const int col[4] = {4 * q, 4 * q + 1, 4 * q + 2, 4 * q + 3};
+    int col[4] = {4 * q, 4 * q + 1, 4 * q + 2, 4 * q + 3};
+    if (y.placed) {          // a row outside the picture: nothing; columns outside it are filtered as the nearest inside one (and masked by the caller)
+        if (y.i0 + r < y.ia || y.i0 + r >= y.ib || y.ja >= y.jb) return;
+        JM_SCL_UNROLL
+        for (int e = 0; e < 4; e++) col[e] = scl::imin(scl::imax(col[e], y.ja - y.j0), y.jb - 1 - y.j0);
+    }
     scl::vpass<4>(y, y.i0 + r, hy, col, Y);
 }
 // ... and the lane's chroma of G
@@ -102,15 +110,37 @@ JM_HD void fetch_identity(const ScaleJob &sj, int i, int x, int n, int Y[4], int
     for (int k = 0; k < 2; k++) if (2 * k < n) { U[k] = pc[2 * k]; V[k] = pc[2 * k + 1]; }
 }
 
-// C of the lane's 4 pixels (n of them valid, 1 <= n <= 4), pixel index px = row * tw + column of the first: planar or interleaved stores
-JM_HD void convert_store(const RgbJob &jb, const int Y[4], const int U[2], const int V[2], size_t px, int n) {
+// Placed jobs: which of the 4 pixels from column x on of output row i lie inside the picture's rectangle (bit e: pixel x + e; x and the rectangle are
+// even, so the bits come in pairs).  An unplaced job: all of them.
+JM_HD uint32_t inside_mask(const ScaleJob &sj, int i, int x) {
+    if (!sj.rw) return 15;
+    if (i < sj.ry || i >= sj.ry + sj.rh) return 0;
+    return (x >= sj.rx && x < sj.rx + sj.rw ? 3u : 0u) | (x + 2 >= sj.rx && x + 2 < sj.rx + sj.rw ? 12u : 0u);
+}
+// Identity geometry of a placed job (pure padding): fetch_identity for the pixel pairs of `inside`, from the picture's own row and column
+JM_HD void fetch_placed(const ScaleJob &sj, int i, int x, uint32_t inside, int Y[4], int U[2], int V[2]) {
+    if (!inside) return;
+    const int pi = i - sj.ry, px = sj.crop_x + x - sj.rx;          // (px + 2 k >= crop_x for the pairs of `inside`)
+    const uint8_t *py = sj.src + (size_t)scl::surface_row(sj.crop_y + pi, sj.lone_field) * sj.pitch;
+    const uint8_t *pc = sj.src + sj.chroma_offset + (size_t)scl::surface_row((sj.crop_y >> 1) + (pi >> 1), sj.lone_field) * sj.pitch;
+    JM_SCL_UNROLL
+    for (int k = 0; k < 2; k++) if ((inside >> (2 * k)) & 1) {
+        Y[2 * k] = py[px + 2 * k]; Y[2 * k + 1] = py[px + 2 * k + 1]; U[k] = pc[px + 2 * k]; V[k] = pc[px + 2 * k + 1]; }
+}
+
+// C of the lane's 4 pixels (n of them valid, 1 <= n <= 4), pixel index px = row * tw + column of the first: planar or interleaved stores.  A pixel
+// whose bit of `inside` is clear is the job's fill colour: its accumulators are fill << 14, through the same sample step.
+JM_HD void convert_store_masked(const RgbJob &jb, const int Y[4], const int U[2], const int V[2], size_t px, int n, uint32_t inside) {
     const ScaleJob &sj = jb.s;
     uint32_t s[3][4];
+    const int fR = ((jb.fill >> 16) & 255) << 14, fG = ((jb.fill >> 8) & 255) << 14, fB = (jb.fill & 255) << 14;
+    const int fa[3] = {jb.bgr ? fB : fR, fG, jb.bgr ? fR : fB};
     JM_SCL_UNROLL
     for (int e = 0; e < 4; e++) {
         const int yv = jb.cy * (Y[e] - jb.yo), d = U[e >> 1] - 128, f = V[e >> 1] - 128;
         const int aR = yv + jb.crv * f, aG = yv - jb.cgu * d - jb.cgv * f, aB = yv + jb.cbu * d;
-        const int a[3] = {jb.bgr ? aB : aR, aG, jb.bgr ? aR : aB};          // storage positions
+        const bool in = (inside >> e) & 1;
+        const int a[3] = {in ? (jb.bgr ? aB : aR) : fa[0], in ? aG : fa[1], in ? (jb.bgr ? aR : aB) : fa[2]};          // storage positions
         JM_SCL_UNROLL
         for (int c = 0; c < 3; c++) {
             if (jb.dtype == RGB_U8) s[c][e] = rgb_u8(a[c]);
@@ -134,6 +164,7 @@ JM_HD void convert_store(const RgbJob &jb, const int Y[4], const int U[2], const
         for (int g = 0; g < 3; g++) store4(d + 4 * g * sz, sz, v + 4 * g, 3 * n - 4 * g);
     }
 }
+JM_HD void convert_store(const RgbJob &jb, const int Y[4], const int U[2], const int V[2], size_t px, int n) { convert_store_masked(jb, Y, U, V, px, n, 15); }
 
 }  // namespace rgbp
 }  // namespace jmamd

@@ -78,6 +78,8 @@ typedef struct {
                                    matrix_coefficients / colour_primaries / transfer_characteristics) -- what the RGB output converts with */
     int vui_full_range;         /* 1: video_full_range_flag 1 (video_signal_type is then written even without a colour description); all four 0: no
                                    video_signal_type */
+    int vui_sar_idc, vui_sar_w, vui_sar_h;   /* vui_sar_idc > 0: the VUI carries this aspect_ratio_idc (255: followed by sar_width = vui_sar_w and sar_height =
+                                   vui_sar_h, 16 bits each); 0: aspect_ratio_idc 1 when there is a VUI for another reason, as before */
 } GenParams;
 
 /* ------------------------------ RNG --------------------------------------- */
@@ -1973,9 +1975,10 @@ static void write_sps_pps(Enc *e) {
     int cr = (e->W - p->width) / 2, cb = (e->H - p->height) / (p->fmo0 ? 4 : 2);   /* CropUnitY = 2 * (2 - frame_mbs_only_flag) */
     if (cr || cb) { bw_put(w, 1, 1); bw_ue(w, 0); bw_ue(w, cr); bw_ue(w, 0); bw_ue(w, cb); } else bw_put(w, 1, 0);
     const int colour_desc = p->vui_matrix > 0 || p->vui_primaries > 0 || p->vui_transfer > 0, signal_type = colour_desc || p->vui_full_range > 0;
-    if (p->vui_fps > 0 || signal_type) {                                  /* vui_parameters() (E.1.1) */
+    if (p->vui_fps > 0 || signal_type || p->vui_sar_idc > 0) {            /* vui_parameters() (E.1.1) */
         bw_put(w, 1, 1);
-        bw_put(w, 1, 1); bw_put(w, 8, 1);                                 /* aspect_ratio_info_present_flag, aspect_ratio_idc 1 (square) */
+        bw_put(w, 1, 1); bw_put(w, 8, p->vui_sar_idc > 0 ? (uint32_t)p->vui_sar_idc & 255 : 1);   /* aspect_ratio_info_present_flag, aspect_ratio_idc (1: square) */
+        if (p->vui_sar_idc == 255) { bw_put(w, 16, (uint32_t)p->vui_sar_w & 65535); bw_put(w, 16, (uint32_t)p->vui_sar_h & 65535); }   /* Extended_SAR */
         bw_put(w, 1, 0);                                                  /* no overscan info */
         bw_put(w, 1, (uint32_t)signal_type);                              /* video_signal_type_present_flag */
         if (signal_type) {
@@ -2683,6 +2686,7 @@ int main(int argc, char **argv) {
         OPT("--bframes", bframes) OPT("--direct-temporal", direct_temporal) OPT("--wp", wp) OPT("--dinf8", dinf8) OPT("--scaling", scaling) OPT("--rplm",
             rplm) OPT("--mmco", mmco) OPT("--nc-corner", nc_corner) OPT("--no-intra", no_intra) OPT("--fmo0", fmo0) OPT("--poc-bottom", poc_bottom) OPT("--paff", paff) OPT("--gaps", gaps) OPT("--redundant", redundant) OPT("--vui-fps", vui_fps)
         OPT("--vui-matrix", vui_matrix) OPT("--vui-primaries", vui_primaries) OPT("--vui-transfer", vui_transfer) OPT("--vui-full-range", vui_full_range)
+        OPT("--vui-sar-idc", vui_sar_idc) OPT("--vui-sar-w", vui_sar_w) OPT("--vui-sar-h", vui_sar_h)
         if (!strcmp(a, "-o")) { outp = v; i++; continue; }
         if (!strcmp(a, "--recon")) { recon = v; i++; continue; }
         fprintf(stderr, "unknown option %s\n", a); return 2;

@@ -55,6 +55,7 @@ typedef struct {
     int vui_fps;                /* > 0: the SPS carries vui_parameters() with vui_timing_info (num_units_in_tick 1, time_scale vui_fps); no effect on decoding */
     int vui_matrix, vui_primaries, vui_transfer;   /* any > 0: the VUI carries video_signal_type with a colour description (these three values) */
     int vui_full_range;         /* 1: video_full_range_flag 1; all four 0: no video_signal_type */
+    int vui_sar_idc, vui_sar_w, vui_sar_h;   /* vui_sar_idc > 0: the VUI carries this aspect_ratio_idc (255: then sar_width / sar_height, 16 bits each) */
 } HevcGenParams;
 
 /* ------------------------------ RNG ------------------------------ */
@@ -1445,9 +1446,10 @@ static void write_sps(Enc *e, BitW *out, int max_dpb, int reorder) {
     if (p->lt_ref) bw_ue(&w, 0);
     bw_put(&w, 1, (uint32_t)p->tmvp); bw_put(&w, 1, (uint32_t)p->strong_intra);
     const int colour_desc = p->vui_matrix > 0 || p->vui_primaries > 0 || p->vui_transfer > 0, signal_type = colour_desc || p->vui_full_range > 0;
-    if (p->vui_fps > 0 || signal_type) {                              /* vui_parameters() (E.2.1) */
+    if (p->vui_fps > 0 || signal_type || p->vui_sar_idc > 0) {        /* vui_parameters() (E.2.1) */
         bw_put(&w, 1, 1);
-        bw_put(&w, 1, 1); bw_put(&w, 8, 1);                           /* aspect_ratio_info_present_flag, aspect_ratio_idc 1 */
+        bw_put(&w, 1, 1); bw_put(&w, 8, p->vui_sar_idc > 0 ? (uint32_t)p->vui_sar_idc & 255 : 1);   /* aspect_ratio_info_present_flag, aspect_ratio_idc */
+        if (p->vui_sar_idc == 255) { bw_put(&w, 16, (uint32_t)p->vui_sar_w & 65535); bw_put(&w, 16, (uint32_t)p->vui_sar_h & 65535); }   /* EXTENDED_SAR */
         bw_put(&w, 1, 0);                                             /* overscan: absent */
         bw_put(&w, 1, (uint32_t)signal_type);                         /* video_signal_type_present_flag */
         if (signal_type) {
@@ -1903,7 +1905,7 @@ int main(int argc, char **argv) {
         {"--cabac-init", &p.cabac_init}, {"--par-mrg", &p.par_mrg}, {"--cb-qp-off", &p.cb_qp_off}, {"--cr-qp-off", &p.cr_qp_off}, {"--search", &p.search},
             {"--rps-sps", &p.rps_sps}, {"--open-gop", &p.open_gop}, {"--vui-fps", &p.vui_fps},
             {"--vui-matrix", &p.vui_matrix}, {"--vui-primaries", &p.vui_primaries}, {"--vui-transfer", &p.vui_transfer},
-            {"--vui-full-range", &p.vui_full_range} };
+            {"--vui-full-range", &p.vui_full_range}, {"--vui-sar-idc", &p.vui_sar_idc}, {"--vui-sar-w", &p.vui_sar_w}, {"--vui-sar-h", &p.vui_sar_h} };
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-o") && i + 1 < argc) { outp = argv[++i]; continue; }
         if (!strcmp(argv[i], "--recon") && i + 1 < argc) { recon = argv[++i]; continue; }

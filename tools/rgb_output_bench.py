@@ -7,7 +7,10 @@ bench's hot loop) with every frame fetched, legs alternated in one process:
 and, frames left in device memory (option device_output, jm_amddec_output_frame_device): c again and RGB planar f32 at 1920x1080.
 One JSON line per leg and round, then a summary line with the median frames / s per leg.
 
-    python tools/rgb_output_bench.py [--streams 32] [--frames 30] [--passes 4] [--rounds 3]
+    python tools/rgb_output_bench.py [--streams 32] [--frames 30] [--passes 4] [--rounds 3] [--fit 1]
+
+--fit 1 / 2: the 224x224 legs letterbox the centre 1440x1080 of the picture (option fit, INTEGRATION.md "Placed output": rectangle 224x168, 6.4:1 down)
+instead of stretching the centre 1080x1080 -- the whole 1920x1080 picture would be 8.6:1 down into 224x126, beyond the resampler's 8:1.
 
 Kernel times per frame: run it under rocprofv3 --kernel-trace --stats and divide the kernels' totals by the frames the legs report."""
 import argparse
@@ -103,6 +106,7 @@ def main():
     ap.add_argument("--passes", type=int, default=4)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--legs", default=",".join(LEGS), help="comma-separated subset of: " + ", ".join(LEGS))
+    ap.add_argument("--fit", type=int, default=0, choices=(0, 1, 2), help="the 224x224 legs letterbox the centre 1440x1080 (1 centred, 2 top left)")
     args = ap.parse_args()
     L = api.lib()
     L.jm_amddec_output_frame_device.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p]
@@ -113,6 +117,8 @@ def main():
     for r in range(args.rounds):
         for name in names:
             opts, rgb, device = LEGS[name]
+            if args.fit and opts:
+                opts = dict(crop_x=240, crop_y=0, crop_w=1440, crop_h=1080, target_width=opts["target_width"], target_height=opts["target_height"], fit=args.fit)
             fps, n, dt = run_leg(L, datas, opts, rgb, device, args.passes)
             rates[name].append(fps)
             print(json.dumps({"leg": name, "round": r, "frames": n, "seconds": round(dt, 3), "frames_per_s": round(fps, 1)}), flush=True)

@@ -2,7 +2,10 @@
 (the bench's hot loop) with every frame fetched into a host buffer -- once at the display size (k_packout) and once with target 960x540
 (k_scale_pack), the two legs alternated in one process.  One JSON line per leg and round, then a summary line.
 
-    python tools/scaled_output_bench.py [--streams 32] [--frames 60] [--passes 2] [--rounds 3] [--target 960x540]
+    python tools/scaled_output_bench.py [--streams 32] [--frames 60] [--passes 2] [--rounds 3] [--target 960x540] [--fit 1]
+
+--fit 1 / 2: the scaled leg letterboxes the picture into the target (option fit, INTEGRATION.md "Placed output") instead of stretching it, e.g.
+--target 640x640 --fit 1 beside --target 640x360.
 
 Kernel times per frame: run it under rocprofv3 --kernel-trace --stats and divide the kernels' totals by the frames the legs report."""
 import argparse
@@ -19,7 +22,7 @@ from jmcodec_amd import api  # noqa: E402
 from tools import streams  # noqa: E402
 
 
-def run_leg(L, datas, target, passes, W, H):
+def run_leg(L, datas, target, passes, W, H, fit=0):
     """One leg: fresh handles, one warm-up pass, then `passes` timed passes of every stream on its own thread.  Returns frames / s and frames."""
     S = len(datas)
     tw, th = target or (W, H)
@@ -28,7 +31,7 @@ def run_leg(L, datas, target, passes, W, H):
     for _ in range(S):
         h = api.jm_nvdec_create_handle()
         if target:
-            for k, v in (("target_width", tw), ("target_height", th)):
+            for k, v in (("target_width", tw), ("target_height", th)) + ((("fit", fit),) if fit else ()):
                 assert L.jm_amddec_set_option(h, k.encode(), v) == 0
         if api.jm_nvdec_init(0, 1, None, 0, h) != 0:
             raise SystemExit("init failed: " + L.jm_amddec_last_error(h).decode())
@@ -83,6 +86,7 @@ def main():
     ap.add_argument("--passes", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--target", default="960x540")
+    ap.add_argument("--fit", type=int, default=0, choices=(0, 1, 2), help="letterbox into the target (1 centred, 2 top left) instead of stretching")
     args = ap.parse_args()
     tw, th = (int(x) for x in args.target.split("x"))
     L = api.lib()
@@ -91,9 +95,9 @@ def main():
     legs = {"full": [], "scaled": []}
     for r in range(args.rounds):
         for name, target in (("full", None), ("scaled", (tw, th))):
-            fps, n, dt = run_leg(L, datas, target, args.passes, 1920, 1080)
+            fps, n, dt = run_leg(L, datas, target, args.passes, 1920, 1080, args.fit if target else 0)
             legs[name].append(fps)
-            print(json.dumps({"leg": name, "round": r, "target": f"{tw}x{th}" if target else "1920x1080", "frames": n, "seconds": round(dt, 3),
+            print(json.dumps({"leg": name, "round": r, "target": f"{tw}x{th}" if target else "1920x1080", "fit": args.fit if target else 0, "frames": n, "seconds": round(dt, 3),
                               "frames_per_s": round(fps, 1)}), flush=True)
     med = {k: sorted(v)[len(v) // 2] for k, v in legs.items()}
     print(json.dumps({"summary": True, "streams": args.streams, "median_full_fps": round(med["full"], 1), "median_scaled_fps": round(med["scaled"], 1),
