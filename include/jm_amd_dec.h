@@ -197,6 +197,22 @@ int  jm_amddec_rgb_device(const void *d_src, int pitch, int chroma_offset, int w
 int  jm_amddec_rgb_rect_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int lone_field, int crop_x, int crop_y, int crop_w,
                                int crop_h, int tw, int th, const jm_amddec_rgb_spec *spec, void *d_dst, void *stream, int rect_x, int rect_y,
                                int rect_w, int rect_h, int fill);
+/* Interpolated chroma (INTEGRATION.md "RGB output" defines it exactly).  Options of an RGB handle, before init (set_option returns -1 after init and for
+ * values out of range):
+ *   "rgb_chroma": 0 (default) nearest chroma of the 4:2:0 frame at target size, as above; 1: the conversion is applied to a 4:4:4 frame whose chroma
+ *     planes are the crop's chroma resampled straight to the full target at the stream's chroma sample location.  Without an RGB spec init fails and
+ *     jm_amddec_last_error names the option.
+ *   "chroma_loc": -1 (default) auto -- the VUI's chroma_sample_loc_type_top_field when present and 0..5, else 0; MJPEG: 1 --, 0..5: that location.  No
+ *     effect without "rgb_chroma".  The frame's siting is applied to every frame handed out; per-field siting is not applied.
+ * Stats: "vui_chroma_loc" / "vui_chroma_loc_bottom" (as transmitted, -1 = absent), "chroma_loc" (in use), "rgb_chroma", "rgb_chroma_frames", and with
+ * option "profile" k_rgb_pack444_ns / _n / _pics (these frames count in k_rgb_pack_* and k_packout_* too).
+ *   jm_amddec_chroma_taps: the tap table of one chroma axis, src_len chroma samples -> dst_len outputs of the full target with the siting shift q
+ *     (-1, 0, +1 quarters of a chroma sample), in jm_amddec_scale_taps' layout and with its return values (host only); q = 0 is jm_amddec_scale_taps.
+ *   jm_amddec_rgb_chroma_device: jm_amddec_rgb_rect_device with interpolated chroma at chroma_loc 0..5; same validation and return codes. */
+int  jm_amddec_chroma_taps(int src_len, int dst_len, int q, int *first, short *weights, int max_taps);
+int  jm_amddec_rgb_chroma_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int lone_field, int crop_x, int crop_y, int crop_w,
+                                 int crop_h, int tw, int th, const jm_amddec_rgb_spec *spec, void *d_dst, void *stream, int rect_x, int rect_y,
+                                 int rect_w, int rect_h, int fill, int chroma_loc);
 /* Picture hash verification (INTEGRATION.md "Picture hash" defines both hashes exactly).  An HEVC stream may say what every decoded picture hashes to:
  * the decoded picture hash SEI message (payload type 132) in a suffix SEI NAL unit (type 40) holds an MD5, a CRC or a checksum per colour component of
  * the picture at its coded size.  Option "verify_hash", before init (set_option returns -1 after init and for other values):

@@ -97,6 +97,8 @@ def lib():
     L.jm_amddec_rgb_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(RgbSpec), vp, vp]
     L.jm_amddec_rgb_rect_device.argtypes = L.jm_amddec_rgb_device.argtypes + [C.c_int] * 5
+    L.jm_amddec_rgb_chroma_device.argtypes = L.jm_amddec_rgb_rect_device.argtypes + [C.c_int]
+    L.jm_amddec_chroma_taps.argtypes = [C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_short), C.c_int]
     L.jm_amddec_picture_hash_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), vp]
     L.jm_amddec_picture_md5_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte * 16), vp]
     _LIB = L
@@ -212,6 +214,24 @@ def rgb_rect_device(src, pitch, chroma_offset, width, height, crop, target, spec
     """jm_amddec_rgb_rect_device: rgb_device with the picture placed at rect = (x, y, w, h) of the target and the rest filled (fill -1: black, else
     0xRRGGBB).  Returns 0 or < 0."""
     return lib().jm_amddec_rgb_rect_device(src, pitch, chroma_offset, width, height, lone_field, *crop, *target, C.byref(spec), dst, stream, *rect, fill)
+
+
+# ---- interpolated chroma of the RGB output (include/jm_amd_dec.h; INTEGRATION.md "RGB output") ----------
+def chroma_taps(src_len, dst_len, q, max_taps=5):
+    """jm_amddec_chroma_taps: the tap table of one chroma axis, src_len chroma samples -> dst_len outputs of the full target with the siting shift q
+    (-1, 0, +1), as scale_taps returns it.  None when the ratio or q is invalid."""
+    first, w = (C.c_int * max(dst_len, 1))(), (C.c_short * max(dst_len * max_taps, 1))()
+    taps = lib().jm_amddec_chroma_taps(src_len, dst_len, q, first, w, max_taps)
+    if taps < 0:
+        return None
+    return list(first[:dst_len]), [list(w[j * max_taps:j * max_taps + taps]) for j in range(dst_len)]
+
+
+def rgb_chroma_device(src, pitch, chroma_offset, width, height, crop, target, spec, dst, chroma_loc, rect=(0, 0, 0, 0), fill=-1, lone_field=0, stream=None):
+    """jm_amddec_rgb_chroma_device: rgb_rect_device with chroma interpolated to full resolution at chroma_sample_loc_type chroma_loc (0..5).
+    Returns 0 or < 0."""
+    return lib().jm_amddec_rgb_chroma_device(src, pitch, chroma_offset, width, height, lone_field, *crop, *target, C.byref(spec), dst, stream, *rect, fill,
+                                             chroma_loc)
 
 
 # ---- picture hash (include/jm_amd_dec.h; both hashes are defined in INTEGRATION.md "Picture hash") ----------

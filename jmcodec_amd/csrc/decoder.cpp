@@ -177,6 +177,14 @@ int Decoder::set_option(const char *key, long long v) {
         if (inited_ || v < 0 || v > 1) return -1;
         verify_md5_ = (int)v;
     }
+    else if (k == "rgb_chroma") {            // RGB output: 1 = chroma interpolated to full resolution at the stream's siting (k_rgb_pack444)
+        if (inited_ || v < 0 || v > 1) return -1;
+        rgb_chroma_ = (int)v;
+    }
+    else if (k == "chroma_loc") {            // ... -1 = the siting from the stream, 0..5 = this chroma_sample_loc_type
+        if (inited_ || v < -1 || v > 5) return -1;
+        chroma_loc_opt_ = (int)v;
+    }
     else if (k == "profile") { profile_ = v != 0; if (engine_) engine_->set_profile(profile_); }
     else if (k.rfind("chain_", 0) == 0 || k == "debug_stall" || k == "debug_no_bi" || k == "early_intra_ahead") {    // engine-wide knobs (every handle of the device), after init
         if (!engine_ || !engine_->set_knob(k, v)) return -1;
@@ -222,6 +230,12 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "vui_matrix") return vui_[3];
     if (k == "color_matrix") return color_matrix_;
     if (k == "color_range") return color_range_;
+    // interpolated chroma: the VUI's chroma sample location as transmitted (-1 = absent), the location in use, the option, frames that went through it
+    if (k == "vui_chroma_loc") return vui_chroma_loc_[0];
+    if (k == "vui_chroma_loc_bottom") return vui_chroma_loc_[1];
+    if (k == "chroma_loc") return chroma_loc_;
+    if (k == "rgb_chroma") return rgb_chroma_;
+    if (k == "rgb_chroma_frames") return stat_rgb_chroma_;
     if (k == "pictures") return stat_pictures_;
     // option verify_hash: pictures that carried a hash message / compared / differing / not compared (failed batch) / carrying MD5 (never compared)
     if (k == "hash_pictures") return stat_hash_pics_;
@@ -305,7 +319,7 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "wait_slot_ns") return stat_wait_slot_ns_;
     if (k == "parse_ns_p") return stat_parse_ns_p_;
     if (k.rfind("k_", 0) == 0 || k.rfind("eng_", 0) == 0) {          // engine-wide (all handles on this device), profile option
-        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5"};
+        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5", "rgb_pack444"};
         if (!engine_) return 0;
         EngineStats es = engine_->stats();
         for (int i = 0; i < kKernelClasses; i++) {
@@ -364,6 +378,7 @@ long long Decoder::get_stat(const char *key) const {
 int Decoder::init(int codec_type, int out_fmt, const uint8_t *extra, int len) {
     codec_ = codec_type; out_fmt_ = out_fmt ? 1 : 0;
     if (codec_type != 0 && codec_type != 1 && codec_type != 2) { fail("only codec_type 0 (H.264), 1 (HEVC) and 2 (MJPEG) are implemented"); return -1; }
+    if (rgb_chroma_ && !rgb_) { fail("option rgb_chroma needs RGB output: set an RGB spec (jm_amddec_set_rgb) before init"); return -1; }
     if (getenv("JM_AMD_DEC_SYNC")) sync_mode_ = true;
     if (const char *js = getenv("JM_AMD_DEC_JOB_SLOTS")) { n_jobs_ = std::max(8, std::min(atoi(js), kMaxJobSlots)); n_jobs_set_ = true; }
     if (const char *dd = getenv("JM_AMD_DEC_DISPLAY_DELAY")) display_delay_ = std::max(0, std::min(atoi(dd), n_jobs_ - 4));
@@ -489,6 +504,7 @@ void Decoder::gpu_free_sequence() {
     for (auto &w : hevc_work_) if (w) { hipFree(w); w = nullptr; }
     if (hevc_bs_) { hipFree(hevc_bs_); hevc_bs_ = nullptr; }
     if (scale_dev_) { hipFree(scale_dev_); scale_dev_ = nullptr; }
+    if (chroma_dev_) { hipFree(chroma_dev_); chroma_dev_ = nullptr; }
     free_job_buffers();
     free_out_slots(true);
 }
@@ -532,6 +548,29 @@ bool upload_scale_tables(int w, int h, int tw, int th, uint8_t **dev, ScaleAxis 
     if (!HIP_OK(hipMalloc((void **)dev, total))) { *dev = nullptr; return false; }
     if (!HIP_OK(hipMemcpy(*dev, host.data(), total, hipMemcpyHostToDevice))) { hipFree(*dev); *dev = nullptr; return false; }
     for (int a = 0; a < 4; a++) { ax[a].first = (const int32_t *)(*dev + off[a][0]); ax[a].w = (const int16_t *)(*dev + off[a][1]); }
+    return true;
+}
+
+// ... and the two chroma tables of an RGB handle with interpolated chroma: Sc = crop / 2 -> the full target, shifted by the siting
+bool upload_chroma_tables(int w, int h, int tw, int th, int loc, uint8_t **dev, ScaleAxis cax[2]) {
+    if (loc < 0 || loc > 5) return false;
+    const int S[2] = {w / 2, h / 2}, D[2] = {tw, th}, q[2] = {chr::siting_qx(loc), chr::siting_qy(loc)};
+    std::vector<int32_t> first[2]; std::vector<int16_t> wt[2];
+    size_t off[2][2], total = 0;
+    for (int a = 0; a < 2; a++) {
+        const int T = build_chroma_taps(S[a], D[a], q[a], first[a], wt[a]);
+        if (T < 0 || T > chr::kChromaMaxTaps) return false;
+        cax[a].taps = T; cax[a].src_len = S[a];
+        off[a][0] = total; total += (first[a].size() * sizeof(int32_t) + 255) & ~(size_t)255;
+        off[a][1] = total; total += (wt[a].size() * sizeof(int16_t) + 255) & ~(size_t)255;
+    }
+    std::vector<uint8_t> host(total, 0);
+    for (int a = 0; a < 2; a++) { memcpy(host.data() + off[a][0], first[a].data(), first[a].size() * sizeof(int32_t));
+        memcpy(host.data() + off[a][1], wt[a].data(), wt[a].size() * sizeof(int16_t)); }
+    *dev = nullptr;
+    if (!HIP_OK(hipMalloc((void **)dev, total))) { *dev = nullptr; return false; }
+    if (!HIP_OK(hipMemcpy(*dev, host.data(), total, hipMemcpyHostToDevice))) { hipFree(*dev); *dev = nullptr; return false; }
+    for (int a = 0; a < 2; a++) { cax[a].first = (const int32_t *)(*dev + off[a][0]); cax[a].w = (const int16_t *)(*dev + off[a][1]); }
     return true;
 }
 
@@ -585,6 +624,15 @@ void Decoder::resolve_color(const int vui[4], int disp_h) {
     if (m == 0) m = vui[3] >= 0 && color_coefs(vui[3], false, c) ? vui[3] : (disp_h > 576 ? 1 : 6);
     const int r = rgb_ && rgb_spec_.range ? rgb_spec_.range : (vui[0] == 1 ? 2 : 1);
     color_matrix_ = m; color_range_ = r;
+}
+
+// auto location: the VUI's top-field value when it is one of the six, else what the codec implies (frame siting only: the bottom-field value is recorded)
+bool Decoder::resolve_chroma_loc(int vui_top, int vui_bottom, int fallback) {
+    vui_chroma_loc_[0] = vui_top; vui_chroma_loc_[1] = vui_bottom;
+    const int loc = chroma_loc_opt_ >= 0 ? chroma_loc_opt_ : (vui_top >= 0 && vui_top <= 5 ? vui_top : fallback);
+    const bool changed = loc != chroma_loc_;
+    chroma_loc_ = loc;
+    return changed && rgb_chroma_ && rgb_;
 }
 
 // the letterbox rectangle in 64-bit integers: W' = cw * sn, H' = ch * sd; the axis that fills the target is the one whose ratio is larger
@@ -693,7 +741,11 @@ bool Decoder::gpu_alloc_sequence() {
     hipSetDevice(device_);
     // (re-activation: nothing is in flight any more, activate() drained the handle)
     if (scale_dev_) { hipFree(scale_dev_); scale_dev_ = nullptr; }
-    if (scaled_ && !upload_scale_tables(crop_[2], crop_[3], place_[2], place_[3], &scale_dev_, scale_ax_)) { fail("scale table allocation failed"); return false; }
+    // (interpolated chroma: every geometry goes through the tables, the identity too, and the chroma tables follow the siting in use)
+    const bool chroma444 = rgb_ && rgb_chroma_;
+    if ((scaled_ || chroma444) && !upload_scale_tables(crop_[2], crop_[3], place_[2], place_[3], &scale_dev_, scale_ax_)) { fail("scale table allocation failed"); return false; }
+    if (chroma_dev_) { hipFree(chroma_dev_); chroma_dev_ = nullptr; }
+    if (chroma444 && !upload_chroma_tables(crop_[2], crop_[3], place_[2], place_[3], chroma_loc_, &chroma_dev_, chroma_ax_)) { fail("chroma table allocation failed"); return false; }
     pitch_ = (mb_w_ * 16 + 127) & ~127;
     chroma_off_ = pitch_ * mb_h_ * 16;
     surf_bytes_ = (size_t)pitch_ * mb_h_ * 16 * 3 / 2;
@@ -898,6 +950,8 @@ bool Decoder::activate(const SeqParams &sps) {
     bool changed = !seq_active_ || sps.mb_w != mb_w_ || sps.mb_h != mb_h_ || sps.disp_w() != disp_w_ || sps.disp_h() != disp_h_;
     // (the colour of every sequence, size change or not: pictures decoded before keep theirs in DpbPic::color)
     { const int vui[4] = {sps.vui_full_range, sps.vui_primaries, sps.vui_transfer, sps.vui_matrix}; resolve_color(vui, sps.disp_h()); }
+    // (interpolated chroma: the tap tables follow the chroma sample location)
+    if (resolve_chroma_loc(sps.vui_chroma_loc, sps.vui_chroma_loc_bottom, 0)) changed = true;
     // (a letterbox that honours the sample aspect ratio is computed again when the ratio changes)
     if (fit_ && fit_sar_ && (sps.sar_num != sar_[0] || sps.sar_den != sar_[1])) changed = true;
     sar_[0] = sps.sar_num; sar_[1] = sps.sar_den;
@@ -1796,6 +1850,7 @@ void Decoder::enqueue_output(int entry, OutSide &out) {
             rj.s = ScaleJob{src, dst_of(s), pitch_, src_chroma, crop_[0], crop_[1], out_w_, out_h_, 0, lone, {}};
             for (int a = 0; a < 4; a++) rj.s.ax[a] = scale_ax_[a];
             rj.identity = rgb_identity_ ? 1 : 0;
+            if (rgb_chroma_) { rj.identity = 0; rj.chroma = 1; rj.cax[0] = chroma_ax_[0]; rj.cax[1] = chroma_ax_[1]; stat_rgb_chroma_++; }
             if (placed_) { rj.s.rx = place_[0]; rj.s.ry = place_[1]; rj.s.rw = place_[2]; rj.s.rh = place_[3]; rj.fill = fill_ < 0 ? 0 : (int)fill_; }
             fill_rgb_color(rj, rgb_spec_, color & 15, (color >> 4) == 2);
             out.rgb.push_back(rj); stat_rgb_++;
@@ -2016,9 +2071,11 @@ int Decoder::decode(const uint8_t *buf, int len, int *got_frame) {
         if (drained && eos_sent_ && !is_exit_) {            // nv_dec.cpp:460-466
             elapsed_ms_ = timer_started_ ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0_).count() : 0.0;
             is_exit_ = true;
-            char fmt[64];
+            char fmt[96];
             if (rgb_) { static const char *const dt[4] = {"u8", "f32", "f16", "bf16"};
-                snprintf(fmt, sizeof fmt, "%s %s %s", rgb_spec_.bgr ? "BGR" : "RGB", rgb_spec_.planar ? "planar" : "interleaved", dt[rgb_spec_.dtype & 3]); }
+                char loc[40] = "";                           // (only with option rgb_chroma)
+                if (rgb_chroma_) snprintf(loc, sizeof loc, ", chroma interpolated (loc %d)", chroma_loc_);
+                snprintf(fmt, sizeof fmt, "%s %s %s%s", rgb_spec_.bgr ? "BGR" : "RGB", rgb_spec_.planar ? "planar" : "interleaved", dt[rgb_spec_.dtype & 3], loc); }
             else snprintf(fmt, sizeof fmt, "%s", out_fmt_ == 0 ? "NV12" : "YV12");
             char deint[96] = "";                             // (only with option deinterlace: the text is the reference's otherwise)
             if (deint_mode_) snprintf(deint, sizeof deint, "Deinterlace:\t%s, %s%s, %lld frames\n", deint_mode_ == 1 ? "bob" : "comb-adaptive",

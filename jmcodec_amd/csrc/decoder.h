@@ -14,6 +14,7 @@
 #include "jpeg_syntax.h"
 #include "jobs.h"
 #include "scale_packed.h"    // build_scale_taps
+#include "chroma_packed.h"   // build_chroma_taps
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -146,6 +147,8 @@ bool fit_rect(int cw, int ch, int sar_num, int sar_den, int tw, int th, int fit,
 // RGB output (INTEGRATION.md "RGB output"): the spec of jm_amddec_set_rgb (same layout as jm_amddec_rgb_spec)
 struct RgbSpec { int dtype, planar, bgr, matrix, range; float scale[3], bias[3]; };
 bool rgb_spec_valid(const RgbSpec &s, bool need_matrix);
+// the chroma x / y tables of crop w x h -> the full target tw x th at chroma_sample_loc_type loc (build_chroma_taps, chroma_packed.h), uploaded
+bool upload_chroma_tables(int w, int h, int tw, int th, int loc, uint8_t **dev, ScaleAxis cax[2]);
 inline int rgb_sample_bytes(int dtype) { return dtype == RGB_U8 ? 1 : (dtype == RGB_F32 ? 4 : 2); }
 // cy, crv, cgu, cgv, cbu of H.273 MatrixCoefficients `matrix` (1, 4, 5, 6, 7, 9), limited or full range; false when unsupported
 bool color_coefs(int matrix, bool full_range, int c[5]);
@@ -252,6 +255,9 @@ private:
     // the colour description of the sequence being activated (vui: full range, primaries, transfer, matrix as transmitted, -1 = absent): the
     // matrix and range its frames are converted with
     void resolve_color(const int vui[4], int disp_h);
+    // the chroma sample location of the sequence being activated (the VUI's top / bottom values as transmitted, -1 = absent; fallback: what the codec
+    // implies without one -- 0 for H.264 / HEVC, 1 for JFIF).  true: the location in use changed and the handle interpolates chroma (new tap tables)
+    bool resolve_chroma_loc(int vui_top, int vui_bottom, int fallback);
     OutSlot *alloc_out_slot();
 
     // configuration
@@ -288,6 +294,11 @@ private:
     int vui_[4] = {-1, -1, -1, -1};            // the active sequence's VUI: full range, primaries, transfer, matrix (-1 = absent)
     int color_matrix_ = 0, color_range_ = 0;   // ... resolved (resolve_color): H.273 matrix, 1 limited / 2 full
     std::atomic<long long> stat_rgb_{0};
+    // interpolated chroma (options rgb_chroma, chroma_loc, before init): C is applied to the 4:4:4 frame G' through k_rgb_pack444 (chroma_packed.h)
+    int rgb_chroma_ = 0, chroma_loc_opt_ = -1;                      // chroma_loc_opt_: -1 auto, 0..5 forced
+    int vui_chroma_loc_[2] = {-1, -1}, chroma_loc_ = 0;             // the active sequence's VUI values (top, bottom); the location in use (frame siting)
+    uint8_t *chroma_dev_ = nullptr; ScaleAxis chroma_ax_[2] = {};   // the sequence's chroma x / y tables to the full target, on the device
+    std::atomic<long long> stat_rgb_chroma_{0};
     // deinterlaced output (options deinterlace*, before init): the frames chosen by deinterlace_when leave as C(R_G(D(F))), D through k_deint
     int deint_mode_ = 0, deint_when_ = 0, deint_field_ = 0, deint_thr_ = 0;      // (deint_thr_: T, 0 = 10)
     int deint_rate_ = 0;                       // option deinterlace_rate: 1 = field rate, a frame chosen for D leaves as D_f(F), D_f'(F) (k_deint2)

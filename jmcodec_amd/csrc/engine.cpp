@@ -581,6 +581,7 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (st & PS_CHAIN) { b.alg[4] += ((st & PS_RECON) ? 0 : p.alg_bytes[0]) + ((st & PS_CHAIN_INTRA) ? p.alg_bytes[1] : 0) + p.alg_bytes[2]; b.npics[4]++; }
     }
     b.alg[3] = b.out.alg_pack; b.npics[3] = b.out.n_frames; b.alg[5] = b.out.alg_rgb; b.npics[5] = b.out.n_rgb;
+    b.alg[10] = b.out.alg_rgb444; b.npics[10] = b.out.n_chroma[0] + b.out.n_chroma[1];
     b.alg[6] = b.out.alg_deint; b.npics[6] = b.out.n_deint;
     // surfaces this batch displays, per decoder: a later batch that decodes into one of them must wait for this batch's pack-out
     // (per lane: pictures of a decoder on different lanes are kept apart by Engine::form)
@@ -757,8 +758,11 @@ void Engine::run_side(Batch &b, int side, hipStream_t s, bool in_launch) {
     if (t.deint.n[side]) { mark(14 + 2 * side); (t.pairs[side] ? launch_deint2 : launch_deint)(t.deint.d(side), t.deint.n[side], t.d_items, s); mark(15 + 2 * side); b.pmask |= side ? 512 : 256; }
     if (t.plain.n[side]) launch_packout(t.plain.d(side), t.plain.n[side], t.max_w, t.max_h, s);
     if (t.scale.n[side]) launch_scale_pack(t.scale.d(side), t.scale.n[side], t.s_tiles, s);
-    if (t.rgb.n[side]) { mark(10 + 2 * side); launch_rgb_pack(t.rgb.d(side), t.rgb.n[side], t.r_tiles[0], t.r_tiles[1], s); mark(11 + 2 * side);
-        b.pmask |= side ? 128 : 64; }
+    if (t.rgb.n[side]) { mark(10 + 2 * side); launch_rgb_pack(t.rgb.d(side), t.rgb.n[side], t.r_tiles[0], t.r_tiles[1], 0, s);
+        // (the jobs with interpolated chroma: k_rgb_pack444 over the same table, timed on its own as well)
+        if (t.n_chroma[side]) { mark(19 + 2 * side); launch_rgb_pack(t.rgb.d(side), t.rgb.n[side], 0, 0, t.r_tiles[2], s); mark(20 + 2 * side);
+            b.pmask |= side ? 16384 : 8192; }
+        mark(11 + 2 * side); b.pmask |= side ? 128 : 64; }
     if (t.any(side)) b.pmask |= side ? 16 : 1;
     if (in_launch && side) { mark(6); hipEventRecord(b.packed, s); }      // from here on the displayed surfaces may be decoded into again
     if (t.any(side)) for (auto &p : b.pics) for (OutSlot *o : p.out[side].slots) if (o->dev && o->host && !o->fetch)
@@ -928,6 +932,7 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
         add(3, 0, 1, b.pmask & 1); add(0, 1, 2, b.pmask & 2); add(1, 2, 3, b.pmask & 4); add(2, 3, 4, b.pmask & 8); add(3, 5, 6, b.pmask & 16);
         add(4, 4, 7, b.pmask & 32); add(5, 10, 11, b.pmask & 64); add(5, 12, 13, b.pmask & 128);
         add(6, 14, 15, b.pmask & 256); add(6, 16, 17, b.pmask & 512); add(8, 4, 18, b.pmask & 2048);
+        add(10, 19, 20, b.pmask & 8192); add(10, 21, 22, b.pmask & 16384);
         if (b.pmask & 1024) { float ms = 0; if (hipEventElapsedTime(&ms, b.jev[0], b.jev[1]) == hipSuccess) { st_.ns[7] += ms * 1e6; st_.launches[7]++; } }
         if (b.pmask & 4096) { float ms = 0; if (hipEventElapsedTime(&ms, b.mev[0], b.mev[1]) == hipSuccess) { st_.ns[9] += ms * 1e6; st_.launches[9]++; } }
         for (int k = 0; k < kKernelClasses; k++) { st_.pics[k] += b.npics[k]; st_.alg_bytes[k] += b.alg[k]; }

@@ -92,7 +92,7 @@ struct EnginePic {
 // per kernel class: 0 recon_inter, 1 intra, 2 deblock (prep+lds), 3 packout (every pack-out kernel), 4 chain (k_chain: recon + deblock),
 // 5 rgb_pack (k_rgb_pack alone: its frames are counted in class 3 too), 6 deint (k_deint alone, likewise), 7 jpeg (k_jpeg_recon),
 // 8 pichash (k_hevc_pichash: pictures hashed, 1.5 w h bytes each), 9 md5 (k_hevc_md5, likewise)
-constexpr int kKernelClasses = 10;
+constexpr int kKernelClasses = 11;
 struct EngineStats {
     double ns[kKernelClasses] = {}; long long launches[kKernelClasses] = {}, pics[kKernelClasses] = {}, alg_bytes[kKernelClasses] = {};
     long long batches = 0, batch_pics = 0, chain_batches = 0, chain_pics = 0, wait_errors = 0, chain_recoveries = 0;
@@ -177,7 +177,7 @@ private:
         // packed: surfaces were read by k_packout (before the copies)
         // (profile events 10 / 11 and 12 / 13 bracket the k_rgb_pack launches before / after the decode kernels, 14 / 15 and 16 / 17 k_deint's;
         // 18 is recorded behind k_hevc_pichash)
-        ihipEvent_t *done = nullptr, *kdone = nullptr, *packed = nullptr, *pre_done = nullptr, *pev[19] = {nullptr};
+        ihipEvent_t *done = nullptr, *kdone = nullptr, *packed = nullptr, *pre_done = nullptr, *pev[23] = {nullptr};
         std::vector<EnginePic> pics;
         unsigned pmask = 0;
         long long alg[kKernelClasses] = {}; int npics[kKernelClasses] = {};

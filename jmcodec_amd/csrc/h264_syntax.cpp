@@ -124,7 +124,8 @@ std::string ParamSets::parse_sps(BitReader &br) {
         if (br.u1()) br.u1();
         if (br.u1()) { br.u(3); s.vui_full_range = (int)br.u1();                                   // video_signal_type
             if (br.u1()) { s.vui_primaries = (int)br.u(8); s.vui_transfer = (int)br.u(8); s.vui_matrix = (int)br.u(8); } }
-        if (br.u1()) { br.ue(); br.ue(); }
+        if (br.u1()) { const uint32_t t = br.ue(), b = br.ue();                                    // chroma_loc_info: as transmitted (values above 5 are reserved)
+            s.vui_chroma_loc = t > 255 ? 255 : (int)t; s.vui_chroma_loc_bottom = b > 255 ? 255 : (int)b; }
         if (br.u1()) { s.num_units_in_tick = br.u(32); s.time_scale = br.u(32); s.fixed_frame_rate = br.u1(); }   // timing_info_present_flag
         bool nal_hrd = br.u1(); if (nal_hrd) skip_hrd(br);
         bool vcl_hrd = br.u1(); if (vcl_hrd) skip_hrd(br);

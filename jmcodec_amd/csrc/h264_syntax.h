@@ -30,6 +30,7 @@ struct SeqParams {
     // VUI video_signal_type (E.1.1): as transmitted, -1 = absent (colour_primaries / transfer_characteristics / matrix_coefficients need
     // colour_description_present_flag too).  The RGB output picks its matrix and range from them (decoder.cpp resolve_color).
     int vui_full_range = -1, vui_primaries = -1, vui_transfer = -1, vui_matrix = -1;
+    int vui_chroma_loc = -1, vui_chroma_loc_bottom = -1;   // chroma_sample_loc_type_top_field / _bottom_field as transmitted, -1 = absent (option rgb_chroma)
     int sar_num = 0, sar_den = 0;       // VUI sample aspect ratio (aspect_ratio_idc 1..16, 255), 0 : 0 = not transmitted (option fit_sar)
     int coded_w() const { return mb_w * 16; }
     int coded_h() const { return mb_h * 16; }

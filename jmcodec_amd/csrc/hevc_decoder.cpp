@@ -84,10 +84,11 @@ void Decoder::hevc_handle_nal(const uint8_t *nal, size_t len) {
 
 bool Decoder::hevc_activate(const HevcSps &sps) {
     const int mbw = (sps.width + 15) / 16, mbh = (sps.height + 15) / 16;
-    const bool changed = !seq_active_ || mbw != mb_w_ || mbh != mb_h_ || sps.width != hsps_.width || sps.height != hsps_.height || sps.disp_w() != disp_w_ ||
+    bool changed = !seq_active_ || mbw != mb_w_ || mbh != mb_h_ || sps.width != hsps_.width || sps.height != hsps_.height || sps.disp_w() != disp_w_ ||
         sps.disp_h() != disp_h_ || (fit_ && fit_sar_ && (sps.sar_num != sar_[0] || sps.sar_den != sar_[1]));      // (the letterbox follows the sample aspect ratio)
     sar_[0] = sps.sar_num; sar_[1] = sps.sar_den;
     { const int vui[4] = {sps.vui_full_range, sps.vui_primaries, sps.vui_transfer, sps.vui_matrix}; resolve_color(vui, sps.disp_h()); }
+    if (resolve_chroma_loc(sps.vui_chroma_loc, sps.vui_chroma_loc_bottom, 0)) changed = true;     // (interpolated chroma: new tap tables)
     h_max_dpb_ = sps.max_dec_pic_buffering; h_reorder_ = sps.max_num_reorder;
     if (!changed) return true;
     if (seq_active_) {

@@ -179,11 +179,13 @@ std::string HevcParamSets::parse_sps(BitReader &br) {
         if (br.u1()) br.u1();                                                                   // overscan
         if (br.u1()) { br.u(3); vst[0] = (int)br.u1();                                          // video signal type
             if (br.u1()) { vst[1] = (int)br.u(8); vst[2] = (int)br.u(8); vst[3] = (int)br.u(8); } }
-        if (br.u1()) { br.ue(); br.ue(); }                                                      // chroma sample location
+        int loc[2] = {-1, -1};
+        if (br.u1()) { const uint32_t t = br.ue(), b = br.ue(); loc[0] = t > 255 ? 255 : (int)t; loc[1] = b > 255 ? 255 : (int)b; }      // chroma sample location
         br.u1(); br.u1(); br.u1();                                                              // neutral chroma, field_seq, frame_field_info
         if (br.u1()) { br.ue(); br.ue(); br.ue(); br.ue(); }                                    // default display window
         if (br.u1()) { const uint32_t tick = br.u(32), scale = br.u(32); if (!br.overrun()) { s.num_units_in_tick = tick; s.time_scale = scale; } }
-        if (!br.overrun()) { s.sar_num = sar[0]; s.sar_den = sar[1]; s.vui_full_range = vst[0]; s.vui_primaries = vst[1]; s.vui_transfer = vst[2]; s.vui_matrix = vst[3]; }
+        if (!br.overrun()) { s.sar_num = sar[0]; s.sar_den = sar[1]; s.vui_full_range = vst[0]; s.vui_primaries = vst[1]; s.vui_transfer = vst[2]; s.vui_matrix = vst[3];
+            s.vui_chroma_loc = loc[0]; s.vui_chroma_loc_bottom = loc[1]; }
     }
     sps[id] = s;
     return "";

@@ -32,6 +32,7 @@ struct HevcSps {
     bool temporal_mvp = false, strong_intra = false;
     uint32_t num_units_in_tick = 0, time_scale = 0;    // vui_timing_info (E.3.1): a picture lasts num_units_in_tick / time_scale seconds; 0 = not transmitted
     int vui_full_range = -1, vui_primaries = -1, vui_transfer = -1, vui_matrix = -1;   // video_signal_type (E.2.1) as transmitted, -1 = absent
+    int vui_chroma_loc = -1, vui_chroma_loc_bottom = -1;   // chroma_sample_loc_type_top_field / _bottom_field as transmitted, -1 = absent (option rgb_chroma)
     int sar_num = 0, sar_den = 0;       // VUI sample aspect ratio (aspect_ratio_idc 1..16, 255), 0 : 0 = not transmitted (option fit_sar)
     // nv_dec.cpp:513-519: target size = display area size, origin forced to (0,0)
     int disp_w() const { return width - 2 * (conf[0] + conf[1]); }

@@ -139,6 +139,18 @@ __attribute__((visibility("default"))) int jm_amddec_scale_taps(int src_len, int
     }
     return taps;
 }
+// ... and of a chroma plane to the full target with the siting shift q (INTEGRATION.md "RGB output": interpolated chroma)
+__attribute__((visibility("default"))) int jm_amddec_chroma_taps(int src_len, int dst_len, int q, int *first, short *weights, int max_taps) {
+    std::vector<int32_t> f; std::vector<int16_t> w;
+    const int taps = jmamd::build_chroma_taps(src_len, dst_len, q, f, w);
+    if (taps < 0 || !first || !weights) return taps;
+    if (taps > max_taps) return -1;
+    for (int j = 0; j < dst_len; j++) {
+        first[j] = f[j];
+        for (int k = 0; k < max_taps; k++) weights[(size_t)j * max_taps + k] = k < taps ? w[(size_t)j * taps + k] : 0;
+    }
+    return taps;
+}
 __attribute__((visibility("default"))) int jm_amddec_fit_rect(int cw, int ch, int sar_num, int sar_den, int tw, int th, int fit, int rect[4]) {
     return jmamd::fit_rect(cw, ch, sar_num, sar_den, tw, th, fit, rect) ? 0 : -1;
 }
@@ -246,9 +258,23 @@ __attribute__((visibility("default"))) int jm_amddec_rgb_device(const void *src,
     return jm_amddec_rgb_rect_device(src, pitch, chroma_offset, w, hgt, lone_field, crop_x, crop_y, crop_w, crop_h, tw, th, spec, dst, stream, 0, 0, 0, 0, -1);
 }
 // ... with the picture placed in the target; a placed job whose rectangle has the crop's size (pure padding) reads the surface directly
+static int rgb_rect_device(const void *src, int pitch, int chroma_offset, int w, int hgt, int lone_field, int crop_x, int crop_y, int crop_w, int crop_h, int tw,
+    int th, const jm_amddec_rgb_spec *spec, void *dst, void *stream, int rect_x, int rect_y, int rect_w, int rect_h, int fill, int chroma_loc);
 __attribute__((visibility("default"))) int jm_amddec_rgb_rect_device(const void *src, int pitch, int chroma_offset, int w, int hgt, int lone_field, int crop_x,
     int crop_y, int crop_w, int crop_h, int tw, int th, const jm_amddec_rgb_spec *spec, void *dst, void *stream, int rect_x, int rect_y, int rect_w, int rect_h,
     int fill) {
+    return rgb_rect_device(src, pitch, chroma_offset, w, hgt, lone_field, crop_x, crop_y, crop_w, crop_h, tw, th, spec, dst, stream, rect_x, rect_y, rect_w, rect_h, fill, -1);
+}
+// ... with interpolated chroma at chroma_sample_loc_type chroma_loc (k_rgb_pack444): every geometry goes through the tap tables
+__attribute__((visibility("default"))) int jm_amddec_rgb_chroma_device(const void *src, int pitch, int chroma_offset, int w, int hgt, int lone_field, int crop_x,
+    int crop_y, int crop_w, int crop_h, int tw, int th, const jm_amddec_rgb_spec *spec, void *dst, void *stream, int rect_x, int rect_y, int rect_w, int rect_h,
+    int fill, int chroma_loc) {
+    if (chroma_loc < 0 || chroma_loc > 5) return -1;
+    return rgb_rect_device(src, pitch, chroma_offset, w, hgt, lone_field, crop_x, crop_y, crop_w, crop_h, tw, th, spec, dst, stream, rect_x, rect_y, rect_w, rect_h, fill, chroma_loc);
+}
+// (chroma_loc -1: nearest chroma, k_rgb_pack)
+static int rgb_rect_device(const void *src, int pitch, int chroma_offset, int w, int hgt, int lone_field, int crop_x, int crop_y, int crop_w, int crop_h, int tw,
+    int th, const jm_amddec_rgb_spec *spec, void *dst, void *stream, int rect_x, int rect_y, int rect_w, int rect_h, int fill, int chroma_loc) {
     if (!src || !dst || !spec || w <= 0 || hgt <= 0 || pitch < w || lone_field < 0 || lone_field > 2) return -1;
     const jmamd::RgbSpec &s = *reinterpret_cast<const jmamd::RgbSpec *>(spec);
     if (!jmamd::rgb_spec_valid(s, true) || ((uintptr_t)dst % (uintptr_t)jmamd::rgb_sample_bytes(s.dtype))) return -1;
@@ -261,13 +287,17 @@ __attribute__((visibility("default"))) int jm_amddec_rgb_rect_device(const void 
     jmamd::RgbJob job = {};
     job.s = jmamd::ScaleJob{static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), pitch, chroma_offset, crop_x, crop_y, tw, th, 0, lone_field, {}};
     if (placed) { job.s.rx = rc[0]; job.s.ry = rc[1]; job.s.rw = rc[2]; job.s.rh = rc[3]; job.fill = fill < 0 ? 0 : (int)fill; }
-    job.identity = rc[2] == crop_w && rc[3] == crop_h;
+    job.identity = chroma_loc < 0 && rc[2] == crop_w && rc[3] == crop_h;
+    job.chroma = chroma_loc >= 0;
     jmamd::fill_rgb_color(job, s, s.matrix, s.range == 2);
-    uint8_t *tables = nullptr;
+    uint8_t *tables = nullptr, *ctables = nullptr;
     if (!job.identity && !jmamd::upload_scale_tables(crop_w, crop_h, rc[2], rc[3], &tables, job.s.ax)) return -1;
+    if (job.chroma && !jmamd::upload_chroma_tables(crop_w, crop_h, rc[2], rc[3], chroma_loc, &ctables, job.cax)) { hipFree(tables); return -1; }
+    const int tiles = jmamd::rgb_tiles(tw, th);
     const int r = run_one_job(job, stream, [&](const jmamd::RgbJob *d_job, hipStream_t st) {
-        jmamd::launch_rgb_pack(d_job, 1, job.identity ? jmamd::rgb_tiles(tw, th) : 0, job.identity ? 0 : jmamd::rgb_tiles(tw, th), st); });
+        jmamd::launch_rgb_pack(d_job, 1, !job.chroma && job.identity ? tiles : 0, !job.chroma && !job.identity ? tiles : 0, job.chroma ? tiles : 0, st); });
     if (tables) hipFree(tables);
+    if (ctables) hipFree(ctables);
     return r;
 }
 

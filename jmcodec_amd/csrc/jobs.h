@@ -167,6 +167,11 @@ struct RgbJob {                   // one display frame to crop + resample + conv
     int dtype, planar, bgr;       // RGB_*; 1 CHW, 0 HWC; 1 B,G,R order
     float k[3], b[3];             // float samples: fl32(fl32(v * k[c]) + b[c]), c = storage position (k = scale / 16384)
     int fill;                     // placed jobs: R << 16 | G << 8 | B outside the rectangle (each colour's accumulator is fill << 14)
+    // Interpolated chroma (option rgb_chroma, k_rgb_pack444, chroma_packed.h): 1 = C is applied to the 4:4:4 frame G' -- chroma resampled straight to the
+    // full target (the rectangle of a placed job) through cax[0 / 1], the chroma x / y tables with the siting shift; s.ax[] is always built (the luma
+    // tables of an identity geometry pass samples through) and identity is 0.  0: the fields are zero and the job is k_rgb_pack's
+    int chroma;
+    ScaleAxis cax[2];
 };
 
 // Deinterlaced output (k_deint; the function D of INTEGRATION.md "Deinterlaced output").  The source is a pitch-linear NV12 surface; the destination is

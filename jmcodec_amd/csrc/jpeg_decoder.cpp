@@ -29,10 +29,12 @@ void Decoder::jpeg_flush() {
 }
 
 bool Decoder::jpeg_activate(const JpegPic &pic) {
-    const bool changed = !seq_active_ || pic.width != j_w_ || pic.height != j_h_ || pic.sampling != j_sampling_;
+    bool changed = !seq_active_ || pic.width != j_w_ || pic.height != j_h_ || pic.sampling != j_sampling_;
     // JFIF: BT.601 coefficients, full range
     { const int vui[4] = {1, -1, -1, 6}; resolve_color(vui, pic.disp_h()); }
     sar_[0] = sar_[1] = 0;
+    // JFIF: chroma centred both ways (location 1), which is also what k_jpeg_recon's 4:2:2 / 4:4:4 -> 4:2:0 averaging produces
+    if (resolve_chroma_loc(-1, -1, 1)) changed = true;
     if (!changed) return true;
     if (seq_active_) {
         // a new size or sampling starts a new sequence, like an SPS change: drain everything that still refers to the old surfaces

@@ -43,9 +43,9 @@ void launch_packout(const PackJob *d_jobs, int n, int max_width, int max_height,
 int  scale_tiles(int tw, int th);
 void launch_scale_pack(const ScaleJob *d_jobs, int n, int max_tiles, hipStream_t st);
 // ... -> RGB frame C(R_G(F)) at the job's target size (k_rgb_pack); identity_tiles / scaled_tiles: the largest rgb_tiles() of the identity / the
-// resampled jobs (0: none of that kind)
+// resampled jobs (0: none of that kind); chroma_tiles: that of the jobs with interpolated chroma (RgbJob::chroma, k_rgb_pack444)
 int  rgb_tiles(int tw, int th);
-void launch_rgb_pack(const RgbJob *d_jobs, int n, int identity_tiles, int scaled_tiles, hipStream_t st);
+void launch_rgb_pack(const RgbJob *d_jobs, int n, int identity_tiles, int scaled_tiles, int chroma_tiles, hipStream_t st);
 // pitch-linear NV12 surface -> D(F), as NV12 at the job's pitch or as a tight I420 frame (k_deint); max_items: the largest deint_items() of the jobs
 int  deint_items(int w, int h);
 void launch_deint(const DeintJob *d_jobs, int n, int max_items, hipStream_t st);

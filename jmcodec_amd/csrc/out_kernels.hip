@@ -14,6 +14,7 @@
 #include "kernel_common.h"     // clip1
 #include "scale_packed.h"      // the resampler (k_scale_pack, k_rgb_pack) and the lone-field row mapping
 #include "rgb_packed.h"        // the colour step (k_rgb_pack)
+#include "chroma_packed.h"     // interpolated chroma at the stream's siting (k_rgb_pack444)
 #include "deint_packed.h"      // deint_strip (k_deint)
 #include "deint2_packed.h"     // deint2_strip (k_deint2)
 
@@ -158,7 +159,8 @@ void launch_scale_pack(const ScaleJob *d_jobs, int n, int max_tiles, hipStream_t
 template <bool SCALED>
 __global__ __launch_bounds__(256) void k_rgb_pack(const RgbJob *jobs) {
     const RgbJob &jb = jobs[blockIdx.y];
-    if (jb.identity == (SCALED ? 1 : 0)) return;             // (a job of the other instantiation)
+    // (a job of the other instantiation, or of k_rgb_pack444: such a job is never an identity job, so only the resampling instantiation has to ask)
+    if (jb.identity == (SCALED ? 1 : 0) || (SCALED && jb.chroma)) return;
     const ScaleJob &sj = jb.s;
     rgbp::Tile t;
     if (!rgbp::tile(sj, blockIdx.x, t)) return;
@@ -189,10 +191,43 @@ __global__ __launch_bounds__(256) void k_rgb_pack(const RgbJob *jobs) {
     rgbp::convert_store_masked(jb, Y, U, V, (size_t)(t.i0 + r) * sj.tw + t.j0 + 4 * q, n, rgbp::inside_mask(sj, t.i0 + r, t.j0 + 4 * q));
 }
 
+// ------------------------------------------------------------------------------------------
+// k_rgb_pack444: output C(G') -- the jobs of the same table with RgbJob::chroma == 1 (option rgb_chroma, INTEGRATION.md "RGB output", chroma_packed.h).
+// G' is 4:4:4: the luma of R_G, and each chroma plane of the crop resampled straight to the full target at the stream's chroma siting.  One workgroup
+// per output tile of 64 x 16 pixels: the luma rows go through k_rgb_pack's horizontal pass into hy, the chroma rows through the same pass as two half
+// tiles of 32 columns x (U, V) into hc (64 columns x (U, V) per source row), then every lane filters its 4 luma samples and its 4 chroma pairs
+// vertically and converts.  Every geometry runs the passes (the luma tables of an identity geometry pass samples through exactly).
+// LDS: 17,408 B (hy) + 17,408 B (hc) = 34,816 B, four workgroups per CU.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_rgb_pack444(const RgbJob *jobs) {
+    const RgbJob &jb = jobs[blockIdx.y];
+    if (!jb.chroma) return;                                   // (a job of k_rgb_pack)
+    const ScaleJob &sj = jb.s;
+    rgbp::Tile t;
+    if (!rgbp::tile(sj, blockIdx.x, t)) return;
+    __shared__ int16_t hy[scl::kScaleMaxRows * scl::kRgbTileW];            // luma source rows after the horizontal pass
+    __shared__ int16_t hc[2 * chr::kChromaMaxRows * scl::kRgbTileW];       // chroma source rows after it: two half tiles of 32 columns x (U, V)
+    const int tid = threadIdx.x, r = tid >> 4, q = tid & 15;
+    scl::PlaneTile ly, lc[2];
+    const bool fits = scl::plane_tile(sj, false, t.j0, t.i0, t.jn, t.in, ly);
+    if (!fits || !chr::chroma_tiles(jb, ly, lc)) return;      // (uniform per workgroup)
+    scl::hpass_lane(ly, tid, hy);
+    chr::hpass_chroma_lane(lc, tid, hc);
+    __syncthreads();
+    const int n = min(4, t.jn - 4 * q);
+    if (r >= t.in || n <= 0) return;
+    const uint32_t inside = rgbp::inside_mask(sj, t.i0 + r, t.j0 + 4 * q);
+    int Y[4] = {0, 0, 0, 0}, U[4] = {128, 128, 128, 128}, V[4] = {128, 128, 128, 128};
+    rgbp::vpass_luma_lane(ly, tid, hy, Y);
+    chr::vpass_chroma_lane(lc, tid, hc, inside, U, V);
+    chr::convert_store_444(jb, Y, U, V, (size_t)(t.i0 + r) * sj.tw + t.j0 + 4 * q, n, inside);
+}
+
 int rgb_tiles(int tw, int th) { return scl::rgb_tiles(tw, th); }
-void launch_rgb_pack(const RgbJob *d_jobs, int n, int identity_tiles, int scaled_tiles, hipStream_t st) {
+void launch_rgb_pack(const RgbJob *d_jobs, int n, int identity_tiles, int scaled_tiles, int chroma_tiles, hipStream_t st) {
     if (n > 0 && identity_tiles > 0) hipLaunchKernelGGL(k_rgb_pack<false>, dim3(identity_tiles, n), dim3(256), 0, st, d_jobs);
     if (n > 0 && scaled_tiles > 0) hipLaunchKernelGGL(k_rgb_pack<true>, dim3(scaled_tiles, n), dim3(256), 0, st, d_jobs);
+    if (n > 0 && chroma_tiles > 0) hipLaunchKernelGGL(k_rgb_pack444, dim3(chroma_tiles, n), dim3(256), 0, st, d_jobs);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -34,10 +34,11 @@ template <class J> struct JobTable {
 struct OutTables {
     JobTable<PackJob> plain; JobTable<ScaleJob> scale; JobTable<RgbJob> rgb; JobTable<DeintJob> deint;
     template <class F> void each(F &&f) { f(plain); f(scale); f(rgb); f(deint); }
-    // grids: k_packout's frame size (over the pictures with a plain job), launch_scale_pack's tiles, launch_rgb_pack's (identity / resampled jobs), launch_deint's
-    int max_w = 0, max_h = 0, s_tiles = 0, r_tiles[2] = {0, 0}, d_items = 0, pairs[2] = {0, 0};
+    // grids: k_packout's frame size (over the pictures with a plain job), launch_scale_pack's tiles, launch_rgb_pack's (identity / resampled jobs / jobs with interpolated chroma), launch_deint's
+    int max_w = 0, max_h = 0, s_tiles = 0, r_tiles[3] = {0, 0, 0}, d_items = 0, pairs[2] = {0, 0};
+    int n_chroma[2] = {0, 0};                       // per side: RGB jobs with interpolated chroma (r_tiles[2] is their grid; k_rgb_pack444)
     // profiling sums: frames and their algorithmic bytes -- of every output kernel together, of k_rgb_pack alone, of k_deint alone
-    long long alg_pack = 0, alg_rgb = 0, alg_deint = 0; int n_frames = 0, n_rgb = 0, n_deint = 0;
+    long long alg_pack = 0, alg_rgb = 0, alg_deint = 0, alg_rgb444 = 0; int n_frames = 0, n_rgb = 0, n_deint = 0;
     uint8_t *scratch = nullptr; size_t scratch_used = 0;
 
     static size_t scratch_bytes(const DeintJob &j) { return ((size_t)j.dst_pitch * j.height * 3 / 2 + 255) & ~(size_t)255; }
@@ -47,8 +48,8 @@ struct OutTables {
 
     void reset(uint8_t *scratch_base) {
         each([](auto &t) { t.n[0] = t.n[1] = 0; });
-        max_w = max_h = s_tiles = r_tiles[0] = r_tiles[1] = d_items = pairs[0] = pairs[1] = 0;
-        alg_pack = alg_rgb = alg_deint = 0; n_frames = n_rgb = n_deint = 0;
+        max_w = max_h = s_tiles = r_tiles[0] = r_tiles[1] = r_tiles[2] = d_items = pairs[0] = pairs[1] = n_chroma[0] = n_chroma[1] = 0;
+        alg_pack = alg_rgb = alg_deint = alg_rgb444 = 0; n_frames = n_rgb = n_deint = 0;
         scratch = scratch_base; scratch_used = 0;
     }
     // The frames of one side of one picture; pictures in batch order, a picture's before side first.  disp_w / disp_h: the picture's display size;
@@ -59,7 +60,8 @@ struct OutTables {
         for (auto &j : o.plain) plain.h(side)[plain.n[side]++] = j;
         if (!o.plain.empty()) { max_w = std::max(max_w, disp_w); max_h = std::max(max_h, disp_h); }
         for (auto &j : o.scale) { scale.h(side)[scale.n[side]++] = j; s_tiles = std::max(s_tiles, scale_tiles(j.tw, j.th)); }
-        for (auto &j : o.rgb) { rgb.h(side)[rgb.n[side]++] = j; int &t = r_tiles[j.identity ? 0 : 1]; t = std::max(t, rgb_tiles(j.s.tw, j.s.th)); }
+        for (auto &j : o.rgb) { rgb.h(side)[rgb.n[side]++] = j; int &t = r_tiles[j.chroma ? 2 : j.identity ? 0 : 1]; t = std::max(t, rgb_tiles(j.s.tw, j.s.th));
+            if (j.chroma) { n_chroma[side]++; alg_rgb444 += pack_bytes; } }
         bool ok = true;
         for (auto &r : o.deint) {
             DeintJob j = r.job;

@@ -10,7 +10,7 @@ void launch_packout(const PackJob *, int, int, int, ihipStream_t *) { abort(); }
 int scale_tiles(int, int) { return 1; }
 void launch_scale_pack(const ScaleJob *, int, int, ihipStream_t *) { abort(); }
 int rgb_tiles(int, int) { return 1; }
-void launch_rgb_pack(const RgbJob *, int, int, int, ihipStream_t *) { abort(); }
+void launch_rgb_pack(const RgbJob *, int, int, int, int, ihipStream_t *) { abort(); }
 int deint_items(int, int) { return 1; }
 void launch_deint(const DeintJob *, int, int, ihipStream_t *) { abort(); }
 int deint2_items(int, int) { return 1; }

@@ -80,6 +80,8 @@ typedef struct {
                                    video_signal_type */
     int vui_sar_idc, vui_sar_w, vui_sar_h;   /* vui_sar_idc > 0: the VUI carries this aspect_ratio_idc (255: followed by sar_width = vui_sar_w and sar_height =
                                    vui_sar_h, 16 bits each); 0: aspect_ratio_idc 1 when there is a VUI for another reason, as before */
+    int vui_chroma_loc;         /* >= 0: the VUI carries chroma_loc_info with this chroma_sample_loc_type for both fields (0..5; larger values are
+                                   reserved and written as they are); -1: chroma_loc_info_present_flag 0, and no VUI for this reason */
 } GenParams;
 
 /* ------------------------------ RNG --------------------------------------- */
@@ -1975,7 +1977,7 @@ static void write_sps_pps(Enc *e) {
     int cr = (e->W - p->width) / 2, cb = (e->H - p->height) / (p->fmo0 ? 4 : 2);   /* CropUnitY = 2 * (2 - frame_mbs_only_flag) */
     if (cr || cb) { bw_put(w, 1, 1); bw_ue(w, 0); bw_ue(w, cr); bw_ue(w, 0); bw_ue(w, cb); } else bw_put(w, 1, 0);
     const int colour_desc = p->vui_matrix > 0 || p->vui_primaries > 0 || p->vui_transfer > 0, signal_type = colour_desc || p->vui_full_range > 0;
-    if (p->vui_fps > 0 || signal_type || p->vui_sar_idc > 0) {            /* vui_parameters() (E.1.1) */
+    if (p->vui_fps > 0 || signal_type || p->vui_sar_idc > 0 || p->vui_chroma_loc >= 0) {   /* vui_parameters() (E.1.1) */
         bw_put(w, 1, 1);
         bw_put(w, 1, 1); bw_put(w, 8, p->vui_sar_idc > 0 ? (uint32_t)p->vui_sar_idc & 255 : 1);   /* aspect_ratio_info_present_flag, aspect_ratio_idc (1: square) */
         if (p->vui_sar_idc == 255) { bw_put(w, 16, (uint32_t)p->vui_sar_w & 65535); bw_put(w, 16, (uint32_t)p->vui_sar_h & 65535); }   /* Extended_SAR */
@@ -1986,7 +1988,8 @@ static void write_sps_pps(Enc *e) {
             if (colour_desc) { bw_put(w, 8, (uint32_t)p->vui_primaries & 255); bw_put(w, 8, (uint32_t)p->vui_transfer & 255);
                 bw_put(w, 8, (uint32_t)p->vui_matrix & 255); }
         }
-        bw_put(w, 1, 0);                                                  /* no chroma location */
+        if (p->vui_chroma_loc >= 0) { bw_put(w, 1, 1); bw_ue(w, (uint32_t)p->vui_chroma_loc); bw_ue(w, (uint32_t)p->vui_chroma_loc); }   /* chroma_loc_info: top, bottom */
+        else bw_put(w, 1, 0);                                             /* no chroma location */
         if (p->vui_fps > 0) { bw_put(w, 1, 1); bw_put(w, 32, 1); bw_put(w, 32, 2u * (uint32_t)p->vui_fps); bw_put(w, 1, 1); }  /* timing_info: tick,
                                                                              time_scale, fixed rate */
         else bw_put(w, 1, 0);
@@ -2673,7 +2676,7 @@ void h264gen_free(void *p) { free(p); }
 int main(int argc, char **argv) {
     GenParams p; memset(&p, 0, sizeof p);
     p.width = 1920; p.height = 1080; p.frames = 30; p.qp = 28; p.gop = 30; p.seed = 0x4A4D0100; p.deblock = 1; p.num_ref = 1; p.slices = 1; p.search = 4;
-    p.dinf8 = 1;
+    p.dinf8 = 1; p.vui_chroma_loc = -1;
     const char *outp = NULL, *recon = NULL;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i]; const char *v = i + 1 < argc ? argv[i + 1] : "0";
@@ -2686,7 +2689,7 @@ int main(int argc, char **argv) {
         OPT("--bframes", bframes) OPT("--direct-temporal", direct_temporal) OPT("--wp", wp) OPT("--dinf8", dinf8) OPT("--scaling", scaling) OPT("--rplm",
             rplm) OPT("--mmco", mmco) OPT("--nc-corner", nc_corner) OPT("--no-intra", no_intra) OPT("--fmo0", fmo0) OPT("--poc-bottom", poc_bottom) OPT("--paff", paff) OPT("--gaps", gaps) OPT("--redundant", redundant) OPT("--vui-fps", vui_fps)
         OPT("--vui-matrix", vui_matrix) OPT("--vui-primaries", vui_primaries) OPT("--vui-transfer", vui_transfer) OPT("--vui-full-range", vui_full_range)
-        OPT("--vui-sar-idc", vui_sar_idc) OPT("--vui-sar-w", vui_sar_w) OPT("--vui-sar-h", vui_sar_h)
+        OPT("--vui-sar-idc", vui_sar_idc) OPT("--vui-sar-w", vui_sar_w) OPT("--vui-sar-h", vui_sar_h) OPT("--vui-chroma-loc", vui_chroma_loc)
         if (!strcmp(a, "-o")) { outp = v; i++; continue; }
         if (!strcmp(a, "--recon")) { recon = v; i++; continue; }
         fprintf(stderr, "unknown option %s\n", a); return 2;

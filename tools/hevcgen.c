@@ -56,6 +56,7 @@ typedef struct {
     int vui_matrix, vui_primaries, vui_transfer;   /* any > 0: the VUI carries video_signal_type with a colour description (these three values) */
     int vui_full_range;         /* 1: video_full_range_flag 1; all four 0: no video_signal_type */
     int vui_sar_idc, vui_sar_w, vui_sar_h;   /* vui_sar_idc > 0: the VUI carries this aspect_ratio_idc (255: then sar_width / sar_height, 16 bits each) */
+    int vui_chroma_loc;         /* >= 0: the VUI carries chroma_loc_info with this chroma_sample_loc_type for both fields; -1: absent, and no VUI for this reason */
 } HevcGenParams;
 
 /* ------------------------------ RNG ------------------------------ */
@@ -1446,7 +1447,7 @@ static void write_sps(Enc *e, BitW *out, int max_dpb, int reorder) {
     if (p->lt_ref) bw_ue(&w, 0);
     bw_put(&w, 1, (uint32_t)p->tmvp); bw_put(&w, 1, (uint32_t)p->strong_intra);
     const int colour_desc = p->vui_matrix > 0 || p->vui_primaries > 0 || p->vui_transfer > 0, signal_type = colour_desc || p->vui_full_range > 0;
-    if (p->vui_fps > 0 || signal_type || p->vui_sar_idc > 0) {        /* vui_parameters() (E.2.1) */
+    if (p->vui_fps > 0 || signal_type || p->vui_sar_idc > 0 || p->vui_chroma_loc >= 0) {   /* vui_parameters() (E.2.1) */
         bw_put(&w, 1, 1);
         bw_put(&w, 1, 1); bw_put(&w, 8, p->vui_sar_idc > 0 ? (uint32_t)p->vui_sar_idc & 255 : 1);   /* aspect_ratio_info_present_flag, aspect_ratio_idc */
         if (p->vui_sar_idc == 255) { bw_put(&w, 16, (uint32_t)p->vui_sar_w & 65535); bw_put(&w, 16, (uint32_t)p->vui_sar_h & 65535); }   /* EXTENDED_SAR */
@@ -1457,7 +1458,8 @@ static void write_sps(Enc *e, BitW *out, int max_dpb, int reorder) {
             if (colour_desc) { bw_put(&w, 8, (uint32_t)p->vui_primaries & 255); bw_put(&w, 8, (uint32_t)p->vui_transfer & 255);
                 bw_put(&w, 8, (uint32_t)p->vui_matrix & 255); }
         }
-        bw_put(&w, 1, 0);                                             /* chroma location: absent */
+        if (p->vui_chroma_loc >= 0) { bw_put(&w, 1, 1); bw_ue(&w, (uint32_t)p->vui_chroma_loc); bw_ue(&w, (uint32_t)p->vui_chroma_loc); }   /* chroma_loc_info: top, bottom */
+        else bw_put(&w, 1, 0);                                        /* chroma location: absent */
         bw_put(&w, 1, 0); bw_put(&w, 1, 0); bw_put(&w, 1, 0);         /* neutral_chroma_indication, field_seq, frame_field_info_present */
         bw_put(&w, 1, 0);                                             /* default_display_window_flag */
         if (p->vui_fps > 0) {
@@ -1890,7 +1892,7 @@ void hevcgen_free(void *p) { free(p); }
 int main(int argc, char **argv) {
     HevcGenParams p; memset(&p, 0, sizeof p);
     p.width = 176; p.height = 144; p.frames = 8; p.qp = 32; p.seed = 1; p.intra_period = 32; p.deblock = 1; p.sao = 1; p.tmvp = 1; p.amp = 1;
-    p.strong_intra = 1; p.depth_inter = 2; p.depth_intra = 2;
+    p.strong_intra = 1; p.depth_inter = 2; p.depth_intra = 2; p.vui_chroma_loc = -1;
     const char *outp = NULL, *recon = NULL;
     struct { const char *name; int *v; } opts[] = { {"--width", &p.width}, {"--height", &p.height}, {"--frames", &p.frames}, {"--qp", &p.qp}, {"--seed",
         &p.seed}, {"--intra-period", &p.intra_period},
@@ -1905,7 +1907,8 @@ int main(int argc, char **argv) {
         {"--cabac-init", &p.cabac_init}, {"--par-mrg", &p.par_mrg}, {"--cb-qp-off", &p.cb_qp_off}, {"--cr-qp-off", &p.cr_qp_off}, {"--search", &p.search},
             {"--rps-sps", &p.rps_sps}, {"--open-gop", &p.open_gop}, {"--vui-fps", &p.vui_fps},
             {"--vui-matrix", &p.vui_matrix}, {"--vui-primaries", &p.vui_primaries}, {"--vui-transfer", &p.vui_transfer},
-            {"--vui-full-range", &p.vui_full_range}, {"--vui-sar-idc", &p.vui_sar_idc}, {"--vui-sar-w", &p.vui_sar_w}, {"--vui-sar-h", &p.vui_sar_h} };
+            {"--vui-full-range", &p.vui_full_range}, {"--vui-sar-idc", &p.vui_sar_idc}, {"--vui-sar-w", &p.vui_sar_w}, {"--vui-sar-h", &p.vui_sar_h},
+            {"--vui-chroma-loc", &p.vui_chroma_loc} };
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-o") && i + 1 < argc) { outp = argv[++i]; continue; }
         if (!strcmp(argv[i], "--recon") && i + 1 < argc) { recon = argv[++i]; continue; }

@@ -20,7 +20,7 @@ class GenParams(C.Structure):
         "pcm_only", "poc_type", "nonref_period", "alpha_off", "beta_off", "chroma_qp_off", "level_idc",
         "cip", "search", "cabac", "cabac_idc", "t8x8", "bframes", "direct_temporal", "wp", "dinf8", "scaling", "rplm", "mmco", "nc_corner", "no_intra",
         "fmo0", "poc_bottom", "paff", "gaps", "redundant", "vui_fps", "vui_matrix", "vui_primaries", "vui_transfer", "vui_full_range",
-        "vui_sar_idc", "vui_sar_w", "vui_sar_h")]
+        "vui_sar_idc", "vui_sar_w", "vui_sar_h", "vui_chroma_loc")]
 
 
 def build_tools():
@@ -47,12 +47,13 @@ def generate(width=64, height=48, frames=4, qp=28, gop=30, seed=0x4A4D0100, mode
              slices=1, pcm_only=0, poc_type=2, nonref_period=0, alpha_off=0, beta_off=0, chroma_qp_off=0,
              level_idc=0, cip=0, search=4, cabac=0, cabac_idc=0, t8x8=0, bframes=0, direct_temporal=0, wp=0, dinf8=1, scaling=0, rplm=0, mmco=0, nc_corner=0,
              no_intra=0, fmo0=0, poc_bottom=0, paff=0, gaps=0, redundant=0, vui_fps=0, vui_matrix=0, vui_primaries=0, vui_transfer=0,
-             vui_full_range=0, vui_sar_idc=0, vui_sar_w=0, vui_sar_h=0, recon_path=None):
-    """Returns the Annex-B stream as bytes (optionally writing the encoder's own reconstruction)."""
+             vui_full_range=0, vui_sar_idc=0, vui_sar_w=0, vui_sar_h=0, vui_chroma_loc=-1, recon_path=None):
+    """Returns the Annex-B stream as bytes (optionally writing the encoder's own reconstruction).  vui_chroma_loc: -1 no chroma_loc_info, else the
+    chroma_sample_loc_type written for both fields."""
     p = GenParams(width, height, frames, qp, gop, seed, mode, deblock, num_ref, slices, pcm_only, poc_type,
                   nonref_period, alpha_off, beta_off, chroma_qp_off, level_idc, cip, search, cabac, cabac_idc, t8x8,
                   bframes, direct_temporal, wp, dinf8, scaling, rplm, mmco, nc_corner, no_intra, fmo0, poc_bottom, paff, gaps, redundant, vui_fps,
-                  vui_matrix, vui_primaries, vui_transfer, vui_full_range, vui_sar_idc, vui_sar_w, vui_sar_h)
+                  vui_matrix, vui_primaries, vui_transfer, vui_full_range, vui_sar_idc, vui_sar_w, vui_sar_h, vui_chroma_loc)
     buf = C.POINTER(C.c_ubyte)()
     n = C.c_size_t(0)
     rc = _genlib().h264gen_generate(C.byref(p), C.byref(buf), C.byref(n), recon_path.encode() if recon_path else None)
@@ -98,7 +99,7 @@ HEVC_FIELDS = ("width", "height", "frames", "qp", "seed", "intra_period", "gop",
                "depth_inter", "depth_intra", "mode", "amp", "sao", "deblock", "tskip", "sdh", "dqp", "pcm", "bypass", "cip", "strong_intra", "tmvp", "wp",
                "rplm", "lt_ref", "scaling", "wpp", "tile_cols", "tile_rows", "slice_ctus", "dep_slices", "merge_cand", "cabac_init", "par_mrg", "rps_sps",
                "cb_qp_off", "cr_qp_off", "search", "open_gop", "vui_fps",
-               "vui_matrix", "vui_primaries", "vui_transfer", "vui_full_range", "vui_sar_idc", "vui_sar_w", "vui_sar_h")
+               "vui_matrix", "vui_primaries", "vui_transfer", "vui_full_range", "vui_sar_idc", "vui_sar_w", "vui_sar_h", "vui_chroma_loc")
 
 
 class HevcGenParams(C.Structure):
@@ -119,7 +120,7 @@ def generate_hevc(recon_path=None, **kw):
         _hgen.hevcgen_generate.argtypes = [C.POINTER(HevcGenParams), C.POINTER(C.POINTER(C.c_ubyte)), C.POINTER(C.c_size_t), C.c_char_p]
         _hgen.hevcgen_free.argtypes = [C.c_void_p]
     d = dict(width=176, height=144, frames=8, qp=32, seed=0x4A4D0300, intra_period=32, deblock=1, sao=1, tmvp=1, amp=1, strong_intra=1, depth_inter=2,
-        depth_intra=2)
+        depth_intra=2, vui_chroma_loc=-1)
     d.update(kw)
     unknown = set(d) - set(HEVC_FIELDS)
     if unknown:
