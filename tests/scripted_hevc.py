@@ -1,8 +1,10 @@
-"""A scripted H.265 stream writer (Main profile, 16x16 CTBs = 16x16 coding units, CABAC) for the analytic known-answer tests.
+"""A scripted H.265 stream writer (Main profile, CABAC; by default 16x16 CTBs = 16x16 coding units) for the analytic known-answer tests.
 
-As tests/scripted_h264.py: the test says which coding unit carries which samples, vector, reference and weight; ``write`` turns the script into Annex-B
-bytes; no residual is ever coded (rqt_root_cbf 0), so the decoded picture follows from the script by arithmetic (tests/analytic_expect_hevc.py).  Typed
-from the syntax clauses (7.3.1.2, 7.3.2.1 - 7.3.2.3, 7.3.3, 7.3.6, 7.3.7, 7.3.8, 9.3) -- not from tools/hevcgen.c, the oracle or the product.
+As tests/scripted_h264.py: the test says which coding unit carries which samples, vector, reference, weight or intra mode; ``write`` turns the script
+into Annex-B bytes; inter units never code a residual (rqt_root_cbf 0) and intra units at most one coefficient at (0, 0) per transform block, so the
+decoded picture follows from the script by arithmetic (tests/analytic_hevc.py, tests/hevc_intra_ref.py).  Typed from the syntax clauses (7.3.1.2,
+7.3.2.1 - 7.3.2.3, 7.3.3, 7.3.6, 7.3.7, 7.3.8.4 - 7.3.8.8, 7.3.8.11, 9.3, the context selection of 9.3.4.2) -- not from tools/hevcgen.c, the oracle or
+the product.
 
 The CABAC encoder is 9.3.4 run backwards (the encoding flowcharts of 9.3.4.x / H.264 9.3.4.2: EncodeDecision, EncodeBypass, EncodeTerminate, EncodeFlush,
 RenormE, PutBit).  Context initial values: the separately typed copy HEVC_INIT of tests/test_table_provenance.py; rangeTabLps: the separately typed copy
@@ -10,18 +12,34 @@ of tests/spec_tables_h264.py (the H.264 and H.265 engines share it); transIdxLps
 be shared by this encoder and the decoder and cancel, and entropy coding is not what these cases pin.
 
 The script
-    seq  = dict(width, height, weighted_pred=0, weighted_bipred=0, deblock=0 (1: filter on in the PPS), pcm_loop_filter_disabled=1, init_qp=26)
+    seq  = dict(width, height, weighted_pred=0, weighted_bipred=0, deblock=0 (1: filter on in the PPS), pcm_loop_filter_disabled=1, init_qp=26,
+                ctb_log2=4 (4, 5, 6), min_cb_log2=ctb_log2 (3 ..), max_tb_log2=4 (.. 5), tu_depth_intra=0 (max_transform_hierarchy_depth_intra),
+                pcm_log2=(4, 4) (smallest and largest PCM unit), strong_intra=0, constrained_intra=0)
+           the coded size is width x height rounded up to the minimum coding block size: a picture may end inside a CTB
     pics = [dict(kind="I" | "P" | "B", poc, layout="ctb" | "row" | "pic", cus=[...], and optionally is_ref (default kind != "B"), qp,
                  deblock=None | 0 | 1 (slice override), wp=dict(ld_y, ld_c, l0=[entry..], l1=[entry..]) with entry = None or
                  dict(y=(weight, offset) | None, c=((weight, offset), (weight, offset)) | None) -- the FINAL weights and offsets of 7.4.7.3)]
-    cus[ctb address] is one of
-        dict(t="pcm", y=(16,16) uint8, cb=(8,8), cr=(8,8))
-        dict(t="skip")                                             cu_skip_flag 1: with no candidate the zero vector on index 0 (both lists in B)
-        dict(t="inter", l0=(pic, (mvx, mvy)) | None, l1=(pic, (mvx, mvy)) | None)      2Nx2N, merge_flag 0; quarter-sample vectors
+    cus[ctb address] is a tree:
+        dict(t="split", sub=[four trees in z order])               a block that crosses the picture edge MUST be a split (the flag is inferred); entries of
+                                                                   sub that lie outside the picture are ignored (None will do)
+      or a leaf, one of
+        dict(t="pcm", y=(n,n) uint8, cb=(n/2,n/2), cr=(n/2,n/2))   n = the leaf's size, inside pcm_log2
+        dict(t="skip")                                             cu_skip_flag 1: MaxNumMergeCand is 1 and every candidate is the zero vector on index 0
+                                                                   (both lists in B) -- with one slice per CTB, or anywhere in a picture whose inter
+                                                                   units are ALL skipped (a neighbour's vector is then that vector too)
+        dict(t="inter", l0=(pic, (mvx, mvy)) | None, l1=(pic, (mvx, mvy)) | None)      2Nx2N, merge_flag 0; quarter-sample vectors; a whole 16x16 CTB
+        dict(t="intra", modes=[m] | [m0, m1, m2, m3], chroma=0..4, tu=depth, dc=[(level_y, level_cb, level_cr) | None per transform unit])
+                                                                   four modes: PART_NxN, only at the minimum coding block size; chroma is the VALUE of
+                                                                   intra_chroma_pred_mode; tu the uniform depth of the transform tree (NxN: >= 1; where
+                                                                   7.4.9.8 infers split_transform_flag the script must say what is inferred); dc in
+                                                                   decoding order, a level 0 = cbf 0; with 4x4 luma blocks the chroma levels of four
+                                                                   blocks are those of the fourth entry (7.3.8.10: blkIdx 3)
 Every picture decoded so far with is_ref stays in the reference picture set (at most 5).  RefPicList0 = pictures before the current one in output
 order, nearest first, then those after it; RefPicList1 the other way round (8.3.4); both lists are active in full.
 layout "ctb": one slice per CTB -- no spatial candidate exists, TMVP is off, both AMVP candidates are zero, mvd = the vector.  "row" / "pic": every CTB
 of a slice repeats one inter unit: once a neighbour exists the first AMVP candidate is that vector (8.5.3.2.6 / 8.5.3.2.7), mvd is 0.
+Context increments follow maps kept per 8x8 block (CtDepth, cu_skip_flag, CuPredMode) and availability as 6.4.1 has it (``_Picture.avail``); the
+three candidates of 8.4.2 come from the writer's own map of intra modes (``mpm_candidates``).
 """
 import os
 import re
@@ -148,8 +166,55 @@ def vps():
     return nal(32, b.bytes())
 
 
+def geometry(seq):
+    """The block sizes of the sequence (7.4.3.2.1), defaults = one 16x16 coding unit per CTB, transform blocks 4 .. 16, PCM at 16x16 only."""
+    ctb = seq.get("ctb_log2", 4)
+    g = dict(ctb=ctb, min_cb=seq.get("min_cb_log2", ctb), max_tb=seq.get("max_tb_log2", 4), tu_depth=seq.get("tu_depth_intra", 0),
+             pcm=tuple(seq.get("pcm_log2", (4, 4))))
+    assert ctb in (4, 5, 6) and 3 <= g["min_cb"] <= ctb and 2 < g["max_tb"] <= min(ctb, 5) and 0 <= g["tu_depth"] <= ctb - 2
+    assert 3 <= g["pcm"][0] <= g["pcm"][1] <= min(ctb, 5) and g["pcm"][0] >= min(g["min_cb"], 5)
+    return g
+
+
 def coded_size(seq):
-    return (seq["width"] + CTB - 1) // CTB * CTB, (seq["height"] + CTB - 1) // CTB * CTB
+    m = 1 << geometry(seq)["min_cb"]                                # pic_width / height_in_luma_samples: multiples of MinCbSizeY (7.4.3.2.1)
+    return (seq["width"] + m - 1) // m * m, (seq["height"] + m - 1) // m * m
+
+
+def ctb_dims(seq):
+    W, H = coded_size(seq)
+    s = 1 << geometry(seq)["ctb"]
+    return (W + s - 1) // s, (H + s - 1) // s
+
+
+def zscan(x, y, ctb_log2, cw):
+    """6.5.2 without tiles: the z-scan order address of the 4x4 block that holds (x, y) -- CTBs in raster order, bits of x and y interleaved inside"""
+    z = 0
+    for i in range(ctb_log2 - 2):
+        z |= (((x >> (2 + i)) & 1) << (2 * i)) | (((y >> (2 + i)) & 1) << (2 * i + 1))
+    return (((y >> ctb_log2) * cw + (x >> ctb_log2)) << (2 * (ctb_log2 - 2))) | z
+
+
+def walk(seq, p):
+    """The leaves of a picture's script in decoding order: (x, y, log2CbSize, CtDepth, unit).  A block that crosses the picture edge is split without
+    a flag (7.3.8.4); children outside the picture do not exist (their script entry is ignored, None will do)."""
+    W, H = coded_size(seq)
+    g = geometry(seq)
+    cw, ch = ctb_dims(seq)
+
+    def tree(x, y, log2, depth, node):
+        if node["t"] == "split":
+            assert log2 > g["min_cb"]
+            for i, sub in enumerate(node["sub"]):
+                x1, y1 = x + ((i & 1) << (log2 - 1)), y + ((i >> 1) << (log2 - 1))
+                if x1 < W and y1 < H:
+                    yield from tree(x1, y1, log2 - 1, depth + 1, sub)
+        else:
+            assert x + (1 << log2) <= W and y + (1 << log2) <= H, "a leaf crosses the picture edge"
+            yield x, y, log2, depth, node
+    assert len(p["cus"]) == cw * ch
+    for a, node in enumerate(p["cus"]):
+        yield from tree((a % cw) << g["ctb"], (a // cw) << g["ctb"], g["ctb"], 0, node)
 
 
 def sps(seq):
@@ -167,14 +232,15 @@ def sps(seq):
     b.ue(0); b.ue(0)                                                # bit depths 8
     b.ue(LOG2_MAX_POC_LSB - 4)
     b.u(1, 1); b.ue(5); b.ue(2); b.ue(0)                            # sub-layer ordering info
-    b.ue(1); b.ue(0)                                                # MinCbLog2SizeY 4, CtbLog2SizeY 4: a CTB is one coding unit, split_cu_flag is never coded
-    b.ue(0); b.ue(2)                                                # transform blocks 4 .. 16
-    b.ue(0); b.ue(0)                                                # max_transform_hierarchy_depth_inter / intra
+    g = geometry(seq)
+    b.ue(g["min_cb"] - 3); b.ue(g["ctb"] - g["min_cb"])             # MinCbLog2SizeY, CtbLog2SizeY (default 4, 4: a CTB is one coding unit, no split_cu_flag)
+    b.ue(0); b.ue(g["max_tb"] - 2)                                  # transform blocks 4 .. 16 (32)
+    b.ue(0); b.ue(g["tu_depth"])                                    # max_transform_hierarchy_depth_inter / intra
     b.u(1, 0); b.u(1, 0); b.u(1, 0)                                 # scaling lists, AMP, SAO: off
-    b.u(1, 1); b.u(4, 7); b.u(4, 7); b.ue(1); b.ue(0)               # PCM on: 8-bit samples, 16x16 only
+    b.u(1, 1); b.u(4, 7); b.u(4, 7); b.ue(g["pcm"][0] - 3); b.ue(g["pcm"][1] - g["pcm"][0])          # PCM on: 8-bit samples (default 16x16 only)
     b.u(1, seq.get("pcm_loop_filter_disabled", 1))
     b.ue(0)                                                         # num_short_term_ref_pic_sets: every slice header carries its own
-    b.u(1, 0); b.u(1, 0); b.u(1, 0)                                 # long-term pictures, TMVP, strong intra smoothing: off
+    b.u(1, 0); b.u(1, 0); b.u(1, seq.get("strong_intra", 0))        # long-term pictures, TMVP: off; strong_intra_smoothing_enabled_flag
     b.u(1, 0); b.u(1, 0)                                            # VUI, extension
     b.trailing()
     return nal(33, b.bytes())
@@ -186,7 +252,7 @@ def pps(seq):
     b.u(1, 0); b.u(1, 0); b.u(3, 0); b.u(1, 0); b.u(1, 0)           # dependent slices, output flag, extra bits, sign hiding, cabac_init_present
     b.ue(0); b.ue(0)                                                # num_ref_idx_default_active_minus1 (every P / B slice overrides)
     b.se(seq.get("init_qp", 26) - 26)
-    b.u(1, 0); b.u(1, 0); b.u(1, 0)                                 # constrained intra, transform skip, cu_qp_delta
+    b.u(1, seq.get("constrained_intra", 0)); b.u(1, 0); b.u(1, 0)   # constrained_intra_pred_flag; transform skip, cu_qp_delta: off
     b.se(0); b.se(0); b.u(1, 0)                                     # chroma QP offsets
     b.u(1, seq.get("weighted_pred", 0)); b.u(1, seq.get("weighted_bipred", 0))
     b.u(1, 0); b.u(1, 0); b.u(1, 0)                                 # transquant bypass, tiles, wavefronts
@@ -276,10 +342,228 @@ def slice_header(b, seq, p, pl, first, addr, n_ctbs):
     b.align_zero()
 
 
+def tu_leaves(log2cb, nxn, tu):
+    """Number of transform units of an intra unit whose transform tree has uniform depth tu (NxN: tu >= 1)"""
+    assert tu >= (1 if nxn else 0) and log2cb - tu >= 2
+    return 4 ** tu
+
+
+def mpm_candidates(a, b):
+    """8.4.2: candModeList from candIntraPredModeA / B"""
+    if a == b:
+        return [0, 1, 26] if a < 2 else [a, 2 + ((a + 29) % 32), 2 + ((a - 2 + 1) % 32)]
+    return [a, b, 0 if 0 not in (a, b) else (1 if 1 not in (a, b) else 26)]
+
+
+class _Picture:
+    """One picture's slice data (7.3.8): the maps that the context selection and the candidate derivation read, and the syntax itself."""
+
+    def __init__(self, seq, p, pl, kind):
+        self.seq, self.p, self.pl, self.kind, self.g = seq, p, pl, kind, geometry(seq)
+        self.W, self.H = coded_size(seq)
+        self.cw, self.ch = ctb_dims(seq)
+        h8, w8 = (self.H + 7) // 8, (self.W + 7) // 8
+        self.depth = np.zeros((h8, w8), np.int32)                   # CtDepth, cu_skip_flag, CuPredMode (0 inter, 1 intra, 2 intra with pcm_flag) per 8x8
+        self.skip = np.zeros((h8, w8), bool)
+        self.pred = np.zeros((h8, w8), np.int32)
+        self.mode = np.ones((self.H // 4, self.W // 4), np.int32)   # IntraPredModeY per 4x4
+        self.slice_of = np.zeros(self.cw * self.ch, np.int32)       # SliceAddrRs per CTB
+        inter = [u["t"] for (_, _, _, _, u) in walk(seq, p) if u["t"] in ("skip", "inter")]
+        self.all_skip = all(t == "skip" for t in inter)
+
+    def z(self, x, y):
+        return zscan(x, y, self.g["ctb"], self.cw)
+
+    def avail(self, xc, yc, xn, yn):
+        """6.4.1: inside the picture, not later in z-scan order, in the same slice (no tiles)"""
+        if xn < 0 or yn < 0 or xn >= self.W or yn >= self.H or self.z(xn, yn) > self.z(xc, yc):
+            return False
+        s = self.g["ctb"]
+        return self.slice_of[(yn >> s) * self.cw + (xn >> s)] == self.slice_of[(yc >> s) * self.cw + (xc >> s)]
+
+    def quadtree(self, c, x, y, log2, depth, node):
+        """7.3.8.4"""
+        n = 1 << log2
+        if x + n <= self.W and y + n <= self.H and log2 > self.g["min_cb"]:
+            split = node["t"] == "split"
+            inc = sum(1 for (xn, yn) in ((x - 1, y), (x, y - 1)) if self.avail(x, y, xn, yn) and self.depth[yn >> 3, xn >> 3] > depth)      # 9.3.4.2.2
+            c.decision("split_cu_flag", inc, 1 if split else 0)
+        else:
+            split = log2 > self.g["min_cb"]                         # inferred
+            assert (node["t"] == "split") == split, (x, y, log2, node["t"])
+        if split:
+            for i, sub in enumerate(node["sub"]):
+                x1, y1 = x + (i & 1) * (n >> 1), y + (i >> 1) * (n >> 1)
+                if x1 < self.W and y1 < self.H:
+                    self.quadtree(c, x1, y1, log2 - 1, depth + 1, sub)
+        else:
+            self.coding_unit(c, x, y, log2, depth, node)
+
+    def coding_unit(self, c, x, y, log2, depth, u):
+        """7.3.8.5"""
+        t, n, kind, b = u["t"], 1 << log2, self.kind, c.b
+        if kind != "I":
+            inc = sum(1 for (xn, yn) in ((x - 1, y), (x, y - 1)) if self.avail(x, y, xn, yn) and self.skip[yn >> 3, xn >> 3])               # 9.3.4.2.2
+            c.decision("cu_skip_flag", inc, 1 if t == "skip" else 0)
+        area = (slice(y >> 3, (y + n) >> 3), slice(x >> 3, (x + n) >> 3))
+        self.depth[area], self.skip[area], self.pred[area] = depth, t == "skip", {"pcm": 2, "intra": 1}.get(t, 0)
+        self.mode[y >> 2:(y + n) >> 2, x >> 2:(x + n) >> 2] = 1
+        if t == "skip":
+            assert kind != "I" and (self.step == 1 or self.all_skip)         # (MaxNumMergeCand 1: no merge_idx)
+            return
+        if kind != "I":
+            c.decision("pred_mode_flag", 0, 0 if t == "inter" else 1)
+        if t == "inter":
+            self.inter_unit(c, x, y, log2, depth, u)
+            return
+        assert t in ("pcm", "intra")
+        nxn = t == "intra" and len(u["modes"]) == 4
+        if log2 == self.g["min_cb"]:
+            c.decision("part_mode", 0, 0 if nxn else 1)             # intra units: one bin, 1 = PART_2Nx2N
+        else:
+            assert not nxn, "NxN only at the minimum coding block size"
+        if not nxn and self.g["pcm"][0] <= log2 <= self.g["pcm"][1]:
+            c.terminate(1 if t == "pcm" else 0)                     # pcm_flag
+        else:
+            assert t != "pcm", "a PCM unit outside the PCM size range"
+        if t == "pcm":
+            b.align_zero()                                          # the flush leaves the writer one bit in front of pcm_alignment_zero_bit
+            for key, s in (("y", n), ("cb", n // 2), ("cr", n // 2)):
+                v = np.asarray(u[key], np.uint8)
+                assert v.shape == (s, s), (key, v.shape, s)
+                b.raw(v.tobytes())
+            c.start()                                               # 9.3.2.5: the engine is initialised again behind the samples (contexts keep their state)
+            return
+        pb = n // 2 if nxn else n
+        coded = []
+        for i, m in enumerate(u["modes"]):
+            bx, by = x + (i & 1) * pb, y + (i >> 1) * pb
+            cand = []
+            for k, (xn, yn) in enumerate(((bx - 1, by), (bx, by - 1))):     # 8.4.2
+                ok = self.avail(bx, by, xn, yn) and self.pred[yn >> 3, xn >> 3] == 1
+                if k == 1 and ok and yn < ((by >> self.g["ctb"]) << self.g["ctb"]):
+                    ok = False
+                cand.append(int(self.mode[yn >> 2, xn >> 2]) if ok else 1)
+            coded.append((mpm_candidates(*cand), m))
+            self.mode[by >> 2:(by + pb) >> 2, bx >> 2:(bx + pb) >> 2] = m
+        for cand, m in coded:
+            c.decision("prev_intra_luma_pred", 0, 1 if m in cand else 0)
+        for cand, m in coded:
+            if m in cand:
+                i = cand.index(m)                                   # mpm_idx: truncated Rice, cMax 2, bypass
+                c.bypass(1 if i else 0)
+                if i:
+                    c.bypass(i - 1)
+            else:
+                rem = m - sum(1 for q in cand if q < m)             # rem_intra_luma_pred_mode: five bits
+                for i in range(4, -1, -1):
+                    c.bypass((rem >> i) & 1)
+        v = u.get("chroma", 4)
+        c.decision("intra_chroma_pred_mode", 0, 0 if v == 4 else 1)
+        if v != 4:
+            c.bypass(v >> 1); c.bypass(v & 1)
+        tu = u.get("tu", 1 if nxn else 0)
+        dc = u.get("dc") or [None] * tu_leaves(log2, nxn, tu)
+        assert len(dc) == tu_leaves(log2, nxn, tu)
+        small = log2 - tu == 2                                      # 4x4 luma blocks: the chroma of four of them is one block, coded with the fourth
+
+        def chroma_levels(first, count, comp):
+            return [(dc[i] or (0, 0, 0))[comp] for i in range(first, first + count) if not small or i % 4 == 3]
+
+        def tree(x0, y0, lg, d, blk, first, par):
+            """7.3.8.8 / 7.3.8.10"""
+            count = 4 ** (tu - d)
+            want = d < tu
+            if lg <= self.g["max_tb"] and lg > 2 and d < self.g["tu_depth"] + nxn and not (nxn and d == 0):
+                c.decision("split_transform_flag", 5 - lg, 1 if want else 0)
+            else:
+                assert want == (lg > self.g["max_tb"] or (nxn and d == 0)), ("the script's depth is not what 7.4.9.8 infers", x0, y0, lg, d, tu)
+            cbf = list(par)
+            if lg > 2:
+                for k in (0, 1):
+                    v_ = 1 if any(chroma_levels(first, count, k + 1)) else 0
+                    if d == 0 or par[k]:
+                        c.decision("cbf_cb_cr", d, v_)
+                    else:
+                        assert not v_
+                    cbf[k] = v_
+            if want:
+                for i in range(4):
+                    tree(x0 + (i & 1) * (1 << (lg - 1)), y0 + (i >> 1) * (1 << (lg - 1)), lg - 1, d + 1, i, first + i * (count // 4), cbf)
+                return
+            lv = dc[first] or (0, 0, 0)
+            c.decision("cbf_luma", 1 if d == 0 else 0, 1 if lv[0] else 0)
+            if lv[0]:
+                self.residual(c, lg, 0, lv[0])
+            if lg > 2 or blk == 3:
+                for k in (0, 1):
+                    if cbf[k]:
+                        self.residual(c, max(lg - 1, 2), k + 1, lv[k + 1])
+        tree(x, y, log2, 0, 0, 0, [0, 0])
+
+    @staticmethod
+    def residual(c, lg, cidx, level):
+        """7.3.8.11 for one coefficient at (0, 0): both last_sig_coeff prefixes 0, no sig_coeff_flag, no coded_sub_block_flag; the first
+        coeff_abs_level_greater1_flag of a block has ctxSet 0 (sub-block 0) and greater1Ctx 1 (9.3.4.2.6), chroma contexts 16 (4) further on"""
+        assert level and abs(level) < 2000
+        off = 15 if cidx else 3 * (lg - 2) + ((lg - 1) >> 2)        # 9.3.4.2.3, binIdx 0
+        c.decision("last_sig_coeff_prefix", off, 0)
+        c.decision("last_sig_coeff_y_prefix", off, 0)
+        a = abs(level)
+        c.decision("coeff_abs_level_greater1", (16 if cidx else 0) + 1, 1 if a > 1 else 0)
+        if a > 1:
+            c.decision("coeff_abs_level_greater2", 4 if cidx else 0, 1 if a > 2 else 0)
+        c.bypass(1 if level < 0 else 0)
+        if a > 2:                                                   # coeff_abs_level_remaining, cRiceParam 0 (9.3.3.11): prefix up to 1111, then EG1
+            rem = a - 3
+            for _ in range(min(rem, 4)):
+                c.bypass(1)
+            if rem < 4:
+                c.bypass(0)
+            else:
+                c.egk(rem - 4, 1)
+
+    def inter_unit(self, c, x, y, log2, depth, u):
+        pl, kind = self.pl, self.kind
+        assert kind != "I" and log2 == self.g["ctb"] and (self.step == 1 or u == self.first_unit), "a slice of several CTBs repeats one inter unit"
+        c.decision("part_mode", 0, 1)
+        c.decision("merge_flag", 0, 0)
+        l0, l1 = u.get("l0"), u.get("l1")
+        if kind == "B":
+            c.decision("inter_pred_idc", depth, 1 if l0 and l1 else 0)          # nPbW + nPbH != 12: first bin with ctxInc = CtDepth
+            if not (l0 and l1):
+                c.decision("inter_pred_idc", 4, 1 if l1 else 0)
+        else:
+            assert l0 and not l1
+        for name, q in (("l0", l0), ("l1", l1)):
+            if not q:
+                continue
+            n, idx = len(pl[name]), pl[name].index(q[0])
+            if n > 1:                                               # ref_idx_lX: truncated unary, cMax = n - 1; bins 0 and 1 with contexts, the rest bypass
+                for i in range(min(idx + 1, n - 1)):
+                    bin_ = 1 if i < idx else 0
+                    c.decision("ref_idx", i, bin_) if i < 2 else c.bypass(bin_)
+            mvd = q[1] if self.at_first else (0, 0)                 # both AMVP candidates zero / the first candidate is this vector (module docstring)
+            g0 = [1 if v else 0 for v in mvd]
+            g1 = [1 if abs(v) > 1 else 0 for v in mvd]
+            c.decision("abs_mvd_greater0", 0, g0[0]); c.decision("abs_mvd_greater0", 0, g0[1])
+            if g0[0]:
+                c.decision("abs_mvd_greater1", 0, g1[0])
+            if g0[1]:
+                c.decision("abs_mvd_greater1", 0, g1[1])
+            for i in (0, 1):
+                if g0[i]:
+                    if g1[i]:
+                        c.egk(abs(mvd[i]) - 2, 1)                   # abs_mvd_minus2: EG1
+                    c.bypass(1 if mvd[i] < 0 else 0)                # mvd_sign_flag
+            c.decision("mvp_flag", 0, 0)
+        c.decision("rqt_root_cbf", 0, 0)
+
+
 def write(seq, pics):
-    W, H = coded_size(seq)
-    cw, ch = W // CTB, H // CTB
+    cw, ch = ctb_dims(seq)
     n_ctbs = cw * ch
+    s = 1 << geometry(seq)["ctb"]
     out = [vps(), sps(seq), pps(seq)]
     plans = plan(seq, pics)
     pocs = [p["poc"] for p in pics]
@@ -287,66 +571,20 @@ def write(seq, pics):
         pl["pocs"] = pocs
         kind, cus = p["kind"], p["cus"]
         assert len(cus) == n_ctbs
-        step = {"ctb": 1, "row": cw, "pic": n_ctbs}[p.get("layout", "ctb" if kind != "I" else "pic")]
+        pic = _Picture(seq, p, pl, kind)
+        pic.step = step = {"ctb": 1, "row": cw, "pic": n_ctbs}[p.get("layout", "ctb" if kind != "I" else "pic")]
         for first in range(0, n_ctbs, step):
             b = Bits()
             slice_header(b, seq, p, pl, first == 0, first, n_ctbs)
             c = Cabac(b, {"I": 0, "P": 1, "B": 2}[kind], p.get("qp", seq.get("init_qp", 26)))
             last = min(first + step, n_ctbs) - 1
+            pic.slice_of[first:last + 1] = first
+            pic.first_unit = cus[first]
             for a in range(first, last + 1):
-                u = cus[a]
-                t = u["t"]
-                x, y = a % cw, a // cw
-                if kind != "I":
-                    # 9.3.4.2.2: ctxInc = the skip flags of the left and upper units where those are available (same slice, decoded)
-                    inc = (1 if x > 0 and a - 1 >= first and cus[a - 1]["t"] == "skip" else 0) + (1 if y > 0 and a - cw >= first and cus[a - cw]["t"] == "skip" else 0)
-                    c.decision("cu_skip_flag", inc, 1 if t == "skip" else 0)
-                if t == "pcm":
-                    if kind != "I":
-                        c.decision("pred_mode_flag", 0, 1)          # MODE_INTRA
-                    c.decision("part_mode", 0, 1)                   # log2CbSize == MinCbLog2SizeY: part_mode is coded for intra units too; PART_2Nx2N
-                    c.terminate(1)                                  # pcm_flag; the flush leaves the writer one bit in front of pcm_alignment_zero_bit
-                    b.align_zero()
-                    b.raw(np.asarray(u["y"], np.uint8).tobytes() + np.asarray(u["cb"], np.uint8).tobytes() + np.asarray(u["cr"], np.uint8).tobytes())
-                    c.start()                                       # 9.3.2.5: the engine is initialised again behind the samples (contexts keep their state)
-                elif t == "inter":
-                    assert kind != "I" and (step == 1 or u == cus[first]), "a slice of several CTBs repeats one inter unit"
-                    c.decision("pred_mode_flag", 0, 0)
-                    c.decision("part_mode", 0, 1)
-                    c.decision("merge_flag", 0, 0)
-                    l0, l1 = u.get("l0"), u.get("l1")
-                    if kind == "B":
-                        c.decision("inter_pred_idc", 0, 1 if l0 and l1 else 0)          # nPbW + nPbH != 12: first bin with ctxInc = CtDepth = 0
-                        if not (l0 and l1):
-                            c.decision("inter_pred_idc", 4, 1 if l1 else 0)
-                    else:
-                        assert l0 and not l1
-                    for name, q in (("l0", l0), ("l1", l1)):
-                        if not q:
-                            continue
-                        n, idx = len(pl[name]), pl[name].index(q[0])
-                        if n > 1:                                   # ref_idx_lX: truncated unary, cMax = n - 1; bins 0 and 1 with contexts, the rest bypass
-                            for i in range(min(idx + 1, n - 1)):
-                                bin_ = 1 if i < idx else 0
-                                c.decision("ref_idx", i, bin_) if i < 2 else c.bypass(bin_)
-                        mvd = q[1] if a == first else (0, 0)        # both AMVP candidates zero / the first candidate is this vector (module docstring)
-                        g0 = [1 if v else 0 for v in mvd]
-                        g1 = [1 if abs(v) > 1 else 0 for v in mvd]
-                        c.decision("abs_mvd_greater0", 0, g0[0]); c.decision("abs_mvd_greater0", 0, g0[1])
-                        if g0[0]:
-                            c.decision("abs_mvd_greater1", 0, g1[0])
-                        if g0[1]:
-                            c.decision("abs_mvd_greater1", 0, g1[1])
-                        for i in (0, 1):
-                            if g0[i]:
-                                if g1[i]:
-                                    c.egk(abs(mvd[i]) - 2, 1)       # abs_mvd_minus2: EG1
-                                c.bypass(1 if mvd[i] < 0 else 0)    # mvd_sign_flag
-                        c.decision("mvp_flag", 0, 0)
-                    c.decision("rqt_root_cbf", 0, 0)
-                else:
-                    assert t == "skip" and kind != "I" and step == 1        # (MaxNumMergeCand 1: no merge_idx)
+                pic.at_first = a == first
+                pic.quadtree(c, (a % cw) * s, (a // cw) * s, geometry(seq)["ctb"], 0, cus[a])
                 c.terminate(1 if a == last else 0)                  # end_of_slice_segment_flag; the flush's last bit is rbsp_slice_segment_trailing_bits' 1
             b.align_zero()
             out.append(nal(pl["typ"], b.bytes()))
     return b"".join(out)
+

@@ -282,6 +282,11 @@ def test_arithmetic_decoder_tables_against_a_separately_typed_copy():
         assert c_array(path, tname) == trans_lps, os.path.basename(path)
 
 
+# H.265 8.4.4.2.6, Tables 8-4 / 8-5: intraPredAngle and invAngle by predModeIntra (tests/hevc_intra_ref.py predicts with these copies)
+HEVC_INTRA_ANGLE = [0, 0] + [32, 26, 21, 17, 13, 9, 5, 2, 0, -2, -5, -9, -13, -17, -21, -26, -32, -26, -21, -17, -13, -9, -5, -2, 0, 2, 5, 9, 13, 17, 21, 26, 32]
+HEVC_INV_ANGLE = [0] * 11 + [-4096, -1638, -910, -630, -482, -390, -315, -256, -315, -390, -482, -630, -910, -1638, -4096] + [0] * 9
+
+
 def test_hevc_constant_tables_against_a_separately_typed_copy():
     """H.265 transform basis, DST, intra angles, interpolation filters, deblocking and chroma-QP tables: typed here from the standard's tables.
     The 32x32 transMatrix is BUILT from its 31 distinct magnitudes and the cosine structure it samples (entry (k, n) = the rounded
@@ -295,8 +300,7 @@ def test_hevc_constant_tables_against_a_separately_typed_copy():
             if m > 64:
                 m = 128 - m
             want.append(mag[m] if m <= 32 else -mag[64 - m])
-    intra_angle = [0, 0] + [32, 26, 21, 17, 13, 9, 5, 2, 0, -2, -5, -9, -13, -17, -21, -26, -32, -26, -21, -17, -13, -9, -5, -2, 0, 2, 5, 9, 13, 17, 21, 26, 32]
-    inv_angle = [0] * 11 + [-4096, -1638, -910, -630, -482, -390, -315, -256, -315, -390, -482, -630, -910, -1638, -4096] + [0] * 9
+    intra_angle, inv_angle = HEVC_INTRA_ANGLE, HEVC_INV_ANGLE
     luma = [0, 0, 0, 64, 0, 0, 0, 0, -1, 4, -10, 58, 17, -5, 1, 0, -1, 4, -11, 40, 40, -11, 4, -1, 0, 1, -5, 17, 58, -10, 4, -1]
     chroma = [0, 64, 0, 0, -2, 58, 10, -2, -4, 54, 16, -2, -6, 46, 28, -4, -4, 36, 36, -4, -4, 28, 46, -6, -2, 16, 54, -4, -2, 10, 58, -2]
     beta = [0] * 16 + list(range(6, 19)) + list(range(20, 65, 2))
