@@ -1,10 +1,10 @@
 """A scripted H.265 stream writer (Main profile, CABAC; by default 16x16 CTBs = 16x16 coding units) for the analytic known-answer tests.
 
 As tests/scripted_h264.py: the test says which coding unit carries which samples, vector, reference, weight or intra mode; ``write`` turns the script
-into Annex-B bytes; inter units never code a residual (rqt_root_cbf 0) and intra units at most one coefficient at (0, 0) per transform block, so the
-decoded picture follows from the script by arithmetic (tests/analytic_hevc.py, tests/hevc_intra_ref.py).  Typed from the syntax clauses (7.3.1.2,
-7.3.2.1 - 7.3.2.3, 7.3.3, 7.3.6, 7.3.7, 7.3.8.4 - 7.3.8.8, 7.3.8.11, 9.3, the context selection of 9.3.4.2) -- not from tools/hevcgen.c, the oracle or
-the product.
+into Annex-B bytes; residuals are scripted level by level (``coef``; ``dc`` is the earlier short form for one coefficient at (0, 0)), so the decoded
+picture follows from the script by arithmetic (tests/analytic_hevc.py, tests/hevc_intra_ref.py, tests/hevc_resid_ref.py).  Typed from the syntax
+clauses (7.3.1.2, 7.3.2.1 - 7.3.2.3, 7.3.3, 7.3.4, 7.3.6, 7.3.7, 7.3.8.4 - 7.3.8.11, 9.3, the context selection of 9.3.4.2, the binarisations of
+9.3.3.10 / 9.3.3.11) -- not from tools/hevcgen.c, the oracle or the product.
 
 The CABAC encoder is 9.3.4 run backwards (the encoding flowcharts of 9.3.4.x / H.264 9.3.4.2: EncodeDecision, EncodeBypass, EncodeTerminate, EncodeFlush,
 RenormE, PutBit).  Context initial values: the separately typed copy HEVC_INIT of tests/test_table_provenance.py; rangeTabLps: the separately typed copy
@@ -14,7 +14,12 @@ be shared by this encoder and the decoder and cancel, and entropy coding is not 
 The script
     seq  = dict(width, height, weighted_pred=0, weighted_bipred=0, deblock=0 (1: filter on in the PPS), pcm_loop_filter_disabled=1, init_qp=26,
                 ctb_log2=4 (4, 5, 6), min_cb_log2=ctb_log2 (3 ..), max_tb_log2=4 (.. 5), tu_depth_intra=0 (max_transform_hierarchy_depth_intra),
-                pcm_log2=(4, 4) (smallest and largest PCM unit), strong_intra=0, constrained_intra=0)
+                pcm_log2=(4, 4) (smallest and largest PCM unit), strong_intra=0, constrained_intra=0,
+                tu_depth_inter=0 (max_transform_hierarchy_depth_inter), transform_skip=0, transquant_bypass=0, sign_hiding=0,
+                cu_qp_delta=0 with diff_cu_qp_delta_depth=0, cb_qp_offset=0, cr_qp_offset=0 (PPS), slice_chroma_qp_offsets=0 (1: every picture's
+                cb_qp_offset / cr_qp_offset go into its slice headers),
+                scaling_lists=None | dict(sps=None | spec, pps=None | spec): scaling_list_enabled_flag 1; sps None = the default lists, a spec is
+                what ``scaling_list_data`` takes; PPS lists replace the SPS ones)
            the coded size is width x height rounded up to the minimum coding block size: a picture may end inside a CTB
     pics = [dict(kind="I" | "P" | "B", poc, layout="ctb" | "row" | "pic", cus=[...], and optionally is_ref (default kind != "B"), qp,
                  deblock=None | 0 | 1 (slice override), wp=dict(ld_y, ld_c, l0=[entry..], l1=[entry..]) with entry = None or
@@ -34,6 +39,13 @@ The script
                                                                    7.4.9.8 infers split_transform_flag the script must say what is inferred); dc in
                                                                    decoding order, a level 0 = cbf 0; with 4x4 luma blocks the chroma levels of four
                                                                    blocks are those of the fourth entry (7.3.8.10: blkIdx 3)
+      intra and inter units (inter units of 16x16 and 32x32 CTBs) may carry, in place of dc,
+        tu=depth, coef=[None | {0: {(x, y): level}, 1: {..}, 2: {..}, "tskip": {components with transform_skip_flag}} per transform unit]
+                                                                   every level as scripted: with sign_hiding the writer asserts the parity that the
+                                                                   hidden sign needs, it does not repair it; an inter unit with any level has
+                                                                   rqt_root_cbf 1 and a transform tree of uniform depth tu
+        bypass=1 (cu_transquant_bypass_flag), dqp=CuQpDeltaVal     dqp is coded with the unit's first transform unit that has a cbf, once per
+                                                                   quantisation group: a unit that cannot carry its dqp is refused
 Every picture decoded so far with is_ref stays in the reference picture set (at most 5).  RefPicList0 = pictures before the current one in output
 order, nearest first, then those after it; RefPicList1 the other way round (8.3.4); both lists are active in full.
 layout "ctb": one slice per CTB -- no spatial candidate exists, TMVP is off, both AMVP candidates are zero, mvd = the vector.  "row" / "pic": every CTB
@@ -170,7 +182,7 @@ def geometry(seq):
     """The block sizes of the sequence (7.4.3.2.1), defaults = one 16x16 coding unit per CTB, transform blocks 4 .. 16, PCM at 16x16 only."""
     ctb = seq.get("ctb_log2", 4)
     g = dict(ctb=ctb, min_cb=seq.get("min_cb_log2", ctb), max_tb=seq.get("max_tb_log2", 4), tu_depth=seq.get("tu_depth_intra", 0),
-             pcm=tuple(seq.get("pcm_log2", (4, 4))))
+             tu_depth_inter=seq.get("tu_depth_inter", 0), pcm=tuple(seq.get("pcm_log2", (4, 4))))
     assert ctb in (4, 5, 6) and 3 <= g["min_cb"] <= ctb and 2 < g["max_tb"] <= min(ctb, 5) and 0 <= g["tu_depth"] <= ctb - 2
     assert 3 <= g["pcm"][0] <= g["pcm"][1] <= min(ctb, 5) and g["pcm"][0] >= min(g["min_cb"], 5)
     return g
@@ -235,8 +247,14 @@ def sps(seq):
     g = geometry(seq)
     b.ue(g["min_cb"] - 3); b.ue(g["ctb"] - g["min_cb"])             # MinCbLog2SizeY, CtbLog2SizeY (default 4, 4: a CTB is one coding unit, no split_cu_flag)
     b.ue(0); b.ue(g["max_tb"] - 2)                                  # transform blocks 4 .. 16 (32)
-    b.ue(0); b.ue(g["tu_depth"])                                    # max_transform_hierarchy_depth_inter / intra
-    b.u(1, 0); b.u(1, 0); b.u(1, 0)                                 # scaling lists, AMP, SAO: off
+    b.ue(g["tu_depth_inter"]); b.ue(g["tu_depth"])                  # max_transform_hierarchy_depth_inter / intra
+    sl = seq.get("scaling_lists")
+    b.u(1, 1 if sl is not None else 0)                              # scaling_list_enabled_flag
+    if sl is not None:
+        b.u(1, 1 if sl.get("sps") is not None else 0)               # sps_scaling_list_data_present_flag (0: the default lists of Tables 7-5 / 7-6)
+        if sl.get("sps") is not None:
+            scaling_list_data(b, sl["sps"])
+    b.u(1, 0); b.u(1, 0)                                            # AMP, SAO: off
     b.u(1, 1); b.u(4, 7); b.u(4, 7); b.ue(g["pcm"][0] - 3); b.ue(g["pcm"][1] - g["pcm"][0])          # PCM on: 8-bit samples (default 16x16 only)
     b.u(1, seq.get("pcm_loop_filter_disabled", 1))
     b.ue(0)                                                         # num_short_term_ref_pic_sets: every slice header carries its own
@@ -249,19 +267,28 @@ def sps(seq):
 def pps(seq):
     b = Bits()
     b.ue(0); b.ue(0)
-    b.u(1, 0); b.u(1, 0); b.u(3, 0); b.u(1, 0); b.u(1, 0)           # dependent slices, output flag, extra bits, sign hiding, cabac_init_present
+    b.u(1, 0); b.u(1, 0); b.u(3, 0); b.u(1, seq.get("sign_hiding", 0)); b.u(1, 0)     # dependent slices, output flag, extra bits, sign hiding, cabac_init_present
     b.ue(0); b.ue(0)                                                # num_ref_idx_default_active_minus1 (every P / B slice overrides)
     b.se(seq.get("init_qp", 26) - 26)
-    b.u(1, seq.get("constrained_intra", 0)); b.u(1, 0); b.u(1, 0)   # constrained_intra_pred_flag; transform skip, cu_qp_delta: off
-    b.se(0); b.se(0); b.u(1, 0)                                     # chroma QP offsets
+    b.u(1, seq.get("constrained_intra", 0)); b.u(1, seq.get("transform_skip", 0))      # constrained_intra_pred_flag, transform_skip_enabled_flag
+    b.u(1, seq.get("cu_qp_delta", 0))                               # cu_qp_delta_enabled_flag
+    if seq.get("cu_qp_delta", 0):
+        assert 0 <= seq.get("diff_cu_qp_delta_depth", 0) <= geometry(seq)["ctb"] - geometry(seq)["min_cb"]
+        b.ue(seq.get("diff_cu_qp_delta_depth", 0))
+    b.se(seq.get("cb_qp_offset", 0)); b.se(seq.get("cr_qp_offset", 0))
+    b.u(1, seq.get("slice_chroma_qp_offsets", 0))                   # pps_slice_chroma_qp_offsets_present_flag
     b.u(1, seq.get("weighted_pred", 0)); b.u(1, seq.get("weighted_bipred", 0))
-    b.u(1, 0); b.u(1, 0); b.u(1, 0)                                 # transquant bypass, tiles, wavefronts
+    b.u(1, seq.get("transquant_bypass", 0)); b.u(1, 0); b.u(1, 0)   # transquant_bypass_enabled_flag; tiles, wavefronts: off
     b.u(1, 1)                                                       # pps_loop_filter_across_slices_enabled_flag
     b.u(1, 1); b.u(1, 1)                                            # deblocking_filter_control_present_flag, override enabled
     b.u(1, 0 if seq.get("deblock", 0) else 1)                       # pps_deblocking_filter_disabled_flag
     if seq.get("deblock", 0):
         b.se(0); b.se(0)
-    b.u(1, 0); b.u(1, 0); b.ue(0); b.u(1, 0); b.u(1, 0)             # scaling lists, list modification, parallel merge level, header extension, extension
+    pl = (seq.get("scaling_lists") or {}).get("pps")
+    b.u(1, 1 if pl is not None else 0)                              # pps_scaling_list_data_present_flag
+    if pl is not None:
+        scaling_list_data(b, pl)
+    b.u(1, 0); b.ue(0); b.u(1, 0); b.u(1, 0)                        # list modification, parallel merge level, header extension, extension
     b.trailing()
     return nal(34, b.bytes())
 
@@ -328,6 +355,8 @@ def slice_header(b, seq, p, pl, first, addr, n_ctbs):
                             b.se(w_ - (1 << wp["ld_c"])); b.se(o_ - 128 + ((128 * w_) >> wp["ld_c"]))
         b.ue(4)                                                     # five_minus_max_num_merge_cand: one candidate, merge_idx is never coded
     b.se(p.get("qp", seq.get("init_qp", 26)) - seq.get("init_qp", 26))
+    if seq.get("slice_chroma_qp_offsets", 0):
+        b.se(p.get("cb_qp_offset", 0)); b.se(p.get("cr_qp_offset", 0))
     ov = p.get("deblock")
     b.u(1, 0 if ov is None else 1)                                  # deblocking_filter_override_flag
     disabled = not seq.get("deblock", 0)
@@ -348,6 +377,114 @@ def tu_leaves(log2cb, nxn, tu):
     return 4 ** tu
 
 
+def scan_order(idx, blk):
+    """6.5.3 - 6.5.5: the (x, y) of a blk x blk array in up-right diagonal (0), horizontal (1) or vertical (2) order"""
+    if idx == 1:
+        return [(x, y) for y in range(blk) for x in range(blk)]
+    if idx == 2:
+        return [(x, y) for x in range(blk) for y in range(blk)]
+    out, x, y = [], 0, 0
+    while len(out) < blk * blk:
+        while y >= 0:
+            if x < blk and y < blk:
+                out.append((x, y))
+            y -= 1
+            x += 1
+        y, x = x, 0
+    return out
+
+
+SCAN = [[scan_order(idx, 1 << lg) for lg in range(4)] for idx in range(3)]       # ScanOrder[log2BlockSize][scanIdx] as SCAN[scanIdx][log2BlockSize]
+SIG_CTX_4X4 = [0, 1, 4, 5, 2, 3, 4, 5, 6, 6, 8, 8, 7, 7, 8]                       # ctxIdxMap of 9.3.4.2.5, i = (yC << 2) + xC
+WRITER_SWITCHES = ("scan_ignored", "hidden_sign_written", "ctxset_not_raised", "rice_never_raised", "csbf_wrong_neighbours")
+
+
+def sig_ctx_inc(lg, cidx, scan_idx, xc, yc, prev_csbf):
+    """9.3.4.2.5: ctxInc of sig_coeff_flag at (xc, yc) of a 2^lg block; prev_csbf = coded_sub_block_flag of the sub-block to the right | below << 1"""
+    if lg == 2:
+        sig = SIG_CTX_4X4[(yc << 2) + xc]
+    elif xc + yc == 0:
+        sig = 0
+    else:
+        xp, yp = xc & 3, yc & 3
+        if prev_csbf == 0:
+            sig = 2 if xp + yp == 0 else (1 if xp + yp < 3 else 0)
+        elif prev_csbf == 1:
+            sig = 2 if yp == 0 else (1 if yp == 1 else 0)
+        elif prev_csbf == 2:
+            sig = 2 if xp == 0 else (1 if xp == 1 else 0)
+        else:
+            sig = 2
+        if cidx == 0:
+            if (xc >> 2) + (yc >> 2) > 0:
+                sig += 3
+            sig += (9 if scan_idx == 0 else 15) if lg == 3 else 21
+        else:
+            sig += 9 if lg == 3 else 12
+    return sig if cidx == 0 else 27 + sig
+
+
+def last_prefix(pos):
+    """7.4.9.11 backwards: (last_sig_coeff prefix, number of suffix bits, suffix) of a coordinate"""
+    if pos < 4:
+        return pos, 0, 0
+    for pre in range(4, 10):
+        nb = (pre >> 1) - 1
+        base = (1 << nb) * (2 + (pre & 1))
+        if base <= pos < base + (1 << nb):
+            return pre, nb, pos - base
+    raise AssertionError(pos)
+
+
+def scaling_list_data(b, spec):
+    """7.3.4.  spec[(sizeId, matrixId)] = ("ref", scaling_list_pred_matrix_id_delta) or ("coded", the 16 / 64 entries in diagonal scan order, dc or None);
+    a list that the spec does not name is predicted with delta 0: the default list (7.4.5).  sizeId 3 has the matrixId 0 and 1."""
+    for size_id in range(4):
+        for matrix_id in range(2 if size_id == 3 else 6):
+            e = spec.get((size_id, matrix_id), ("ref", 0))
+            b.u(1, 1 if e[0] == "coded" else 0)                     # scaling_list_pred_mode_flag
+            if e[0] == "ref":
+                assert 0 <= e[1] <= matrix_id
+                b.ue(e[1])
+                continue
+            coefs, dc = e[1], e[2]
+            assert len(coefs) == min(64, 1 << (4 + (size_id << 1))) and all(1 <= v <= 255 for v in coefs) and (dc is None) == (size_id < 2)
+            nxt = 8
+            if size_id > 1:
+                assert 1 <= dc <= 255
+                b.se(dc - 8)
+                nxt = dc
+            for v in coefs:
+                d = (v - nxt + 128) % 256 - 128                     # scaling_list_delta_coef in -128 .. 127; nextCoef = (nextCoef + delta + 256) % 256
+                b.se(d)
+                nxt = v
+
+
+def intra_chroma_mode(v, luma_mode):
+    """8.4.3 (ChromaArrayType 1): only to choose scanIdx"""
+    if v == 4:
+        return luma_mode
+    m = (0, 26, 10, 1)[v]
+    return 34 if m == luma_mode else m
+
+
+def unit_tus(u, count):
+    """The transform units of a unit's script in one form: [{0: {(x, y): level}, 1: {..}, 2: {..}, "tskip": set of components}] -- from ``coef`` or ``dc``"""
+    if u.get("coef") is not None:
+        assert u.get("dc") is None and len(u["coef"]) == count, (len(u["coef"]), count)
+        out = []
+        for e in u["coef"]:
+            e = e or {}
+            t = {k: dict(e.get(k) or {}) for k in (0, 1, 2)}
+            assert all(lv for k in (0, 1, 2) for lv in t[k].values()), "a level 0 is not a coefficient"
+            t["tskip"] = set(e.get("tskip", ()))
+            out.append(t)
+        return out
+    dc = u.get("dc") or [None] * count
+    assert len(dc) == count
+    return [{k: ({(0, 0): (e or (0, 0, 0))[k]} if (e or (0, 0, 0))[k] else {}) for k in (0, 1, 2)} | {"tskip": set()} for e in dc]
+
+
 def mpm_candidates(a, b):
     """8.4.2: candModeList from candIntraPredModeA / B"""
     if a == b:
@@ -358,8 +495,10 @@ def mpm_candidates(a, b):
 class _Picture:
     """One picture's slice data (7.3.8): the maps that the context selection and the candidate derivation read, and the syntax itself."""
 
-    def __init__(self, seq, p, pl, kind):
+    def __init__(self, seq, p, pl, kind, sw=None, stats=None):
         self.seq, self.p, self.pl, self.kind, self.g = seq, p, pl, kind, geometry(seq)
+        self.sw, self.dqp_coded, self.dqp_units = sw or {}, False, []
+        self.stats = stats if stats is not None else {}             # what the residual syntax met, counted by name (the host test asserts coverage from it)
         self.W, self.H = coded_size(seq)
         self.cw, self.ch = ctb_dims(seq)
         h8, w8 = (self.H + 7) // 8, (self.W + 7) // 8
@@ -384,6 +523,8 @@ class _Picture:
     def quadtree(self, c, x, y, log2, depth, node):
         """7.3.8.4"""
         n = 1 << log2
+        if self.seq.get("cu_qp_delta", 0) and log2 >= self.g["ctb"] - self.seq.get("diff_cu_qp_delta_depth", 0):
+            self.dqp_coded = False                                  # IsCuQpDeltaCoded = 0 at the start of a quantisation group
         if x + n <= self.W and y + n <= self.H and log2 > self.g["min_cb"]:
             split = node["t"] == "split"
             inc = sum(1 for (xn, yn) in ((x - 1, y), (x, y - 1)) if self.avail(x, y, xn, yn) and self.depth[yn >> 3, xn >> 3] > depth)      # 9.3.4.2.2
@@ -402,6 +543,10 @@ class _Picture:
     def coding_unit(self, c, x, y, log2, depth, u):
         """7.3.8.5"""
         t, n, kind, b = u["t"], 1 << log2, self.kind, c.b
+        if self.seq.get("transquant_bypass", 0):
+            c.decision("cu_transquant_bypass", 0, 1 if u.get("bypass", 0) else 0)
+        else:
+            assert not u.get("bypass", 0)
         if kind != "I":
             inc = sum(1 for (xn, yn) in ((x - 1, y), (x, y - 1)) if self.avail(x, y, xn, yn) and self.skip[yn >> 3, xn >> 3])               # 9.3.4.2.2
             c.decision("cu_skip_flag", inc, 1 if t == "skip" else 0)
@@ -462,26 +607,31 @@ class _Picture:
         c.decision("intra_chroma_pred_mode", 0, 0 if v == 4 else 1)
         if v != 4:
             c.bypass(v >> 1); c.bypass(v & 1)
-        tu = u.get("tu", 1 if nxn else 0)
-        dc = u.get("dc") or [None] * tu_leaves(log2, nxn, tu)
-        assert len(dc) == tu_leaves(log2, nxn, tu)
-        small = log2 - tu == 2                                      # 4x4 luma blocks: the chroma of four of them is one block, coded with the fourth
+        self.transform_tree(c, u, x, y, log2, nxn, True)
 
-        def chroma_levels(first, count, comp):
-            return [(dc[i] or (0, 0, 0))[comp] for i in range(first, first + count) if not small or i % 4 == 3]
+    def transform_tree(self, c, u, x, y, log2, nxn, intra):
+        """7.3.8.8 / 7.3.8.10 for a tree of uniform depth u["tu"]"""
+        tu = u.get("tu", 1 if nxn else 0)
+        tus = unit_tus(u, tu_leaves(log2, nxn, tu))
+        small = log2 - tu == 2                                      # 4x4 luma blocks: the chroma of four of them is one block, coded with the fourth
+        max_depth = self.g["tu_depth"] + nxn if intra else self.g["tu_depth_inter"]
+        bypass = bool(u.get("bypass", 0))
+        cm = intra_chroma_mode(u.get("chroma", 4), u["modes"][0]) if intra else None
+
+        def chroma_coded(first, count, comp):
+            return any(tus[i][comp] for i in range(first, first + count) if not small or i % 4 == 3)
 
         def tree(x0, y0, lg, d, blk, first, par):
-            """7.3.8.8 / 7.3.8.10"""
             count = 4 ** (tu - d)
             want = d < tu
-            if lg <= self.g["max_tb"] and lg > 2 and d < self.g["tu_depth"] + nxn and not (nxn and d == 0):
+            if lg <= self.g["max_tb"] and lg > 2 and d < max_depth and not (nxn and d == 0):
                 c.decision("split_transform_flag", 5 - lg, 1 if want else 0)
             else:
                 assert want == (lg > self.g["max_tb"] or (nxn and d == 0)), ("the script's depth is not what 7.4.9.8 infers", x0, y0, lg, d, tu)
             cbf = list(par)
             if lg > 2:
                 for k in (0, 1):
-                    v_ = 1 if any(chroma_levels(first, count, k + 1)) else 0
+                    v_ = 1 if chroma_coded(first, count, k + 1) else 0
                     if d == 0 or par[k]:
                         c.decision("cbf_cb_cr", d, v_)
                     else:
@@ -491,41 +641,149 @@ class _Picture:
                 for i in range(4):
                     tree(x0 + (i & 1) * (1 << (lg - 1)), y0 + (i >> 1) * (1 << (lg - 1)), lg - 1, d + 1, i, first + i * (count // 4), cbf)
                 return
-            lv = dc[first] or (0, 0, 0)
-            c.decision("cbf_luma", 1 if d == 0 else 0, 1 if lv[0] else 0)
-            if lv[0]:
-                self.residual(c, lg, 0, lv[0])
+            t = tus[first]
+            if intra or d != 0 or cbf[0] or cbf[1]:
+                c.decision("cbf_luma", 1 if d == 0 else 0, 1 if t[0] else 0)
+            else:
+                assert t[0], "cbf_luma is inferred to be 1 at depth 0 of an inter unit without chroma coefficients"
+            if (t[0] or cbf[0] or cbf[1]) and self.seq.get("cu_qp_delta", 0) and not self.dqp_coded:       # 7.3.8.10: cbfLuma || cbfChroma (4x4: the parent's)
+                self.dqp_coded, self.dqp_units = True, self.dqp_units + [id(u)]
+                v = u.get("dqp", 0)
+                assert -26 <= v <= 25
+                for i in range(min(abs(v), 5)):                     # cu_qp_delta_abs: prefix TU, cMax 5, ctxInc 0 for the first bin and 1 for the others
+                    c.decision("cu_qp_delta_abs", 1 if i else 0, 1)
+                if abs(v) < 5:
+                    c.decision("cu_qp_delta_abs", 1 if v else 0, 0)
+                else:
+                    c.egk(abs(v) - 5, 0)
+                if v:
+                    c.bypass(1 if v < 0 else 0)                     # cu_qp_delta_sign_flag
+            luma_mode = (u["modes"][(first >> (2 * (tu - 1))) & 3] if nxn else u["modes"][0]) if intra else None
+            if t[0]:
+                self.residual(c, lg, 0, t[0], luma_mode, 0 in t["tskip"], bypass)
+            else:
+                assert 0 not in t["tskip"]
             if lg > 2 or blk == 3:
                 for k in (0, 1):
                     if cbf[k]:
-                        self.residual(c, max(lg - 1, 2), k + 1, lv[k + 1])
+                        self.residual(c, max(lg - 1, 2), k + 1, t[k + 1], cm, (k + 1) in t["tskip"], bypass)
+                    else:
+                        assert (k + 1) not in t["tskip"]
+            elif u.get("coef") is not None:                         # (``dc`` ignores the chroma levels of the first three, as it always did)
+                assert not t[1] and not t[2] and not (t["tskip"] - {0}), "the chroma of four 4x4 luma blocks is scripted with the fourth"
         tree(x, y, log2, 0, 0, 0, [0, 0])
 
-    @staticmethod
-    def residual(c, lg, cidx, level):
-        """7.3.8.11 for one coefficient at (0, 0): both last_sig_coeff prefixes 0, no sig_coeff_flag, no coded_sub_block_flag; the first
-        coeff_abs_level_greater1_flag of a block has ctxSet 0 (sub-block 0) and greater1Ctx 1 (9.3.4.2.6), chroma contexts 16 (4) further on"""
-        assert level and abs(level) < 2000
-        off = 15 if cidx else 3 * (lg - 2) + ((lg - 1) >> 2)        # 9.3.4.2.3, binIdx 0
-        c.decision("last_sig_coeff_prefix", off, 0)
-        c.decision("last_sig_coeff_y_prefix", off, 0)
-        a = abs(level)
-        c.decision("coeff_abs_level_greater1", (16 if cidx else 0) + 1, 1 if a > 1 else 0)
-        if a > 1:
-            c.decision("coeff_abs_level_greater2", 4 if cidx else 0, 1 if a > 2 else 0)
-        c.bypass(1 if level < 0 else 0)
-        if a > 2:                                                   # coeff_abs_level_remaining, cRiceParam 0 (9.3.3.11): prefix up to 1111, then EG1
-            rem = a - 3
-            for _ in range(min(rem, 4)):
-                c.bypass(1)
-            if rem < 4:
-                c.bypass(0)
+    def residual(self, c, lg, cidx, coefs, intra_mode, tskip, bypass):
+        """7.3.8.11 with the context selection of 9.3.4.2.3 - 9.3.4.2.7 and the binarisation of 9.3.3.11.  coefs {(x, y): level}, not empty;
+        intra_mode: the block's intra prediction mode (None in an inter unit)"""
+        sw, n = self.sw, 1 << lg
+
+        def met(*key):
+            self.stats[key] = self.stats.get(key, 0) + 1
+        assert coefs and all(0 <= x < n and 0 <= y < n and lv and -32768 <= lv <= 32767 for (x, y), lv in coefs.items()), (lg, coefs)
+        if self.seq.get("transform_skip", 0) and not bypass and lg == 2:
+            c.decision("transform_skip_flag", 1 if cidx else 0, 1 if tskip else 0)
+        else:
+            assert not tskip
+        scan_idx = 0
+        if intra_mode is not None and (lg == 2 or (lg == 3 and cidx == 0)) and not sw.get("scan_ignored"):
+            scan_idx = 2 if 6 <= intra_mode <= 14 else (1 if 22 <= intra_mode <= 30 else 0)
+        sb_scan, pos_scan = SCAN[scan_idx][lg - 2], SCAN[scan_idx][2]
+        met("scan", "intra" if intra_mode is not None else "inter", lg, min(cidx, 1), scan_idx)
+        last_sb, last_pos = max((i, k) for i, (xs, ys) in enumerate(sb_scan) for k, (xp, yp) in enumerate(pos_scan) if (4 * xs + xp, 4 * ys + yp) in coefs)
+        lx, ly = 4 * sb_scan[last_sb][0] + pos_scan[last_pos][0], 4 * sb_scan[last_sb][1] + pos_scan[last_pos][1]
+        if scan_idx == 2:
+            lx, ly = ly, lx                                         # 7.3.8.11: the coded pair is swapped for the vertical scan
+        off, shift = (15, lg - 2) if cidx else (3 * (lg - 2) + ((lg - 1) >> 2), (lg + 1) >> 2)     # 9.3.4.2.3
+        pre = [last_prefix(lx), last_prefix(ly)]
+        for name, (p_, _, _) in zip(("last_sig_coeff_prefix", "last_sig_coeff_y_prefix"), pre):
+            for i in range(p_):
+                c.decision(name, off + (i >> shift), 1)
+            if p_ < 2 * lg - 1:                                     # truncated unary, cMax = (log2TrafoSize << 1) - 1
+                c.decision(name, off + (p_ >> shift), 0)
+        for (_, nb, suf) in pre:
+            met("last_suffix_bits", nb)
+            for i in range(nb - 1, -1, -1):
+                c.bypass((suf >> i) & 1)
+        hiding = self.seq.get("sign_hiding", 0) and not bypass
+        csbf = {}
+        g1ctx, first_group = 1, True                                # greater1Ctx as the last flag of the previous sub-block left it (9.3.4.2.6)
+        for i in range(last_sb, -1, -1):
+            xs, ys = sb_scan[i]
+            pos = [(4 * xs + xp, 4 * ys + yp) for (xp, yp) in pos_scan]
+            lev = [coefs.get(q, 0) for q in pos]
+            right, below = csbf.get((xs + 1, ys), 0), csbf.get((xs, ys + 1), 0)
+            infer = False
+            if 0 < i < last_sb:
+                csbf[(xs, ys)] = 1 if any(lev) else 0
+                ctx = csbf.get((xs - 1, ys), 0) | csbf.get((xs, ys - 1), 0) if sw.get("csbf_wrong_neighbours") else right | below
+                c.decision("coded_sub_block_flag", ctx + (2 if cidx else 0), csbf[(xs, ys)])        # 9.3.4.2.4
+                infer = True
+                met("coded_sub_block_flag", csbf[(xs, ys)], right | below)
             else:
-                c.egk(rem - 4, 1)
+                csbf[(xs, ys)] = 1                                  # inferred for the first and the last sub-block
+            if not csbf[(xs, ys)]:
+                continue
+            for k in range(last_pos - 1 if i == last_sb else 15, -1, -1):
+                if k > 0 or not infer:
+                    c.decision("sig_coeff_flag", sig_ctx_inc(lg, cidx, scan_idx, pos[k][0], pos[k][1], right | (below << 1)), 1 if lev[k] else 0)
+                    if lev[k]:
+                        infer = False
+                else:
+                    assert lev[0], "sig_coeff_flag of position 0 is inferred to be 1"
+                    met("sig_coeff_flag inferred")
+            sig = [k for k in range(15, -1, -1) if lev[k]]          # in decoding order
+            if not sig:
+                continue
+            ctx_set = 0 if (i == 0 or cidx) else 2
+            if not first_group:
+                met("greater1Ctx carried", min(3, g1ctx))
+            if not first_group and g1ctx == 0 and not sw.get("ctxset_not_raised"):
+                ctx_set += 1
+            if sum(1 for k in sig if abs(lev[k]) > 1) > 8:
+                met("more than 8 levels above 1")
+            first_group, g1ctx = False, 1
+            first_g1 = None
+            for k in sig[:8]:
+                f = 1 if abs(lev[k]) > 1 else 0
+                c.decision("coeff_abs_level_greater1", (16 if cidx else 0) + 4 * ctx_set + min(3, g1ctx), f)
+                if g1ctx > 0:
+                    g1ctx = 0 if f else g1ctx + 1
+                if f and first_g1 is None:
+                    first_g1 = k
+            if first_g1 is not None:
+                c.decision("coeff_abs_level_greater2", (4 if cidx else 0) + ctx_set, 1 if abs(lev[first_g1]) > 2 else 0)
+            hidden = bool(hiding and sig[0] - sig[-1] > 3)
+            if self.seq.get("sign_hiding", 0):
+                met("sign hiding", "bypass" if bypass else "coded", min(sig[0] - sig[-1], 5), sum(abs(lev[k]) for k in sig) & 1)
+            if hidden:
+                assert (sum(abs(lev[k]) for k in sig) & 1) == (1 if lev[sig[-1]] < 0 else 0), "sign data hiding: the parity of the sum is the hidden sign"
+            for k in sig:
+                if not hidden or k != sig[-1] or sw.get("hidden_sign_written"):
+                    c.bypass(1 if lev[k] < 0 else 0)
+            rice = 0
+            for m, k in enumerate(sig):
+                base = (3 if k == first_g1 else 2) if m < 8 else 1
+                if abs(lev[k]) >= base:
+                    rem = abs(lev[k]) - base                        # coeff_abs_level_remaining, 9.3.3.11
+                    cmax = 4 << rice
+                    for _ in range(min(rem, cmax) >> rice):
+                        c.bypass(1)
+                    if rem < cmax:
+                        c.bypass(0)
+                        for j in range(rice - 1, -1, -1):
+                            c.bypass((rem >> j) & 1)
+                    else:
+                        c.egk(rem - cmax, rice + 1)
+                        met("escape at cRiceParam", rice)
+                    if abs(lev[k]) > 3 * (1 << rice) and not sw.get("rice_never_raised"):
+                        rice = min(rice + 1, 4)
+                        met("cRiceParam raised to", rice)
 
     def inter_unit(self, c, x, y, log2, depth, u):
         pl, kind = self.pl, self.kind
-        assert kind != "I" and log2 == self.g["ctb"] and (self.step == 1 or u == self.first_unit), "a slice of several CTBs repeats one inter unit"
+        assert kind != "I" and log2 == self.g["ctb"] and log2 <= 5 and (self.step == 1 or u is self.first_unit or u == self.first_unit), \
+            "a slice of several CTBs repeats one inter unit"
         c.decision("part_mode", 0, 1)
         c.decision("merge_flag", 0, 0)
         l0, l1 = u.get("l0"), u.get("l1")
@@ -557,10 +815,17 @@ class _Picture:
                         c.egk(abs(mvd[i]) - 2, 1)                   # abs_mvd_minus2: EG1
                     c.bypass(1 if mvd[i] < 0 else 0)                # mvd_sign_flag
             c.decision("mvp_flag", 0, 0)
-        c.decision("rqt_root_cbf", 0, 0)
+        tus = unit_tus(u, tu_leaves(log2, False, u.get("tu", 0)))
+        root = 1 if any(t[k] for t in tus for k in (0, 1, 2)) else 0
+        c.decision("rqt_root_cbf", 0, root)
+        if root:
+            self.transform_tree(c, u, x, y, log2, False, False)
 
 
-def write(seq, pics):
+def write(seq, pics, stats=None, **sw):
+    """Annex-B bytes of the script.  The keyword arguments (WRITER_SWITCHES) make the residual syntax wrong on purpose; stats: a dict that
+    counts what residual_coding met."""
+    assert all(k in WRITER_SWITCHES for k in sw), sw
     cw, ch = ctb_dims(seq)
     n_ctbs = cw * ch
     s = 1 << geometry(seq)["ctb"]
@@ -571,7 +836,7 @@ def write(seq, pics):
         pl["pocs"] = pocs
         kind, cus = p["kind"], p["cus"]
         assert len(cus) == n_ctbs
-        pic = _Picture(seq, p, pl, kind)
+        pic = _Picture(seq, p, pl, kind, sw, stats)
         pic.step = step = {"ctb": 1, "row": cw, "pic": n_ctbs}[p.get("layout", "ctb" if kind != "I" else "pic")]
         for first in range(0, n_ctbs, step):
             b = Bits()
@@ -586,5 +851,6 @@ def write(seq, pics):
                 c.terminate(1 if a == last else 0)                  # end_of_slice_segment_flag; the flush's last bit is rbsp_slice_segment_trailing_bits' 1
             b.align_zero()
             out.append(nal(pl["typ"], b.bytes()))
+        assert all(id(u) in pic.dqp_units for (_, _, _, _, u) in walk(seq, p) if u.get("dqp")), "a dqp that no transform unit could carry"
     return b"".join(out)
 

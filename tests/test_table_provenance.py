@@ -287,10 +287,8 @@ HEVC_INTRA_ANGLE = [0, 0] + [32, 26, 21, 17, 13, 9, 5, 2, 0, -2, -5, -9, -13, -1
 HEVC_INV_ANGLE = [0] * 11 + [-4096, -1638, -910, -630, -482, -390, -315, -256, -315, -390, -482, -630, -910, -1638, -4096] + [0] * 9
 
 
-def test_hevc_constant_tables_against_a_separately_typed_copy():
-    """H.265 transform basis, DST, intra angles, interpolation filters, deblocking and chroma-QP tables: typed here from the standard's tables.
-    The 32x32 transMatrix is BUILT from its 31 distinct magnitudes and the cosine structure it samples (entry (k, n) = the rounded
-    64 * sqrt(2) * cos((2n + 1) k pi / 64), of which the standard lists the integers), not copied as 1024 numbers."""
+def hevc_trans_matrix():
+    """The 32x32 transMatrix of 8.6.4.2 as 1024 numbers, row k = basis function k (tests/hevc_resid_ref.py transforms with this copy)"""
     mag = {0: 64, 16: 64, 8: 83, 24: 36, 4: 89, 12: 75, 20: 50, 28: 18, 2: 90, 6: 87, 10: 80, 14: 70, 18: 57, 22: 43, 26: 25, 30: 9,
            1: 90, 3: 90, 5: 88, 7: 85, 9: 82, 11: 78, 13: 73, 15: 67, 17: 61, 19: 54, 21: 46, 23: 38, 25: 31, 27: 22, 29: 13, 31: 4}
     want = []
@@ -300,6 +298,14 @@ def test_hevc_constant_tables_against_a_separately_typed_copy():
             if m > 64:
                 m = 128 - m
             want.append(mag[m] if m <= 32 else -mag[64 - m])
+    return want
+
+
+def test_hevc_constant_tables_against_a_separately_typed_copy():
+    """H.265 transform basis, DST, intra angles, interpolation filters, deblocking and chroma-QP tables: typed here from the standard's tables.
+    The 32x32 transMatrix is BUILT from its 31 distinct magnitudes and the cosine structure it samples (entry (k, n) = the rounded
+    64 * sqrt(2) * cos((2n + 1) k pi / 64), of which the standard lists the integers), not copied as 1024 numbers."""
+    want = hevc_trans_matrix()
     intra_angle, inv_angle = HEVC_INTRA_ANGLE, HEVC_INV_ANGLE
     luma = [0, 0, 0, 64, 0, 0, 0, 0, -1, 4, -10, 58, 17, -5, 1, 0, -1, 4, -11, 40, 40, -11, 4, -1, 0, 1, -5, 17, 58, -10, 4, -1]
     chroma = [0, 64, 0, 0, -2, 58, 10, -2, -4, 54, 16, -2, -6, 46, 28, -4, -4, 36, 36, -4, -4, 28, 46, -6, -2, 16, 54, -4, -2, 10, 58, -2]
@@ -320,6 +326,55 @@ def test_hevc_constant_tables_against_a_separately_typed_copy():
         assert arr("luma_filter") == luma and arr("chroma_filter") == chroma, os.path.basename(path)
         assert arr("beta_tab") == beta and arr("tc_tab") == tc and arr("qpc_tab") == qpc, os.path.basename(path)
         assert arr("level_scale") == [40, 45, 51, 57, 64, 72], os.path.basename(path)
+
+
+# H.265 residual coding and scaling (tests/scripted_hevc.py codes with its own scan_order / sig_ctx_inc, tests/hevc_resid_ref.py scales with these copies)
+HEVC_LEVEL_SCALE = [40, 45, 51, 57, 64, 72]                         # 8.6.3
+# Table 7-6, i = 0 .. 63 in up-right diagonal order: matrixId 0 .. 2 (intra), 3 .. 5 (inter).  Typed from memory of the table and cross-checked against
+# the same matrices remembered in raster order (HEVC_DEFAULT_8X8_RASTER): the two recollections must be one matrix.  The matrices are symmetric, so
+# they cannot tell a transposed reading from a right one: coded lists do that (tests/analytic_hevc_resid.py).
+HEVC_DEFAULT_8X8 = [
+    [16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 17, 16, 17, 16, 17, 18, 17, 18, 18, 17, 18, 21, 19, 20, 21, 20, 19, 21, 24, 22, 22, 24,
+     24, 22, 22, 24, 25, 25, 27, 30, 27, 25, 25, 29, 31, 35, 35, 31, 29, 36, 41, 44, 41, 36, 47, 54, 54, 47, 65, 70, 65, 88, 88, 115],
+    [16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 17, 17, 17, 17, 17, 18, 18, 18, 18, 18, 18, 20, 20, 20, 20, 20, 20, 20, 24, 24, 24, 24,
+     24, 24, 24, 24, 25, 25, 25, 25, 25, 25, 25, 28, 28, 28, 28, 28, 28, 33, 33, 33, 33, 33, 41, 41, 41, 41, 54, 54, 54, 71, 71, 91]]
+HEVC_DEFAULT_8X8_RASTER = [
+    [16, 16, 16, 16, 17, 18, 21, 24, 16, 16, 16, 16, 17, 19, 22, 25, 16, 16, 17, 18, 20, 22, 25, 29, 16, 16, 18, 21, 24, 27, 31, 36,
+     17, 17, 20, 24, 30, 35, 41, 47, 18, 19, 22, 27, 35, 44, 54, 65, 21, 22, 25, 31, 41, 54, 70, 88, 24, 25, 29, 36, 47, 65, 88, 115],
+    [16, 16, 16, 16, 17, 18, 20, 24, 16, 16, 16, 17, 18, 20, 24, 25, 16, 16, 17, 18, 20, 24, 25, 28, 16, 17, 18, 20, 24, 25, 28, 33,
+     17, 18, 20, 24, 25, 28, 33, 41, 18, 20, 24, 25, 28, 33, 41, 54, 20, 24, 25, 28, 33, 41, 54, 71, 24, 25, 28, 33, 41, 54, 71, 91]]
+# 6.5.3: the up-right diagonal scan of a 4x4 array as (x, y); 6.5.4 / 6.5.5 are the raster orders by rows / by columns
+HEVC_DIAG_4X4 = [(0, 0), (0, 1), (1, 0), (0, 2), (1, 1), (2, 0), (0, 3), (1, 2), (2, 1), (3, 0), (1, 3), (2, 2), (3, 1), (2, 3), (3, 2), (3, 3)]
+HEVC_DIAG_2X2 = [(0, 0), (0, 1), (1, 0), (1, 1)]
+# 9.3.4.2.5: ctxIdxMap (4x4 blocks, by (yC << 2) + xC) and sigCtx by [prevCsbf][yP][xP] for larger blocks
+HEVC_SIG_MAP_4X4 = [0, 1, 4, 5, 2, 3, 4, 5, 6, 6, 8, 8, 7, 7, 8]
+HEVC_SIG_PATTERN = [[[2, 1, 1, 0], [1, 1, 0, 0], [1, 0, 0, 0], [0, 0, 0, 0]], [[2, 2, 2, 2], [1, 1, 1, 1], [0, 0, 0, 0], [0, 0, 0, 0]],
+                    [[2, 1, 0, 0]] * 4, [[2, 2, 2, 2]] * 4]
+
+
+def test_hevc_scans_significance_patterns_and_default_lists_against_separately_typed_copies():
+    import scripted_hevc as hw
+    assert hw.scan_order(0, 4) == HEVC_DIAG_4X4 and hw.scan_order(0, 2) == HEVC_DIAG_2X2 and hw.scan_order(0, 1) == [(0, 0)]
+    d8 = hw.scan_order(0, 8)
+    assert d8[:10] == HEVC_DIAG_4X4[:10] and d8[10:15] == [(0, 4), (1, 3), (2, 2), (3, 1), (4, 0)] and d8[-3:] == [(6, 7), (7, 6), (7, 7)] and len(set(d8)) == 64
+    for blk in (2, 4, 8):
+        assert hw.scan_order(1, blk) == [(i % blk, i // blk) for i in range(blk * blk)] and hw.scan_order(2, blk) == [(i // blk, i % blk) for i in range(blk * blk)]
+    assert hw.SIG_CTX_4X4 == HEVC_SIG_MAP_4X4
+    for prev in range(4):
+        for yp in range(4):
+            for xp in range(4):
+                want = HEVC_SIG_PATTERN[prev][yp][xp]
+                assert hw.sig_ctx_inc(4, 0, 0, 4 + xp, 8 + yp, prev) == want + 3 + 21 and hw.sig_ctx_inc(5, 0, 0, xp, yp, prev) == (want + 21 if xp + yp else 0)
+                assert hw.sig_ctx_inc(3, 0, 0, 4 + xp, yp, prev) == want + 3 + 9 and hw.sig_ctx_inc(3, 0, 1, xp, 4 + yp, prev) == want + 3 + 15
+                assert hw.sig_ctx_inc(3, 1, 0, 4 + xp, yp, prev) == 27 + want + 9 and hw.sig_ctx_inc(4, 2, 0, 4 + xp, 4 + yp, prev) == 27 + want + 12
+    assert [hw.sig_ctx_inc(2, 0, 0, i & 3, i >> 2, 0) for i in range(15)] == HEVC_SIG_MAP_4X4
+    assert [hw.sig_ctx_inc(2, 1, 2, i & 3, i >> 2, 3) for i in range(15)] == [27 + v for v in HEVC_SIG_MAP_4X4]
+    for k in (0, 1):                                                # the two recollections of Table 7-6 agree, and the matrices are symmetric
+        m = [[HEVC_DEFAULT_8X8_RASTER[k][y * 8 + x] for x in range(8)] for y in range(8)]
+        assert [m[y][x] for (x, y) in d8] == HEVC_DEFAULT_8X8[k] and all(m[y][x] == m[x][y] for x in range(8) for y in range(8))
+    for path, name in ((PROD_HEVC, "hevc_scaling_default"), (ORC_HEVC, "orch_scaling_default"), (GEN_HEVC, "hg_scaling_default")):
+        assert c_array(path, name) == HEVC_DEFAULT_8X8[0] + HEVC_DEFAULT_8X8[1], os.path.basename(path)
+        assert c_array(path, name.replace("scaling_default", "level_scale")) == HEVC_LEVEL_SCALE, os.path.basename(path)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
