@@ -4,7 +4,7 @@ As tests/scripted_h264.py: the test says which coding unit carries which samples
 into Annex-B bytes; residuals are scripted level by level (``coef``; ``dc`` is the earlier short form for one coefficient at (0, 0)), so the decoded
 picture follows from the script by arithmetic (tests/analytic_hevc.py, tests/hevc_intra_ref.py, tests/hevc_resid_ref.py).  Typed from the syntax
 clauses (7.3.1.2, 7.3.2.1 - 7.3.2.3, 7.3.3, 7.3.4, 7.3.6, 7.3.7, 7.3.8.4 - 7.3.8.11, 9.3, the context selection of 9.3.4.2, the binarisations of
-9.3.3.10 / 9.3.3.11) -- not from tools/hevcgen.c, the oracle or the product.
+9.3.3.10 / 9.3.3.11, the part_mode binarisation of 9.3.3.7) -- not from tools/hevcgen.c, the oracle or the product.
 
 The CABAC encoder is 9.3.4 run backwards (the encoding flowcharts of 9.3.4.x / H.264 9.3.4.2: EncodeDecision, EncodeBypass, EncodeTerminate, EncodeFlush,
 RenormE, PutBit).  Context initial values: the separately typed copy HEVC_INIT of tests/test_table_provenance.py; rangeTabLps: the separately typed copy
@@ -46,8 +46,25 @@ The script
                                                                    rqt_root_cbf 1 and a transform tree of uniform depth tu
         bypass=1 (cu_transquant_bypass_flag), dqp=CuQpDeltaVal     dqp is coded with the unit's first transform unit that has a cbf, once per
                                                                    quantisation group: a unit that cannot carry its dqp is refused
+Inter prediction as SYNTAX (tests/hevc_inter_ref.py derives the motion; the writer derives none), all with defaults that leave the forms above as they were:
+    seq:  amp=0 (amp_enabled_flag), tmvp=0 (sps_temporal_mvp_enabled_flag), par_mrg_log2=2 (Log2ParMrgLevel, 2 .. CtbLog2SizeY)
+    pics: max_merge=1 (MaxNumMergeCand, 1 .. 5), tmvp=the sequence's (slice_temporal_mvp_enabled_flag), col=(collocated_from_l0_flag, collocated_ref_idx)
+          = (1, 0), mvd_l1_zero=0, n_ref=(entries of list 0, of list 1) that the slice header activates (default: as many as pictures are held; more
+          repeat the pictures in turn, 8-8 / 8-10), slice_n_ref=[n_ref per slice, decoding order]: the slices of one picture with lists of their own
+    leaves:
+        dict(t="skip", merge=idx)                                  cu_skip_flag 1 and merge_idx
+        dict(t="inter", part="2Nx2N" | "2NxN" | "Nx2N" | "NxN" | "2NxnU" | "2NxnD" | "nLx2N" | "nRx2N", pus=[one per prediction block, partIdx order])
+                                                                   part_mode as 9.3.3.7 has it (NxN only at a minimum size above 8, AMP only above the
+                                                                   minimum size with amp=1); any size the quadtree gives, any slice layout
+            a prediction unit is dict(merge=idx)                   merge_flag 1, merge_idx (first bin with a context, the others bypass, cMax max_merge - 1)
+                           or dict(l0=(ref_idx, (mvdx, mvdy), mvp_flag) | None, l1=...)
+                                                                   merge_flag 0, inter_pred_idc (8x4 / 4x8: one bin, never both lists), ref_idx_lX, mvd_coding,
+                                                                   mvp_lX_flag; with mvd_l1_zero the list 1 difference of a two-list unit is not coded
+        coef / tu / dqp / bypass stay valid on such a unit: rqt_root_cbf is absent (and 1) only for a 2Nx2N merge unit; with tu_depth_inter 0 a unit
+        that is not 2Nx2N has its transform tree split once without a flag (interSplitFlag), so tu is 1
 Every picture decoded so far with is_ref stays in the reference picture set (at most 5).  RefPicList0 = pictures before the current one in output
-order, nearest first, then those after it; RefPicList1 the other way round (8.3.4); both lists are active in full.
+order, nearest first, then those after it; RefPicList1 the other way round (8.3.4); both lists are active in full unless n_ref says otherwise.
+The script must keep sps_max_num_reorder_pics = 2: at most two pictures precede a picture in decoding order and follow it in output order.
 layout "ctb": one slice per CTB -- no spatial candidate exists, TMVP is off, both AMVP candidates are zero, mvd = the vector.  "row" / "pic": every CTB
 of a slice repeats one inter unit: once a neighbour exists the first AMVP candidate is that vector (8.5.3.2.6 / 8.5.3.2.7), mvd is 0.
 Context increments follow maps kept per 8x8 block (CtDepth, cu_skip_flag, CuPredMode) and availability as 6.4.1 has it (``_Picture.avail``); the
@@ -254,11 +271,11 @@ def sps(seq):
         b.u(1, 1 if sl.get("sps") is not None else 0)               # sps_scaling_list_data_present_flag (0: the default lists of Tables 7-5 / 7-6)
         if sl.get("sps") is not None:
             scaling_list_data(b, sl["sps"])
-    b.u(1, 0); b.u(1, 0)                                            # AMP, SAO: off
+    b.u(1, seq.get("amp", 0)); b.u(1, 0)                            # amp_enabled_flag; SAO: off
     b.u(1, 1); b.u(4, 7); b.u(4, 7); b.ue(g["pcm"][0] - 3); b.ue(g["pcm"][1] - g["pcm"][0])          # PCM on: 8-bit samples (default 16x16 only)
     b.u(1, seq.get("pcm_loop_filter_disabled", 1))
     b.ue(0)                                                         # num_short_term_ref_pic_sets: every slice header carries its own
-    b.u(1, 0); b.u(1, 0); b.u(1, seq.get("strong_intra", 0))        # long-term pictures, TMVP: off; strong_intra_smoothing_enabled_flag
+    b.u(1, 0); b.u(1, seq.get("tmvp", 0)); b.u(1, seq.get("strong_intra", 0))      # long-term pictures: off; sps_temporal_mvp_enabled_flag; strong_intra_smoothing_enabled_flag
     b.u(1, 0); b.u(1, 0)                                            # VUI, extension
     b.trailing()
     return nal(33, b.bytes())
@@ -288,7 +305,8 @@ def pps(seq):
     b.u(1, 1 if pl is not None else 0)                              # pps_scaling_list_data_present_flag
     if pl is not None:
         scaling_list_data(b, pl)
-    b.u(1, 0); b.ue(0); b.u(1, 0); b.u(1, 0)                        # list modification, parallel merge level, header extension, extension
+    assert 2 <= seq.get("par_mrg_log2", 2) <= geometry(seq)["ctb"]
+    b.u(1, 0); b.ue(seq.get("par_mrg_log2", 2) - 2); b.u(1, 0); b.u(1, 0)         # list modification, log2_parallel_merge_level_minus2, header extension, extension
     b.trailing()
     return nal(34, b.bytes())
 
@@ -300,7 +318,11 @@ def plan(seq, pics):
         before = sorted((i for i in held if pics[i]["poc"] < p["poc"]), key=lambda i: -pics[i]["poc"])
         after = sorted((i for i in held if pics[i]["poc"] > p["poc"]), key=lambda i: pics[i]["poc"])
         is_ref = p.get("is_ref", p["kind"] != "B")
-        out.append(dict(before=before, after=after, l0=before + after, l1=after + before, is_ref=is_ref, typ=19 if k == 0 else (1 if is_ref else 0)))
+        n0, n1 = p.get("n_ref") or (len(held), len(held))          # num_ref_idx_l0 / l1_active_minus1 + 1: the lists' first entries
+        assert k == 0 or p["kind"] == "I" or (1 <= n0 <= 15 and 1 <= n1 <= 15 and held), (k, n0, n1, held)
+        cyc = lambda lst, n: [lst[i % len(lst)] for i in range(n)] if lst else []       # 8-8 / 8-10: more active entries than pictures repeat them in turn
+        out.append(dict(before=before, after=after, l0=cyc(before + after, n0), l1=cyc(after + before, n1), is_ref=is_ref,
+                        typ=19 if k == 0 else (1 if is_ref else 0)))
         if k == 0:
             held = []
         if is_ref:
@@ -309,8 +331,19 @@ def plan(seq, pics):
     return out
 
 
-def slice_header(b, seq, p, pl, first, addr, n_ctbs):
+def slice_plan(pl, p, ordinal):
+    """The plan of a picture as slice number `ordinal` (decoding order) sees it: with slice_n_ref the slice activates its own number of entries"""
+    if p.get("slice_n_ref") is None:
+        return pl
+    n0, n1 = p["slice_n_ref"][ordinal]
+    assert 1 <= n0 <= 15 and 1 <= n1 <= 15 and p.get("wp") is None
+    cyc = lambda lst, n: [lst[i % len(lst)] for i in range(n)]
+    return dict(pl, l0=cyc(pl["before"] + pl["after"], n0), l1=cyc(pl["after"] + pl["before"], n1))
+
+
+def slice_header(b, seq, p, pl, first, addr, n_ctbs, sw={}):
     kind = p["kind"]
+    tmvp = 0
     b.u(1, 1 if first else 0)
     if pl["typ"] >= 16:
         b.u(1, 0)                                                   # no_output_of_prior_pics_flag
@@ -330,12 +363,22 @@ def slice_header(b, seq, p, pl, first, addr, n_ctbs):
         for i in pl["after"]:
             b.ue(pl["pocs"][i] - prev - 1); b.u(1, 1)
             prev = pl["pocs"][i]
+        if seq.get("tmvp", 0):
+            tmvp = p.get("tmvp", 1)
+            b.u(1, tmvp)                                            # slice_temporal_mvp_enabled_flag
     if kind != "I":
         b.u(1, 1)                                                   # num_ref_idx_active_override_flag
         b.ue(len(pl["l0"]) - 1)
         if kind == "B":
             b.ue(len(pl["l1"]) - 1)
-            b.u(1, 0)                                               # mvd_l1_zero_flag
+            b.u(1, p.get("mvd_l1_zero", 0))                         # mvd_l1_zero_flag
+        if tmvp and kind != "I":
+            from_l0, idx = p.get("col", (1, 0))
+            assert (from_l0 == 1 or kind == "B") and 0 <= idx < len(pl["l0" if from_l0 else "l1"])
+            if kind == "B":
+                b.u(1, from_l0)                                     # collocated_from_l0_flag
+            if len(pl["l0" if from_l0 else "l1"]) > 1 or sw.get("col_ref_idx_always"):
+                b.ue(idx)                                           # collocated_ref_idx
         if (kind == "P" and seq.get("weighted_pred", 0)) or (kind == "B" and seq.get("weighted_bipred", 0)):
             wp = p.get("wp", dict(ld_y=0, ld_c=0))
             b.ue(wp["ld_y"]); b.se(wp["ld_c"] - wp["ld_y"])
@@ -353,7 +396,8 @@ def slice_header(b, seq, p, pl, first, addr, n_ctbs):
                         for (w_, o_) in e["c"]:
                             # 7-56: ChromaOffset = Clip3(-128, 127, 128 + delta - ((128 * ChromaWeight) >> ChromaLog2WeightDenom)): delta for the offset
                             b.se(w_ - (1 << wp["ld_c"])); b.se(o_ - 128 + ((128 * w_) >> wp["ld_c"]))
-        b.ue(4)                                                     # five_minus_max_num_merge_cand: one candidate, merge_idx is never coded
+        assert 1 <= p.get("max_merge", 1) <= 5
+        b.ue(5 - p.get("max_merge", 1))                             # five_minus_max_num_merge_cand (default: one candidate, merge_idx is never coded)
     b.se(p.get("qp", seq.get("init_qp", 26)) - seq.get("init_qp", 26))
     if seq.get("slice_chroma_qp_offsets", 0):
         b.se(p.get("cb_qp_offset", 0)); b.se(p.get("cr_qp_offset", 0))
@@ -369,6 +413,15 @@ def slice_header(b, seq, p, pl, first, addr, n_ctbs):
         b.u(1, 1)                                                   # slice_loop_filter_across_slices_enabled_flag
     b.u(1, 1)                                                       # byte_alignment()
     b.align_zero()
+
+
+def partitions(part, x, y, n):
+    """7.3.8.5: the prediction blocks (x, y, width, height) of a coding unit in partIdx order"""
+    h, q = n // 2, n // 4
+    return {"2Nx2N": [(x, y, n, n)], "2NxN": [(x, y, n, h), (x, y + h, n, h)], "Nx2N": [(x, y, h, n), (x + h, y, h, n)],
+            "NxN": [(x, y, h, h), (x + h, y, h, h), (x, y + h, h, h), (x + h, y + h, h, h)],
+            "2NxnU": [(x, y, n, q), (x, y + q, n, n - q)], "2NxnD": [(x, y, n, n - q), (x, y + n - q, n, q)],
+            "nLx2N": [(x, y, q, n), (x + q, y, n - q, n)], "nRx2N": [(x, y, n - q, n), (x + n - q, y, q, n)]}[part]
 
 
 def tu_leaves(log2cb, nxn, tu):
@@ -396,6 +449,7 @@ def scan_order(idx, blk):
 
 SCAN = [[scan_order(idx, 1 << lg) for lg in range(4)] for idx in range(3)]       # ScanOrder[log2BlockSize][scanIdx] as SCAN[scanIdx][log2BlockSize]
 SIG_CTX_4X4 = [0, 1, 4, 5, 2, 3, 4, 5, 6, 6, 8, 8, 7, 7, 8]                       # ctxIdxMap of 9.3.4.2.5, i = (yC << 2) + xC
+INTER_WRITER_SWITCHES = ("merge_idx_all_context", "amp_bypass_inverted", "col_ref_idx_always", "idc_first_bin_for_8x4")
 WRITER_SWITCHES = ("scan_ignored", "hidden_sign_written", "ctxset_not_raised", "rice_never_raised", "csbf_wrong_neighbours")
 
 
@@ -554,12 +608,16 @@ class _Picture:
         self.depth[area], self.skip[area], self.pred[area] = depth, t == "skip", {"pcm": 2, "intra": 1}.get(t, 0)
         self.mode[y >> 2:(y + n) >> 2, x >> 2:(x + n) >> 2] = 1
         if t == "skip":
-            assert kind != "I" and (self.step == 1 or self.all_skip)         # (MaxNumMergeCand 1: no merge_idx)
+            assert kind != "I"
+            if "merge" in u:
+                self.merge_idx(c, u["merge"])                       # prediction_unit() of a skipped unit: merge_idx alone
+            else:
+                assert (self.step == 1 or self.all_skip) and self.p.get("max_merge", 1) == 1     # (MaxNumMergeCand 1: no merge_idx)
             return
         if kind != "I":
             c.decision("pred_mode_flag", 0, 0 if t == "inter" else 1)
         if t == "inter":
-            self.inter_unit(c, x, y, log2, depth, u)
+            self.partitioned_unit(c, x, y, log2, depth, u) if "pus" in u else self.inter_unit(c, x, y, log2, depth, u)
             return
         assert t in ("pcm", "intra")
         nxn = t == "intra" and len(u["modes"]) == 4
@@ -615,6 +673,7 @@ class _Picture:
         tus = unit_tus(u, tu_leaves(log2, nxn, tu))
         small = log2 - tu == 2                                      # 4x4 luma blocks: the chroma of four of them is one block, coded with the fourth
         max_depth = self.g["tu_depth"] + nxn if intra else self.g["tu_depth_inter"]
+        inter_split = not intra and self.g["tu_depth_inter"] == 0 and u.get("part", "2Nx2N") != "2Nx2N"       # interSplitFlag (7.4.9.8), at depth 0
         bypass = bool(u.get("bypass", 0))
         cm = intra_chroma_mode(u.get("chroma", 4), u["modes"][0]) if intra else None
 
@@ -627,7 +686,7 @@ class _Picture:
             if lg <= self.g["max_tb"] and lg > 2 and d < max_depth and not (nxn and d == 0):
                 c.decision("split_transform_flag", 5 - lg, 1 if want else 0)
             else:
-                assert want == (lg > self.g["max_tb"] or (nxn and d == 0)), ("the script's depth is not what 7.4.9.8 infers", x0, y0, lg, d, tu)
+                assert want == (lg > self.g["max_tb"] or ((nxn or inter_split) and d == 0)), ("the script's depth is not what 7.4.9.8 infers", x0, y0, lg, d, tu)
             cbf = list(par)
             if lg > 2:
                 for k in (0, 1):
@@ -780,6 +839,96 @@ class _Picture:
                         rice = min(rice + 1, 4)
                         met("cRiceParam raised to", rice)
 
+    def merge_idx(self, c, idx):
+        """merge_idx (9.3.3: truncated Rice, cMax = MaxNumMergeCand - 1; the first bin with a context, the others bypass)"""
+        cmax = self.p.get("max_merge", 1) - 1
+        assert 0 <= idx <= cmax, (idx, cmax)
+        for i in range(min(idx + 1, cmax)):
+            bin_ = 1 if i < idx else 0
+            c.decision("merge_idx", 0, bin_) if i == 0 or self.sw.get("merge_idx_all_context") else c.bypass(bin_)
+
+    def part_mode(self, c, log2, part):
+        """9.3.3.7 for an inter unit.  Contexts 9.3.4.2: bin 0 -> 0, bin 1 -> 1, bin 2 -> 2 at the minimum size, else 3; bin 3 bypass"""
+        at_min, amp = log2 == self.g["min_cb"], self.seq.get("amp", 0)
+        if at_min:
+            bins = {"2Nx2N": "1", "2NxN": "01", "Nx2N": "00"} if log2 == 3 else {"2Nx2N": "1", "2NxN": "01", "Nx2N": "001", "NxN": "000"}
+        elif not amp:
+            bins = {"2Nx2N": "1", "2NxN": "01", "Nx2N": "00"}
+        else:
+            bins = {"2Nx2N": "1", "2NxN": "011", "2NxnU": "0100", "2NxnD": "0101", "Nx2N": "001", "nLx2N": "0000", "nRx2N": "0001"}
+        assert part in bins, (part, log2, "not a partition of this size")
+        for i, ch in enumerate(bins[part]):
+            if i == 3:
+                c.bypass(int(ch) ^ (1 if self.sw.get("amp_bypass_inverted") else 0))
+            else:
+                c.decision("part_mode", i if i < 2 or at_min else 3, int(ch))
+
+    def partitioned_unit(self, c, x, y, log2, depth, u):
+        """7.3.8.5 / 7.3.8.6 / 7.3.8.9 as scripted: part_mode, then per prediction unit merge_flag and merge_idx or inter_pred_idc, ref_idx_lX, mvd_lX and
+        mvp_lX_flag; the writer derives no motion"""
+        pl, kind, n = self.pl, self.kind, 1 << log2
+        assert kind != "I"
+        self.part_mode(c, log2, u["part"])
+        pbs = partitions(u["part"], x, y, n)
+        assert len(pbs) == len(u["pus"]), (u["part"], len(u["pus"]))
+        merged = False
+        for (xp, yp, w, h), pu in zip(pbs, u["pus"]):
+            merged = "merge" in pu
+            c.decision("merge_flag", 0, 1 if merged else 0)
+            if merged:
+                self.merge_idx(c, pu["merge"])
+                continue
+            l0, l1 = pu.get("l0"), pu.get("l1")
+            assert l0 or l1
+            if kind == "B":
+                assert not (l0 and l1 and w + h == 12), "8x4 and 4x8 blocks are never bi-predictive"
+                if w + h != 12 or self.sw.get("idc_first_bin_for_8x4"):
+                    c.decision("inter_pred_idc", depth, 1 if l0 and l1 else 0)
+                if not (l0 and l1):
+                    c.decision("inter_pred_idc", 4, 1 if l1 else 0)
+            else:
+                assert l0 and not l1
+            for name, q in (("l0", l0), ("l1", l1)):
+                if not q:
+                    continue
+                idx, mvd, flag = q
+                cnt = len(pl[name])
+                assert 0 <= idx < cnt
+                if cnt > 1:
+                    for i in range(min(idx + 1, cnt - 1)):
+                        bin_ = 1 if i < idx else 0
+                        c.decision("ref_idx", i, bin_) if i < 2 else c.bypass(bin_)
+                if name == "l1" and self.p.get("mvd_l1_zero", 0) and l0 and l1:
+                    assert tuple(mvd) == (0, 0), "mvd_l1_zero_flag: MvdL1 of a bi-predictive unit is not coded"
+                else:
+                    self.mvd(c, mvd)
+                c.decision("mvp_flag", 0, flag)
+        tus = unit_tus(u, tu_leaves(log2, False, u.get("tu", 0)))
+        root = 1 if any(t[k] for t in tus for k in (0, 1, 2)) else 0
+        if u["part"] == "2Nx2N" and merged:
+            assert root, "a 2Nx2N merge unit without residual is a skipped unit: rqt_root_cbf is not coded and inferred to be 1"
+        else:
+            c.decision("rqt_root_cbf", 0, root)
+        if root:
+            self.transform_tree(c, u, x, y, log2, False, False)
+
+    @staticmethod
+    def mvd(c, mvd):
+        """7.3.8.9"""
+        assert all(-32768 <= v <= 32767 for v in mvd)
+        g0 = [1 if v else 0 for v in mvd]
+        g1 = [1 if abs(v) > 1 else 0 for v in mvd]
+        c.decision("abs_mvd_greater0", 0, g0[0]); c.decision("abs_mvd_greater0", 0, g0[1])
+        if g0[0]:
+            c.decision("abs_mvd_greater1", 0, g1[0])
+        if g0[1]:
+            c.decision("abs_mvd_greater1", 0, g1[1])
+        for i in (0, 1):
+            if g0[i]:
+                if g1[i]:
+                    c.egk(abs(mvd[i]) - 2, 1)                       # abs_mvd_minus2: EG1
+                c.bypass(1 if mvd[i] < 0 else 0)                    # mvd_sign_flag
+
     def inter_unit(self, c, x, y, log2, depth, u):
         pl, kind = self.pl, self.kind
         assert kind != "I" and log2 == self.g["ctb"] and log2 <= 5 and (self.step == 1 or u is self.first_unit or u == self.first_unit), \
@@ -823,9 +972,9 @@ class _Picture:
 
 
 def write(seq, pics, stats=None, **sw):
-    """Annex-B bytes of the script.  The keyword arguments (WRITER_SWITCHES) make the residual syntax wrong on purpose; stats: a dict that
-    counts what residual_coding met."""
-    assert all(k in WRITER_SWITCHES for k in sw), sw
+    """Annex-B bytes of the script.  The keyword arguments (WRITER_SWITCHES, INTER_WRITER_SWITCHES) make the residual / the inter syntax wrong on
+    purpose; stats: a dict that counts what residual_coding met."""
+    assert all(k in WRITER_SWITCHES + INTER_WRITER_SWITCHES for k in sw), sw
     cw, ch = ctb_dims(seq)
     n_ctbs = cw * ch
     s = 1 << geometry(seq)["ctb"]
@@ -840,7 +989,8 @@ def write(seq, pics, stats=None, **sw):
         pic.step = step = {"ctb": 1, "row": cw, "pic": n_ctbs}[p.get("layout", "ctb" if kind != "I" else "pic")]
         for first in range(0, n_ctbs, step):
             b = Bits()
-            slice_header(b, seq, p, pl, first == 0, first, n_ctbs)
+            pic.pl = spl = slice_plan(pl, p, first // step)
+            slice_header(b, seq, p, spl, first == 0, first, n_ctbs, sw)
             c = Cabac(b, {"I": 0, "P": 1, "B": 2}[kind], p.get("qp", seq.get("init_qp", 26)))
             last = min(first + step, n_ctbs) - 1
             pic.slice_of[first:last + 1] = first

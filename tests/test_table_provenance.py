@@ -377,6 +377,20 @@ def test_hevc_scans_significance_patterns_and_default_lists_against_separately_t
         assert c_array(path, name.replace("scaling_default", "level_scale")) == HEVC_LEVEL_SCALE, os.path.basename(path)
 
 
+HEVC_COMBINED_PAIRS = [(0, 1), (1, 0), (0, 2), (2, 0), (1, 2), (2, 1), (0, 3), (3, 0), (1, 3), (3, 1), (2, 3), (3, 2)]     # Table 8-7 as (l0CandIdx, l1CandIdx) by combIdx
+
+
+def test_hevc_combined_candidate_order_against_a_separately_typed_copy():
+    """Table 8-7 typed as pairs here, as two rows in tests/hevc_inter_ref.py and as two arrays in each of the three programs: every unordered pair
+    {a, b} of the first four candidates appears as (a, b) and then (b, a), pairs in the order 01 02 12 03 13 23"""
+    import hevc_inter_ref as hr
+    assert list(zip(hr.COMB_L0, hr.COMB_L1)) == HEVC_COMBINED_PAIRS
+    assert [p for b in (1, 2, 3) for a in range(b) for p in ((a, b), (b, a))] == HEVC_COMBINED_PAIRS
+    for path, n0, n1 in ((os.path.join(ROOT, "jmcodec_amd", "csrc", "hevc_slice.cpp"), "a0", "a1"), (os.path.join(ROOT, "oracle", "orc_hevc_ctu.c"), "i0", "i1"),
+                         (os.path.join(ROOT, "tools", "hevcgen.c"), "a0", "a1")):
+        assert list(zip(c_array(path, n0), c_array(path, n1))) == HEVC_COMBINED_PAIRS, os.path.basename(path)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------
 def table_digests():
     """{table: sha256 of its comma-joined integers} for every table of the product headers, with the clause each restates."""
