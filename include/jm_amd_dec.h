@@ -152,6 +152,10 @@ int  jm_amddec_scale_rect_device(const void *d_src, int pitch, int chroma_offset
  *   "deinterlace_rate": 0 one frame per picture; 1 field rate -- every frame chosen for D leaves as TWO consecutive output frames, D with the
  *     field "deinterlace_field" picks kept, then D with the other field kept (a lone field: one frame).  No effect while "deinterlace" is 0.  Each
  *     decode / poll call still hands out one frame; the second of a pair is the next one.
+ *   "deinterlace_temporal": 0 / 1 -- with "deinterlace" 2 a frame chosen for D is deinterlaced against the previous display frame (the function D3 of
+ *     a missing sample is interpolated where one of the nine samples around it changed by more than T, and woven elsewhere) when
+ *     that frame was chosen for D too, neither is a lone field and both belong to one activation; else as mode 2.  H.264 and HEVC; an MJPEG handle
+ *     with the option set fails init.  Stats: "deint_temporal_frames", "display_temporal:<n>" (output frame n: 0 / 1).
  * Stats: "deint_frames" (output frames that went through D), "field_rate_pairs", "interlaced_sequence" (0 / 1, the active SPS), "display_field:<n>"
  * (output frame n: 0 not deinterlaced, 1 top kept, 2 bottom kept), "display_picture:<n>" (the display picture, index of "display_poc:<k>", that output
  * frame n shows), "out_fps_num" / "out_fps_den" (fps_num / fps_den, the numerator doubled while a field-rate handle deinterlaces the active sequence),
@@ -167,6 +171,12 @@ int  jm_amddec_deinterlace_device(const void *d_src, int pitch, int chroma_offse
  *     addition the two destinations must not overlap each other and neither may overlap the source (-1). */
 int  jm_amddec_deinterlace2_device(const void *d_src, int pitch, int chroma_offset, int w, int h, int mode, int first_field, int threshold,
                                    void *d_dst_first, void *d_dst_second, int dst_pitch, int dst_chroma_offset, void *stream);
+/*   jm_amddec_deinterlace3_device: the motion-adaptive deinterlacer D3 (option "deinterlace_temporal", k_deint3) -- d_src against d_prev, the surface
+ *     of the previous display frame (same w x h, a pitch and chroma offset of its own): d_dst_first gets D3 with first_field (1 top / 2 bottom) kept
+ *     and d_dst_second, unless NULL, D3 with the other field kept.  Arguments and returns as jm_amddec_deinterlace2_device (no mode: D3 is one
+ *     function); -1 also for a NULL d_prev and for a destination that overlaps either source. */
+int  jm_amddec_deinterlace3_device(const void *d_src, int pitch, int chroma_offset, const void *d_prev, int prev_pitch, int prev_chroma_offset, int w, int h,
+                                   int first_field, int threshold, void *d_dst_first, void *d_dst_second, int dst_pitch, int dst_chroma_offset, void *stream);
 /* RGB output (INTEGRATION.md "RGB output" defines the conversion C exactly).  A handle with an RGB spec hands out every display frame as
  * C(R_G(F)): three samples per pixel of the target size, planar (CHW) or interleaved (HWC), R,G,B or B,G,R order, u8 / f32 / f16 / bf16
  * (f16 and bf16 as their 16-bit patterns), frame bytes 3 * w * h * sizeof(sample).  matrix 0 / range 0 = from the stream's VUI (matrix: the VUI

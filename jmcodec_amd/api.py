@@ -69,6 +69,8 @@ def lib():
     L.jm_amddec_fit_rect.argtypes = [C.c_int] * 7 + [ip]
     L.jm_amddec_deinterlace_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
     L.jm_amddec_deinterlace2_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp]
+    if hasattr(L, "jm_amddec_deinterlace3_device"):      # (a library of before the call, loaded through JM_AMD_DEC_LIB by the bench tools, lacks it)
+        L.jm_amddec_deinterlace3_device.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp]
     L.jm_amddec_feed_annexb.argtypes = [cp, C.c_long, C.c_int, C.POINTER(C.c_ubyte), C.c_int, vp]
     L.jm_amddec_feed_annexb.restype = C.c_long
     L.jm_amddec_poll_frame.argtypes = [ip, vp]
@@ -187,6 +189,17 @@ def deinterlace2_device(src, pitch, chroma_offset, width, height, mode, first_fi
     dp = width if dst_pitch is None else dst_pitch
     return lib().jm_amddec_deinterlace2_device(src, pitch, chroma_offset, width, height, mode, first_field, threshold, dst_first, dst_second, dp,
                                                dp * height if dst_chroma_offset is None else dst_chroma_offset, stream)
+
+
+def deinterlace3_device(src, pitch, chroma_offset, prev, prev_pitch, prev_chroma_offset, width, height, first_field, dst_first, dst_second=None,
+                        dst_pitch=None, dst_chroma_offset=None, threshold=0, stream=None):
+    """jm_amddec_deinterlace3_device: the motion-adaptive deinterlacer D3 (INTEGRATION.md "Deinterlaced output") on one pitch-linear NV12 surface
+    against the surface of the previous display frame -- dst_first gets D3 with first_field (1 top / 2 bottom) kept, dst_second (optional) D3 with
+    the other field kept; both in deinterlace_device's destination layout.  No destination may overlap a source or the other destination.
+    Returns 0 or < 0."""
+    dp = width if dst_pitch is None else dst_pitch
+    return lib().jm_amddec_deinterlace3_device(src, pitch, chroma_offset, prev, prev_pitch, prev_chroma_offset, width, height, first_field, threshold,
+                                               dst_first, dst_second, dp, dp * height if dst_chroma_offset is None else dst_chroma_offset, stream)
 
 
 def scale_device(src, pitch, chroma_offset, width, height, crop, target, out_fmt, dst, lone_field=0, stream=None):

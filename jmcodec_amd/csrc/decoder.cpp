@@ -169,6 +169,10 @@ int Decoder::set_option(const char *key, long long v) {
         if (inited_ || v < 0 || v > 1) return -1;
         deint_rate_ = (int)v;
     }
+    else if (k == "deinterlace_temporal") {  // 1: motion-adaptive -- D reads the previous display frame (acts while deinterlace is 2)
+        if (inited_ || v < 0 || v > 1) return -1;
+        deint_temporal_ = (int)v;
+    }
     else if (k == "verify_hash") {           // HEVC: check the decoded picture hash SEI (CRC, checksum) on the device; 2: a mismatch fails the handle
         if (inited_ || v < 0 || v > 2) return -1;
         verify_hash_ = (int)v;
@@ -218,6 +222,7 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "rgb_frames") return stat_rgb_;
     // deinterlaced output: frames that went through D, whether the active SPS allows field pictures, and (below) display_field:<n>
     if (k == "deint_frames") return stat_deint_;
+    if (k == "deint_temporal_frames") return stat_temporal_;    // output frames whose D read the previous display frame (a pair counts 2)
     if (k == "field_rate_pairs") return stat_pairs_;         // display pictures handed out as two frames (option deinterlace_rate)
     if (k == "interlaced_sequence") return codec_ == 0 && seq_active_ && !seq_.frame_mbs_only ? 1 : 0;
     if (k == "out_frame_bytes") { std::lock_guard<std::mutex> lk(const_cast<std::mutex &>(mtx_));
@@ -365,6 +370,8 @@ long long Decoder::get_stat(const char *key) const {
     }
     if (k.rfind("display_field:", 0) == 0) { size_t i = (size_t)atoll(k.c_str() + 14);
         return i < display_fields_.size() ? display_fields_[i] : (i < display_pocs_.size() ? 0 : -1); }
+    if (k.rfind("display_temporal:", 0) == 0) { size_t i = (size_t)atoll(k.c_str() + 17);
+        return i < display_temporal_.size() ? display_temporal_[i] : (i < display_pocs_.size() ? 0 : -1); }
     // the display picture (index of display_poc) that output frame n shows: the identity unless the handle is at field rate
     if (k.rfind("display_picture:", 0) == 0) { size_t i = (size_t)atoll(k.c_str() + 16);
         if (field_rate()) return i < display_pics_.size() ? (long long)display_pics_[i] : -1;
@@ -378,6 +385,8 @@ long long Decoder::get_stat(const char *key) const {
 int Decoder::init(int codec_type, int out_fmt, const uint8_t *extra, int len) {
     codec_ = codec_type; out_fmt_ = out_fmt ? 1 : 0;
     if (codec_type != 0 && codec_type != 1 && codec_type != 2) { fail("only codec_type 0 (H.264), 1 (HEVC) and 2 (MJPEG) are implemented"); return -1; }
+    if (codec_type == 2 && deint_temporal_) { fail("option deinterlace_temporal is not available for MJPEG (codec_type 2): its surfaces are dealt round robin, "
+        "a displayed one cannot be kept for the next picture"); return -1; }
     if (rgb_chroma_ && !rgb_) { fail("option rgb_chroma needs RGB output: set an RGB spec (jm_amddec_set_rgb) before init"); return -1; }
     if (getenv("JM_AMD_DEC_SYNC")) sync_mode_ = true;
     if (const char *js = getenv("JM_AMD_DEC_JOB_SLOTS")) { n_jobs_ = std::max(8, std::min(atoi(js), kMaxJobSlots)); n_jobs_set_ = true; }
@@ -979,8 +988,9 @@ bool Decoder::activate(const SeqParams &sps) {
         } else free_job_buffers();
     }
     mb_w_ = sps.mb_w; mb_h_ = sps.mb_h; disp_w_ = sps.disp_w(); disp_h_ = sps.disp_h();
-    n_surf_ = 18;                                  // 16 (max DPB) + current + one spare; also covers later SPSs with a larger DPB
+    n_surf_ = 18 + (temporal() ? 1 : 0);           // 16 (max DPB) + current + one spare (+ the held one); also covers later SPSs with a larger DPB
     for (auto &d : dpb_) d = DpbPic();
+    hold_ = -1;                                    // (a new activation: its first display frame has no previous one)
     if (!gpu_alloc_sequence()) return false;
     seq_active_ = true;
     if (!timer_started_) { t0_ = std::chrono::steady_clock::now(); timer_started_ = true; }   // nv_dec.cpp:537
@@ -1071,7 +1081,7 @@ void Decoder::infer_frame(int fn) {
     int slot = -1;
     for (;;) {
         for (int i = 0; i < n_surf_; i++) if (dpb_[i].in_use && i != pending_first_ && !dpb_[i].ref && !dpb_[i].wait_output) dpb_[i].in_use = false;
-        for (int k = 1; k <= n_surf_ && slot < 0; k++) { const int i = (last_surf_ + k) % n_surf_; if (!dpb_[i].in_use) slot = i; }
+        for (int k = 1; k <= n_surf_ && slot < 0; k++) { const int i = (last_surf_ + k) % n_surf_; if (slot_free(i)) slot = i; }
         if (slot >= 0) break;
         int best = -1;                                      // C.4.5.3: no empty frame buffer -> the picture first in output order goes
         for (int i = 0; i < n_surf_; i++) if (dpb_[i].wait_output && !dpb_[i].waiting_second && (best < 0 || dpb_[i].poc < dpb_[best].poc)) best = i;
@@ -1122,26 +1132,31 @@ bool Decoder::start_picture(const SliceHeader &sh, const SeqParams &sps, const P
     else {
         // Surface for the new picture.  A surface that was displayed after picture n is still being packed out while picture
         // n+1 decodes (the engine overlaps pack-out with the next batch), so prefer one that has "cooled" for a picture.
-        int warm = -1;
         // Round robin over the free surfaces (starting behind the one chosen last), so that a surface is reused as LATE as possible: the engine
         // runs consecutive pictures of a stream in one launch only while none of them decodes into a surface an earlier one still reads or displays.
-        for (int k = 1; k <= n_surf_; k++) { const int i = (last_surf_ + k) % n_surf_; if (!dpb_[i].in_use) { if (decode_count_ >= dpb_[i].out_at + 2) {
-            slot = i;
-            break; } if (warm < 0) warm = i; } }
-        if (slot < 0 && warm >= 0) { slot = warm; wait_pack = true; }
+        auto find_free = [&] {
+            int warm = -1;
+            for (int k = 1; k <= n_surf_; k++) { const int i = (last_surf_ + k) % n_surf_; if (slot_free(i)) { if (decode_count_ >= dpb_[i].out_at + 2) {
+                slot = i;
+                break; } if (warm < 0) warm = i; } }
+            if (slot < 0 && warm >= 0) { slot = warm; wait_pack = true; }
+        };
+        find_free();
         while (slot < 0) {
             // C.4.5.3: no empty frame buffer -> the pictures first in output order go until one is free (frames inferred from gaps in frame_num take buffers
             // without passing through the output process, so this happens in conforming streams too)
             int best = -1;
             for (int i = 0; i < n_surf_; i++) if (dpb_[i].wait_output && !dpb_[i].waiting_second && (best < 0 || dpb_[i].poc < dpb_[best].poc)) best = i;
             if (best < 0) {                  // nothing left to display, every buffer a reference: non-conformant stream -- the oldest reference goes
-                for (int i = 0; i < n_surf_; i++) if (best < 0 || dpb_[i].frame_num_wrap < dpb_[best].frame_num_wrap) best = i;
+                for (int i = 0; i < n_surf_; i++) if (i != hold_ && (best < 0 || dpb_[i].frame_num_wrap < dpb_[best].frame_num_wrap)) best = i;
                 dpb_[best].set_ref(0); dpb_[best].in_use = false; slot = best; stat_errors_++;
                 break;
             }
             carry_out_.push_back(display_entry(best)); display_pocs_.push_back(dpb_[best].poc); dpb_[best].wait_output = false;
             dpb_[best].out_at = decode_count_ - 1;
-            if (!dpb_[best].ref) { dpb_[best].in_use = false; slot = best; wait_pack = true; }
+            if (!dpb_[best].ref) { dpb_[best].in_use = false;
+                if (best != hold_) { slot = best; wait_pack = true; }
+                else find_free(); }            // (the frame just displayed is held for its successor: the surface held until now has come free instead)
         }
         last_surf_ = slot;
         DpbPic &c = dpb_[slot];
@@ -1795,7 +1810,7 @@ void Decoder::submit_ready() {
 // has one count only (HEVC) -- unless the option names one; a frame of which one field was decoded keeps that one.
 int Decoder::display_entry(int slot) {
     const DpbPic &d = dpb_[slot];
-    int field = 0, both = 0;
+    int field = 0, both = 0, prev = -1;
     if (deint_mode_) {
         if (d.deint) field = d.lone ? d.lone : (deint_field_ ? deint_field_ : (codec_ == 0 && d.fpoc[1] < d.fpoc[0] ? 2 : 1));
         display_fields_.push_back((uint8_t)field);
@@ -1803,22 +1818,33 @@ int Decoder::display_entry(int slot) {
         both = deint_rate_ && field && !d.lone;
         if (both) display_fields_.push_back((uint8_t)(3 - field));
         if (deint_rate_) display_pics_.insert(display_pics_.end(), both ? 2 : 1, display_count_);
+        if (temporal()) {
+            // motion-adaptive: this frame reads the held surface -- the display picture before it, chosen for D, whole, of this activation -- when it is
+            // such a frame itself, and is the one held from now on (a lone field, an inferred frame or a frame not chosen for D breaks the chain).
+            // The surface held until now comes free like one displayed now: it cools for a picture (its last reader is this frame's pack-out).
+            const bool chain = field && !d.lone && !d.non_existing;
+            if (chain && hold_ >= 0 && hold_ != slot) prev = hold_;
+            if (hold_ >= 0 && hold_ != slot) dpb_[hold_].out_at = decode_count_ - 1;
+            hold_ = chain ? slot : -1;
+        }
+        display_temporal_.insert(display_temporal_.end(), both ? 2 : 1, (uint8_t)(prev >= 0));
     }
     display_count_++;
-    return slot | d.lone << 8 | d.color << 16 | field << 24 | both << 26;
+    return (int)((unsigned)(slot | d.lone << 8 | d.color << 16 | field << 24 | both << 26) | (unsigned)(prev + 1) << 27);
 }
 
 // a display frame leaves the DPB: reserve an output slot (display order) and describe the pack-out for the engine
 void Decoder::enqueue_output(int entry, OutSide &out) {
     // display_entry: bits 8..15 = the one field that was decoded, if only one was; bits 16..23 = the matrix and range of the picture's sequence;
     // bits 24.. = the field the deinterlacer keeps (0: the frame is not deinterlaced)
-    const int slot = entry & 255, color = (entry >> 16) & 255, field = (entry >> 24) & 3, both = (entry >> 26) & 1;
+    const int slot = entry & 255, color = (entry >> 16) & 255, field = (entry >> 24) & 3, both = (entry >> 26) & 1, prev = (int)(((unsigned)entry >> 27) & 31) - 1;
     int lone = (entry >> 8) & 255;
     // (a field-rate pair: two slots in display order, the frame that keeps `field` first)
     OutSlot *o, *o2 = nullptr;
     { std::lock_guard<std::mutex> lk(mtx_); o = alloc_out_slot(); ready_.push_back(o); num_frames_++;   // nv_dec.cpp:48 num_frames++
       if (both) { o2 = alloc_out_slot(); ready_.push_back(o2); num_frames_++; } }
     if (both) stat_pairs_++;
+    if (prev >= 0) stat_temporal_ += both ? 2 : 1;
     if (placed_ && !failed_) stat_placed_ += both ? 2 : 1;
     if (parse_only_ || failed_) { std::lock_guard<std::mutex> lk(mtx_); o->ready = true; done_unfetched_++; if (field) stat_deint_++;
         if (both) { o2->ready = true; done_unfetched_++; stat_deint_++; } return; }
@@ -1836,6 +1862,8 @@ void Decoder::enqueue_output(int entry, OutSide &out) {
         const int t = deint_thr_ ? deint_thr_ : 10;
         DeintReq r{DeintJob{surf_[slot], dst_of(o), pitch_, chroma_off_, disp_w_, disp_h_, disp_w_, disp_w_ * disp_h_, out_fmt_, lone ? 1 : deint_mode_,
                             field - 1, 4 * t * t, both ? dst_of(o2) : nullptr}, 0, 0, 0};
+        // (motion-adaptive: k_deint3 reads the surface of the display frame before this one as well)
+        if (prev >= 0) { r.job.prev = surf_[prev]; r.job.prev_pitch = pitch_; r.job.prev_chroma_offset = chroma_off_; r.job.t = t; }
         if (rgb_ || scaled_) {
             r.feeds = rgb_ ? 2 : 1; r.index = (int)(rgb_ ? out.rgb.size() : out.scale.size()); r.index2 = both ? r.index + 1 : 0;
             r.job.dst = r.job.dst2 = nullptr; r.job.dst_pitch = pitch_; r.job.dst_chroma_offset = src_chroma = pitch_ * disp_h_; r.job.out_fmt = 0;
@@ -1873,7 +1901,9 @@ void Decoder::submit_task(PicTask *t) {
     EnginePic ep;
     ep.dec = this; ep.has_picture = t->has_picture && !parse_only_ && !failed_; ep.job_slot = t->job_slot;
     ep.mb_w = mb_w_; ep.mb_h = mb_h_; ep.disp_w = disp_w_; ep.disp_h = disp_h_; ep.wait_prev_pack = t->wait_prev_pack;
-    for (int s : t->out_before) { enqueue_output(s, ep.out[kBefore]); ep.out_mask |= 1u << (s & 255); }
+    // (a frame whose D reads the previous display frame reads that surface too: bits 27.. of the entry)
+    auto read_mask = [](int s) { const unsigned prev = ((unsigned)s >> 27) & 31; return 1u << (s & 255) | (prev ? 1u << (prev - 1) : 0u); };
+    for (int s : t->out_before) { enqueue_output(s, ep.out[kBefore]); ep.out_mask |= read_mask(s); }
     memset(&ep.pp, 0, sizeof ep.pp);
     if (ep.has_picture && t->hevc) hevc_fill_engine_pic(t, ep);
     else if (t->hevc && (t->hevc->hash.type > 0 || (t->hevc->hash.type == 0 && verify_md5_)) && !parse_only_) stat_hash_unchecked_++;      // (a failed handle's picture is not decoded: nothing to compare)
@@ -1940,7 +1970,7 @@ void Decoder::submit_task(PicTask *t) {
     // (an RGB handle reads the crop rectangle too, and writes its RGB frame)
     ep.alg_bytes[3] = (scaled_ || rgb_ ? (long long)crop_[2] * crop_[3] * 3 / 2 : (long long)surf_bytes_) + (long long)frame_bytes_;
     ep.alg_bytes[4] = 2ll * disp_w_ * disp_h_ * 3 / 2;       // (k_deint reads the display area and writes as much)
-    for (int s : t->out_after) { enqueue_output(s, ep.out[kAfter]); ep.out_mask |= 1u << (s & 255); }
+    for (int s : t->out_after) { enqueue_output(s, ep.out[kAfter]); ep.out_mask |= read_mask(s); }
     stat_submit_ns_ += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - st0).count();
     if (parse_only_ || failed_ || !engine_) { on_engine_done(ep); return; }
     engine_->submit(std::move(ep));
@@ -2078,7 +2108,7 @@ int Decoder::decode(const uint8_t *buf, int len, int *got_frame) {
                 snprintf(fmt, sizeof fmt, "%s %s %s%s", rgb_spec_.bgr ? "BGR" : "RGB", rgb_spec_.planar ? "planar" : "interleaved", dt[rgb_spec_.dtype & 3], loc); }
             else snprintf(fmt, sizeof fmt, "%s", out_fmt_ == 0 ? "NV12" : "YV12");
             char deint[96] = "";                             // (only with option deinterlace: the text is the reference's otherwise)
-            if (deint_mode_) snprintf(deint, sizeof deint, "Deinterlace:\t%s, %s%s, %lld frames\n", deint_mode_ == 1 ? "bob" : "comb-adaptive",
+            if (deint_mode_) snprintf(deint, sizeof deint, "Deinterlace:\t%s, %s%s, %lld frames\n", deint_mode_ == 1 ? "bob" : temporal() ? "comb-adaptive + temporal" : "comb-adaptive",
                 deint_when_ ? "always" : "auto", deint_rate_ ? ", field rate" : "", (long long)stat_deint_);
             char place[64] = "";                             // (only when frames are placed)
             if (placed_) snprintf(place, sizeof place, "Placement:\t%d,%d %dx%d\n", place_[0], place_[1], place_[2], place_[3]);

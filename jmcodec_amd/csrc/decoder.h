@@ -39,7 +39,8 @@ constexpr int kJobSlotsSmall = 40;
 constexpr int kJpegJobSlots = 16, kJpegSurfaces = 18;
 
 struct DpbPic {                                // one frame store (C.4.5): a frame, or the one or two field pictures of a frame
-    bool in_use = false;
+    bool in_use = false;                       // NOT the test for a free surface: a surface may be free of a picture and still held for the next display
+                                               // frame (Decoder::hold_) -- every place that hands out a surface asks Decoder::slot_free
     // marking.  fmark[]: each field (top, bottom): 0 not a reference, 1 short-term, 2 long-term.  ref is derived (sync_ref): 1 / 2 = BOTH fields so,
     // i.e. a reference FRAME in the sense of 8.2.4.2.1; 3 = some field is a reference (field pictures can use it, and the store stays occupied)
     int ref = 0; int fmark[2] = {0, 0};
@@ -213,7 +214,8 @@ private:
     void mark_current_field(const SliceHeader &sh);
     void store_done(int slot, std::vector<int> &out);
     // a display frame as the engine gets it: slot | lone field << 8 | colour << 16 | kept field << 24 (DpbPic::lone, DpbPic::color, the
-    // deinterlacer's decision: 0 = not deinterlaced, 1 top, 2 bottom), taken when the frame is queued
+    // deinterlacer's decision: 0 = not deinterlaced, 1 top, 2 bottom), taken when the frame is queued; bit 26: a field-rate pair; bits 27..31: 1 + the
+    // slot of the previous display frame when D reads it (option deinterlace_temporal), 0 = none
     int  display_entry(int slot);
     void infer_frame(int frame_num);
     void bump_after_current(std::vector<int> &out);
@@ -303,6 +305,14 @@ private:
     int deint_mode_ = 0, deint_when_ = 0, deint_field_ = 0, deint_thr_ = 0;      // (deint_thr_: T, 0 = 10)
     int deint_rate_ = 0;                       // option deinterlace_rate: 1 = field rate, a frame chosen for D leaves as D_f(F), D_f'(F) (k_deint2)
     std::atomic<long long> stat_deint_{0}, stat_pairs_{0};
+    // motion-adaptive deinterlacing (option deinterlace_temporal, acts while deinterlace is 2): a frame chosen for D leaves as D3(F, F') -- k_deint3 -- when
+    // the display picture before it, F', was chosen for D too, neither is a lone field and both belong to this activation.  F' is kept by holding its
+    // SURFACE: hold_ is the slot of the last display picture chosen for D; it is not handed to a new picture (slot_free) until the next display picture
+    // has been queued (display_entry), whose task names it in its out_mask -- the engine orders every writer of a surface behind those readers.
+    int deint_temporal_ = 0, hold_ = -1;
+    bool temporal() const { return deint_temporal_ && deint_mode_ == 2; }
+    bool slot_free(int i) const { return !dpb_[i].in_use && i != hold_; }
+    std::atomic<long long> stat_temporal_{0};
 
     // DPB / picture state (front end only)
     DpbPic dpb_[kMaxSurfaces];
@@ -387,6 +397,7 @@ private:
     struct HashSeen { int poc; HevcPicHash h; };
     std::vector<HashSeen> hash_seen_;          // diagnostic (stats hash_sei_*): the hash messages in decode order, the first 65536
     std::vector<uint8_t> display_fields_;      // per output frame: the kept field (display_entry); only filled with option deinterlace
+    std::vector<uint8_t> display_temporal_;    // per output frame: 1 = its D read the previous display frame (display_entry); only filled with option deinterlace
     std::vector<uint32_t> display_pics_;       // per output frame: the display picture it shows (display_entry); only filled at field rate
     uint32_t display_count_ = 0;               // display pictures queued so far (display_entry calls)
     // MJPEG state (front end only unless noted)

@@ -755,7 +755,7 @@ void Engine::run_side(Batch &b, int side, hipStream_t s, bool in_launch) {
     const OutTables &t = b.out;
     auto mark = [&](int i) { if (in_launch && profile_) hipEventRecord(b.pev[i], s); };
     mark(side ? 5 : 0);
-    if (t.deint.n[side]) { mark(14 + 2 * side); (t.pairs[side] ? launch_deint2 : launch_deint)(t.deint.d(side), t.deint.n[side], t.d_items, s); mark(15 + 2 * side); b.pmask |= side ? 512 : 256; }
+    if (t.deint.n[side]) { mark(14 + 2 * side); (t.temporal[side] ? launch_deint3 : t.pairs[side] ? launch_deint2 : launch_deint)(t.deint.d(side), t.deint.n[side], t.d_items, s); mark(15 + 2 * side); b.pmask |= side ? 512 : 256; }
     if (t.plain.n[side]) launch_packout(t.plain.d(side), t.plain.n[side], t.max_w, t.max_h, s);
     if (t.scale.n[side]) launch_scale_pack(t.scale.d(side), t.scale.n[side], t.s_tiles, s);
     if (t.rgb.n[side]) { mark(10 + 2 * side); launch_rgb_pack(t.rgb.d(side), t.rgb.n[side], t.r_tiles[0], t.r_tiles[1], 0, s);

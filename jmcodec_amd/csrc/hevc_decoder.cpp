@@ -107,8 +107,9 @@ bool Decoder::hevc_activate(const HevcSps &sps) {
         } else for (auto &j : jobs_) { free(j.host); j = JobSlot(); }
     }
     mb_w_ = mbw; mb_h_ = mbh; disp_w_ = sps.disp_w(); disp_h_ = sps.disp_h();
-    n_surf_ = 18; extra_surf_ = 0;                 // 16 (max DPB) + current + one spare (the pre-SAO work surfaces are separate: hevc_work_)
+    n_surf_ = 18 + (temporal() ? 1 : 0); extra_surf_ = 0;      // 16 (max DPB) + current + one spare (+ the held one, decoder.h) (the pre-SAO work surfaces are separate: hevc_work_)
     for (auto &d : dpb_) d = DpbPic();
+    hold_ = -1;
     seq_.profile_idc = 100;                        // sizes the shared job buffers (gpu_alloc_sequence)
     if (!gpu_alloc_sequence()) return false;
     seq_active_ = true;
@@ -170,13 +171,14 @@ bool Decoder::hevc_start_picture(const HevcSliceHeader &sh, int nal_type, int ti
     if (!(irap && no_rasl)) hevc_bump(carry_out_, false, true);            // C.5.2.2 "bumping" before the current picture is stored
     // surface for the new picture (cooling rule as for H.264: a surface displayed after picture n is still being packed out during n + 1)
     int slot = -1, warm = -1; bool wait_pack = false;
-    for (int i = 0; i < n_surf_; i++) if (!dpb_[i].in_use) { if (decode_count_ >= dpb_[i].out_at + 2) { slot = i; break; } if (warm < 0) warm = i; }
+    for (int i = 0; i < n_surf_; i++) if (slot_free(i)) { if (decode_count_ >= dpb_[i].out_at + 2) { slot = i; break; } if (warm < 0) warm = i; }
     if (slot < 0 && warm >= 0) { slot = warm; wait_pack = true; }
     if (slot < 0) {                                // non-conformant stream: make room
         int best = -1;
         for (int i = 0; i < n_surf_; i++) if (dpb_[i].wait_output && (best < 0 || dpb_[i].poc < dpb_[best].poc)) best = i;
         if (best >= 0) { carry_out_.push_back(display_entry(best)); display_pocs_.push_back(dpb_[best].poc); dpb_[best].wait_output = false; }
-        else { for (int i = 0; i < n_surf_; i++) if (best < 0 || dpb_[i].poc < dpb_[best].poc) best = i; }
+        else { for (int i = 0; i < n_surf_; i++) if (i != hold_ && (best < 0 || dpb_[i].poc < dpb_[best].poc)) best = i; }
+        if (best == hold_) hold_ = -1;             // (the frame just displayed is decoded over: its successor has no previous frame)
         dpb_[best].ref = 0; dpb_[best].in_use = false; slot = best; stat_errors_++;
     }
     cur_ = slot;
@@ -206,7 +208,7 @@ bool Decoder::hevc_build_refs(const HevcSliceHeader &sh, HevcSliceRefs &rf) {
     auto find_st = [&](int want) { for (int k = 0; k < n_surf_; k++) if (k != cur_ && dpb_[k].in_use && dpb_[k].ref == 1 && dpb_[k].poc == want) return k;
         return -1; };
     auto missing = [&](int want, int ref) {       // 8.3.3: a grey stand-in (conformant streams never get here after the first IRAP)
-        for (int k = 0; k < n_surf_; k++) if (k != cur_ && !dpb_[k].in_use) {
+        for (int k = 0; k < n_surf_; k++) if (k != cur_ && slot_free(k)) {
             dpb_[k] = DpbPic(); dpb_[k].in_use = true; dpb_[k].ref = ref; dpb_[k].poc = want; dpb_[k].decode_idx = -1;
             stat_errors_++;
             return k;

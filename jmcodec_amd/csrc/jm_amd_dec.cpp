@@ -207,6 +207,27 @@ __attribute__((visibility("default"))) int jm_amddec_deinterlace2_device(const v
     return run_one_job(job, stream, [&](const jmamd::DeintJob *d_job, hipStream_t st) { jmamd::launch_deint2(d_job, 1, jmamd::deint2_items(w, hgt), st); });
 }
 
+// the motion-adaptive deinterlacer D3 on one surface and the surface of the previous frame (k_deint3): first_field kept, and -- when d_dst_second is
+// given -- the other field kept as well
+__attribute__((visibility("default"))) int jm_amddec_deinterlace3_device(const void *src, int pitch, int chroma_offset, const void *prev, int prev_pitch,
+    int prev_chroma_offset, int w, int hgt, int first_field, int threshold, void *dst_first, void *dst_second, int dst_pitch, int dst_chroma_offset, void *stream) {
+    if (!src || !prev || !dst_first || w <= 0 || hgt < 4 || ((w | hgt) & 1) || pitch < w || prev_pitch < w || dst_pitch < w) return -1;
+    if ((first_field != 1 && first_field != 2) || threshold < 0 || threshold > 255) return -1;
+    if (chroma_offset < 0 || prev_chroma_offset < 0 || dst_chroma_offset < 0) return -1;
+    {   // no destination may overlap either source, nor the other destination
+        const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)chroma_offset + (size_t)pitch * (hgt / 2 - 1) + w;
+        const uintptr_t q0 = (uintptr_t)prev, q1 = q0 + (size_t)prev_chroma_offset + (size_t)prev_pitch * (hgt / 2 - 1) + w;
+        const size_t dn = (size_t)dst_chroma_offset + (size_t)dst_pitch * (hgt / 2 - 1) + w;
+        const uintptr_t a0 = (uintptr_t)dst_first, a1 = a0 + dn, b0 = (uintptr_t)dst_second, b1 = b0 + dn;
+        if ((a0 < s1 && s0 < a1) || (a0 < q1 && q0 < a1)) return -1;
+        if (dst_second && ((a0 < b1 && b0 < a1) || (b0 < s1 && s0 < b1) || (b0 < q1 && q0 < b1))) return -1;
+    }
+    const int t = threshold ? threshold : 10;
+    jmamd::DeintJob job{static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst_first), pitch, chroma_offset, w, hgt, dst_pitch, dst_chroma_offset, 0, 2,
+        first_field - 1, 4 * t * t, static_cast<uint8_t *>(dst_second), static_cast<const uint8_t *>(prev), prev_pitch, prev_chroma_offset, t};
+    return run_one_job(job, stream, [&](const jmamd::DeintJob *d_job, hipStream_t st) { jmamd::launch_deint3(d_job, 1, jmamd::deint2_items(w, hgt), st); });
+}
+
 // the two parallel picture hashes of one surface: the kernel the decoder runs behind a picture with a hash SEI, on a one-picture batch
 __attribute__((visibility("default"))) int jm_amddec_picture_hash_device(const void *src, int pitch, int chroma_offset, int w, int hgt, unsigned crc[3],
     unsigned checksum[3], void *stream) {

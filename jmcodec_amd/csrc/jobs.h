@@ -186,6 +186,10 @@ struct DeintJob {                 // one display frame to deinterlace (k_deint, 
     int parity;                   // the kept rows: 0 top field, 1 bottom field
     int thr;                      // 4 * T * T
     uint8_t *dst2;                // field rate (k_deint2): D with the OTHER parity kept goes here, in dst's layout; nullptr = one output
+    // motion-adaptive (option deinterlace_temporal, k_deint3): the surface of the previous display frame, same size; nullptr = D as above.
+    // A job with prev is D3 whatever the mode says; t is T itself (thr is 4 T^2)
+    const uint8_t *prev = nullptr;
+    int prev_pitch = 0, prev_chroma_offset = 0, t = 0;
 };
 // host side: a DeintJob on its way to the engine.  feeds 0: job.dst is the frame's output slot; 1 / 2: D(F) goes to a surface in the batch's scratch
 // (job.dst_pitch / dst_chroma_offset describe it) and entry `index` of the ScaleJob / RgbJob list beside it reads that surface -- the engine sets

@@ -53,6 +53,8 @@ void launch_deint(const DeintJob *d_jobs, int n, int max_items, hipStream_t st);
 // max_items: the largest deint_items() / deint2_items() of the jobs
 int  deint2_items(int w, int h);
 void launch_deint2(const DeintJob *d_jobs, int n, int max_items, hipStream_t st);
+// the same table through k_deint3: jobs with a previous frame (DeintJob::prev) put out D3, one or both parities; the others are k_deint2's work
+void launch_deint3(const DeintJob *d_jobs, int n, int max_items, hipStream_t st);
 // tight I420 (fmt 1) / NV12 (fmt 0) frame in device memory -> ARGB32 in device memory
 void launch_frame_to_argb(const uint8_t *d_src, int w, int h, int fmt, uint8_t *d_dst, int dst_pitch, hipStream_t st);
 // tight I420 / NV12 -> pitch NV12 (encoder input)

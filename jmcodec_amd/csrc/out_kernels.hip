@@ -4,6 +4,7 @@
 //   k_packout       pitch NV12 surface -> tight NV12 / I420 display frame
 //   k_scale_pack    ... cropped and resampled (scale_packed.h);  k_rgb_pack  ... and converted to RGB (rgb_packed.h)
 //   k_deint         ... deinterlaced (deint_packed.h);  k_deint2  both fields of a frame in one pass (deint2_packed.h)
+//   k_deint3        ... deinterlaced against the previous display frame (deint3_packed.h)
 //   k_frame_to_argb, k_frame_to_nv12_pitch   tight frame -> ARGB32 / pitch NV12
 // All fully parallel, 8-bit integer pixel work: HBM / LDS bound, no MFMA.  The arithmetic of the resampler, the colour step and the deinterlacer lives in
 // the four __host__ __device__ headers, which the host tests run on the CPU; the kernels here are set-up, LDS buffers, barriers and calls.
@@ -17,6 +18,7 @@
 #include "chroma_packed.h"     // interpolated chroma at the stream's siting (k_rgb_pack444)
 #include "deint_packed.h"      // deint_strip (k_deint)
 #include "deint2_packed.h"     // deint2_strip (k_deint2)
+#include "deint3_packed.h"     // deint3_strip (k_deint3)
 
 namespace jmamd {
 
@@ -258,9 +260,7 @@ void launch_deint(const DeintJob *d_jobs, int n, int max_items, hipStream_t st) 
 // once and stores 16.  A job without a second destination is k_deint's work, item by item (the branch is uniform per workgroup), so one launch serves a
 // side that mixes both; a side without pairs is launched as k_deint.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_deint2(const DeintJob *jobs) {
-    const DeintJob jb = jobs[blockIdx.y];
-    const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+__device__ __forceinline__ void deint2_job(const DeintJob &jb, int first, int stride) {
     if (!jb.dst2) { deint_job(jb, first, stride); return; }
     const dei::gbyte *src = (const dei::gbyte *)jb.src; dei::gbyte *dst = (dei::gbyte *)jb.dst, *dst2 = (dei::gbyte *)jb.dst2;
     const int total = dei::frame2_items(jb.width, jb.height);
@@ -268,9 +268,32 @@ __global__ __launch_bounds__(256) void k_deint2(const DeintJob *jobs) {
         dei::deint2_item(src, jb.parity ? dst2 : dst, jb.parity ? dst : dst2, jb.pitch, jb.chroma_offset, jb.width, jb.height, jb.dst_pitch, jb.dst_chroma_offset,
                          jb.out_fmt, jb.mode, jb.thr, i);
 }
+__global__ __launch_bounds__(256) void k_deint2(const DeintJob *jobs) {
+    const DeintJob jb = jobs[blockIdx.y];
+    deint2_job(jb, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
 int deint2_items(int w, int h) { return dei::frame2_items(w, h); }
 void launch_deint2(const DeintJob *d_jobs, int n, int max_items, hipStream_t st) {
     if (n > 0 && max_items > 0) hipLaunchKernelGGL(k_deint2, dim3((max_items + 255) / 256, n), dim3(256), 0, st, d_jobs);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_deint3: motion-adaptive deinterlacing (option deinterlace_temporal, deint3_packed.h).  A job with a previous frame puts out D3: a lane owns a 16-byte
+// column chunk and 8 rows, loads its 10 rows of the frame and of the previous frame once, keeps the frame's rows and ONE mask register per row, and
+// stores 8 rows (or 16: a field-rate pair, both parities from the same masks).  A job without a previous frame is k_deint2's work, item by item (the
+// branch is uniform per workgroup), so one launch serves a side that mixes them; a side without such a job is launched as before.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_deint3(const DeintJob *jobs) {
+    const DeintJob jb = jobs[blockIdx.y];
+    const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    if (!jb.prev) { deint2_job(jb, first, stride); return; }
+    const int total = dei::frame2_items(jb.width, jb.height);
+    for (int i = first; i < total; i += stride)
+        dei::deint3_item((const dei::gbyte *)jb.src, (const dei::gbyte *)jb.prev, (dei::gbyte *)jb.dst, (dei::gbyte *)jb.dst2, jb.pitch, jb.chroma_offset,
+                         jb.prev_pitch, jb.prev_chroma_offset, jb.width, jb.height, jb.dst_pitch, jb.dst_chroma_offset, jb.out_fmt, jb.parity, jb.t, i);
+}
+void launch_deint3(const DeintJob *d_jobs, int n, int max_items, hipStream_t st) {
+    if (n > 0 && max_items > 0) hipLaunchKernelGGL(k_deint3, dim3((max_items + 255) / 256, n), dim3(256), 0, st, d_jobs);
 }
 
 }  // namespace jmamd

@@ -7,7 +7,7 @@
 // writes it, the ScaleJob / RgbJob at DeintReq::index of the same picture and side reads it; surfaces are handed out in the order of the add() calls, each
 // rounded up to 256 bytes.  A field-rate pair (DeintReq::pair) is ONE entry of k_deint's table with two destinations and, for a scaled / RGB handle, two
 // scratch surfaces (first field first) read by the jobs at DeintReq::index and index2; it counts as two frames.  pairs[side] says whether a side holds one
-// (the engine then launches the table through k_deint2).
+// (the engine then launches the table through k_deint2), temporal[side] whether it holds a job that reads a previous frame (DeintJob::prev: k_deint3).
 // Host code, header-only, no HIP: the tables' memory is the caller's.  tests/test_out_tables.py checks the layout against a restatement of these rules.
 #pragma once
 #include "jobs.h"
@@ -35,7 +35,7 @@ struct OutTables {
     JobTable<PackJob> plain; JobTable<ScaleJob> scale; JobTable<RgbJob> rgb; JobTable<DeintJob> deint;
     template <class F> void each(F &&f) { f(plain); f(scale); f(rgb); f(deint); }
     // grids: k_packout's frame size (over the pictures with a plain job), launch_scale_pack's tiles, launch_rgb_pack's (identity / resampled jobs / jobs with interpolated chroma), launch_deint's
-    int max_w = 0, max_h = 0, s_tiles = 0, r_tiles[3] = {0, 0, 0}, d_items = 0, pairs[2] = {0, 0};
+    int max_w = 0, max_h = 0, s_tiles = 0, r_tiles[3] = {0, 0, 0}, d_items = 0, pairs[2] = {0, 0}, temporal[2] = {0, 0};
     int n_chroma[2] = {0, 0};                       // per side: RGB jobs with interpolated chroma (r_tiles[2] is their grid; k_rgb_pack444)
     // profiling sums: frames and their algorithmic bytes -- of every output kernel together, of k_rgb_pack alone, of k_deint alone
     long long alg_pack = 0, alg_rgb = 0, alg_deint = 0, alg_rgb444 = 0; int n_frames = 0, n_rgb = 0, n_deint = 0;
@@ -48,7 +48,7 @@ struct OutTables {
 
     void reset(uint8_t *scratch_base) {
         each([](auto &t) { t.n[0] = t.n[1] = 0; });
-        max_w = max_h = s_tiles = r_tiles[0] = r_tiles[1] = r_tiles[2] = d_items = pairs[0] = pairs[1] = n_chroma[0] = n_chroma[1] = 0;
+        max_w = max_h = s_tiles = r_tiles[0] = r_tiles[1] = r_tiles[2] = d_items = pairs[0] = pairs[1] = temporal[0] = temporal[1] = n_chroma[0] = n_chroma[1] = 0;
         alg_pack = alg_rgb = alg_deint = alg_rgb444 = 0; n_frames = n_rgb = n_deint = 0;
         scratch = scratch_base; scratch_used = 0;
     }
@@ -76,8 +76,10 @@ struct OutTables {
             deint.h(side)[deint.n[side]++] = j;
             d_items = std::max(d_items, deint_items(j.width, j.height));        // (a pair has no more items than a frame: the grid covers it)
             // (a pair reads the surface once and writes two frames: 3 S against a frame's 2 S)
-            if (pair) { pairs[side]++; alg_deint += deint_bytes * 3 / 2; n_deint += 2; }
-            else { alg_deint += deint_bytes; n_deint++; }
+            // (a job with a previous frame reads that surface too: 3 S and 4 S; temporal[side]: the side goes through k_deint3)
+            if (j.prev) temporal[side]++;
+            if (pair) { pairs[side]++; alg_deint += deint_bytes * (j.prev ? 4 : 3) / 2; n_deint += 2; }
+            else { alg_deint += deint_bytes * (j.prev ? 3 : 2) / 2; n_deint++; }
         }
         const int f = (int)o.frames(), nr = (int)o.rgb.size();
         alg_pack += pack_bytes * f; n_frames += f; alg_rgb += pack_bytes * nr; n_rgb += nr;

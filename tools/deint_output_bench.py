@@ -4,11 +4,16 @@ the twins is identical: the streams are progressive), the twins alternated in on
 `hbm` frames left in device memory, `scaled` 960x540 fetched, `rgb` planar u8 RGB fetched.  One JSON line per leg, twin and round -- with the
 engine's profile counters: k_deint and all pack-out kernels, microseconds per frame and GB/s -- then a summary line per leg.
 
-    python tools/deint_output_bench.py [--streams 32] [--frames 60] [--passes 2] [--rounds 3] [--mode 2] [--rate 0] [--legs host,hbm,scaled,rgb]
+    python tools/deint_output_bench.py [--streams 32] [--frames 60] [--passes 2] [--rounds 3] [--mode 2] [--rate 0] [--temporal] [--legs host,hbm,scaled,rgb]
 
 --rate 1 compares field rate with frame rate instead: the twins are deinterlace = MODE with deinterlace_rate = 0 and with deinterlace_rate = 1.
 Frames per second count OUTPUT frames (a field-rate handle puts out two per picture; `pictures_per_s` is the decode rate), and the pair counters
 are printed: `field_rate_pairs` and k_deint's microseconds per pair.
+
+--temporal compares the motion-adaptive deinterlacer with mode 2: the twins are deinterlace = 2 (at the --rate given) without and with
+deinterlace_temporal = 1, so k_deint / k_deint2 and k_deint3 are timed side by side in one run (`deint_us_per_frame`, at field rate also
+`deint_us_per_pair`; `deint_temporal_frames` says how many frames read a previous one).  Without the flag the key is never set, so the tool
+also runs against a library of before the option (JM_AMD_DEC_LIB), which is how the off side is compared across builds.
 
 The twin's k_packout time per frame is its `pack_us_per_frame` on the `host` / `hbm` legs (k_packout is the only pack-out kernel there); launch
 counts: run one leg under rocprofv3 --kernel-trace --stats."""
@@ -30,7 +35,7 @@ LEGS = {"host": dict(), "hbm": dict(device=True), "scaled": dict(target=(960, 54
 COUNTERS = ("k_deint_ns", "k_deint_pics", "k_deint_alg_bytes", "k_deint_n", "k_packout_ns", "k_packout_pics", "k_packout_n")
 
 
-def run_leg(L, datas, leg, mode, passes, parse_only=False, rate=0):
+def run_leg(L, datas, leg, mode, passes, parse_only=False, rate=0, temporal=0):
     """One twin of one leg: fresh handles, one warm-up pass, then `passes` timed passes of every stream on its own thread."""
     S = len(datas)
     cfg = LEGS[leg]
@@ -48,6 +53,8 @@ def run_leg(L, datas, leg, mode, passes, parse_only=False, rate=0):
             opts.update(target_width=tw, target_height=th)
         if mode:
             opts.update(deinterlace=mode, deinterlace_when=1, deinterlace_rate=rate)
+        if temporal:
+            opts["deinterlace_temporal"] = 1
         for k, v in opts.items():
             assert L.jm_amddec_set_option(h, k.encode(), v) == 0, k
         if cfg.get("rgb"):
@@ -99,15 +106,18 @@ def run_leg(L, datas, leg, mode, passes, parse_only=False, rate=0):
     dt = time.perf_counter() - t0
     c1 = counters()
     d = {k: c1[k] - c0[k] for k in COUNTERS}
-    deint_frames = pairs = 0
+    deint_frames = pairs = temporal_frames = 0
     for h in hs:
         assert L.jm_amddec_get_stat(h, b"errors") == 0
         deint_frames += L.jm_amddec_get_stat(h, b"deint_frames")
+        temporal_frames += max(0, L.jm_amddec_get_stat(h, b"deint_temporal_frames")) if temporal else 0
         pairs += max(0, L.jm_amddec_get_stat(h, b"field_rate_pairs"))
         api.jm_nvdec_deinit(h)
     n = sum(counts)
     res = {"leg": leg, "deinterlace": mode, "rate": rate, "frames": n, "seconds": round(dt, 3), "frames_per_s": round(n / dt, 1),
            "deint_frames": deint_frames, "field_rate_pairs": pairs}
+    if temporal:
+        res.update(temporal=1, deint_temporal_frames=temporal_frames)
     if rate:
         # (the handles' counters include the warm-up pass; the timed passes hold passes / (passes + 1) of the pairs)
         res["pictures_per_s"] = round(n / 2 / dt, 1)
@@ -130,6 +140,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--mode", type=int, default=2, choices=[1, 2])
     ap.add_argument("--rate", type=int, default=0, choices=[0, 1], help="1: the twins are frame rate and field rate of the same mode")
+    ap.add_argument("--temporal", action="store_true", help="the twins are mode 2 without and with deinterlace_temporal (at the --rate given)")
     ap.add_argument("--legs", default="host,hbm,scaled,rgb")
     ap.add_argument("--parse-only", action="store_true", help="host half only (no GPU): checks the tool itself, the numbers mean nothing")
     args = ap.parse_args()
@@ -139,13 +150,17 @@ def main():
     with ThreadPoolExecutor(16) as ex:
         datas = list(ex.map(lambda i: streams.generate(**streams.config_c1(stream_id=i, frames=args.frames)), range(args.streams)))
     # the twins of a leg as (deinterlace, deinterlace_rate): plain against deinterlaced, or -- --rate 1 -- frame rate against field rate
-    twins = [(args.mode, 0), (args.mode, 1)] if args.rate else [(0, 0), (args.mode, 0)]
+    # (or -- --temporal -- mode 2 against the motion-adaptive deinterlacer; the third entry is deinterlace_temporal)
+    twins = [(args.mode, 0, 0), (args.mode, 1, 0)] if args.rate else [(0, 0, 0), (args.mode, 0, 0)]
+    if args.temporal:
+        assert args.mode == 2, "deinterlace_temporal acts while deinterlace is 2"
+        twins = [(2, args.rate, 0), (2, args.rate, 1)]
     fps = {(l, t): [] for l in legs for t in twins}
     last = {}
     for r in range(args.rounds):
         for leg in legs:
             for t in twins:
-                res = run_leg(L, datas, leg, t[0], args.passes, args.parse_only, t[1])
+                res = run_leg(L, datas, leg, t[0], args.passes, args.parse_only, t[1], t[2])
                 res["round"] = r
                 fps[(leg, t)].append(res["frames_per_s"])
                 last[(leg, t)] = res
@@ -153,7 +168,13 @@ def main():
     for leg in legs:
         med = {t: sorted(fps[(leg, t)])[len(fps[(leg, t)]) // 2] for t in twins}
         b, a = last[(leg, twins[0])], last[(leg, twins[1])]
-        if args.rate:
+        if args.temporal:
+            key = "deint_us_per_pair" if args.rate else "deint_us_per_frame"
+            out = {"summary": True, "leg": leg, "streams": args.streams, "rate": args.rate, "median_mode2_fps": med[twins[0]], "median_temporal_fps": med[twins[1]],
+                   "ratio": round(med[twins[1]] / med[twins[0]], 3) if med[twins[0]] else None}
+            if key in a and key in b:
+                out.update({"temporal_" + key: a[key], "mode2_" + key: b[key], "temporal_over_mode2": round(a[key] / b[key], 3)})
+        elif args.rate:
             out = {"summary": True, "leg": leg, "streams": args.streams, "median_frame_rate_fps": med[twins[0]], "median_field_rate_fps": med[twins[1]],
                    "ratio": round(med[twins[1]] / med[twins[0]], 3) if med[twins[0]] else None}
             if "deint_us_per_pair" in a and "deint_us_per_frame" in b:

@@ -15,6 +15,7 @@ int deint_items(int, int) { return 1; }
 void launch_deint(const DeintJob *, int, int, ihipStream_t *) { abort(); }
 int deint2_items(int, int) { return 1; }
 void launch_deint2(const DeintJob *, int, int, ihipStream_t *) { abort(); }
+void launch_deint3(const DeintJob *, int, int, ihipStream_t *) { abort(); }
 void launch_recon_inter(const PicParams *, int, int, bool, bool, int *, ihipStream_t *) { abort(); }
 void launch_intra_lds(const PicParams *, int, int, int *, int *, ihipStream_t *) { abort(); }
 void launch_recon_intra(const PicParams *, int, ihipStream_t *) { abort(); }
