@@ -79,8 +79,8 @@ class Pic:
         self.cw, self.ch = hw.ctb_dims(seq)
         self.ctb = self.g["ctb"]
         self.f = Field(self.W, self.H)
-        self.step = step = {"ctb": 1, "row": self.cw, "pic": self.cw * self.ch}[self.p.get("layout", "ctb" if self.kind != "I" else "pic")]
-        self.slice_of = (np.arange(self.cw * self.ch) // step * step).reshape(self.ch, self.cw)
+        self.starts = [sl["first"] for sl in hw.slice_table(seq, self.p)]
+        self.slice_of = hw.slice_map(seq, self.p).reshape(self.ch, self.cw)
         self.slice_lists = {}
         self.par = seq.get("par_mrg_log2", 2)
         self.max_merge = self.p.get("max_merge", 1)
@@ -91,7 +91,7 @@ class Pic:
 
     def set_slice(self, x, y=None):
         """the lists of the slice that holds (x, y) (or of slice number x): a slice activates its own entries (slice_n_ref of the script)"""
-        n = x if y is None else ((y >> self.ctb) * self.cw + (x >> self.ctb)) // self.step
+        n = x if y is None else self.starts.index(self.slice_of[y >> self.ctb, x >> self.ctb])
         if n not in self.slice_lists:
             spl = hw.slice_plan(self.pl, self.p, n)
             lists = (spl["l0"], spl["l1"] if self.kind == "B" else [])
@@ -331,8 +331,10 @@ class Pic:
         return cands[flag][1], cands, rules
 
 
-def expect(seq, pics, **sw):
-    """-> ([(Y, Cb, Cr)] per picture in DECODE order, coded size, uint8; [one record per prediction unit, in decoding order])"""
+def expect(seq, pics, post=None, **sw):
+    """-> ([(Y, Cb, Cr)] per picture in DECODE order, coded size, uint8; [one record per prediction unit, in decoding order]).
+    post(k, planes, dict(field=the picture's Field)) -> the planes that picture k leaves for later pictures and for the output (tests/hevc_loop_ref.py:
+    the loop filters); by default the reconstruction itself"""
     assert all(k in SWITCHES + UNOBSERVABLE for k in sw), sw
     assert not seq.get("cu_qp_delta", 0) and seq.get("scaling_lists") is None and not seq.get("transquant_bypass", 0)
     W, H = hw.coded_size(seq)
@@ -427,7 +429,7 @@ def expect(seq, pics, **sw):
                                 lev[cy, cx] = v
                             r = rr.residual(lev, qpc[c], bn.bit_length() - 1, flat[bn], False, c in e["tskip"], False)[0]
                             planes[c][by:by + bn, bx:bx + bn] = np.clip(planes[c][by:by + bn, bx:bx + bn].astype(np.int64) + r, 0, 255)
-        out.append(tuple(planes))
+        out.append(tuple(post(k, planes, dict(field=P.f)) if post else planes))
         fields.append(P.f)
     return out, records
 

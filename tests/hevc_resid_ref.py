@@ -120,8 +120,10 @@ def chroma_qp(qpy, offset, sw={}):
 
 
 # ---- the pictures ---------------------------------------------------------------------------------------------------------------------------------
-def expect(seq, pics, **sw):
-    """-> ([(Y, Cb, Cr)] per picture in DECODE order, coded size, uint8; [one record per transform block with coefficients, in decoding order])"""
+def expect(seq, pics, post=None, **sw):
+    """-> ([(Y, Cb, Cr)] per picture in DECODE order, coded size, uint8; [one record per transform block with coefficients, in decoding order]).
+    post(k, planes, dict(qpy=QpY per 4x4)) -> the planes that picture k leaves for later pictures and for the output (tests/hevc_loop_ref.py: the loop
+    filters); by default the reconstruction itself, as every stream without loop filters has it"""
     assert all(k in SWITCHES for k in sw), sw
     W, H = hw.coded_size(seq)
     g = hw.geometry(seq)
@@ -134,8 +136,7 @@ def expect(seq, pics, **sw):
     for k, (p, pl) in enumerate(zip(pics, plans)):
         planes = [np.zeros((H, W), np.uint8), np.zeros((H // 2, W // 2), np.uint8), np.zeros((H // 2, W // 2), np.uint8)]
         qpy = np.zeros((H // 4, W // 4), np.int64)                  # QpY per 4x4
-        step = {"ctb": 1, "row": cw, "pic": cw * ch}[p.get("layout", "ctb" if p["kind"] != "I" else "pic")]
-        slice_of = (np.arange(cw * ch) // step * step).reshape(ch, cw)
+        slice_of = hw.slice_map(seq, p).reshape(ch, cw)
         slice_qp = p.get("qp", seq.get("init_qp", 26))
         offs = (0, seq.get("cb_qp_offset", 0) + p.get("cb_qp_offset", 0), seq.get("cr_qp_offset", 0) + p.get("cr_qp_offset", 0))
         state = dict(qg=None, prev_qp=slice_qp, last_qp=slice_qp, delta=0, coded=False, pred=slice_qp, slice=None, reset=False)
@@ -247,7 +248,7 @@ def expect(seq, pics, **sw):
                         intra_block(c, cx, cy, cn, cm)
                     if e[c]:
                         add(c, cx, cy, cn, e[c], qp_y, intra, c in e["tskip"], bypass, u, cm)
-        out.append(tuple(planes))
+        out.append(tuple(post(k, planes, dict(qpy=qpy)) if post else planes))
     return out, records
 
 

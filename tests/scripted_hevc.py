@@ -3,7 +3,7 @@
 As tests/scripted_h264.py: the test says which coding unit carries which samples, vector, reference, weight or intra mode; ``write`` turns the script
 into Annex-B bytes; residuals are scripted level by level (``coef``; ``dc`` is the earlier short form for one coefficient at (0, 0)), so the decoded
 picture follows from the script by arithmetic (tests/analytic_hevc.py, tests/hevc_intra_ref.py, tests/hevc_resid_ref.py).  Typed from the syntax
-clauses (7.3.1.2, 7.3.2.1 - 7.3.2.3, 7.3.3, 7.3.4, 7.3.6, 7.3.7, 7.3.8.4 - 7.3.8.11, 9.3, the context selection of 9.3.4.2, the binarisations of
+clauses (7.3.1.2, 7.3.2.1 - 7.3.2.3, 7.3.3, 7.3.4, 7.3.6, 7.3.7, 7.3.8.3 - 7.3.8.11, 9.3, the context selection of 9.3.4.2, the binarisations of
 9.3.3.10 / 9.3.3.11, the part_mode binarisation of 9.3.3.7) -- not from tools/hevcgen.c, the oracle or the product.
 
 The CABAC encoder is 9.3.4 run backwards (the encoding flowcharts of 9.3.4.x / H.264 9.3.4.2: EncodeDecision, EncodeBypass, EncodeTerminate, EncodeFlush,
@@ -62,6 +62,19 @@ Inter prediction as SYNTAX (tests/hevc_inter_ref.py derives the motion; the writ
                                                                    mvp_lX_flag; with mvd_l1_zero the list 1 difference of a two-list unit is not coded
         coef / tu / dqp / bypass stay valid on such a unit: rqt_root_cbf is absent (and 1) only for a 2Nx2N merge unit; with tu_depth_inter 0 a unit
         that is not 2Nx2N has its transform tree split once without a flag (interSplitFlag), so tu is 1
+The loop filters as SYNTAX (tests/hevc_loop_ref.py filters; the writer filters nothing), all with defaults that leave every earlier stream as it was:
+    seq:  sao=0 (sample_adaptive_offset_enabled_flag), pps_beta=0, pps_tc=0 (pps_beta_offset_div2, pps_tc_offset_div2: written with deblock=1),
+          pps_across=1 (pps_loop_filter_across_slices_enabled_flag)
+    pics: slices=[dict(first=CTB address, ...)]: slices that begin where the script says (in place of layout); each entry may carry its own values of
+          the keys below, which otherwise are the picture's:
+          deblock=None | 0 | 1 (the override, as before), beta=0, tc=0 (slice_beta_offset_div2 / slice_tc_offset_div2: only under the override with
+          deblock=1; without the override the slice has the PPS offsets), across=pps_across (slice_loop_filter_across_slices_enabled_flag: the
+          script must say what is inferred where 7.3.6.1 leaves the flag out), sao=(slice_sao_luma_flag, slice_sao_chroma_flag)=(0, 0)
+          sao_ctbs=[per CTB address dict(merge="left" | "up" | None, y=entry, c=(entry of Cb, entry of Cr)) or None (everything off)]
+            an entry is None (SaoTypeIdx 0), ("band", sao_band_position, four signed offsets) or ("edge", SaoEoClass, four magnitudes); Cr has Cb's
+            type and class; a merged CTB says nothing else; a merge from outside the slice or the picture is refused; the entries of a component
+            whose slice flag is 0 must be None
+``slice_table`` gives the slices of a picture with every such value resolved.
 Every picture decoded so far with is_ref stays in the reference picture set (at most 5).  RefPicList0 = pictures before the current one in output
 order, nearest first, then those after it; RefPicList1 the other way round (8.3.4); both lists are active in full unless n_ref says otherwise.
 The script must keep sps_max_num_reorder_pics = 2: at most two pictures precede a picture in decoding order and follow it in output order.
@@ -271,7 +284,7 @@ def sps(seq):
         b.u(1, 1 if sl.get("sps") is not None else 0)               # sps_scaling_list_data_present_flag (0: the default lists of Tables 7-5 / 7-6)
         if sl.get("sps") is not None:
             scaling_list_data(b, sl["sps"])
-    b.u(1, seq.get("amp", 0)); b.u(1, 0)                            # amp_enabled_flag; SAO: off
+    b.u(1, seq.get("amp", 0)); b.u(1, seq.get("sao", 0))            # amp_enabled_flag; sample_adaptive_offset_enabled_flag
     b.u(1, 1); b.u(4, 7); b.u(4, 7); b.ue(g["pcm"][0] - 3); b.ue(g["pcm"][1] - g["pcm"][0])          # PCM on: 8-bit samples (default 16x16 only)
     b.u(1, seq.get("pcm_loop_filter_disabled", 1))
     b.ue(0)                                                         # num_short_term_ref_pic_sets: every slice header carries its own
@@ -296,11 +309,14 @@ def pps(seq):
     b.u(1, seq.get("slice_chroma_qp_offsets", 0))                   # pps_slice_chroma_qp_offsets_present_flag
     b.u(1, seq.get("weighted_pred", 0)); b.u(1, seq.get("weighted_bipred", 0))
     b.u(1, seq.get("transquant_bypass", 0)); b.u(1, 0); b.u(1, 0)   # transquant_bypass_enabled_flag; tiles, wavefronts: off
-    b.u(1, 1)                                                       # pps_loop_filter_across_slices_enabled_flag
+    b.u(1, seq.get("pps_across", 1))                                # pps_loop_filter_across_slices_enabled_flag
     b.u(1, 1); b.u(1, 1)                                            # deblocking_filter_control_present_flag, override enabled
     b.u(1, 0 if seq.get("deblock", 0) else 1)                       # pps_deblocking_filter_disabled_flag
     if seq.get("deblock", 0):
-        b.se(0); b.se(0)
+        assert -6 <= seq.get("pps_beta", 0) <= 6 and -6 <= seq.get("pps_tc", 0) <= 6
+        b.se(seq.get("pps_beta", 0)); b.se(seq.get("pps_tc", 0))    # pps_beta_offset_div2, pps_tc_offset_div2
+    else:
+        assert not seq.get("pps_beta", 0) and not seq.get("pps_tc", 0), "the PPS offsets are written only with the filter on in the PPS"
     pl = (seq.get("scaling_lists") or {}).get("pps")
     b.u(1, 1 if pl is not None else 0)                              # pps_scaling_list_data_present_flag
     if pl is not None:
@@ -341,8 +357,52 @@ def slice_plan(pl, p, ordinal):
     return dict(pl, l0=cyc(pl["before"] + pl["after"], n0), l1=cyc(pl["after"] + pl["before"], n1))
 
 
-def slice_header(b, seq, p, pl, first, addr, n_ctbs, sw={}):
+def slice_table(seq, p):
+    """The slices of a picture in decoding order, every value resolved: [dict(first, count, disabled (slice_deblocking_filter_disabled_flag),
+    override (deblocking_filter_override_flag), beta, tc (the offsets in effect, div2), across, across_coded, sao=(luma, chroma))]"""
+    cw, ch = ctb_dims(seq)
+    n = cw * ch
+    if p.get("slices") is not None:
+        own = p["slices"]
+        firsts = [o["first"] for o in own]
+        assert firsts[0] == 0 and all(a < b_ for a, b_ in zip(firsts, firsts[1:])) and firsts[-1] < n and "layout" not in p, firsts
+    else:
+        step = {"ctb": 1, "row": cw, "pic": n}[p.get("layout", "ctb" if p["kind"] != "I" else "pic")]
+        firsts = list(range(0, n, step))
+        own = [{}] * len(firsts)
+    out = []
+    for i, (f, o) in enumerate(zip(firsts, own)):
+        get = lambda key, d: o.get(key, p.get(key, d))
+        ov = get("deblock", None)
+        disabled = (not seq.get("deblock", 0)) if ov is None else (not ov)
+        beta, tc = get("beta", None), get("tc", None)
+        if ov is None or disabled:
+            assert beta is None and tc is None, "slice offsets are coded only under the override, with the filter on"
+            beta, tc = (seq.get("pps_beta", 0), seq.get("pps_tc", 0)) if ov is None else (0, 0)
+        beta, tc = beta or 0, tc or 0
+        assert -6 <= beta <= 6 and -6 <= tc <= 6
+        sao = tuple(get("sao", (0, 0)))
+        assert seq.get("sao", 0) or sao == (0, 0), "slice_sao_*_flag without sample_adaptive_offset_enabled_flag"
+        pa = seq.get("pps_across", 1)
+        coded = bool(pa and (sao[0] or sao[1] or not disabled))     # 7.3.6.1
+        across = get("across", pa)
+        assert coded or across == pa, "slice_loop_filter_across_slices_enabled_flag is absent and inferred to be the PPS flag"
+        out.append(dict(first=f, count=(firsts[i + 1] if i + 1 < len(firsts) else n) - f, disabled=bool(disabled), override=ov is not None,
+                        beta=beta, tc=tc, across=across, across_coded=coded, sao=sao))
+    return out
+
+
+def slice_map(seq, p):
+    """SliceAddrRs per CTB address"""
+    m = np.zeros(ctb_dims(seq)[0] * ctb_dims(seq)[1], np.int32)
+    for sl in slice_table(seq, p):
+        m[sl["first"]:sl["first"] + sl["count"]] = sl["first"]
+    return m
+
+
+def slice_header(b, seq, p, pl, first, addr, n_ctbs, sw={}, sl=None, stats=None):
     kind = p["kind"]
+    sl = sl or [q for q in slice_table(seq, p) if q["first"] == addr][0]
     tmvp = 0
     b.u(1, 1 if first else 0)
     if pl["typ"] >= 16:
@@ -366,6 +426,8 @@ def slice_header(b, seq, p, pl, first, addr, n_ctbs, sw={}):
         if seq.get("tmvp", 0):
             tmvp = p.get("tmvp", 1)
             b.u(1, tmvp)                                            # slice_temporal_mvp_enabled_flag
+    if seq.get("sao", 0):
+        b.u(1, sl["sao"][0]); b.u(1, sl["sao"][1])                  # slice_sao_luma_flag, slice_sao_chroma_flag
     if kind != "I":
         b.u(1, 1)                                                   # num_ref_idx_active_override_flag
         b.ue(len(pl["l0"]) - 1)
@@ -401,16 +463,18 @@ def slice_header(b, seq, p, pl, first, addr, n_ctbs, sw={}):
     b.se(p.get("qp", seq.get("init_qp", 26)) - seq.get("init_qp", 26))
     if seq.get("slice_chroma_qp_offsets", 0):
         b.se(p.get("cb_qp_offset", 0)); b.se(p.get("cr_qp_offset", 0))
-    ov = p.get("deblock")
-    b.u(1, 0 if ov is None else 1)                                  # deblocking_filter_override_flag
-    disabled = not seq.get("deblock", 0)
-    if ov is not None:
-        disabled = not ov
-        b.u(1, 1 if disabled else 0)
-        if not disabled:
-            b.se(0); b.se(0)
-    if not disabled:
-        b.u(1, 1)                                                   # slice_loop_filter_across_slices_enabled_flag
+    b.u(1, 1 if sl["override"] else 0)                              # deblocking_filter_override_flag
+    if sl["override"]:
+        b.u(1, 1 if sl["disabled"] else 0)                          # slice_deblocking_filter_disabled_flag
+        if not sl["disabled"]:
+            b.se(sl["beta"]); b.se(sl["tc"])                        # slice_beta_offset_div2, slice_tc_offset_div2
+    present = (seq.get("pps_across", 1) and not sl["disabled"]) if sw.get("across_tied_to_deblock") else sl["across_coded"]
+    if present:
+        b.u(1, sl["across"])                                        # slice_loop_filter_across_slices_enabled_flag
+    if stats is not None:
+        for key in (("slice", "override", sl["override"], sl["disabled"]), ("slice", "across", sl["across"], "coded" if present else "inferred"),
+                    ("slice", "sao", sl["sao"]), ("slice", "offsets", sl["beta"], sl["tc"])):
+            stats[key] = stats.get(key, 0) + 1
     b.u(1, 1)                                                       # byte_alignment()
     b.align_zero()
 
@@ -450,6 +514,8 @@ def scan_order(idx, blk):
 SCAN = [[scan_order(idx, 1 << lg) for lg in range(4)] for idx in range(3)]       # ScanOrder[log2BlockSize][scanIdx] as SCAN[scanIdx][log2BlockSize]
 SIG_CTX_4X4 = [0, 1, 4, 5, 2, 3, 4, 5, 6, 6, 8, 8, 7, 7, 8]                       # ctxIdxMap of 9.3.4.2.5, i = (yC << 2) + xC
 INTER_WRITER_SWITCHES = ("merge_idx_all_context", "amp_bypass_inverted", "col_ref_idx_always", "idc_first_bin_for_8x4")
+LOOP_WRITER_SWITCHES = ("across_tied_to_deblock", "sao_edge_signs_coded", "sao_type_second_bin_context", "sao_cr_class_coded", "sao_up_after_left",
+                        "sao_abs_cmax_31")
 WRITER_SWITCHES = ("scan_ignored", "hidden_sign_written", "ctxset_not_raised", "rice_never_raised", "csbf_wrong_neighbours")
 
 
@@ -573,6 +639,66 @@ class _Picture:
             return False
         s = self.g["ctb"]
         return self.slice_of[(yn >> s) * self.cw + (xn >> s)] == self.slice_of[(yc >> s) * self.cw + (xc >> s)]
+
+    def sao(self, c, a, sl):
+        """7.3.8.3 for the CTB at address a of the slice sl.  sao_merge_*_flag on their one context; sao_type_idx: a context bin, then a bypass bin;
+        sao_offset_abs: truncated unary, cMax 7 (8 bits), bypass; signs for band offsets that are not 0; sao_band_position 5 bits; sao_eo_class 2 bits"""
+        sw = self.sw
+
+        def met(*key):
+            self.stats[("sao",) + key] = self.stats.get(("sao",) + key, 0) + 1
+        e = (self.p.get("sao_ctbs") or [None] * (self.cw * self.ch))[a] or {}
+        merge = e.get("merge")
+        assert merge in (None, "left", "up") and (merge is None or (e.get("y") is None and e.get("c") is None)), e
+        rx, ry = a % self.cw, a // self.cw
+        left_ok, up_ok = rx > 0 and a - 1 >= sl["first"], ry > 0 and a - self.cw >= sl["first"]
+        assert merge != "left" or left_ok, "sao_merge_left_flag: the CTB on the left lies outside the slice or the picture"
+        assert merge != "up" or up_ok, "sao_merge_up_flag: the CTB above lies outside the slice or the picture"
+        if left_ok:
+            c.decision("sao_merge_flag", 0, 1 if merge == "left" else 0)
+            met("merge_left", 1 if merge == "left" else 0)
+        if up_ok and (merge != "left" or sw.get("sao_up_after_left")):
+            c.decision("sao_merge_flag", 0, 1 if merge == "up" else 0)
+            met("merge_up", 1 if merge == "up" else 0)
+        if merge:
+            return
+        cb, cr = e.get("c") or (None, None)
+        assert (cb is None) == (cr is None) and (cb is None or (cb[0] == cr[0] and (cb[0] == "band" or cb[1] == cr[1]))), "Cr has Cb's type and class"
+        for cidx, ent in enumerate((e.get("y"), cb, cr)):
+            if not sl["sao"][1 if cidx else 0]:
+                assert ent is None, "an entry for a component whose slice flag is 0"
+                continue
+            typ = 0 if ent is None else {"band": 1, "edge": 2}[ent[0]]
+            if cidx < 2:
+                c.decision("sao_type_idx", 0, 1 if typ else 0)
+                if typ:
+                    c.decision("sao_type_idx", 0, typ - 1) if sw.get("sao_type_second_bin_context") else c.bypass(typ - 1)
+            met("type", cidx, typ)
+            if not typ:
+                continue
+            _, where, offs = ent
+            assert len(offs) == 4 and all(abs(v) <= 7 for v in offs) and (typ == 1 or all(v >= 0 for v in offs)), ent
+            cmax = 31 if sw.get("sao_abs_cmax_31") else 7
+            for v in offs:
+                for _ in range(abs(v)):
+                    c.bypass(1)
+                if abs(v) < cmax:
+                    c.bypass(0)
+                met("abs", abs(v))
+            if typ == 1 or sw.get("sao_edge_signs_coded"):
+                for v in offs:
+                    if v:
+                        c.bypass(1 if v < 0 else 0)
+                        met("sign", 1 if v < 0 else 0)
+            if typ == 1:
+                assert 0 <= where <= 31
+                for i in range(4, -1, -1):
+                    c.bypass((where >> i) & 1)
+                met("band_position", cidx, where)
+            elif cidx < 2 or sw.get("sao_cr_class_coded"):
+                assert 0 <= where <= 3
+                c.bypass(where >> 1); c.bypass(where & 1)
+                met("class", cidx, where)
 
     def quadtree(self, c, x, y, log2, depth, node):
         """7.3.8.4"""
@@ -972,9 +1098,9 @@ class _Picture:
 
 
 def write(seq, pics, stats=None, **sw):
-    """Annex-B bytes of the script.  The keyword arguments (WRITER_SWITCHES, INTER_WRITER_SWITCHES) make the residual / the inter syntax wrong on
-    purpose; stats: a dict that counts what residual_coding met."""
-    assert all(k in WRITER_SWITCHES + INTER_WRITER_SWITCHES for k in sw), sw
+    """Annex-B bytes of the script.  The keyword arguments (WRITER_SWITCHES, INTER_WRITER_SWITCHES, LOOP_WRITER_SWITCHES) make the residual / the inter / the
+    loop filter syntax wrong on purpose; stats: a dict that counts what residual_coding, sao() and the slice headers met."""
+    assert all(k in WRITER_SWITCHES + INTER_WRITER_SWITCHES + LOOP_WRITER_SWITCHES for k in sw), sw
     cw, ch = ctb_dims(seq)
     n_ctbs = cw * ch
     s = 1 << geometry(seq)["ctb"]
@@ -986,17 +1112,22 @@ def write(seq, pics, stats=None, **sw):
         kind, cus = p["kind"], p["cus"]
         assert len(cus) == n_ctbs
         pic = _Picture(seq, p, pl, kind, sw, stats)
-        pic.step = step = {"ctb": 1, "row": cw, "pic": n_ctbs}[p.get("layout", "ctb" if kind != "I" else "pic")]
-        for first in range(0, n_ctbs, step):
+        assert p.get("sao_ctbs") is None or len(p["sao_ctbs"]) == n_ctbs
+        for ordinal, sl in enumerate(slice_table(seq, p)):
+            first, pic.step = sl["first"], sl["count"]
             b = Bits()
-            pic.pl = spl = slice_plan(pl, p, first // step)
-            slice_header(b, seq, p, spl, first == 0, first, n_ctbs, sw)
+            pic.pl = spl = slice_plan(pl, p, ordinal)
+            slice_header(b, seq, p, spl, first == 0, first, n_ctbs, sw, sl, stats)
             c = Cabac(b, {"I": 0, "P": 1, "B": 2}[kind], p.get("qp", seq.get("init_qp", 26)))
-            last = min(first + step, n_ctbs) - 1
+            last = first + sl["count"] - 1
             pic.slice_of[first:last + 1] = first
             pic.first_unit = cus[first]
             for a in range(first, last + 1):
                 pic.at_first = a == first
+                if sl["sao"][0] or sl["sao"][1]:
+                    pic.sao(c, a, sl)
+                else:
+                    assert not (p.get("sao_ctbs") or [None] * n_ctbs)[a], "SAO parameters in a slice with both flags 0"
                 pic.quadtree(c, (a % cw) * s, (a // cw) * s, geometry(seq)["ctb"], 0, cus[a])
                 c.terminate(1 if a == last else 0)                  # end_of_slice_segment_flag; the flush's last bit is rbsp_slice_segment_trailing_bits' 1
             b.align_zero()
