@@ -37,11 +37,15 @@ extern "C" {
 typedef void *jm_amddec_handle;
 
 jm_amddec_handle jm_amddec_create_handle(void);
-/* codec_type: 0 = H.264, 1 = H.265 / HEVC Main, 2 = MJPEG (enum nv_dec.h:37-46); out_fmt: 0 = NV12, 1 = "YV12" = planar Y,U,V.
+/* codec_type: 0 = H.264, 1 = H.265 / HEVC Main, 2 = MJPEG, 4 = MPEG-2 video (enum nv_dec.h:37-46; the other values are refused); out_fmt: 0 = NV12, 1 = "YV12" = planar Y,U,V.
  * MJPEG: the input is any chunking of a byte stream of concatenated baseline JPEG pictures (SOI .. EOI; 4:2:0 / 4:2:2 / 4:4:4 / grey, 8 bits, one
  * interleaved Huffman scan), every picture lands in the usual NV12 surface and every output option applies; progressive, arithmetic, lossless, 12-bit,
  * CMYK and other samplings fail the handle with an error string (INTEGRATION.md "MJPEG").  extra_data is not used.  Stats: jpeg_pictures, jpeg_sampling
- * (0x22 / 0x21 / 0x11 / 0x10), jpeg_restart_intervals; with option profile k_jpeg_ns / _n / _pics / _alg_bytes. */
+ * (0x22 / 0x21 / 0x11 / 0x10), jpeg_restart_intervals; with option profile k_jpeg_ns / _n / _pics / _alg_bytes.
+ * MPEG-2: the input is any chunking of an ISO/IEC 13818-2 video elementary stream (one start-code unit per call included); frame pictures I / P / B,
+ * 4:2:0, progressive and interlaced; MPEG-1, field pictures, dual prime, 4:2:2 / 4:4:4, the scalable extensions and D pictures fail the handle with
+ * an error string that names the feature (INTEGRATION.md "MPEG-2").  extra_data, if given, is read as the beginning of the stream.  Stats:
+ * dropped_pictures, mpeg2_clamped_mbs, mpeg2_repeat_first_field, mpeg2_profile_level; with option profile k_mpeg2_ns / _n / _pics / _alg_bytes. */
 int  jm_amddec_init(int codec_type, int out_fmt, char *extra_data, int len, jm_amddec_handle h);
 int  jm_amddec_deinit(jm_amddec_handle h);
 /* in_buf may hold any chunk of an Annex-B stream; (NULL, 0) signals end of stream and then

@@ -23,4 +23,5 @@ from .api import (  # noqa: F401
     lib_path,
     split_nalus,
     split_jpegs,
+    split_mpeg2_pictures,
 )

@@ -402,6 +402,24 @@ def split_jpegs(data):
     return [data[a:b] for a, b in zip(cuts, cuts[1:] + [n])]
 
 
+def split_mpeg2_pictures(data):
+    """Split an MPEG-2 video elementary stream (codec_type 4) into one chunk per picture: a chunk starts at the first sequence header, group header or
+    picture header that follows a slice (or the sequence end code), so the headers in front of a picture travel with it; what precedes the first
+    such start code goes with the first picture.  (The decoder itself accepts any chunking: this is a convenience for callers that want one picture
+    per call.)"""
+    data = bytes(data)
+    cuts, after_slice, o = [0], False, data.find(b"\x00\x00\x01")
+    while 0 <= o and o + 3 < len(data):
+        code = data[o + 3]
+        if code in (0x00, 0xB3, 0xB8) and after_slice:
+            cuts.append(o)
+            after_slice = False
+        elif 0x01 <= code <= 0xAF or code == 0xB7:
+            after_slice = True
+        o = data.find(b"\x00\x00\x01", o + 3)
+    return [data[a:b] for a, b in zip(cuts, cuts[1:] + [len(data)])] if data else []
+
+
 def annexb_to_avcc(data, length_size=4):
     """(avcC record, [length-prefixed packets]) of an Annex-B stream: what a demuxer hands test_player for an MP4 source when no
     h264_mp4toannexb filter is in the way (test_player.cpp:221-226).  One packet per access unit (split before each first slice)."""
@@ -452,7 +470,10 @@ def annexb_to_hvcc(data, length_size=4):
 
 
 class JmAmdDec:
-    """Convenience wrapper reproducing test_nv_dec's main loop (test_nv_dec.cpp:163-259)."""
+    """Convenience wrapper reproducing test_nv_dec's main loop (test_nv_dec.cpp:163-259).
+
+    codec_type: 0 H.264, 1 HEVC, 2 MJPEG, 4 MPEG-2 video (frame pictures, 4:2:0: INTEGRATION.md "MPEG-2"); the other values of the
+    reference's NV_CODEC_TYPE are refused at init."""
 
     def __init__(self, codec_type=0, out_fmt=1, options=None, extra_data=None, rgb=None):
         self.h = jm_nvdec_create_handle()

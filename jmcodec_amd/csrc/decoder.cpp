@@ -224,7 +224,7 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "deint_frames") return stat_deint_;
     if (k == "deint_temporal_frames") return stat_temporal_;    // output frames whose D read the previous display frame (a pair counts 2)
     if (k == "field_rate_pairs") return stat_pairs_;         // display pictures handed out as two frames (option deinterlace_rate)
-    if (k == "interlaced_sequence") return codec_ == 0 && seq_active_ && !seq_.frame_mbs_only ? 1 : 0;
+    if (k == "interlaced_sequence") return codec_ == 4 ? (seq_active_ && !m2seq_.progressive_sequence ? 1 : 0) : (codec_ == 0 && seq_active_ && !seq_.frame_mbs_only ? 1 : 0);
     if (k == "out_frame_bytes") { std::lock_guard<std::mutex> lk(const_cast<std::mutex &>(mtx_));
         return (long long)(cur_out_ ? cur_out_->fbytes : !ready_.empty() ? ready_.front()->fbytes : frame_bytes_); }
     if (k == "out_slot_bytes") { std::lock_guard<std::mutex> lk(const_cast<std::mutex &>(mtx_)); long long n = 0;
@@ -287,6 +287,11 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "jpeg_pictures") return stat_jpeg_pics_;
     if (k == "jpeg_sampling") return codec_ == 2 && seq_active_ ? j_sampling_ : 0;
     if (k == "jpeg_restart_intervals") return stat_jpeg_ri_;
+    // MPEG-2: pictures dropped for want of their anchors, macroblocks whose vectors the host clamped, pictures with repeat_first_field, the profile
+    if (k == "dropped_pictures") return stat_dropped_;
+    if (k == "mpeg2_clamped_mbs") return stat_m2_clamped_;
+    if (k == "mpeg2_repeat_first_field") return stat_m2_rff_;
+    if (k == "mpeg2_profile_level") return codec_ == 4 && seq_active_ ? m2seq_.profile_level : 0;
     if (k == "copy_engines") return copier_ ? (long long)copier_->engine_mask() : 0;      // SDMA engines the direct route uses (bit mask)
     if (k == "direct_frames") return stat_direct_;
     // ... and the time their callers spent waiting for them // frames that went out by the "direct" route (one DMA into the caller's registered buffer)
@@ -294,17 +299,19 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "device_wait_errors") return stat_wait_errors_;
     if (k == "intra_mbs") return stat_intra_mbs_;
     if (k == "coef_int16") return stat_coef_;
-    if (k == "syntax_digest") return codec_ == 1 ? (long long)hdigest_.h : (long long)digest_.h;
+    if (k == "syntax_digest") return codec_ == 4 ? (long long)m2_digest_ : codec_ == 1 ? (long long)hdigest_.h : (long long)digest_.h;
     if (k == "job_digest") return (long long)job_digest_;
-    if (k == "digest_mbs") return codec_ == 1 ? (long long)hdigest_.n_cu : (long long)digest_.mbs;
+    if (k == "digest_mbs") return codec_ == 4 ? m2_digest_mbs_ : codec_ == 1 ? (long long)hdigest_.n_cu : (long long)digest_.mbs;
     if (k == "i_pictures") return stat_i_;
     if (k == "p_pictures") return stat_p_;
     if (k == "b_pictures") return stat_b_;
     // frame rate of the active sequence as a fraction (VUI timing information; 0 / 0 when the stream carries none): H.264 counts FIELD ticks (E.2.1)
+    if (codec_ == 4 && (k == "fps_num" || k == "fps_den")) { long long n = 0, d = 0; if (seq_active_) m2seq_.fps(&n, &d); return k == "fps_num" ? n : d; }
     if (k == "fps_num") return codec_ == 1 ? (long long)hsps_.time_scale : (long long)seq_.time_scale;
     if (k == "fps_den") return codec_ == 1 ? (long long)hsps_.num_units_in_tick : 2ll * seq_.num_units_in_tick;
     // ... of the frames handed out: the numerator doubles while a field-rate handle deinterlaces the active sequence's frames
-    if (k == "out_fps_num") { const bool chosen = deint_when_ == 1 || (codec_ == 0 && seq_active_ && !seq_.frame_mbs_only);
+    if (k == "out_fps_num") { const bool chosen = deint_when_ == 1 || (codec_ == 0 && seq_active_ && !seq_.frame_mbs_only) ||
+            (codec_ == 4 && seq_active_ && !m2seq_.progressive_sequence);
         return (field_rate() && chosen ? 2 : 1) * get_stat("fps_num"); }
     if (k == "out_fps_den") return get_stat("fps_den");
     // display frames decided and not yet made current by a decode / poll call (finished or still on the device)
@@ -324,7 +331,7 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "wait_slot_ns") return stat_wait_slot_ns_;
     if (k == "parse_ns_p") return stat_parse_ns_p_;
     if (k.rfind("k_", 0) == 0 || k.rfind("eng_", 0) == 0) {          // engine-wide (all handles on this device), profile option
-        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5", "rgb_pack444"};
+        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5", "rgb_pack444", "mpeg2"};
         if (!engine_) return 0;
         EngineStats es = engine_->stats();
         for (int i = 0; i < kKernelClasses; i++) {
@@ -384,7 +391,10 @@ long long Decoder::get_stat(const char *key) const {
 // MI355X-class device can be opened, because silently continuing would mean a CPU fallback.
 int Decoder::init(int codec_type, int out_fmt, const uint8_t *extra, int len) {
     codec_ = codec_type; out_fmt_ = out_fmt ? 1 : 0;
-    if (codec_type != 0 && codec_type != 1 && codec_type != 2) { fail("only codec_type 0 (H.264), 1 (HEVC) and 2 (MJPEG) are implemented"); return -1; }
+    if (codec_type != 0 && codec_type != 1 && codec_type != 2 && codec_type != 4) {
+        fail("only codec_type 0 (H.264), 1 (HEVC), 2 (MJPEG) and 4 (MPEG-2) are implemented"); return -1; }
+    if (codec_type == 4 && deint_temporal_) { fail("option deinterlace_temporal is not available for MPEG-2 (codec_type 4): keeping the previous display "
+        "surface is tied to the H.264 / HEVC picture buffer"); return -1; }
     if (codec_type == 2 && deint_temporal_) { fail("option deinterlace_temporal is not available for MJPEG (codec_type 2): its surfaces are dealt round robin, "
         "a displayed one cannot be kept for the next picture"); return -1; }
     if (rgb_chroma_ && !rgb_) { fail("option rgb_chroma needs RGB output: set an RGB spec (jm_amddec_set_rgb) before init"); return -1; }
@@ -429,7 +439,8 @@ int Decoder::init(int codec_type, int out_fmt, const uint8_t *extra, int len) {
     // optional SPS/PPS given up front (nv_dec.cpp:334-360).  FFmpeg hands test_player either Annex-B parameter sets or, for MP4 /
     // MKV sources, an AVCDecoderConfigurationRecord ("avcC", ISO/IEC 14496-15 5.2.4.1); with avcC the packets that follow are
     // length-prefixed NAL units unless a bitstream filter already converted them (test_player.cpp:221-226 uses h264_mp4toannexb).
-    if (extra && len > 0 && codec_ == 1 && len >= 23 && extra[0] == 1) {
+    if (codec_ == 4) { if (extra && len > 0) feed(extra, (size_t)len); }      // (sequence headers given up front: part of the stream)
+    else if (extra && len > 0 && codec_ == 1 && len >= 23 && extra[0] == 1) {
         // HEVCDecoderConfigurationRecord ("hvcC", ISO/IEC 14496-15 8.3.3.1): what a demuxer hands test_player for HEVC in MP4 / MKV
         avcc_len_size_ = (extra[21] & 3) + 1;
         int o = 23;
@@ -730,8 +741,9 @@ bool Decoder::gpu_alloc_sequence() {
     job_cap_ = std::min(job_cap_max_, n_mbs * (sizeof(MbRec) + per_mb) + 256 * (sizeof(SliceRec) + 452) + 4096);
     if (getenv("JM_AMD_DEC_JOB_WORST_CASE")) job_cap_ = job_cap_max_;
     if (codec_ == 1) job_cap_ = n_mbs * 128 + (1u << 20);            // HEVC job lists vary a lot in size: start small, grow on demand (ensure_job_cap)
+    if (codec_ == 4) job_cap_ = n_mbs * 224 + (1u << 16);            // MPEG-2: a 32-byte record per macroblock + a typical share of levels; grown on demand too
     if (codec_ == 2) job_cap_ = n_mbs * 160 + (1u << 16);            // MJPEG: 6 block records per macroblock + a typical share of levels; grown on demand too
-    if (!n_jobs_set_) n_jobs_ = codec_ == 2 ? kJpegJobSlots : codec_ == 0 && n_mbs <= 8704 ? kJobSlotsSmall : kJobSlots;      // (decoder.h)
+    if (!n_jobs_set_) n_jobs_ = codec_ == 2 || codec_ == 4 ? kJpegJobSlots : codec_ == 0 && n_mbs <= 8704 ? kJobSlotsSmall : kJobSlots;      // (decoder.h)
     if (!n_jobs_set_ && rgb_ && !parse_only_) {
         // an RGB frame is 2-8x an NV12 one and the handle keeps n_jobs_ + 4 output slots: at most 1 GiB of them (device staging + page-locked), at least
         // 8 job slots
@@ -836,6 +848,7 @@ OutSlot *Decoder::alloc_out_slot() {   // mtx_ held
 // front end: Annex-B splitting (replaces the NAL scanning half of cuvidParseVideoData, nv_dec.cpp:394)
 // =============================================================================================
 void Decoder::feed(const uint8_t *buf, size_t len) {
+    if (codec_ == 4) { mpeg2_feed(buf, len); return; }     // an MPEG-2 elementary stream, cut anywhere (mpeg2_decoder.cpp)
     if (codec_ == 2) { jpeg_feed(buf, len); return; }      // concatenated JPEG pictures, cut anywhere (jpeg_decoder.cpp)
     if (avcc_len_size_ && !have_start_ && in_.empty()) {
         // avcC mode: a packet is a whole number of length-prefixed NAL units -- unless it starts with a start code (already converted)
@@ -891,6 +904,7 @@ void Decoder::feed(const uint8_t *buf, size_t len) {
 // ENDOFSTREAM packet (nv_dec.cpp:389-392)
 void Decoder::flush_stream() {
     if (codec_ == 2) jpeg_flush();
+    if (codec_ == 4) mpeg2_flush();
     if (have_start_) {
         size_t end = in_.size();
         while (end > nal_start_ && in_[end - 1] == 0) end--;
@@ -1049,6 +1063,7 @@ int Decoder::compute_poc(const SliceHeader &sh, DpbPic &store) {
 
 void Decoder::flush_dpb(std::vector<int> &out) {
     if (codec_ == 2) return;                       // (a JPEG picture is displayed by its own task: nothing waits)
+    if (codec_ == 4) { mpeg2_show_anchor(out); return; }      // (the last anchor picture)
     if (codec_ == 1) { for (int i = 0; i < n_surf_; i++) if (i != cur_) dpb_[i].ref = 0; hevc_bump(out, true, true);
         for (int i = 0; i < n_surf_; i++) if (i != cur_ && !dpb_[i].wait_output) dpb_[i].in_use = false; return; }
     if (pending_first_ >= 0) { const int pf = pending_first_; pending_first_ = -1; dpb_[pf].waiting_second = false; store_done(pf, out); }
@@ -1637,6 +1652,7 @@ void Decoder::push_task(std::unique_ptr<PicTask> t) {
 void Decoder::parse_task(PicTask *t, ParseScratch &scratch) {
     if (t->hevc) { hevc_parse_task(t); return; }
     if (t->jpeg) { jpeg_parse_task(t); return; }
+    if (t->mpeg2) { mpeg2_parse_task(t); return; }
     auto pt0 = std::chrono::steady_clock::now();
     JobSlot &js = jobs_[t->job_slot];
     const int n_mbs = t->sps.mb_w * t->sps.mb_h;
@@ -1812,7 +1828,7 @@ int Decoder::display_entry(int slot) {
     const DpbPic &d = dpb_[slot];
     int field = 0, both = 0, prev = -1;
     if (deint_mode_) {
-        if (d.deint) field = d.lone ? d.lone : (deint_field_ ? deint_field_ : (codec_ == 0 && d.fpoc[1] < d.fpoc[0] ? 2 : 1));
+        if (d.deint) field = d.lone ? d.lone : (deint_field_ ? deint_field_ : ((codec_ == 0 || codec_ == 4) && d.fpoc[1] < d.fpoc[0] ? 2 : 1));
         display_fields_.push_back((uint8_t)field);
         // field rate: the frame leaves twice, the other field second (a lone field has no other one); bit 26 of the entry says so
         both = deint_rate_ && field && !d.lone;
@@ -1908,6 +1924,7 @@ void Decoder::submit_task(PicTask *t) {
     if (ep.has_picture && t->hevc) hevc_fill_engine_pic(t, ep);
     else if (t->hevc && (t->hevc->hash.type > 0 || (t->hevc->hash.type == 0 && verify_md5_)) && !parse_only_) stat_hash_unchecked_++;      // (a failed handle's picture is not decoded: nothing to compare)
     else if (ep.has_picture && t->jpeg) jpeg_fill_engine_pic(t, ep);
+    else if (ep.has_picture && t->mpeg2) mpeg2_fill_engine_pic(t, ep);
     else if (ep.has_picture) {
         JobSlot &js = jobs_[t->job_slot];
         const int n_mbs = t->sps.mb_w * t->sps.mb_h;
@@ -2122,7 +2139,7 @@ int Decoder::decode(const uint8_t *buf, int len, int *got_frame) {
                      "Elapsed Time:\t%d ms\n"
                      "Decode FPS:\t%f fps\n"
                      "==========================================\n",
-                     codec_ == 0 ? "H.264" : (codec_ == 1 ? "H.265" : "MJPEG"), out_w_, out_h_, fmt, deint, place, (int)num_frames_,
+                     codec_ == 0 ? "H.264" : (codec_ == 1 ? "H.265" : (codec_ == 4 ? "MPEG-2" : "MJPEG")), out_w_, out_h_, fmt, deint, place, (int)num_frames_,
                      (int)elapsed_ms_, elapsed_ms_ > 0 ? (double)num_frames_ * 1000.0 / elapsed_ms_ : 0.0);
         }
     }

@@ -12,6 +12,7 @@
 #include "hevc_slice.h"
 #include "hevc_sei.h"
 #include "jpeg_syntax.h"
+#include "mpeg2_syntax.h"
 #include "jobs.h"
 #include "scale_packed.h"    // build_scale_taps
 #include "chroma_packed.h"   // build_chroma_taps
@@ -87,6 +88,9 @@ struct HevcTask {
 // MJPEG picture (codec_type 2): its headers' snapshot, its entropy-coded bytes, and where the packed job list sits in the job buffer
 struct JpegTask { JpegPic pic; std::vector<uint8_t> data; size_t off_first = 0, off_count = 0, off_entries = 0; int n_entries = 0; };
 
+// MPEG-2 picture (codec_type 4): its headers' snapshot with the slices' bytes, the reference surfaces, and where the job list sits in the job buffer
+struct Mpeg2Task { Mpeg2Pic pic; int ref_slot[2] = {-1, -1}; size_t off_mbs = 0, off_entries = 0; int n_entries = 0; };
+
 struct PicTask {
     uint64_t seq = 0;
     bool has_picture = false;
@@ -97,6 +101,7 @@ struct PicTask {
     std::vector<SliceTask> slices;
     std::unique_ptr<HevcTask> hevc;            // codec_type 1
     std::unique_ptr<JpegTask> jpeg;            // codec_type 2
+    std::unique_ptr<Mpeg2Task> mpeg2;          // codec_type 4
     std::vector<int> out_before, out_after;    // frames to display before / after this picture (Decoder::display_entry)
     bool wait_prev_pack = false;               // current surface was displayed by the previous picture (no cooling slack)
     // written by the parse worker
@@ -249,6 +254,15 @@ private:
     bool jpeg_activate(const JpegPic &pic);
     void jpeg_parse_task(PicTask *t);
     void jpeg_fill_engine_pic(PicTask *t, struct EnginePic &ep);
+    // ---- MPEG-2 front end (mpeg2_decoder.cpp) ----
+    void mpeg2_feed(const uint8_t *buf, size_t len);
+    void mpeg2_flush();
+    void mpeg2_after_split();
+    void mpeg2_handle_picture(Mpeg2Pic &pic);
+    bool mpeg2_activate(const Mpeg2Seq &seq);
+    void mpeg2_show_anchor(std::vector<int> &out);
+    void mpeg2_parse_task(PicTask *t);
+    void mpeg2_fill_engine_pic(PicTask *t, struct EnginePic &ep);
     void gpu_close();
     void submit_ready();
     void submit_task(PicTask *t);
@@ -404,6 +418,12 @@ private:
     JpegSplitter jsplit_; JpegTables jtab_;
     int j_w_ = 0, j_h_ = 0, j_sampling_ = 0; unsigned j_surf_rr_ = 0;
     std::atomic<long long> stat_jpeg_pics_{0}, stat_jpeg_ri_{0};
+    // MPEG-2 state (front end only unless noted)
+    Mpeg2Splitter m2split_; Mpeg2Seq m2seq_; long long m2_damaged_seen_ = 0;
+    int m2_anchor_[2] = {-1, -1};              // surfaces of the older / newer anchor picture (-1: none)
+    bool m2_anchor_shown_ = true;              // the newer anchor has been queued for display (it waits for the next anchor, or the flush)
+    std::atomic<long long> stat_dropped_{0}, stat_m2_clamped_{0}, stat_m2_rff_{0};
+    uint64_t m2_digest_ = 1469598103934665603ull; long long m2_digest_mbs_ = 0;      // written by the parse worker (sync option)
     struct TraceRec { uint64_t seq; long long t_dispatch, t_parsed, t_submit0, t_submit1; int is_i; };
     std::vector<TraceRec> trace_; bool trace_on_ = false;
 };

@@ -487,6 +487,19 @@ void Engine::launch(Lane &ln, Batch &b) {
         }
     }
     if (any_jpeg && profile_ && !b.jev[0]) for (auto &e : b.jev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
+    // ... and the same for MPEG-2 pictures
+    bool any_mpeg2 = false; int max_mpeg2_items = 0;
+    for (auto &p : b.pics) any_mpeg2 |= p.codec == 4 && p.has_picture;
+    if (any_mpeg2 && !b.h_mpics) {
+        if (hipHostMalloc((void **)&b.h_mpics, sizeof(Mpeg2PicParams) * kMaxBatch, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc((void **)&b.d_mpics, sizeof(Mpeg2PicParams) * kMaxBatch) != hipSuccess) {
+            (void)hipGetLastError();
+            if (b.h_mpics) hipHostFree(b.h_mpics);
+            b.h_mpics = nullptr; b.d_mpics = nullptr; any_mpeg2 = false;
+            for (auto &p : b.pics) if (p.codec == 4 && p.has_picture) { p.has_picture = false; p.dec->on_engine_error("hipMalloc(MPEG-2 parameter table) failed"); }
+        }
+    }
+    if (any_mpeg2 && profile_ && !b.m2ev[0]) for (auto &e : b.m2ev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
     // pictures to verify (option verify_hash): the result words, when the batch first holds one.  Without them the pictures go unverified, and say so
     b.any_hash = false;
     for (auto &p : b.pics) b.any_hash |= p.codec == 1 && p.has_picture && p.hp.hash_mode != 0;
@@ -526,6 +539,10 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (any_jpeg) {
             if (p.codec == 2 && p.has_picture) { b.h_jpics[i] = p.jp; max_jpeg_items = std::max(max_jpeg_items, p.jp.n_items); b.alg[7] += p.jpeg_alg_bytes; b.npics[7]++; }
             else b.h_jpics[i].n_items = 0;
+        }
+        if (any_mpeg2) {
+            if (p.codec == 4 && p.has_picture) { b.h_mpics[i] = p.mp; max_mpeg2_items = std::max(max_mpeg2_items, p.mp.n_items); b.alg[11] += p.mpeg2_alg_bytes; b.npics[11]++; }
+            else b.h_mpics[i].n_items = 0;
         }
         b.h_pics[i] = p.pp;
         if (!p.has_picture || hevc) b.h_pics[i].stages = 0;
@@ -608,6 +625,7 @@ void Engine::launch(Lane &ln, Batch &b) {
     if (any_hevc) hipMemcpyAsync(b.d_hpics, b.h_hpics, sizeof(HevcPicParams) * n, hipMemcpyHostToDevice, ps);
     else hipMemcpyAsync(b.d_pics, b.h_pics, sizeof(PicParams) * n, hipMemcpyHostToDevice, ps);
     if (any_jpeg) hipMemcpyAsync(b.d_jpics, b.h_jpics, sizeof(JpegPicParams) * n, hipMemcpyHostToDevice, ps);
+    if (any_mpeg2) hipMemcpyAsync(b.d_mpics, b.h_mpics, sizeof(Mpeg2PicParams) * n, hipMemcpyHostToDevice, ps);
     b.out.each([&](auto &t) { for (int side : {kBefore, kAfter}) if (t.n[side])
         hipMemcpyAsync(t.dev + side * kOutSideCap, t.h(side), sizeof(*t.host) * t.n[side], hipMemcpyHostToDevice, ps); });
     // job lists were copied on the (in-order) copy stream when the pictures were parsed: waiting for the most recently
@@ -653,6 +671,14 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (timed) hipEventRecord(b.jev[0], st);
         launch_jpeg_recon(b.d_jpics, n, max_jpeg_items, st);
         if (timed) { hipEventRecord(b.jev[1], st); b.pmask |= 1024; }
+    }
+    // MPEG-2 pictures of the batch: Engine::form let a stream's further pictures in only when they reference nothing the batch writes, so one launch
+    // reconstructs them all (their references were finished by earlier batches on this in-order stream)
+    if (any_mpeg2 && max_mpeg2_items > 0) {
+        const bool timed = profile_ && b.m2ev[0] && b.m2ev[1];
+        if (timed) hipEventRecord(b.m2ev[0], st);
+        launch_mpeg2_recon(b.d_mpics, n, max_mpeg2_items, st);
+        if (timed) { hipEventRecord(b.m2ev[1], st); b.pmask |= 32768; }
     }
     b.any_bipred = b.any_field = false;
     for (auto &p : b.pics) { b.any_bipred |= p.has_picture && p.codec == 0 && p.bipred; b.any_field |= p.has_picture && p.codec == 0 && p.pp.field != 0; }
@@ -934,6 +960,7 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
         add(6, 14, 15, b.pmask & 256); add(6, 16, 17, b.pmask & 512); add(8, 4, 18, b.pmask & 2048);
         add(10, 19, 20, b.pmask & 8192); add(10, 21, 22, b.pmask & 16384);
         if (b.pmask & 1024) { float ms = 0; if (hipEventElapsedTime(&ms, b.jev[0], b.jev[1]) == hipSuccess) { st_.ns[7] += ms * 1e6; st_.launches[7]++; } }
+        if (b.pmask & 32768) { float ms = 0; if (hipEventElapsedTime(&ms, b.m2ev[0], b.m2ev[1]) == hipSuccess) { st_.ns[11] += ms * 1e6; st_.launches[11]++; } }
         if (b.pmask & 4096) { float ms = 0; if (hipEventElapsedTime(&ms, b.mev[0], b.mev[1]) == hipSuccess) { st_.ns[9] += ms * 1e6; st_.launches[9]++; } }
         for (int k = 0; k < kKernelClasses; k++) { st_.pics[k] += b.npics[k]; st_.alg_bytes[k] += b.alg[k]; }
         st_.batches++; st_.batch_pics += (long long)b.pics.size();

@@ -17,6 +17,7 @@
 #include "out_tables.h"
 #include "hevc_jobs.h"
 #include "jpeg_jobs.h"
+#include "mpeg2_jobs.h"
 #include <atomic>
 #include <condition_variable>
 #include <deque>
@@ -56,9 +57,11 @@ struct EnginePic {
     Decoder *dec = nullptr;
     bool has_picture = false;
     PicParams pp;                                   // device pointers already resolved by the decoder
-    int codec = 0;                                  // 0 = H.264 (pp), 1 = HEVC (hp), 2 = MJPEG (jp; hp is zero but for hp.cur, the surface slot)
+    int codec = 0;                                  // 0 = H.264 (pp), 1 = HEVC (hp), 2 = MJPEG (jp; hp is zero but for hp.cur, the surface slot),
+                                                    // 4 = MPEG-2 (mp; hp likewise)
     HevcPicParams hp;
     JpegPicParams jp; long long jpeg_alg_bytes = 0;
+    Mpeg2PicParams mp; long long mpeg2_alg_bytes = 0;
     int job_slot = -1;
     ihipEvent_t *uploaded = nullptr; unsigned long long upload_seq = 0;   // job list copy (copy stream), see Engine::upload
     OutSide out[2];                                 // display frames to pack before (kBefore) / after (kAfter) this picture's kernels
@@ -82,8 +85,8 @@ struct EnginePic {
     bool hash_md5 = false; uint8_t md5_want[3][16] = {};
     // chaining: the engine currently forms chain launches -- an intra picture that can join one stays on the ordinary lane
     int lane(bool chaining = false) const {
-        // MJPEG pictures ride the HEVC lane: its batches run everything on the lane's stream, with no pre-stream and no chain logic
-        if (codec == 2) return kHevcLane;
+        // MJPEG and MPEG-2 pictures ride the HEVC lane: its batches run everything on the lane's stream, with no pre-stream and no chain logic
+        if (codec == 2 || codec == 4) return kHevcLane;
         if (codec == 1) return (has_picture && hp.n_pus == 0 && hp.n_itbs > 0) ? kHevcIntraLane : kHevcLane;
         return (has_picture && (pp.stages & PS_INTRA_LDS) && !(chaining && chain_intra)) ? kIntraLane : kOrdinaryLane;
     }
@@ -91,8 +94,9 @@ struct EnginePic {
 
 // per kernel class: 0 recon_inter, 1 intra, 2 deblock (prep+lds), 3 packout (every pack-out kernel), 4 chain (k_chain: recon + deblock),
 // 5 rgb_pack (k_rgb_pack alone: its frames are counted in class 3 too), 6 deint (k_deint alone, likewise), 7 jpeg (k_jpeg_recon),
-// 8 pichash (k_hevc_pichash: pictures hashed, 1.5 w h bytes each), 9 md5 (k_hevc_md5, likewise)
-constexpr int kKernelClasses = 11;
+// 8 pichash (k_hevc_pichash: pictures hashed, 1.5 w h bytes each), 9 md5 (k_hevc_md5, likewise), 10 rgb_pack444 (k_rgb_pack444 alone),
+// 11 mpeg2 (k_mpeg2_recon)
+constexpr int kKernelClasses = 12;
 struct EngineStats {
     double ns[kKernelClasses] = {}; long long launches[kKernelClasses] = {}, pics[kKernelClasses] = {}, alg_bytes[kKernelClasses] = {};
     long long batches = 0, batch_pics = 0, chain_batches = 0, chain_pics = 0, wait_errors = 0, chain_recoveries = 0;
@@ -158,6 +162,8 @@ private:
         // the same for MJPEG pictures, and the two profile events around k_jpeg_recon: all created when the batch first holds such a picture
         // (Engine::launch) -- a process without a codec-2 handle never allocates them
         JpegPicParams *h_jpics = nullptr, *d_jpics = nullptr; ihipEvent_t *jev[2] = {nullptr, nullptr};
+        // ... and for MPEG-2 pictures, around k_mpeg2_recon
+        Mpeg2PicParams *h_mpics = nullptr, *d_mpics = nullptr; ihipEvent_t *m2ev[2] = {nullptr, nullptr};
         int *d_progress = nullptr;                            // CTB row progress counters of k_hevc_intra
         int *d_ctl = nullptr;                                 // H.264: kMaxBatch control blocks (chain_common.h), cleared once per batch
         int *h_err = nullptr, *d_err = nullptr;               // error words, one per picture: pinned host memory and its device address

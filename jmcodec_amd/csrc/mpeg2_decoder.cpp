@@ -1,0 +1,182 @@
+// jmcodec_amd/csrc/mpeg2_decoder.cpp -- the MPEG-2 half of jmamd::Decoder (codec_type 4 = NV_CODEC_MPEG2, nv_dec/nv_dec.h:37-46 of the reference).
+//
+// The input is any chunking of an ISO/IEC 13818-2 video elementary stream.  The caller thread cuts it at start codes, reads the headers and
+// reassembles pictures (Mpeg2Splitter; what is accepted, what fails the handle: INTEGRATION.md "MPEG-2"), keeps the two anchor pictures and the
+// display order, and picks a surface; a parse worker runs the slice / macroblock VLC decode into the job list (mpeg2_jobs.h); the engine runs
+// k_mpeg2_recon on the HEVC lane and packs the display frames out behind it.  Job slots, output slots and the hand-over to the engine are shared
+// with the other codecs (decoder.cpp).
+#include "decoder.h"
+#include "engine.h"
+#include "mpeg2_jobs.h"
+#include <hip/hip_runtime_api.h>
+#include <algorithm>
+#include <cstring>
+
+namespace jmamd {
+
+// Two anchors and the picture being decoded are held by the stream itself; the rest lets pictures stay in flight: a surface is free once it is
+// neither an anchor nor waiting for its pack-out, and the cold ones (displayed two pictures ago or earlier) are taken first, as for HEVC.  The
+// engine orders every writer of a surface behind the batches that read or display it.
+constexpr int kMpeg2Surfaces = 8;
+
+void Decoder::mpeg2_feed(const uint8_t *buf, size_t len) {
+    m2split_.feed(buf, len, [&](Mpeg2Pic &p) { if (!failed_) mpeg2_handle_picture(p); });
+    mpeg2_after_split();
+}
+
+// end of stream: the picture in progress is decoded as far as its slices go
+void Decoder::mpeg2_flush() {
+    m2split_.flush([&](Mpeg2Pic &p) { if (!failed_) mpeg2_handle_picture(p); });
+    mpeg2_after_split();
+}
+
+void Decoder::mpeg2_after_split() {
+    if (m2split_.damaged_headers > m2_damaged_seen_) {
+        stat_errors_ += m2split_.damaged_headers - m2_damaged_seen_; m2_damaged_seen_ = m2split_.damaged_headers;
+        note_error("MPEG-2: a damaged header was skipped");
+    }
+    if (m2split_.refused() && !failed_) { stat_errors_++; fail(m2split_.error()); }
+}
+
+// the newer anchor leaves for display: when the next anchor arrives, at a new sequence, at the flush.  at: the decode index it is displayed behind
+void Decoder::mpeg2_show_anchor(std::vector<int> &out) {
+    const int s = m2_anchor_[1];
+    if (s < 0 || m2_anchor_shown_) return;
+    out.push_back(display_entry(s)); display_pocs_.push_back(dpb_[s].poc);
+    dpb_[s].out_at = decode_count_;
+    m2_anchor_shown_ = true;
+}
+
+bool Decoder::mpeg2_activate(const Mpeg2Seq &s) {
+    bool changed = !seq_active_ || s.width != m2seq_.width || s.height != m2seq_.height || s.progressive_sequence != m2seq_.progressive_sequence;
+    // the colour description of a sequence_display_extension; without one the standard's default, matrix 1.  Limited range either way
+    { const int vui[4] = {0, s.have_colour ? s.primaries : -1, s.have_colour ? s.transfer : -1, s.have_colour ? s.matrix : 1}; resolve_color(vui, (s.height + 1) & ~1); }
+    s.sar(&sar_[0], &sar_[1]);
+    // 4:2:0 of MPEG-2: chroma sited with the left luma column, between the lines (location 0)
+    if (resolve_chroma_loc(-1, -1, 0)) changed = true;
+    if (!changed) { m2seq_ = s; return true; }
+    if (s.mb_w() > 1024 || s.mb_h() > 1056 || (long long)s.mb_w() * s.mb_h() > 139264) {
+        stat_errors_++; fail("MPEG-2: a picture of " + std::to_string(s.width) + "x" + std::to_string(s.height) + " is larger than the handle's surfaces carry");
+        return false;
+    }
+    if (seq_active_) {
+        // a new size starts a new sequence, like an SPS change: the last anchor is displayed, then everything that refers to the old surfaces drains
+        mpeg2_show_anchor(carry_out_);
+        auto t = std::make_unique<PicTask>();
+        t->out_before = std::move(carry_out_); carry_out_.clear();
+        push_task(std::move(t));
+        { std::unique_lock<std::mutex> lk(mtx_); cv_.wait(lk, [&] { return outstanding_ == 0 && parse_pending_ == 0; }); }
+        if (gpu_open_) { hipSetDevice(device_); free_surfaces(); free_job_buffers(); free_out_slots(false); }
+        else free_job_buffers();
+    }
+    m2seq_ = s;
+    disp_w_ = (s.width + 1) & ~1; disp_h_ = (s.height + 1) & ~1;
+    mb_w_ = s.mb_w(); mb_h_ = s.mb_h();
+    n_surf_ = kMpeg2Surfaces; extra_surf_ = 0;
+    for (auto &d : dpb_) d = DpbPic();
+    m2_anchor_[0] = m2_anchor_[1] = -1; m2_anchor_shown_ = true;
+    if (n_jobs_set_) n_jobs_ = std::min(n_jobs_, kJpegJobSlots);
+    if (!gpu_alloc_sequence()) return false;
+    display_delay_ = std::min(display_delay_, n_jobs_ - 4);
+    seq_active_ = true;
+    if (!timer_started_) { t0_ = std::chrono::steady_clock::now(); timer_started_ = true; }
+    return true;
+}
+
+void Decoder::mpeg2_handle_picture(Mpeg2Pic &pic) {
+    if (!pic.have_ext) { stat_errors_++; note_error("MPEG-2: a picture header without its picture coding extension was skipped"); return; }
+    if (!mpeg2_activate(pic.seq)) return;
+    const bool anchor = pic.type != 3;
+    // a P picture before the first I, a B picture without both of its anchors (the leading B pictures of an open group): dropped, not errors
+    if ((pic.type == 2 && m2_anchor_[1] < 0) || (pic.type == 3 && (m2_anchor_[0] < 0 || m2_anchor_[1] < 0))) { stat_dropped_++; return; }
+    auto mt = std::make_unique<Mpeg2Task>();
+    mt->ref_slot[0] = pic.type == 2 ? m2_anchor_[1] : (pic.type == 3 ? m2_anchor_[0] : -1);
+    mt->ref_slot[1] = pic.type == 3 ? m2_anchor_[1] : -1;
+    // (a new anchor references the newer anchor at most: the older one, displayed when the newer one arrived, retires first)
+    if (anchor && m2_anchor_[0] >= 0) dpb_[m2_anchor_[0]].in_use = false;
+    int slot = -1, warm = -1; bool wait_pack = false;
+    for (int i = 0; i < n_surf_; i++) if (slot_free(i)) { if (decode_count_ >= dpb_[i].out_at + 2) { slot = i; break; } if (warm < 0) warm = i; }
+    if (slot < 0 && warm >= 0) { slot = warm; wait_pack = true; }
+    if (slot < 0) { stat_errors_++; fail("MPEG-2: no free surface"); return; }
+    DpbPic &c = dpb_[slot];
+    c = DpbPic(); c.decode_idx = decode_count_; c.poc = decode_count_;
+    c.color = color_matrix_ | color_range_ << 4;
+    c.deint = deint_when_ == 1 || !pic.progressive_frame;        // auto: the pictures that say they are two fields
+    c.fpoc[0] = pic.top_field_first ? 0 : 1; c.fpoc[1] = 1 - c.fpoc[0];      // (the field first in time is the one the deinterlacer keeps)
+    c.in_use = anchor;
+    auto t = std::make_unique<PicTask>();
+    t->has_picture = true; t->cur_slot = slot; t->wait_prev_pack = wait_pack;
+    t->out_before = std::move(carry_out_); carry_out_.clear();
+    if (anchor) {                                                // the anchor before it is displayed now; this one when the next arrives, or at the flush
+        mpeg2_show_anchor(t->out_after);
+        m2_anchor_[0] = m2_anchor_[1]; m2_anchor_[1] = slot; m2_anchor_shown_ = false;
+    } else { t->out_after.push_back(display_entry(slot)); display_pocs_.push_back(c.poc); c.out_at = decode_count_; }
+    decode_count_++;
+    (pic.type == 1 ? stat_i_ : (pic.type == 2 ? stat_p_ : stat_b_))++;
+    if (pic.repeat_first_field) stat_m2_rff_++;                  // recorded; no frame is repeated
+    first_sh_ = SliceHeader(); first_sh_.type = pic.type == 1 ? SL_I : (pic.type == 2 ? SL_P : SL_B);
+    mt->pic = std::move(pic);
+    t->mpeg2 = std::move(mt);
+    t->job_slot = acquire_job_slot();
+    push_task(std::move(t));
+}
+
+// worker: the slices of one picture into macroblock records and entries
+void Decoder::mpeg2_parse_task(PicTask *t) {
+    auto pt0 = std::chrono::steady_clock::now();
+    Mpeg2Task &mt = *t->mpeg2;
+    JobSlot &js = jobs_[t->job_slot];
+    static thread_local Mpeg2Jobs jobs;
+    bool refuse = false;
+    const std::string e = mpeg2_decode_picture(mt.pic, jobs, &refuse);
+    if (!e.empty()) { t->error = e; stat_errors_++; if (refuse) fail(e); else note_error(e); }
+    if (jobs.clamped) { stat_m2_clamped_ += jobs.clamped; stat_errors_++; note_error("MPEG-2: vectors that reach outside the reference picture were clamped"); }
+    std::vector<uint8_t>().swap(mt.pic.data);
+    size_t off = 0;
+    auto place = [&](size_t bytes) { size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
+    mt.off_mbs = place(jobs.mbs.size() * sizeof(Mpeg2Mb)); mt.off_entries = place(jobs.entries.size() * 4);
+    mt.n_entries = (int)jobs.entries.size();
+    t->n_slices = 1;
+    if (!ensure_job_cap(js, off + 64)) fail("job buffer allocation failed");
+    else {
+        memset(js.host, 0, off);
+        memcpy(js.host + mt.off_mbs, jobs.mbs.data(), jobs.mbs.size() * sizeof(Mpeg2Mb));
+        if (!jobs.entries.empty()) memcpy(js.host + mt.off_entries, jobs.entries.data(), jobs.entries.size() * 4);
+        t->upload_bytes = off;
+        if (want_digest_ || want_job_digest_) {      // over the records and the entries (pictures are parsed in order: the digest option is synchronous)
+            uint64_t h = m2_digest_; for (size_t i = 0; i < off; i++) { h ^= js.host[i]; h *= 1099511628211ull; }
+            m2_digest_ = h; m2_digest_mbs_ += (long long)jobs.mbs.size();
+            if (want_job_digest_) job_digest_ = h;
+        }
+        stat_pictures_++; stat_job_bytes_ += (long long)off; stat_coef_ += (long long)jobs.entries.size();
+        if (!parse_only_ && !failed_) t->upload_seq = engine_->upload(js.dev, js.host, off, js.uploaded, false);
+    }
+    (mt.pic.type == 1 ? stat_parse_ns_i_ : stat_parse_ns_p_) += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - pt0).count();
+    t->state.store(1, std::memory_order_release);
+    submit_ready();
+    { std::lock_guard<std::mutex> lk(mtx_); parse_pending_--; cv_.notify_all(); }
+}
+
+// describe the picture to the device engine (called by submit_task)
+void Decoder::mpeg2_fill_engine_pic(PicTask *t, EnginePic &ep) {
+    const Mpeg2Task &mt = *t->mpeg2;
+    JobSlot &js = jobs_[t->job_slot];
+    ep.codec = 4; ep.uploaded = js.uploaded; ep.upload_seq = t->upload_seq;
+    memset(&ep.hp, 0, sizeof ep.hp);
+    ep.hp.cur = t->cur_slot;                             // (the engine's surface bookkeeping reads the slot here for every codec but H.264)
+    Mpeg2PicParams &mp = ep.mp;
+    memset(&mp, 0, sizeof mp);
+    mp.surf = surf_[t->cur_slot]; mp.pitch = pitch_; mp.chroma_offset = chroma_off_;
+    int n_refs = 0;
+    // (the independence rule of Engine::form: a picture stays out of a batch that writes one of the surfaces named here)
+    for (int d = 0; d < 2; d++) if (mt.ref_slot[d] >= 0) { mp.ref[d] = surf_[mt.ref_slot[d]]; ep.ref_mask |= 1u << mt.ref_slot[d]; n_refs++; }
+    mp.mb_w = mb_w_; mp.mb_h = mb_h_;
+    mp.n_items = mb_h_ * ((mb_w_ + 3) / 4);
+    mp.n_entries = mt.n_entries; mp.dc_mult = 8 >> mt.pic.intra_dc_precision;
+    mp.mbs = (const Mpeg2Mb *)(js.dev + mt.off_mbs); mp.entries = (const uint32_t *)(js.dev + mt.off_entries);
+    memcpy(mp.w, mt.pic.seq.w, sizeof mp.w);
+    // algorithmic bytes: the job list in, the reference rows of each direction in, 1.5 W H out
+    ep.mpeg2_alg_bytes = (long long)t->upload_bytes + (long long)(n_refs + 1) * mb_w_ * mb_h_ * 384;
+}
+
+}  // namespace jmamd

@@ -1,0 +1,126 @@
+// jmcodec_amd/csrc/mpeg2_kernels.hip -- k_mpeg2_recon: MPEG-2 frame pictures (codec_type 4) from their job lists into NV12 surfaces, gfx950.
+//
+// One wave per work item; blockIdx.y = picture.  An item is four neighbouring macroblocks of one macroblock row: a 64 x 16 luma strip and a 64 x 8
+// strip of interleaved chroma.  Its 24 blocks go through the IDCT in three rounds of eight: round 0 the blocks Y0 Y1 of the four macroblocks, round 1
+// Y2 Y3, round 2 Cb Cr.  Per round:
+//   scatter   lane l: block b = l >> 3 (macroblock b >> 1), entry lane i = l & 7.  The block's levels go into zeroed LDS, dequantised and saturated on
+//             the way (mpeg2_dequant);
+//   pass 1    lane l: column i of block b.  The eight lanes of a block add up their columns (three xor shuffles inside the group of eight) and the
+//             lane of column 7 toggles the low bit of F[7][7] when the sum is even -- mismatch control, only for a block that has entries;
+//   pass 2    lane l: row y = l >> 3 of block bb = l & 7, eight residuals.  The lane fetches the prediction of its eight samples straight from the
+//             reference surfaces (byte rows at a stride of pitch, or 2 pitch for field prediction; every coordinate clamped to the picture, so no
+//             record can make it read outside a surface), reconstructs and stores 8 bytes.  Luma: strip row 8 r + y (frame DCT) or 2 y + r (field
+//             DCT, which only changes which strip rows a block's rows land on), bytes 8 bb ..: a store instruction writes eight 64-byte rows.  Chroma:
+//             the lanes of Cb and Cr of one macroblock (bb ^ 1) swap halves with one xor shuffle, so that each writes 8 interleaved bytes: eight
+//             64-byte rows again.
+// The arithmetic is mpeg2_recon.h's, shared with the host checks.  No MFMA: a 1080p picture is 50 M integer multiply-adds.
+// LDS, by the bank rules of gfx950 (a 4-byte or narrower read and every write: bank = dword mod 32, serviced in 32-lane halves; a 16-byte read: bank =
+// dword mod 64, in four fixed 16-lane groups) -- the layout and the access patterns are those of k_jpeg_recon:
+//   F  int16, 8 x 8 per block, block stride kFStride = 72 (36 dwords): the column read of pass 1 takes 4 dwords per block, 4 blocks per half at
+//      dwords 0, 36, 72, 108 -- banks 0, 4, 8, 12: no conflict.  (The scatter's 2-byte writes go where the entries say; the zeroing is one 16-byte
+//      write per lane at consecutive addresses.)
+//   g  int32, row stride kGRow = 12, block stride kGStride = 112: the write of pass 1 puts 8 lanes of each of 4 blocks at banks 0, 16, 0, 16 (+ 12 y):
+//      2-way, which a 4-byte write hides behind its own data transfer; the two 16-byte reads of pass 2 (lane = block l & 7, row l >> 3) take 16
+//      distinct 4-bank slots in each of the four groups: no conflict.
+// 4 waves x (8 x 72 x 2 + 8 x 112 x 4) = 18,944 bytes per workgroup.  These counts are worked out from the addresses, not measured.
+// Every barrier is reached by every wave of the workgroup: the three rounds are unconditional, inactive waves and macroblocks beyond the row's end run
+// with empty blocks and store nothing, and the only early return is taken by a whole workgroup before the first barrier.  No lane leaves before the
+// last shuffle.
+#include <hip/hip_runtime.h>
+#include "mpeg2_jobs.h"
+#include "mpeg2_recon.h"
+
+namespace jmamd {
+
+constexpr int kM2Waves = 4;
+constexpr int kM2FStride = 72, kM2GRow = 12, kM2GStride = 112;
+
+__global__ __launch_bounds__(64 * kM2Waves) void k_mpeg2_recon(const Mpeg2PicParams *pics) {
+    const Mpeg2PicParams &pp = pics[blockIdx.y];
+    if ((int)blockIdx.x * kM2Waves >= pp.n_items) return;              // (the whole workgroup: no barrier is left behind)
+    __shared__ __attribute__((aligned(16))) int16_t sF[kM2Waves][8][kM2FStride];
+    __shared__ __attribute__((aligned(16))) int sG[kM2Waves][8][kM2GStride];
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int item = (int)blockIdx.x * kM2Waves + wave;
+    const bool active = item < pp.n_items;
+    const int spr = (pp.mb_w + 3) >> 2;                                 // strips per macroblock row
+    const int row = item / spr, mbx0 = (item - row * spr) * 4;
+    const int W = pp.mb_w * 16, H = pp.mb_h * 16;
+    const int b = l >> 3, i = l & 7;                                    // scatter and pass 1: block b, entry lane / column i
+    const int bb = l & 7, y = l >> 3;                                   // pass 2: row y of block bb
+    // the macroblock whose blocks this lane scatters (ms) and the one whose samples it reconstructs (mp)
+    Mpeg2Mb ms = {}, mp = {};
+    const bool valid_s = active && mbx0 + (b >> 1) < pp.mb_w, valid_p = active && mbx0 + (bb >> 1) < pp.mb_w;
+    if (valid_s) ms = pp.mbs[(size_t)row * pp.mb_w + mbx0 + (b >> 1)];
+    if (valid_p) mp = pp.mbs[(size_t)row * pp.mb_w + mbx0 + (bb >> 1)];
+    const bool intra_s = (ms.flags & M2_INTRA) != 0;
+    const uint8_t *wq = pp.w[intra_s ? 0 : 1];
+#pragma unroll 1
+    for (int r = 0; r < 3; r++) {
+        *reinterpret_cast<uint4 *>(&sF[wave][b][i * 8]) = make_uint4(0, 0, 0, 0);
+        __syncthreads();
+        const int k = r < 2 ? 2 * r + (b & 1) : 4 + (b & 1);
+        uint32_t first = 0;
+        const int cnt = valid_s ? mpeg2_block_entries(ms, k, pp.n_entries, &first) : 0;
+        for (int e = i; e < cnt; e += 8) {
+            const uint32_t v = pp.entries[first + e];
+            const int pos = (int)(v & 63);
+            sF[wave][b][pos] = (int16_t)mpeg2_dequant((int)(int16_t)(v >> 16), pos, intra_s, wq[pos], ms.qscale, pp.dc_mult);
+        }
+        __syncthreads();
+        {
+            int F[8], g[8], sum = 0;
+#pragma unroll
+            for (int v = 0; v < 8; v++) { F[v] = sF[wave][b][v * 8 + i]; sum += F[v]; }
+            sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 2); sum += __shfl_xor(sum, 4);
+            if (cnt > 0 && i == 7 && !(sum & 1)) F[7] ^= 1;
+            jpeg_pass1(F, g);
+#pragma unroll
+            for (int yy = 0; yy < 8; yy++) sG[wave][b][yy * kM2GRow + i] = g[yy];
+        }
+        __syncthreads();
+        int res[8]; uint8_t s[8];
+        {
+            int g[8];
+            const int4 g0 = *reinterpret_cast<const int4 *>(&sG[wave][bb][y * kM2GRow]), g1 = *reinterpret_cast<const int4 *>(&sG[wave][bb][y * kM2GRow + 4]);
+            g[0] = g0.x; g[1] = g0.y; g[2] = g0.z; g[3] = g0.w; g[4] = g1.x; g[5] = g1.y; g[6] = g1.z; g[7] = g1.w;
+            mpeg2_pass2(g, res);
+        }
+        if (r < 2) {
+            const int sr = (mp.flags & M2_FIELD_DCT) ? 2 * y + r : 8 * r + y;
+            const int X = (mbx0 + (bb >> 1)) * 16 + (bb & 1) * 8, Y = row * 16 + sr;
+            if (valid_p) {
+                mpeg2_recon8(mp, pp.ref, pp.pitch, 1, false, W, H, X, Y, res, s);
+                uint2 px;
+                px.x = (uint32_t)s[0] | (uint32_t)s[1] << 8 | (uint32_t)s[2] << 16 | (uint32_t)s[3] << 24;
+                px.y = (uint32_t)s[4] | (uint32_t)s[5] << 8 | (uint32_t)s[6] << 16 | (uint32_t)s[7] << 24;
+                if (X + 8 <= W && Y < H) *reinterpret_cast<uint2 *>(pp.surf + (size_t)Y * pp.pitch + X) = px;
+            }
+        } else {
+            const int c = bb & 1, X = (mbx0 + (bb >> 1)) * 8, Y = row * 8 + y;
+            s[0] = s[1] = s[2] = s[3] = s[4] = s[5] = s[6] = s[7] = 0;
+            if (valid_p) {
+                const uint8_t *refc[2] = {pp.ref[0] ? pp.ref[0] + pp.chroma_offset + c : nullptr, pp.ref[1] ? pp.ref[1] + pp.chroma_offset + c : nullptr};
+                mpeg2_recon8(mp, refc, pp.pitch, 2, true, W >> 1, H >> 1, X, Y, res, s);
+            }
+            // the Cb lane keeps samples 0..3 and gets Cr's 0..3; the Cr lane keeps 4..7 and gets Cb's 4..7
+            const uint32_t lo = (uint32_t)s[0] | (uint32_t)s[1] << 8 | (uint32_t)s[2] << 16 | (uint32_t)s[3] << 24;
+            const uint32_t hi = (uint32_t)s[4] | (uint32_t)s[5] << 8 | (uint32_t)s[6] << 16 | (uint32_t)s[7] << 24;
+            const uint32_t got = (uint32_t)__shfl_xor((int)(c ? lo : hi), 1);
+            const uint32_t cb = c ? got : lo, cr = c ? hi : got;      // four Cb and four Cr samples of the same positions
+            uint2 px;
+            px.x = (cb & 0xff) | (cr & 0xff) << 8 | (cb & 0xff00) << 8 | (cr & 0xff00) << 16;
+            px.y = (cb >> 16 & 0xff) | (cr >> 16 & 0xff) << 8 | (cb >> 24) << 16 | (cr >> 24) << 24;
+            if (valid_p && 2 * X + 16 <= W && Y < (H >> 1))
+                *reinterpret_cast<uint2 *>(pp.surf + pp.chroma_offset + (size_t)Y * pp.pitch + 2 * X + c * 8) = px;
+        }
+        __syncthreads();                                                // (sG is read above and written by the next round's pass 1)
+    }
+}
+
+void launch_mpeg2_recon(const Mpeg2PicParams *d_pics, int n, int max_items, ihipStream_t *st) {
+    if (n <= 0 || max_items <= 0) return;
+    hipLaunchKernelGGL(k_mpeg2_recon, dim3((max_items + kM2Waves - 1) / kM2Waves, n), dim3(64 * kM2Waves), 0, st, d_pics);
+}
+
+}  // namespace jmamd

@@ -36,10 +36,12 @@ namespace jmamd { void launch_frame_to_argb(const uint8_t *, int, int, int, uint
 void launch_frame_to_nv12_pitch(const uint8_t *, int, int, int, uint8_t *, int, ihipStream_t *) { abort(); } }
 #include "../jmcodec_amd/csrc/hevc_kernels.h"
 #include "../jmcodec_amd/csrc/jpeg_jobs.h"
+#include "../jmcodec_amd/csrc/mpeg2_jobs.h"
 namespace jmamd {
 void launch_hevc_picture_batch(const HevcPicParams *, int, const HevcBatchDims &, int *, ihipStream_t *, ihipEvent_t **, uint32_t *) { abort(); }
 void launch_hevc_pichash(const HevcPicParams *, int, int, uint32_t *, ihipStream_t *) { abort(); }
 void launch_hevc_md5(const HevcPicParams *, int, uint32_t *, ihipStream_t *) { abort(); }
 void launch_jpeg_recon(const JpegPicParams *, int, int, ihipStream_t *) { abort(); }
+void launch_mpeg2_recon(const Mpeg2PicParams *, int, int, ihipStream_t *) { abort(); }
 void hevc_kernels_init() {}
 }
