@@ -42,6 +42,13 @@ jm_amddec_handle jm_amddec_create_handle(void);
  * interleaved Huffman scan), every picture lands in the usual NV12 surface and every output option applies; progressive, arithmetic, lossless, 12-bit,
  * CMYK and other samplings fail the handle with an error string (INTEGRATION.md "MJPEG").  extra_data is not used.  Stats: jpeg_pictures, jpeg_sampling
  * (0x22 / 0x21 / 0x11 / 0x10), jpeg_restart_intervals; with option profile k_jpeg_ns / _n / _pics / _alg_bytes.
+ * Option "jpeg_device_entropy" (before init; 0 default / 1 / 2; other values and other codecs are refused): 1 = a picture whose scan has a restart interval and
+ * at least 2 segments is Huffman-decoded on the device (k_jpeg_entropy, one lane per restart segment), the others on the host; 2 = every picture is (one
+ * without DRI as a single segment: slow for a lone large picture).  The host then uploads the Huffman tables, a segment table and the unstuffed bytes
+ * instead of the job list (layout: INTEGRATION.md "MJPEG").  Undamaged pictures decode identically; damage is contained per segment -- the rest of that
+ * segment is empty, the other segments decode -- where the host path empties everything behind the damage.  Stats: jpeg_dev_pictures, jpeg_host_pictures,
+ * jpeg_dev_segments, jpeg_dev_damaged_segments; with option profile k_jpeg_entropy_ns / _n / _pics / _alg_bytes.  It pays with many streams or many segments
+ * per picture; a lone 1080p stream loses with one MCU row per segment and draws level from about 340 segments on (INTEGRATION.md has the figures).
  * MPEG-2: the input is any chunking of an ISO/IEC 13818-2 video elementary stream (one start-code unit per call included); frame pictures I / P / B,
  * 4:2:0, progressive and interlaced; MPEG-1, field pictures, dual prime, 4:2:2 / 4:4:4, the scalable extensions and D pictures fail the handle with
  * an error string that names the feature (INTEGRATION.md "MPEG-2").  extra_data, if given, is read as the beginning of the stream.  Stats:

@@ -181,6 +181,10 @@ int Decoder::set_option(const char *key, long long v) {
         if (inited_ || v < 0 || v > 1) return -1;
         verify_md5_ = (int)v;
     }
+    else if (k == "jpeg_device_entropy") {   // MJPEG: 1 = restart-interval pictures are Huffman-decoded on the device (k_jpeg_entropy), 2 = every picture
+        if (inited_ || v < 0 || v > 2) return -1;
+        jpeg_dev_entropy_ = (int)v;
+    }
     else if (k == "rgb_chroma") {            // RGB output: 1 = chroma interpolated to full resolution at the stream's siting (k_rgb_pack444)
         if (inited_ || v < 0 || v > 1) return -1;
         rgb_chroma_ = (int)v;
@@ -287,6 +291,11 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "jpeg_pictures") return stat_jpeg_pics_;
     if (k == "jpeg_sampling") return codec_ == 2 && seq_active_ ? j_sampling_ : 0;
     if (k == "jpeg_restart_intervals") return stat_jpeg_ri_;
+    // option jpeg_device_entropy: pictures whose scan went to k_jpeg_entropy / to the host decoder, segments of the former, and how many the device found damaged
+    if (k == "jpeg_dev_pictures") return stat_jpeg_dev_pics_;
+    if (k == "jpeg_host_pictures") return stat_jpeg_host_pics_;
+    if (k == "jpeg_dev_segments") return stat_jpeg_dev_segs_;
+    if (k == "jpeg_dev_damaged_segments") return stat_jpeg_dev_damaged_;
     // MPEG-2: pictures dropped for want of their anchors, macroblocks whose vectors the host clamped, pictures with repeat_first_field, the profile
     if (k == "dropped_pictures") return stat_dropped_;
     if (k == "mpeg2_clamped_mbs") return stat_m2_clamped_;
@@ -331,7 +340,7 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "wait_slot_ns") return stat_wait_slot_ns_;
     if (k == "parse_ns_p") return stat_parse_ns_p_;
     if (k.rfind("k_", 0) == 0 || k.rfind("eng_", 0) == 0) {          // engine-wide (all handles on this device), profile option
-        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5", "rgb_pack444", "mpeg2"};
+        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5", "rgb_pack444", "mpeg2", "jpeg_entropy"};
         if (!engine_) return 0;
         EngineStats es = engine_->stats();
         for (int i = 0; i < kKernelClasses; i++) {
@@ -397,6 +406,7 @@ int Decoder::init(int codec_type, int out_fmt, const uint8_t *extra, int len) {
         "surface is tied to the H.264 / HEVC picture buffer"); return -1; }
     if (codec_type == 2 && deint_temporal_) { fail("option deinterlace_temporal is not available for MJPEG (codec_type 2): its surfaces are dealt round robin, "
         "a displayed one cannot be kept for the next picture"); return -1; }
+    if (codec_type != 2 && jpeg_dev_entropy_) { fail("option jpeg_device_entropy is only available for MJPEG (codec_type 2)"); return -1; }
     if (rgb_chroma_ && !rgb_) { fail("option rgb_chroma needs RGB output: set an RGB spec (jm_amddec_set_rgb) before init"); return -1; }
     if (getenv("JM_AMD_DEC_SYNC")) sync_mode_ = true;
     if (const char *js = getenv("JM_AMD_DEC_JOB_SLOTS")) { n_jobs_ = std::max(8, std::min(atoi(js), kMaxJobSlots)); n_jobs_set_ = true; }
@@ -500,7 +510,7 @@ void Decoder::free_job_buffers() {
     for (auto &j : jobs_) {
         if (j.big >= 0) { j.host = j.own_host; j.dev = j.own_dev; j.big = -1; }       // (a borrowed buffer is freed with the others below)
         if (gpu_open_ && !parse_only_) { if (j.host) hipHostFree(j.host); if (j.dev) hipFree(j.dev); if (j.dbrec) hipFree(j.dbrec);
-            if (j.resid) hipFree(j.resid); if (j.uploaded) hipEventDestroy(j.uploaded); }
+            if (j.resid) hipFree(j.resid); if (j.dev_only) hipFree(j.dev_only); if (j.uploaded) hipEventDestroy(j.uploaded); }
         else free(j.host);
         j = JobSlot();
     }

@@ -86,7 +86,11 @@ struct HevcTask {
 };
 
 // MJPEG picture (codec_type 2): its headers' snapshot, its entropy-coded bytes, and where the packed job list sits in the job buffer
-struct JpegTask { JpegPic pic; std::vector<uint8_t> data; size_t off_first = 0, off_count = 0, off_entries = 0; int n_entries = 0; };
+// on_device: option jpeg_device_entropy sends the picture's scan to k_jpeg_entropy -- the job buffer then holds tables, segment table and clean bytes
+// (off_tab, off_segs, off_bytes), and off_first / off_count / off_entries are offsets into the slot's device-only buffer; host_error: the
+// segmenter has already counted the picture in `errors`
+struct JpegTask { JpegPic pic; std::vector<uint8_t> data; size_t off_first = 0, off_count = 0, off_entries = 0; int n_entries = 0;
+    bool on_device = false, host_error = false; size_t off_tab = 0, off_segs = 0, off_bytes = 0; int n_segs = 0; };
 
 // MPEG-2 picture (codec_type 4): its headers' snapshot with the slices' bytes, the reference surfaces, and where the job list sits in the job buffer
 struct Mpeg2Task { Mpeg2Pic pic; int ref_slot[2] = {-1, -1}; size_t off_mbs = 0, off_entries = 0; int n_entries = 0; };
@@ -121,6 +125,9 @@ struct JobSlot {                       // one picture's job list: pinned host bu
     // device scratch of k_deblock_prep for this picture (96 B per macroblock): per slot, because pictures of a chain run concurrently
     uint8_t *dbrec = nullptr;
     ihipEvent_t *uploaded = nullptr;   // recorded behind the H2D copy on the engine's copy stream
+    // MJPEG, option jpeg_device_entropy: what only the device reads and writes (first / count / entries of k_jpeg_entropy): device memory with no
+    // page-locked mirror, grown on demand (Decoder::ensure_dev_only); a parse-only handle records the size and allocates nothing
+    uint8_t *dev_only = nullptr; size_t dev_only_cap = 0;
     bool busy = false;                 // from dispatch until the engine reports the picture done
     int big = -1;                      // >= 0: host / dev / cap are those of borrowed big buffer `big` (an I picture); the slot's own are kept below
     uint8_t *own_host = nullptr, *own_dev = nullptr; size_t own_cap = 0;
@@ -199,6 +206,8 @@ public:
     void on_picture_hash(const struct EnginePic &p, const uint32_t *words, int bad);
     // ... and of a picture that carried an MD5 SEI (option verify_md5): digests = 3 x 16 bytes, Y, Cb, Cr; bad as above
     void on_picture_md5(const struct EnginePic &p, const uint8_t *digests, int bad);
+    // engine: the status words k_jpeg_entropy left for a device-path MJPEG picture (damaged segments, kinds of damage: jpeg_jobs.h)
+    void on_jpeg_entropy_status(const struct EnginePic &p, uint32_t damaged, uint32_t kinds);
     struct EngineDecoderState &engine_state() { return *eng_state_; }
     // display frames that are decoded and packed and that the caller has not fetched yet (the engine asks: is this handle's next picture urgent?)
     int frames_done_unfetched() const { return done_unfetched_.load(std::memory_order_relaxed); }
@@ -247,12 +256,14 @@ private:
     void hevc_parse_task(PicTask *t);
     void hevc_fill_engine_pic(PicTask *t, struct EnginePic &ep);
     bool ensure_job_cap(JobSlot &js, size_t bytes, size_t keep = 0);
+    bool ensure_dev_only(JobSlot &js, size_t bytes);      // (jpeg_decoder.cpp)
     // ---- MJPEG front end (jpeg_decoder.cpp) ----
     void jpeg_feed(const uint8_t *buf, size_t len);
     void jpeg_flush();
     void jpeg_handle_picture(const uint8_t *p, size_t n, bool truncated);
     bool jpeg_activate(const JpegPic &pic);
     void jpeg_parse_task(PicTask *t);
+    void jpeg_parse_task_device(PicTask *t);   // option jpeg_device_entropy: the segmenter instead of the Huffman decode
     void jpeg_fill_engine_pic(PicTask *t, struct EnginePic &ep);
     // ---- MPEG-2 front end (mpeg2_decoder.cpp) ----
     void mpeg2_feed(const uint8_t *buf, size_t len);
@@ -418,6 +429,10 @@ private:
     JpegSplitter jsplit_; JpegTables jtab_;
     int j_w_ = 0, j_h_ = 0, j_sampling_ = 0; unsigned j_surf_rr_ = 0;
     std::atomic<long long> stat_jpeg_pics_{0}, stat_jpeg_ri_{0};
+    // option jpeg_device_entropy (before init): 0 host Huffman decode; 1 pictures with a restart interval and at least 2 segments are entropy-decoded
+    // by k_jpeg_entropy; 2 every picture is
+    int jpeg_dev_entropy_ = 0;
+    std::atomic<long long> stat_jpeg_dev_pics_{0}, stat_jpeg_host_pics_{0}, stat_jpeg_dev_segs_{0}, stat_jpeg_dev_damaged_{0};
     // MPEG-2 state (front end only unless noted)
     Mpeg2Splitter m2split_; Mpeg2Seq m2seq_; long long m2_damaged_seen_ = 0;
     int m2_anchor_[2] = {-1, -1};              // surfaces of the older / newer anchor picture (-1: none)

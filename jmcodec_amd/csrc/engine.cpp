@@ -487,6 +487,24 @@ void Engine::launch(Lane &ln, Batch &b) {
         }
     }
     if (any_jpeg && profile_ && !b.jev[0]) for (auto &e : b.jev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
+    // ... of which some are entropy-decoded on the device (option jpeg_device_entropy): the parameter table of k_jpeg_entropy, the status words and
+    // their pinned copy, when this slot of the ring first holds one.  A batch without such a picture reaches none of this
+    b.any_jdev = false; int max_jpeg_segs = 0;
+    if (any_jpeg) for (auto &p : b.pics) b.any_jdev |= p.codec == 2 && p.has_picture && p.jpeg_on_device;
+    if (b.any_jdev && !b.h_jents) {
+        const size_t sb = sizeof(uint32_t) * kMaxBatch * kJpegStatusWords;
+        if (hipHostMalloc((void **)&b.h_jents, sizeof(JpegEntropyParams) * kMaxBatch, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc((void **)&b.d_jents, sizeof(JpegEntropyParams) * kMaxBatch) != hipSuccess ||
+            hipMalloc((void **)&b.d_jstatus, sb) != hipSuccess || hipHostMalloc((void **)&b.h_jstatus, sb, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            if (b.h_jents) hipHostFree(b.h_jents); if (b.d_jents) hipFree(b.d_jents); if (b.d_jstatus) hipFree(b.d_jstatus);
+            b.h_jents = nullptr; b.d_jents = nullptr; b.d_jstatus = nullptr; b.h_jstatus = nullptr; b.any_jdev = false;
+            // no quiet fall-back: the pictures' lists would never be written
+            for (auto &p : b.pics) if (p.codec == 2 && p.has_picture && p.jpeg_on_device) { p.has_picture = false; p.dec->on_engine_error("hipMalloc(MJPEG entropy parameter table) failed"); }
+            any_jpeg = false; for (auto &p : b.pics) any_jpeg |= p.codec == 2 && p.has_picture;
+        }
+    }
+    if (b.any_jdev && profile_ && !b.jeev[0]) for (auto &e : b.jeev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
     // ... and the same for MPEG-2 pictures
     bool any_mpeg2 = false; int max_mpeg2_items = 0;
     for (auto &p : b.pics) any_mpeg2 |= p.codec == 4 && p.has_picture;
@@ -539,6 +557,11 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (any_jpeg) {
             if (p.codec == 2 && p.has_picture) { b.h_jpics[i] = p.jp; max_jpeg_items = std::max(max_jpeg_items, p.jp.n_items); b.alg[7] += p.jpeg_alg_bytes; b.npics[7]++; }
             else b.h_jpics[i].n_items = 0;
+        }
+        if (b.any_jdev) {
+            if (p.codec == 2 && p.has_picture && p.jpeg_on_device) { b.h_jents[i] = p.je; b.h_jents[i].status = b.d_jstatus + (size_t)i * kJpegStatusWords;
+                max_jpeg_segs = std::max(max_jpeg_segs, p.je.n_segs); b.alg[12] += p.jpeg_entropy_alg_bytes; b.npics[12]++; }
+            else b.h_jents[i].n_segs = 0;
         }
         if (any_mpeg2) {
             if (p.codec == 4 && p.has_picture) { b.h_mpics[i] = p.mp; max_mpeg2_items = std::max(max_mpeg2_items, p.mp.n_items); b.alg[11] += p.mpeg2_alg_bytes; b.npics[11]++; }
@@ -625,6 +648,7 @@ void Engine::launch(Lane &ln, Batch &b) {
     if (any_hevc) hipMemcpyAsync(b.d_hpics, b.h_hpics, sizeof(HevcPicParams) * n, hipMemcpyHostToDevice, ps);
     else hipMemcpyAsync(b.d_pics, b.h_pics, sizeof(PicParams) * n, hipMemcpyHostToDevice, ps);
     if (any_jpeg) hipMemcpyAsync(b.d_jpics, b.h_jpics, sizeof(JpegPicParams) * n, hipMemcpyHostToDevice, ps);
+    if (b.any_jdev) hipMemcpyAsync(b.d_jents, b.h_jents, sizeof(JpegEntropyParams) * n, hipMemcpyHostToDevice, ps);
     if (any_mpeg2) hipMemcpyAsync(b.d_mpics, b.h_mpics, sizeof(Mpeg2PicParams) * n, hipMemcpyHostToDevice, ps);
     b.out.each([&](auto &t) { for (int side : {kBefore, kAfter}) if (t.n[side])
         hipMemcpyAsync(t.dev + side * kOutSideCap, t.h(side), sizeof(*t.host) * t.n[side], hipMemcpyHostToDevice, ps); });
@@ -665,6 +689,16 @@ void Engine::launch(Lane &ln, Batch &b) {
         }
         if (hd.any_hash || (hd.any_md5 && b.d_hash)) hipMemcpyAsync(b.h_hash, b.d_hash, sizeof(uint32_t) * (size_t)n * kHashStride, hipMemcpyDeviceToHost, st);
         if (hd.any_hash) { b.pmask |= 2048; b.last_ev = 18; }
+    }
+    // MJPEG pictures whose scan the device decodes: k_jpeg_entropy writes the lists k_jpeg_recon reads, on the same in-order stream; the status words
+    // come back behind the kernel, as the hashes do (Engine::complete hands them to the handles)
+    if (b.any_jdev && max_jpeg_segs > 0) {
+        const bool timed = profile_ && b.jeev[0] && b.jeev[1];
+        hipMemsetAsync(b.d_jstatus, 0, sizeof(uint32_t) * (size_t)n * kJpegStatusWords, st);
+        if (timed) hipEventRecord(b.jeev[0], st);
+        launch_jpeg_entropy(b.d_jents, n, max_jpeg_segs, st);
+        if (timed) { hipEventRecord(b.jeev[1], st); b.pmask |= 65536; }
+        hipMemcpyAsync(b.h_jstatus, b.d_jstatus, sizeof(uint32_t) * (size_t)n * kJpegStatusWords, hipMemcpyDeviceToHost, st);
     }
     if (any_jpeg && max_jpeg_items > 0) {        // MJPEG pictures of the batch: independent of everything else in it
         const bool timed = profile_ && b.jev[0] && b.jev[1];
@@ -960,6 +994,7 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
         add(6, 14, 15, b.pmask & 256); add(6, 16, 17, b.pmask & 512); add(8, 4, 18, b.pmask & 2048);
         add(10, 19, 20, b.pmask & 8192); add(10, 21, 22, b.pmask & 16384);
         if (b.pmask & 1024) { float ms = 0; if (hipEventElapsedTime(&ms, b.jev[0], b.jev[1]) == hipSuccess) { st_.ns[7] += ms * 1e6; st_.launches[7]++; } }
+        if (b.pmask & 65536) { float ms = 0; if (hipEventElapsedTime(&ms, b.jeev[0], b.jeev[1]) == hipSuccess) { st_.ns[12] += ms * 1e6; st_.launches[12]++; } }
         if (b.pmask & 32768) { float ms = 0; if (hipEventElapsedTime(&ms, b.m2ev[0], b.m2ev[1]) == hipSuccess) { st_.ns[11] += ms * 1e6; st_.launches[11]++; } }
         if (b.pmask & 4096) { float ms = 0; if (hipEventElapsedTime(&ms, b.mev[0], b.mev[1]) == hipSuccess) { st_.ns[9] += ms * 1e6; st_.launches[9]++; } }
         for (int k = 0; k < kKernelClasses; k++) { st_.pics[k] += b.npics[k]; st_.alg_bytes[k] += b.alg[k]; }
@@ -1023,6 +1058,11 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
         int bad = -1;
         for (int c = 2; c >= 0; c--) if (got[c] != p.hash_want[c]) bad = c;
         p.dec->on_picture_hash(p, words, bad);
+    }
+    // option jpeg_device_entropy: the damage k_jpeg_entropy met, per picture (a failed batch's pictures are reported failed below)
+    if (b.any_jdev && b.h_jstatus && !failed) for (size_t i = 0; i < b.pics.size(); i++) {
+        const EnginePic &p = b.pics[i];
+        if (p.codec == 2 && p.has_picture && p.jpeg_on_device) p.dec->on_jpeg_entropy_status(p, b.h_jstatus[i * kJpegStatusWords], b.h_jstatus[i * kJpegStatusWords + 1]);
     }
     for (auto &p : b.pics) p.dec->on_engine_done(p, failed);
     b.pics.clear();

@@ -61,6 +61,8 @@ struct EnginePic {
                                                     // 4 = MPEG-2 (mp; hp likewise)
     HevcPicParams hp;
     JpegPicParams jp; long long jpeg_alg_bytes = 0;
+    // option jpeg_device_entropy: k_jpeg_entropy decodes the scan in front of k_jpeg_recon (je.status is set by Engine::launch)
+    bool jpeg_on_device = false, jpeg_host_error = false; JpegEntropyParams je; long long jpeg_entropy_alg_bytes = 0;
     Mpeg2PicParams mp; long long mpeg2_alg_bytes = 0;
     int job_slot = -1;
     ihipEvent_t *uploaded = nullptr; unsigned long long upload_seq = 0;   // job list copy (copy stream), see Engine::upload
@@ -95,8 +97,8 @@ struct EnginePic {
 // per kernel class: 0 recon_inter, 1 intra, 2 deblock (prep+lds), 3 packout (every pack-out kernel), 4 chain (k_chain: recon + deblock),
 // 5 rgb_pack (k_rgb_pack alone: its frames are counted in class 3 too), 6 deint (k_deint alone, likewise), 7 jpeg (k_jpeg_recon),
 // 8 pichash (k_hevc_pichash: pictures hashed, 1.5 w h bytes each), 9 md5 (k_hevc_md5, likewise), 10 rgb_pack444 (k_rgb_pack444 alone),
-// 11 mpeg2 (k_mpeg2_recon)
-constexpr int kKernelClasses = 12;
+// 11 mpeg2 (k_mpeg2_recon), 12 jpeg_entropy (k_jpeg_entropy)
+constexpr int kKernelClasses = 13;
 struct EngineStats {
     double ns[kKernelClasses] = {}; long long launches[kKernelClasses] = {}, pics[kKernelClasses] = {}, alg_bytes[kKernelClasses] = {};
     long long batches = 0, batch_pics = 0, chain_batches = 0, chain_pics = 0, wait_errors = 0, chain_recoveries = 0;
@@ -162,6 +164,10 @@ private:
         // the same for MJPEG pictures, and the two profile events around k_jpeg_recon: all created when the batch first holds such a picture
         // (Engine::launch) -- a process without a codec-2 handle never allocates them
         JpegPicParams *h_jpics = nullptr, *d_jpics = nullptr; ihipEvent_t *jev[2] = {nullptr, nullptr};
+        // MJPEG pictures with option jpeg_device_entropy: the parameter table of k_jpeg_entropy, the status words (kJpegStatusWords per picture) with
+        // their pinned copy, the two profile events -- created when the batch first holds such a picture, like h_jpics and d_hash
+        JpegEntropyParams *h_jents = nullptr, *d_jents = nullptr; uint32_t *d_jstatus = nullptr, *h_jstatus = nullptr; ihipEvent_t *jeev[2] = {nullptr, nullptr};
+        bool any_jdev = false;
         // ... and for MPEG-2 pictures, around k_mpeg2_recon
         Mpeg2PicParams *h_mpics = nullptr, *d_mpics = nullptr; ihipEvent_t *m2ev[2] = {nullptr, nullptr};
         int *d_progress = nullptr;                            // CTB row progress counters of k_hevc_intra

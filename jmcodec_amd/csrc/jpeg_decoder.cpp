@@ -82,6 +82,9 @@ void Decoder::jpeg_handle_picture(const uint8_t *p, size_t n, bool truncated) {
     decode_count_++;
     stat_i_++; stat_jpeg_pics_++;
     if (jt->pic.restart_interval) stat_jpeg_ri_++;
+    // option jpeg_device_entropy: 1 takes the pictures whose scan is at least two restart segments, 2 takes every picture (one without DRI is one segment)
+    jt->on_device = jpeg_dev_entropy_ == 2 || (jpeg_dev_entropy_ == 1 && jt->pic.restart_interval > 0 && jpeg_expected_segments(jt->pic) >= 2);
+    if (jt->on_device) { stat_jpeg_dev_pics_++; stat_jpeg_dev_segs_ += jpeg_expected_segments(jt->pic); } else if (jpeg_dev_entropy_) stat_jpeg_host_pics_++;
     t->jpeg = std::move(jt);
     first_sh_ = SliceHeader(); first_sh_.type = SL_I;
     t->job_slot = acquire_job_slot();
@@ -93,6 +96,7 @@ void Decoder::jpeg_parse_task(PicTask *t) {
     auto pt0 = std::chrono::steady_clock::now();
     JpegTask &jt = *t->jpeg;
     JobSlot &js = jobs_[t->job_slot];
+    if (jt.on_device) { jpeg_parse_task_device(t); return; }
     static thread_local JpegJobs jobs;
     const std::string e = jpeg_decode_scan(jt.pic, jt.data.data(), jt.data.size(), jobs);
     if (!e.empty()) { t->error = e; stat_errors_++; note_error(e); }
@@ -118,6 +122,71 @@ void Decoder::jpeg_parse_task(PicTask *t) {
     { std::lock_guard<std::mutex> lk(mtx_); parse_pending_--; cv_.notify_all(); }
 }
 
+// what only the device touches: no page-locked mirror (ensure_job_cap sizes both sides alike, which is right for what is uploaded)
+bool Decoder::ensure_dev_only(JobSlot &js, size_t bytes) {
+    if (bytes <= js.dev_only_cap) return true;
+    const size_t cap = bytes + bytes / 2 + 4096;
+    if (parse_only_ || !gpu_open_) { js.dev_only_cap = cap; return true; }           // (nothing reads it: only the size is kept)
+    hipSetDevice(device_);
+    uint8_t *d = nullptr;
+    if (hipMalloc((void **)&d, cap) != hipSuccess) { (void)hipGetLastError(); return false; }
+    // the slot belongs to the picture being parsed: nothing on the device refers to the old buffer any more (see acquire_job_slot)
+    if (js.dev_only) hipFree(js.dev_only);
+    js.dev_only = d; js.dev_only_cap = cap;
+    return true;
+}
+
+// worker, option jpeg_device_entropy: one pass over the scan cuts it into clean segments; the Huffman decode itself is k_jpeg_entropy's
+void Decoder::jpeg_parse_task_device(PicTask *t) {
+    auto pt0 = std::chrono::steady_clock::now();
+    JpegTask &jt = *t->jpeg;
+    JobSlot &js = jobs_[t->job_slot];
+    static thread_local JpegSegments segs;
+    const std::string e = jpeg_segment_scan(jt.pic, jt.data.data(), jt.data.size(), segs);
+    if (!e.empty()) { t->error = e; jt.host_error = true; stat_errors_++; note_error(e); }
+    std::vector<uint8_t>().swap(jt.data);
+    const size_t n_blocks = (size_t)jt.pic.n_blocks();
+    size_t off = 0;
+    auto place = [&](size_t bytes) { size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
+    // uploaded: tables, segment table, clean bytes
+    jt.off_tab = place(6 * sizeof(JpegDevHuff)); jt.off_segs = place(segs.segs.size() * sizeof(JpegSegment)); jt.off_bytes = place(segs.bytes.size());
+    const size_t up = off;
+    // device only: the three arrays k_jpeg_entropy writes and k_jpeg_recon reads
+    off = 0;
+    jt.off_first = place(n_blocks * 4); jt.off_count = place(n_blocks); jt.off_entries = place((size_t)segs.n_entries * 4);
+    const size_t dev_only = off;
+    jt.n_entries = (int)segs.n_entries; jt.n_segs = (int)segs.segs.size();
+    t->n_slices = 1;
+    if (!ensure_job_cap(js, up + 64) || !ensure_dev_only(js, dev_only + 64)) fail("job buffer allocation failed");
+    else {
+        jpeg_device_tables(jt.pic, (JpegDevHuff *)(js.host + jt.off_tab));
+        memset(js.host + jt.off_tab + 6 * sizeof(JpegDevHuff), 0, jt.off_segs - jt.off_tab - 6 * sizeof(JpegDevHuff));
+        if (!segs.segs.empty()) memcpy(js.host + jt.off_segs, segs.segs.data(), segs.segs.size() * sizeof(JpegSegment));
+        memset(js.host + jt.off_segs + segs.segs.size() * sizeof(JpegSegment), 0, jt.off_bytes - jt.off_segs - segs.segs.size() * sizeof(JpegSegment));
+        if (!segs.bytes.empty()) memcpy(js.host + jt.off_bytes, segs.bytes.data(), segs.bytes.size());
+        memset(js.host + jt.off_bytes + segs.bytes.size(), 0, up - jt.off_bytes - segs.bytes.size());
+        t->upload_bytes = up;
+        if (want_job_digest_) { uint64_t h = job_digest_; for (size_t i = 0; i < up; i++) { h ^= js.host[i]; h *= 1099511628211ull; } job_digest_ = h; }
+        stat_pictures_++; stat_job_bytes_ += (long long)up;
+        if (!parse_only_ && !failed_) t->upload_seq = engine_->upload(js.dev, js.host, up, js.uploaded, false);
+    }
+    stat_parse_ns_i_ += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - pt0).count();
+    t->state.store(1, std::memory_order_release);
+    submit_ready();
+    { std::lock_guard<std::mutex> lk(mtx_); parse_pending_--; cv_.notify_all(); }
+}
+
+// engine thread: what k_jpeg_entropy reported for a device-path picture.  Damage is contained per segment (INTEGRATION.md "MJPEG"); the picture is
+// handed out, and counted in `errors` once -- not again when the segmenter had counted it already
+void Decoder::on_jpeg_entropy_status(const EnginePic &p, uint32_t damaged, uint32_t kinds) {
+    if (!damaged) return;
+    stat_jpeg_dev_damaged_ += damaged;
+    if (p.jpeg_host_error) return;
+    stat_errors_++;
+    note_error((kinds & (kJpegDamageCode | kJpegDamageCap)) ? "MJPEG: an invalid Huffman code (damaged picture)"
+                                                           : "MJPEG: the entropy-coded data ends early (damaged or truncated picture)");
+}
+
 // describe the picture to the device engine (called by submit_task)
 void Decoder::jpeg_fill_engine_pic(PicTask *t, EnginePic &ep) {
     const JpegTask &jt = *t->jpeg;
@@ -134,7 +203,18 @@ void Decoder::jpeg_fill_engine_pic(PicTask *t, EnginePic &ep) {
     jp.n_items_y = ((jp.y_bw + 7) / 8) * jp.y_bh;
     jp.n_items = jp.n_items_y + ((jp.c_bw + 3) / 4) * jp.c_bh;
     jp.n_blocks = jt.pic.n_blocks(); jp.n_entries = jt.n_entries;
-    jp.first = (const uint32_t *)(js.dev + jt.off_first); jp.count = js.dev + jt.off_count; jp.entries = (const uint32_t *)(js.dev + jt.off_entries);
+    uint8_t *lists = jt.on_device ? js.dev_only : js.dev;        // (device path: written by k_jpeg_entropy in front of k_jpeg_recon; n_entries is the capacity)
+    jp.first = (const uint32_t *)(lists + jt.off_first); jp.count = lists + jt.off_count; jp.entries = (const uint32_t *)(lists + jt.off_entries);
+    ep.jpeg_on_device = jt.on_device; ep.jpeg_host_error = jt.host_error;
+    if (jt.on_device) {
+        JpegEntropyParams &je = ep.je;
+        memset(&je, 0, sizeof je);
+        je.n_segs = jt.n_segs; je.geom = jpeg_scan_geom(jt.pic);
+        je.tab = (const JpegDevHuff *)(js.dev + jt.off_tab); je.segs = (const JpegSegment *)(js.dev + jt.off_segs); je.bytes = (const uint32_t *)(js.dev + jt.off_bytes);
+        je.first = (uint32_t *)(lists + jt.off_first); je.count = lists + jt.off_count; je.entries = (uint32_t *)(lists + jt.off_entries);
+        // algorithmic bytes of k_jpeg_entropy: what was uploaded in, a record per block out (the entries it writes are not known here)
+        ep.jpeg_entropy_alg_bytes = (long long)t->upload_bytes + 5ll * jt.pic.n_blocks();
+    }
     memcpy(jp.q, jt.pic.q, sizeof jp.q);
     // algorithmic bytes: the job list in, 1.5 W H out
     ep.jpeg_alg_bytes = (long long)t->upload_bytes + (long long)disp_w_ * disp_h_ * 3 / 2;

@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
+#include "jpeg_entropy.h"
 
 namespace jmamd {
 
@@ -25,5 +26,22 @@ struct JpegPicParams {
 
 // blockIdx.y = picture; a picture with n_items == 0 takes no part.  max_items: the largest n_items of the batch
 void launch_jpeg_recon(const JpegPicParams *d_pics, int n, int max_items, hipStream_t st);
+
+// Option jpeg_device_entropy: a picture whose scan the device entropy-decodes (k_jpeg_entropy, in front of k_jpeg_recon on the same stream).  The
+// host uploads tables, segment table and clean bytes (jpeg_entropy.h); first / count / entries -- the arrays JpegPicParams names too -- exist in
+// device memory only and are written here.  status: two words of the batch's status array, zeroed before the launch: [0] counts the picture's
+// damaged segments, [1] collects the kinds of damage (kJpegDamage*).
+constexpr int kJpegStatusWords = 2;
+struct JpegEntropyParams {
+    int n_segs;                   // 0: the picture takes no part (host path, another codec, no picture)
+    JpegScanGeom geom;
+    const JpegDevHuff *tab;       // [6]
+    const JpegSegment *segs;      // [n_segs]
+    const uint32_t *bytes;
+    uint32_t *first; uint8_t *count; uint32_t *entries;
+    uint32_t *status;
+};
+// blockIdx.y = picture, one lane per segment.  max_segs: the largest n_segs of the batch
+void launch_jpeg_entropy(const JpegEntropyParams *d_pics, int n, int max_segs, hipStream_t st);
 
 }  // namespace jmamd

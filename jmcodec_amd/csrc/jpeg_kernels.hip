@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include "jpeg_jobs.h"
 #include "jpeg_recon.h"
+#include "jpeg_entropy.h"
 
 namespace jmamd {
 
@@ -112,6 +113,38 @@ __global__ __launch_bounds__(64 * kJpegWaves) void k_jpeg_recon(const JpegPicPar
 void launch_jpeg_recon(const JpegPicParams *d_pics, int n, int max_items, hipStream_t st) {
     if (n <= 0 || max_items <= 0) return;
     hipLaunchKernelGGL(k_jpeg_recon, dim3((max_items + kJpegWaves - 1) / kJpegWaves, n), dim3(64 * kJpegWaves), 0, st, d_pics);
+}
+
+// k_jpeg_entropy: option jpeg_device_entropy -- the Huffman decode of the pictures' restart segments (jpeg_entropy.h has the routine, the layout
+// of what it reads and the bounds of its loops).  blockIdx.y = picture, one lane per segment, 64 consecutive segments of a picture per wave, one
+// wave per workgroup.  Every lane runs the same decode-one-symbol sequence on its own bit window, so lanes diverge only where their blocks begin
+// and end, and where one of them meets damage.
+// Tables: staged in LDS by the workgroup (6 x 1420 = 8520 bytes).  The decode of a lane is one chain of dependent steps -- window -> look[] ->
+// shift -> window -- so the latency of the table read is paid once per symbol and nothing hides it but the other waves of the SIMD; an LDS read
+// is several times shorter than a read that has to come from the vector cache, and 64 lanes index the table at unrelated places, which LDS serves
+// by bank while the cache would serve it by line.  Staging costs 8.5 KB of coalesced reads per wave against some 6 KB of stream bytes per LANE
+// (1080p, one MCU row per segment).  This is reasoning from the code; profiles/r19_mjpeg_device_entropy.txt has what was measured.
+// The stream bytes are read as aligned dwords from global memory, a lane's own 64-byte line lasting it 16 refills; entries, first[] and count[]
+// are plain vector stores.  The status words are raised with ordinary atomics on vector addresses, and only by a lane that met damage.
+__global__ __launch_bounds__(64) void k_jpeg_entropy(const JpegEntropyParams *pics) {
+    const JpegEntropyParams &pp = pics[blockIdx.y];
+    if ((int)blockIdx.x * 64 >= pp.n_segs) return;                      // (the whole workgroup: no barrier is left behind)
+    __shared__ __attribute__((aligned(16))) uint32_t sTab[6 * sizeof(JpegDevHuff) / 4];
+    {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(pp.tab);
+        for (int i = threadIdx.x; i < (int)(6 * sizeof(JpegDevHuff) / 4); i += 64) sTab[i] = src[i];
+    }
+    __syncthreads();
+    const int seg = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (seg >= pp.n_segs) return;
+    const JpegSegment sg = pp.segs[seg];
+    const int damage = jpeg_entropy_segment(pp.geom, reinterpret_cast<const JpegDevHuff *>(sTab), sg, pp.bytes, pp.first, pp.count, pp.entries, nullptr);
+    if (damage) { atomicAdd(pp.status, 1u); atomicOr(pp.status + 1, (uint32_t)damage); }
+}
+
+void launch_jpeg_entropy(const JpegEntropyParams *d_pics, int n, int max_segs, hipStream_t st) {
+    if (n <= 0 || max_segs <= 0) return;
+    hipLaunchKernelGGL(k_jpeg_entropy, dim3((max_segs + 63) / 64, n), dim3(64), 0, st, d_pics);
 }
 
 }  // namespace jmamd

@@ -1,5 +1,6 @@
 // jmcodec_amd/csrc/jpeg_syntax.cpp -- see jpeg_syntax.h.
 #include "jpeg_syntax.h"
+#include <algorithm>
 #include <cstring>
 
 namespace jmamd {
@@ -277,6 +278,55 @@ std::string jpeg_decode_scan(const JpegPic &pic, const uint8_t *data, size_t n, 
         }
     }
     return "";
+}
+
+std::string jpeg_segment_scan(const JpegPic &pic, const uint8_t *data, size_t n, JpegSegments &out) {
+    out.segs.clear(); out.bytes.clear(); out.n_entries = 0;
+    const long long mcus = (long long)pic.mcus_x * pic.mcus_y, want = jpeg_expected_segments(pic);
+    const uint32_t bpm = pic.ncomp == 3 ? (uint32_t)(pic.mcu_w / 8) * (uint32_t)(pic.mcu_h / 8) + 2 : 1;
+    const long long per = pic.restart_interval > 0 ? pic.restart_interval : mcus;
+    std::string err;
+    size_t o = pic.scan_off, end = pic.scan_end;
+    if (o > n || end > n || o > end) { o = end = 0; err = "MJPEG: no entropy-coded data"; }
+    out.bytes.reserve(end - o + (size_t)want * (3 + kJpegSegGuard));
+    bool data_left = true;
+    for (long long i = 0; i < want; i++) {
+        JpegSegment sg;
+        sg.byte_off = (uint32_t)out.bytes.size();
+        sg.first_mcu = (uint32_t)(i * per); sg.n_mcus = (uint32_t)std::min(per, mcus - i * per);
+        bool at_rst = false;
+        while (data_left && o < end) {
+            const uint8_t *f = (const uint8_t *)memchr(data + o, 0xFF, end - o);
+            const size_t stop = f ? (size_t)(f - data) : end;
+            out.bytes.insert(out.bytes.end(), data + o, data + stop);
+            o = stop;
+            if (o >= end) break;
+            if (o + 1 < end && data[o + 1] == 0) { out.bytes.push_back(0xFF); o += 2; continue; }      // a stuffed FF
+            size_t q = o; while (q < end && data[q] == 0xFF) q++;                                    // fill bytes, then the marker
+            if (q < end && data[q] >= 0xD0 && data[q] <= 0xD7) { o = q + 1; at_rst = true; break; }
+            data_left = false;                                  // another marker, or FF at the very end: the data ends here
+        }
+        if (!at_rst && i + 1 < want) {
+            if (data_left || o >= end) { if (err.empty()) err = "MJPEG: a restart marker is missing"; }
+            data_left = false;
+        }
+        sg.n_bytes = (uint32_t)(out.bytes.size() - sg.byte_off);
+        out.bytes.resize(sg.byte_off + jpeg_entropy_padded(sg.n_bytes), 0);
+        sg.first_entry = out.n_entries; sg.entry_cap = jpeg_entropy_capacity(sg.n_bytes, sg.n_mcus * bpm);
+        out.n_entries += sg.entry_cap;
+        out.segs.push_back(sg);
+        if (at_rst && i + 1 == want && err.empty()) err = "MJPEG: more restart markers than the picture has restart intervals (damaged picture)";
+    }
+    return err;
+}
+
+void jpeg_device_tables(const JpegPic &pic, JpegDevHuff out[6]) {
+    memset(out, 0, 6 * sizeof(JpegDevHuff));
+    for (int c = 0; c < pic.ncomp && c < 3; c++) for (int cls = 0; cls < 2; cls++) {
+        const JpegHuff &h = cls ? pic.ac[c] : pic.dc[c]; JpegDevHuff &d = out[3 * cls + c];
+        memcpy(d.look, h.look, sizeof d.look); memcpy(d.maxcode, h.maxcode, sizeof d.maxcode);
+        memcpy(d.valoff, h.valoff, sizeof d.valoff); memcpy(d.vals, h.vals, sizeof d.vals);
+    }
 }
 
 bool JpegSplitter::next(size_t &b, size_t &e) {

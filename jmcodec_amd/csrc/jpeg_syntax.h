@@ -2,6 +2,7 @@
 // ITU-T T.81 baseline / extended sequential Huffman, 8 bits, one interleaved scan; what is accepted and what is refused: INTEGRATION.md "MJPEG".
 // No HIP: the parse pool, tests/native/jpeg_check.cpp and tools/fuzz_jpeg.cpp all build it.
 #pragma once
+#include "jpeg_entropy.h"
 #include <stdint.h>
 #include <stddef.h>
 #include <string>
@@ -57,6 +58,27 @@ struct JpegJobs {
 // Entropy-decode the scan of `pic` (data = the picture's bytes, as given to jpeg_parse_picture).  Every block gets a record whatever happens: after
 // damage (truncation, an invalid code, a missing restart marker) decoding stops, the remaining blocks are empty and the reason is returned.
 std::string jpeg_decode_scan(const JpegPic &pic, const uint8_t *data, size_t n, JpegJobs &jobs);
+
+// Option jpeg_device_entropy: what the device needs to entropy-decode the scan itself (jpeg_entropy.h has the layout and the routine).
+struct JpegSegments {
+    std::vector<JpegSegment> segs;     // one per restart interval (one for the whole scan without DRI); every MCU belongs to exactly one
+    std::vector<uint8_t> bytes;        // the segments' clean bytes: unstuffed, each padded to 4 bytes + kJpegSegGuard zeros
+    uint32_t n_entries = 0;            // sum of the segments' entry capacities
+};
+// One linear pass over [scan_off, scan_end) of `data`.  Fill bytes and RSTn markers (any index) are removed.  Fewer markers than the picture's
+// intervals need: the MCUs not covered get empty segments (length 0) and the reason is returned; more: the surplus is dropped and the reason is
+// returned.  The picture is decodable either way.
+std::string jpeg_segment_scan(const JpegPic &pic, const uint8_t *data, size_t n, JpegSegments &out);
+// the device form of the picture's tables: DC of components 0..2, then AC (components a grey picture lacks: zeros)
+void jpeg_device_tables(const JpegPic &pic, JpegDevHuff out[6]);
+inline JpegScanGeom jpeg_scan_geom(const JpegPic &pic) {
+    return JpegScanGeom{pic.ncomp, pic.mcu_w / 8, pic.mcu_h / 8, pic.mcus_x, pic.y_bw, pic.y_bh, pic.c_bw, pic.c_bh};
+}
+// segments a picture's scan consists of by its headers
+inline long long jpeg_expected_segments(const JpegPic &pic) {
+    const long long mcus = (long long)pic.mcus_x * pic.mcus_y;
+    return pic.restart_interval > 0 ? (mcus + pic.restart_interval - 1) / pic.restart_interval : 1;
+}
 
 // Incremental picture splitter: feed any chunking of a byte stream of concatenated pictures; complete pictures come out whole.
 class JpegSplitter {
