@@ -111,6 +111,10 @@ void Decoder::jpeg_parse_task(PicTask *t) {
         if (!jobs.first.empty()) memcpy(js.host + jt.off_first, jobs.first.data(), jobs.first.size() * 4);
         if (!jobs.count.empty()) memcpy(js.host + jt.off_count, jobs.count.data(), jobs.count.size());
         if (!jobs.entries.empty()) memcpy(js.host + jt.off_entries, jobs.entries.data(), jobs.entries.size() * 4);
+        // the bytes that round each array up to 16 are uploaded and enter the job digest: zero, as on the device path below, not what the allocation held
+        memset(js.host + jt.off_first + jobs.first.size() * 4, 0, jt.off_count - jt.off_first - jobs.first.size() * 4);
+        memset(js.host + jt.off_count + jobs.count.size(), 0, jt.off_entries - jt.off_count - jobs.count.size());
+        memset(js.host + jt.off_entries + jobs.entries.size() * 4, 0, off - jt.off_entries - jobs.entries.size() * 4);
         t->upload_bytes = off;
         if (want_job_digest_) { uint64_t h = job_digest_; for (size_t i = 0; i < off; i++) { h ^= js.host[i]; h *= 1099511628211ull; } job_digest_ = h; }
         stat_pictures_++; stat_job_bytes_ += (long long)off; stat_coef_ += (long long)jobs.entries.size();

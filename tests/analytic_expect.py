@@ -5,11 +5,13 @@ checks the vectorised form against the scalar one), and the chroma formula 8-270
 prediction are 8.3.3 / 8.3.4 typed out.  The closed forms (ramps, half-sample chroma, flat fields) live beside them and are checked against these
 restatements in tests/test_analytic_host.py before any stream relies on them.  Deblocking is clause 8.7 typed out in tests/deblock_ref.py, applied to
 every finished picture before it serves as a reference (the identity cases choose streams on which it changes nothing; the deblock_filters_* cases
-streams on which it changes most macroblocks).  The one residual a script can carry -- a single DC coefficient of +-1 -- is ``dc_only_residual``.
+streams on which it changes most macroblocks).  A single DC coefficient of +-1 (resid=) is ``dc_only_residual``; Intra4x4 / Intra8x8 prediction and the
+levels of coef=dict(...) are clauses 8.3.1, 8.3.2 and 8.5 typed out in tests/h264_recon_ref.py.
 """
 import numpy as np
 
 import deblock_ref
+import h264_recon_ref as rr
 import scripted_h264 as sw
 from spec_tables_h264 import NORM_ADJUST_4x4
 
@@ -157,16 +159,20 @@ def partitions(m):
     return [(0, 0, 16, 8, a, None), (0, 8, 16, 8, b, None)] if m["t"] == "16x8" else [(0, 0, 8, 16, a, None), (8, 0, 8, 16, b, None)]
 
 
-def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None):
+def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong=frozenset(), rstats=None):
     """[(Y, Cb, Cr)] per picture in DECODE order, coded size (multiples of 16), uint8.  stats: counters of deblock_ref; unfiltered: a list that receives
     each picture as reconstructed, before 8.7; stale_ref_of = k: picture k alone is predicted from the UNFILTERED picture k - 1 (what a decoder computes
-    that reads its reference too early; the host test shows that this is visible)."""
+    that reads its reference too early; the host test shows that this is visible).  wrong: wrong-on-purpose switches of tests/h264_recon_ref.py;
+    rstats: a set that receives what the Intra4x4 / Intra8x8 blocks and the residuals exercised."""
     mbw, mbh = (seq["width"] + 15) // 16, (seq["height"] + 15) // 16
     pl = sw.plan(seq, pics)
+    wrong = frozenset(wrong)
+    lists = rr.scaling_matrices(seq, wrong)
     out, raw = [], []
     for k, p in enumerate(pics):
         kind = p["kind"]
         qps = sw.mb_qps(seq, p)
+        nxn_modes = rr.mode_tables(seq, p, wrong, rstats)[1]
         refs = out if stale_ref_of != k else out[:k - 1] + [raw[k - 1]]
         planes = [np.zeros((mbh * 16, mbw * 16), np.uint8), np.zeros((mbh * 8, mbw * 8), np.uint8), np.zeros((mbh * 8, mbw * 8), np.uint8)]
         step = {"mb": 1, "row": mbw, "pic": mbw * mbh}[p.get("layout", "mb" if kind != "I" else "pic")]
@@ -179,15 +185,35 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None):
             x, y = a % mbw, a // mbw
             first = a - a % step
             t = m["t"]
+
+            avail = rr.mb_avail(seq, p, a)
+            RES = rr.mb_residual(seq, m, qps[a], wrong, lists) if "coef" in m else None
+            if RES is not None and rstats is not None:
+                rstats.add(("qp", t, qps[a]))
+                for c in (0, 1, 2):
+                    s = 16 if c == 0 else 8
+                    v = None if t in ("i4", "i8") and c == 0 else RES[c]      # (the luma of I_NxN is counted block by block)
+                    if v is not None and v.any():
+                        rstats.add(("residual_sign", t, c, int(v.min()) < 0, int(v.max()) > 0))
             if t == "pcm":
                 for c, key in enumerate(("y", "cb", "cr")):
                     s = 16 if c == 0 else 8
                     planes[c][y * s:(y + 1) * s, x * s:(x + 1) * s] = m[key]
-            elif t == "i16":
-                al, at = x > 0 and a - 1 >= first, y > 0 and a - mbw >= first
-                planes[0][y * 16:(y + 1) * 16, x * 16:(x + 1) * 16] = intra16_luma(planes[0], x * 16, y * 16, m["mode"], al, at)
+            elif t in ("i16", "i4", "i8"):
+                al, at = avail(-1, 0), avail(0, -1)
+                assert (t != "i16" or m["mode"] != 3) and m["cmode"] != 3 or (al and at and avail(-1, -1)), "plane prediction needs the corner"
+                assert (t != "i16" or (m["mode"] != 0 or at) and (m["mode"] != 1 or al)) and (m["cmode"] != 2 or at) and (m["cmode"] != 1 or al)
+                if t == "i16":
+                    planes[0][y * 16:(y + 1) * 16, x * 16:(x + 1) * 16] = intra16_luma(planes[0], x * 16, y * 16, m["mode"], al, at)
+                else:
+                    rr.intra_nxn_luma(planes[0], x * 16, y * 16, m, nxn_modes[a], RES[0] if RES else np.zeros((16, 16), np.int64), avail, wrong, rstats)
                 for c in (1, 2):
                     planes[c][y * 8:(y + 1) * 8, x * 8:(x + 1) * 8] = intra_chroma(planes[c], x * 8, y * 8, m["cmode"], al, at)
+                if rstats is not None:
+                    rstats.add(("kind", kind, t, "T" * at + "L" * al + "C" * avail(-1, -1) + "R" * avail(1, -1)))
+                    if t == "i16":
+                        rstats.add(("i16", m["mode"], m["cmode"], bool(RES and np.asarray(m["coef"].get("ydc", [0])).any()),
+                                    bool(RES and m["coef"].get("y")), bool(RES and np.asarray(m["coef"].get("cdc", [0])).any()), bool(RES and m["coef"].get("cac"))))
             else:
                 if t == "skip":
                     m = dict(t="16x16", l0=(pl[k]["l0"][0], (0, 0)))        # 8.4.1.1: no neighbour available -> zero vector, RefPicList0[0]
@@ -217,10 +243,24 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None):
                             w0, w1 = implicit_weights(p["poc"], pics[l0[0]]["poc"], pics[l1[0]]["poc"])
                             ent = [(w0, 0), (w1, 0)]
                         planes[c][Yy:Yy + Hh, X:X + W] = weighted(pr[0], pr[1], mode, logwd, ent[0], ent[1])
+                if rstats is not None and RES is not None:
+                    rstats.add(("kind", kind, "inter_t8" if m.get("t8", 0) else "inter", ""))
                 if "resid" in m:
                     bx, by = sw.BLK_XY[m["resid"][0]]
                     blk = planes[0][y * 16 + by:y * 16 + by + 4, x * 16 + bx:x * 16 + bx + 4]
                     blk[:] = clip1(blk.astype(np.int64) + dc_only_residual(qps[a], m["resid"][1]))      # 8.5.14: Clip1(pred + r)
+            if RES is not None and t != "pcm":
+                for c in (0, 1, 2):                                 # 8.5.14: u = Clip1(pred + r) (Intra4x4 / Intra8x8 luma: done block by block above)
+                    if c == 0 and t in ("i4", "i8"):
+                        continue
+                    s = 16 if c == 0 else 8
+                    blk = planes[c][y * s:(y + 1) * s, x * s:(x + 1) * s]
+                    v = blk.astype(np.int64) + RES[c]
+                    if rstats is not None and v.min() < 0:
+                        rstats.add(("clip1_at_0", t, c))
+                    if rstats is not None and v.max() > 255:
+                        rstats.add(("clip1_at_255", t, c))
+                    blk[:] = clip1(v)
         raw.append(tuple(planes))
         out.append(deblock_ref.deblock_picture(seq, pics, pl, k, tuple(planes), stats))
     if unfiltered is not None:
@@ -248,7 +288,7 @@ def expected_frames(seq, pics, fmt, planes=None):
 
 
 def describe_mb(m):
-    return {k: (v if not isinstance(v, np.ndarray) else "samples") for k, v in m.items()}
+    return {k: ("samples" if isinstance(v, np.ndarray) else (sorted(v) if k == "coef" else v)) for k, v in m.items()}
 
 
 def first_difference(seq, pics, got_frames, fmt, planes=None, units="mbs"):

@@ -2,10 +2,11 @@
 macroblock the vertical edges left to right, then the horizontal edges top to bottom, luma and both chroma planes.  Plain Python on lists: it is meant to
 be read beside the clause, not to be fast.  Tables come from tests/spec_tables_h264.py only.
 
-What the script knows decides everything: bS (8.7.2.1) from the macroblock types, the one coded coefficient a macroblock may carry and the vectors and
-reference PICTURES of the 4x4 blocks; qPp / qPq per macroblock (I_PCM counts 0); chroma through QPC with chroma_qp_index_offset, each side mapped before
-the average; FilterOffsetA / B and disable_deblocking_filter_idc of the slice that holds q0; idc 2 leaves slice edges alone; the left and top picture
-edges are never filtered.
+What the script knows decides everything: bS (8.7.2.1) from the macroblock types, the luma 4x4 blocks that carry levels (under the 8x8 transform all
+four blocks of a coded 8x8; scripted_h264.coded_luma_blocks) and the vectors and reference PICTURES of the 4x4 blocks; transform_size_8x8_flag leaves
+the inner 4x4 edges alone; qPp / qPq per macroblock (I_PCM counts 0); chroma through QPC with the plane's own offset (chroma_qp_index_offset for Cb,
+second_chroma_qp_index_offset for Cr), each side mapped before the average; FilterOffsetA / B and disable_deblocking_filter_idc of the slice that
+holds q0; idc 2 leaves slice edges alone; the left and top picture edges are never filtered.
 
 ``stats`` (a dict of counters, keyed "<plane><direction>:<what>" with plane Y / C and direction V / H (vertical / horizontal EDGES)) records which paths
 of the clause the pictures took; tests/test_analytic_host.py asserts from them that the filtering cases really filter on every path."""
@@ -126,8 +127,9 @@ def mb_table(seq, pics, pl, k):
         first = a - a % step
         idc, ao, bo = sw.slice_fields(seq, p, step, p["mbs"][first])[1]
         # 8.7.2.2: qPp = 0 for an I_PCM macroblock
-        out.append(dict(m=m, intra=m["t"] in ("pcm", "i16"), qp=0 if m["t"] == "pcm" else qps[a], slice=first, idc=idc, off_a=2 * ao, off_b=2 * bo,
-                        coef={m["resid"][0]} if "resid" in m else set()))
+        # the luma 4x4 blocks that count as holding coefficients (under the 8x8 transform: all four of a coded 8x8) and transform_size_8x8_flag
+        out.append(dict(m=m, intra=m["t"] in sw.INTRA, qp=0 if m["t"] == "pcm" else qps[a], slice=first, idc=idc, off_a=2 * ao, off_b=2 * bo,
+                        coef=sw.coded_luma_blocks(m), t8=m["t"] == "i8" or bool(m.get("t8", 0) and sw.coded_luma_blocks(m))))
     return out
 
 
@@ -140,6 +142,7 @@ def deblock_picture(seq, pics, pl, k, planes, stats=None):
     if all(q["idc"] == 1 for q in info):
         return planes
     off_c = seq.get("chroma_qp_off", 0)
+    off_cr = seq.get("second_chroma_qp_off", off_c)                 # 8.7.2.2: each chroma plane with its own offset
     skip_ref = pl[k]["l0"][0] if pl[k]["l0"] else None
     S = [pl_.astype(np.int64).tolist() for pl_ in planes]
     blk_at = {xy: i for i, xy in enumerate(sw.BLK_XY)}
@@ -155,6 +158,8 @@ def deblock_picture(seq, pics, pl, k, planes, stats=None):
             nb = (info[a - 1] if mx > 0 else None) if d == 0 else (info[a - mbw] if my > 0 else None)
             for e in range(4):
                 pmb = q
+                if q["t8"] and e % 2 == 1:
+                    continue                                        # transform_size_8x8_flag: the inner 4x4 edges are not filtered (chroma has none there)
                 if e == 0:
                     if nb is None:
                         continue                                    # picture edge
@@ -165,10 +170,12 @@ def deblock_picture(seq, pics, pl, k, planes, stats=None):
                 # ---- per edge: thresholds.  qPp is the p macroblock's QPY (0 for I_PCM); offsets of the slice that holds q0 ----
                 qpav = (pmb["qp"] + q["qp"] + 1) >> 1
                 ia, ib = qpav + q["off_a"], qpav + q["off_b"]
-                cav = (qpc(pmb["qp"], off_c) + qpc(q["qp"], off_c) + 1) >> 1
-                ica, icb = cav + q["off_a"], cav + q["off_b"]
                 lum = (ALPHA[clip3(0, 51, ia)], BETA[clip3(0, 51, ib)], TC0[clip3(0, 51, ia)])
-                chr_ = (ALPHA[clip3(0, 51, ica)], BETA[clip3(0, 51, icb)], TC0[clip3(0, 51, ica)])
+                chr_of = {}
+                for c, off in ((1, off_c), (2, off_cr)):
+                    cav = (qpc(pmb["qp"], off) + qpc(q["qp"], off) + 1) >> 1
+                    ica, icb = cav + q["off_a"], cav + q["off_b"]
+                    chr_of[c] = (ALPHA[clip3(0, 51, ica)], BETA[clip3(0, 51, icb)], TC0[clip3(0, 51, ica)])
                 edge_on = {"Y": 0, "C": 0}
                 edge_bs = 0
                 for seg in range(4):
@@ -205,6 +212,7 @@ def deblock_picture(seq, pics, pl, k, planes, stats=None):
                     # ---- chroma: edges 0 and 2 are the chroma edges 0 and 4; chroma line j takes the bS of luma line 2 j ----
                     if e % 2 == 0:
                         for c in (1, 2):
+                            chr_ = chr_of[c]
                             for j in range(2 * seg, 2 * seg + 2):
                                 x0, y0 = mx * 8, my * 8
                                 pos = [(x0 + 2 * e + t, y0 + j) for t in range(-2, 2)] if d == 0 else [(x0 + j, y0 + 2 * e + t) for t in range(-2, 2)]

@@ -1,37 +1,54 @@
-"""A scripted H.264 stream writer (CAVLC, pic_order_cnt_type 0, frame pictures, Baseline / Main subset) for the analytic known-answer tests.
+"""A scripted H.264 stream writer (CAVLC, pic_order_cnt_type 0, frame pictures, 4:2:0, 8 bit; Baseline / Main subset and the High tools below) for the
+analytic known-answer tests.
 
-The test says which macroblock carries which samples, vector, reference, weight and mode; ``write`` turns that script into Annex-B bytes.  No residual is
-ever coded, so the decoded picture follows from the script by arithmetic alone (tests/analytic_expect.py).  Typed from the syntax clauses (7.3.2.1, 7.3.2.2,
-7.3.3, 7.3.4, 7.3.5, 9.1, 9.2.1) -- not from tools/h264gen.c, the oracle or the product: a fourth typing of the syntax is part of the value.
+The test says which macroblock carries which samples, vector, reference, weight, mode and levels; ``write`` turns that script into Annex-B bytes.  The
+decoded picture follows from the script by arithmetic alone (tests/analytic_expect.py, tests/h264_recon_ref.py).  Typed from the syntax clauses (7.3.2.1,
+7.3.2.1.1.1, 7.3.2.2, 7.3.3, 7.3.4, 7.3.5, 7.3.5.1, 7.3.5.3, 9.1, 9.2) -- not from tools/h264gen.c, the oracle or the product: a fourth typing of the
+syntax is part of the value.  The code tables are the separately typed ones of tests/spec_tables_h264.py.
 
 The script
-    seq  = dict(width, height, num_ref_frames=1, profile=66 | 77, weighted_pred=0, weighted_bipred=0, init_qp=26, chroma_qp_off=0)
+    seq  = dict(width, height, num_ref_frames=1, profile=66 | 77 | 100, weighted_pred=0, weighted_bipred=0, init_qp=26, chroma_qp_off=0,
+                constrained_intra=0) and, with profile=100 only: transform8x8=0 | 1, second_chroma_qp_off, sps_lists, pps_lists -- eight scaling lists
+                each (Intra Y, Cb, Cr, Inter Y, Cb, Cr 4x4, Intra Y, Inter Y 8x8): None (absent: the fall-back rule of Table 7-2 applies), "default" (the
+                first delta_scale gives nextScale 0) or the 16 / 64 values in zig-zag order; key absent: no matrix in that parameter set
     pics = [dict(kind="I" | "P" | "B", poc=even int, layout="mb" | "row" | "pic", mbs=[...], and optionally
                  is_ref (default: kind != "B"), qp (slice QP, default init_qp), deblock=(disable_idc, alpha_div2, beta_div2) (default (1, 0, 0)),
                  num_ref=(n0, n1) (active entries, sent with num_ref_idx_active_override), wp=dict(ld_y, ld_c, l0=[entry..], l1=[entry..]) with
                  entry = None (both flags 0) or dict(y=(w, o) | None, c=((w, o), (w, o)) | None))]
     mbs[addr] is one of
         dict(t="pcm", y=(16,16) uint8, cb=(8,8), cr=(8,8))
-        dict(t="i16", mode=0..3, cmode=0..3)                       Intra16x16 without coefficients
+        dict(t="i16", mode=0..3, cmode=0..3)                       Intra16x16
+        dict(t="i4", modes=[16 Intra4x4PredMode in luma4x4BlkIdx order], cmode=0..3)
+        dict(t="i8", modes=[4 Intra8x8PredMode], cmode=0..3)       needs transform8x8=1
         dict(t="skip")                                             P_Skip
         dict(t="16x16", l0=(pic, (mvx, mvy)) | None, l1=(pic, (mvx, mvy)) | None)      pic = index into pics (decode order), vectors in quarter samples
         dict(t="16x8" | "8x16", parts=[(pic, mv), (pic, mv)])      P only
+    any of these but pcm and skip may carry levels, every matrix in RASTER order:
+        coef=dict(y={blkIdx: 16 levels} (Intra16x16: the AC, element 0 is 0) or, under the 8x8 transform (t="i8", or t8=1 on an inter macroblock),
+                  y8={8x8 block: 64 levels}; ydc=16 levels (Intra16x16 DC, the matrix c of 8.5.10); cdc=(4 Cb, 4 Cr); cac={(plane, blk): 15 levels, raster
+                  positions 1 .. 15}) and dqp=.. (mb_qp_delta, accumulated per 7.4.5 within the slice: ``mb_qps``)
+    The writer derives mb_type (the 24 Intra16x16 types among them), coded_block_pattern through me(v), transform_size_8x8_flag, prev_intra4x4 / 8x8_
+    pred_mode_flag and rem_intra4x4 / 8x8_pred_mode from a mode derivation of its own (PicState.pred_mode), nC of 9.2.1 across macroblocks and slices
+    (I_PCM counts 16, skipped macroblocks and blocks switched off by the pattern 0, the Intra16x16 DC block takes block 0's nC, chroma DC -1, the four
+    interleaved 4x4 blocks of an 8x8 block each count their own levels) and the level coding of 9.2.2.1; it refuses by assertion what it cannot state,
+    a level that needs level_prefix 16 outside profile 100 among it.
     and, for the streams on which the deblocking filter has to filter (tests/deblock_ref.py computes what it does):
         qp=.., deblock=(idc, a, b) on any macroblock of layout "mb": the macroblock is a slice, so slice_qp_delta and the three deblocking fields carry them
-        dqp=.. on t="i16": mb_qp_delta, accumulated per 7.4.5 within the slice (``mb_qps``); layouts "row" / "pic"
         resid=(blkIdx, +1 | -1) on a P 16x16 / 16x8 / 8x16 macroblock of layout "mb": ONE coded coefficient, the DC of luma block blkIdx (6.4.3 order), level
         +-1 -- coded_block_pattern has the luma bit of that block's 8x8 and nothing else, mb_qp_delta is 0; the block's sixteen samples move by one constant
         (analytic_expect.dc_only_residual)
 layout "mb": one slice per macroblock (no neighbour is available: every vector predictor is (0, 0), mvd = the vector); "row" / "pic": one slice per
-macroblock row / per picture -- inter macroblocks of such a slice must be 16x16 with ONE vector and reference per list throughout the slice (the
-predictor is then that vector as soon as a neighbour exists, whichever of 8.4.1.3's branches applies) and may not be P_Skip; intra macroblocks may sit
-between them only in a picture one macroblock wide.  seq may carry frame_mbs_only=0 (frame pictures of a stream that could hold fields).
+macroblock row / per picture -- the inter macroblocks of such a slice are 16x16 and not P_Skip.  Where they all repeat ONE vector and reference per list
+the predictor is that vector as soon as a neighbour exists, whichever of 8.4.1.3's branches applies (B slices: only this); any other mixture of 16x16 P
+and intra macroblocks goes through 8.4.1.3 typed out (``mv_predictor_16x16``).  seq may carry frame_mbs_only=0 (frame pictures of a stream that could
+hold fields).
 """
 import re
 
 import numpy as np
 
-from spec_tables_h264 import CBP_OF_CODENUM, COEFF_TOKEN, TOTAL_ZEROS_4x4, parse_code_table
+from spec_tables_h264 import (CBP_OF_CODENUM, COEFF_TOKEN, RUN_BEFORE, TOTAL_ZEROS_4x4, TOTAL_ZEROS_CHROMA_DC, ZIGZAG_4x4, ZIGZAG_8x8,
+                              parse_code_table)
 
 
 class Bits:
@@ -89,15 +106,51 @@ LOG2_MAX_FRAME_NUM = 8
 LOG2_MAX_POC_LSB = 8
 
 
+def high_syntax(seq):
+    """The PPS carries transform_8x8_mode_flag, pic_scaling_matrix_present_flag and second_chroma_qp_index_offset (7.3.2.2, after more_rbsp_data)"""
+    return bool(seq.get("transform8x8", 0)) or "pps_lists" in seq or "second_chroma_qp_off" in seq
+
+
+def scaling_matrix(b, lists, n):
+    """7.3.2.1.1 / 7.3.2.2: the matrix present flag, then per list its present flag and scaling_list() (7.3.2.1.1.1).  lists[i]: None (absent: a fall-back
+    rule applies), "default" (the first delta_scale makes nextScale 0: UseDefaultScalingMatrixFlag), or the 16 / 64 values in zig-zag order."""
+    b.u(1, 0 if lists is None else 1)
+    if lists is None:
+        return
+    assert len(lists) == 8
+    for i in range(n):
+        v = lists[i]
+        b.u(1, 0 if v is None else 1)
+        if v is None:
+            continue
+        if isinstance(v, str):
+            assert v == "default"
+            b.se(-8)                                                # nextScale = (8 - 8 + 256) % 256 = 0 at j = 0
+            continue
+        assert len(v) == (16 if i < 6 else 64) and all(1 <= x <= 255 for x in v), (i, v)
+        last = 8
+        for x in v:                                                 # every value coded: nextScale never becomes 0
+            d = x - last
+            b.se(d - 256 if d > 127 else (d + 256 if d < -128 else d))
+            last = x
+
+
 def sps(seq):
     b = Bits()
     w, h = seq["width"], seq["height"]
     mbw, mbh = (w + 15) // 16, (h + 15) // 16
     prof = seq.get("profile", 66)
     b.u(8, prof)
-    b.u(8, 0x80 if prof == 66 else 0x40)                            # constraint_set0 / set1, reserved zero bits
+    b.u(8, {66: 0x80, 77: 0x40, 100: 0}[prof])                      # constraint_set0 / set1, reserved zero bits
     b.u(8, 40)                                                      # level_idc
     b.ue(0)                                                         # seq_parameter_set_id
+    if prof == 100:
+        b.ue(1)                                                     # chroma_format_idc: 4:2:0
+        b.ue(0); b.ue(0)                                            # bit_depth_luma_minus8, bit_depth_chroma_minus8
+        b.u(1, 0)                                                   # qpprime_y_zero_transform_bypass_flag
+        scaling_matrix(b, seq.get("sps_lists"), 8)                  # seq_scaling_matrix_present_flag and the lists
+    else:
+        assert not high_syntax(seq) and "sps_lists" not in seq, "the 8x8 transform, scaling lists and the second chroma offset need profile 100"
     b.ue(LOG2_MAX_FRAME_NUM - 4)
     b.ue(0)                                                         # pic_order_cnt_type
     b.ue(LOG2_MAX_POC_LSB - 4)
@@ -137,8 +190,14 @@ def pps(seq):
     b.se(0)                                                         # pic_init_qs_minus26
     b.se(seq.get("chroma_qp_off", 0))                               # chroma_qp_index_offset
     b.u(1, 1)                                                       # deblocking_filter_control_present_flag
-    b.u(1, 0)                                                       # constrained_intra_pred_flag
+    b.u(1, seq.get("constrained_intra", 0))                         # constrained_intra_pred_flag
     b.u(1, 0)                                                       # redundant_pic_cnt_present_flag
+    if high_syntax(seq):
+        assert seq.get("profile", 66) == 100
+        t8 = seq.get("transform8x8", 0)
+        b.u(1, t8)                                                  # transform_8x8_mode_flag
+        scaling_matrix(b, seq.get("pps_lists"), 6 + 2 * t8)         # pic_scaling_matrix_present_flag and 6 + 2 * transform_8x8_mode_flag lists
+        b.se(seq.get("second_chroma_qp_off", seq.get("chroma_qp_off", 0)))
     b.trailing()
     return nal(3, 8, b.bytes())
 
@@ -237,6 +296,221 @@ def one_dc_coefficient(b, blk, sign):
             b.u(ln, val)
 
 
+_TOTAL_ZEROS_CDC = parse_code_table(TOTAL_ZEROS_CHROMA_DC, 3)
+_RUN_BEFORE = parse_code_table(RUN_BEFORE, 7)
+INTRA = ("pcm", "i16", "i4", "i8")
+
+
+def put(b, code):
+    assert code is not None, "the table has no code for this combination"
+    b.u(*code)
+
+
+def residual_block(b, lv, nc, high, seen=None):
+    """residual_block_cavlc (7.3.5.3.2, 9.2) of the levels lv in scan order (4, 15 or 16 of them) under nC = nc; returns TotalCoeff.  high: profile 100,
+    which alone may use level_prefix 16.  seen: a set that receives what the block exercised (tests/analytic_h264_recon.py asserts from it)."""
+    seen = seen if seen is not None else set()
+    max_num = len(lv)
+    nz = [i for i, v in enumerate(lv) if v]
+    total = len(nz)
+    t1 = 0
+    for i in reversed(nz):                                          # trailing ones: up to three +-1 at the high-frequency end
+        if abs(lv[i]) != 1 or t1 == 3:
+            break
+        t1 += 1
+    col = 4 if nc == -1 else (0 if nc < 2 else (1 if nc < 4 else (2 if nc < 8 else 3)))
+    seen.add(("nC", col))
+    put(b, _COEFF_TOKEN[(t1, total)][col])
+    if total == 0:
+        return 0
+    sl = 1 if total > 10 and t1 < 3 else 0                          # suffixLength
+    if sl:
+        seen.add("more_than_10_coefficients_fewer_than_3_trailing_ones")
+    for k, i in enumerate(reversed(nz)):
+        v = lv[i]
+        if k < t1:
+            b.u(1, int(v < 0))                                      # trailing_ones_sign_flag
+            continue
+        code = 2 * v - 2 if v > 0 else -2 * v - 1                   # levelCode
+        if k == t1 and t1 < 3:
+            code -= 2                                               # the first level after fewer than three trailing ones cannot be +-1
+            seen.add("minus_2_after_fewer_than_3_trailing_ones")
+        seen.add(("suffixLength", sl))
+        # 9.2.2.1 backwards: levelCode = (Min(15, level_prefix) << suffixLength) + level_suffix, + 15 when level_prefix >= 15 and suffixLength = 0,
+        # + (1 << (level_prefix - 3)) - 4096 when level_prefix >= 16; levelSuffixSize 4 for prefix 14 at suffixLength 0, level_prefix - 3 from 15 on
+        if sl == 0 and code < 14:
+            pre, nsuf, suf = code, 0, 0
+        elif sl == 0 and code < 30:
+            pre, nsuf, suf = 14, 4, code - 14
+        elif sl > 0 and code < (15 << sl):
+            pre, nsuf, suf = code >> sl, sl, code & ((1 << sl) - 1)
+        else:
+            rest = code - (15 << sl) - (15 if sl == 0 else 0)
+            if rest < 4096:
+                pre, nsuf, suf = 15, 12, rest
+            else:
+                assert high and rest < 4096 + 8192, "a level that needs level_prefix 16 (or more) -- profile 100 only, and 16 is the most this writer states"
+                pre, nsuf, suf = 16, 13, rest - 4096
+        if sl == 0 and pre >= 14 or pre == 16:
+            seen.add(("level_prefix", pre, sl))
+        b.u(pre + 1, 1)                                             # level_prefix: `pre` zeros and a one
+        if nsuf:
+            b.u(nsuf, suf)
+        if sl == 0:
+            sl = 1
+        if abs(v) > (3 << (sl - 1)) and sl < 6:
+            sl += 1
+    if total < max_num:
+        tz = nz[-1] + 1 - total                                     # zeros below the last coefficient
+        put(b, (_TOTAL_ZEROS_CDC if max_num == 4 else _TOTAL_ZEROS)[(tz,)][total - 1])
+        left = tz
+        for k in range(total - 1, 0, -1):                           # run_before of every coefficient but the lowest, from the highest down
+            if left == 0:
+                break
+            run = nz[k] - nz[k - 1] - 1
+            if run > 6:
+                seen.add("run_before_above_6")
+            put(b, _RUN_BEFORE[(run,)][min(left, 7) - 1])
+            left -= run
+    return total
+
+
+def mb_levels(m):
+    """The levels of macroblock m in PARSING form, from its coef=dict(...) (every matrix there is in raster order):
+    dc16: the 16 Intra16x16DCLevel in scan order or None; y[blk]: 16 (15 for Intra16x16: the AC) levels of every luma 4x4 block in scan order -- under the
+    8x8 transform the four interleaved blocks of 7.3.5.3.1 (CAVLC): block i of an 8x8 takes levels 4 k + i of its 64; cdc[plane]: 4; cac[plane][blk]: 15;
+    and the coded_block_pattern that follows from them: (luma bits, chroma 0 | 1 | 2)."""
+    c = m.get("coef", {})
+    t = m["t"]
+    assert set(c) <= {"y", "y8", "ydc", "cdc", "cac"} and t != "pcm" and t != "skip", (t, sorted(c))
+    t8 = t == "i8" or m.get("t8", 0)
+    assert ("y8" not in c or t8) and ("y" not in c or not t8) and ("ydc" not in c or t == "i16") and (not t8 or t != "i16")
+    y = [[0] * (15 if t == "i16" else 16) for _ in range(16)]
+    for blk, lv in c.get("y", {}).items():
+        lv = [int(v) for v in np.asarray(lv).reshape(16)]
+        assert t != "i16" or lv[0] == 0, "the DC of an Intra16x16 block is coded in ydc"
+        y[blk] = [lv[ZIGZAG_4x4[k]] for k in range(1 if t == "i16" else 0, 16)]
+    for b8, lv in c.get("y8", {}).items():
+        lv = [int(v) for v in np.asarray(lv).reshape(64)]
+        scan = [lv[ZIGZAG_8x8[k]] for k in range(64)]
+        for i in range(4):
+            y[4 * b8 + i] = scan[i::4]
+    dc16 = None
+    if t == "i16":
+        lv = [int(v) for v in np.asarray(c.get("ydc", [0] * 16)).reshape(16)]
+        dc16 = [lv[ZIGZAG_4x4[k]] for k in range(16)]
+    cdc = [[int(v) for v in q] for q in c.get("cdc", ([0] * 4, [0] * 4))]
+    cac = [[[0] * 15 for _ in range(4)] for _ in range(2)]
+    for (pl_, blk), lv in c.get("cac", {}).items():
+        lv = [0] + [int(v) for v in lv]
+        assert len(lv) == 16
+        cac[pl_][blk] = [lv[ZIGZAG_4x4[k]] for k in range(1, 16)]
+    luma = sum(1 << b8 for b8 in range(4) if any(any(y[4 * b8 + i]) for i in range(4)))
+    if t == "i16" and luma:
+        luma = 15                                                   # Table 7-11: Intra16x16 has all of the AC or none of it
+    chroma = 2 if any(any(q) for pl_ in cac for q in pl_) else (1 if any(any(q) for q in cdc) else 0)
+    return dict(dc16=dc16, y=y, cdc=cdc, cac=cac, cbp=(luma, chroma), t8=int(bool(t8)))
+
+
+def coded_luma_blocks(m):
+    """The luma 4x4 blocks of m that 8.7.2.1 counts as "containing non-zero transform coefficients": under the 8x8 transform all four blocks of an 8x8
+    that has one (the Intra16x16 DC levels count for no block: such a macroblock is intra, where the coefficients do not decide bS)."""
+    if "resid" in m:
+        return {m["resid"][0]}
+    if "coef" not in m:
+        return set()
+    lv = mb_levels(m)
+    if lv["t8"]:
+        return {4 * b8 + i for b8 in range(4) for i in range(4) if any(any(lv["y"][4 * b8 + j]) for j in range(4))}
+    return {k for k in range(16) if any(lv["y"][k])}
+
+
+class PicState:
+    """What one macroblock's syntax needs of the macroblocks before it: TotalCoeff of every 4x4 block (9.2.1), the Intra4x4 / Intra8x8 modes (8.3.1.1,
+    8.3.2.1), whether a macroblock is inter.  Availability (6.4.x): inside the picture and in the same slice."""
+    def __init__(self, seq, mbs, step):
+        self.mbw = (seq["width"] + 15) // 16
+        self.mbs, self.step = mbs, step
+        self.constrained = seq.get("constrained_intra", 0)
+        self.tc = [None] * len(mbs)                                 # per macroblock: [16 luma by (y / 4) * 4 + x / 4, 4 Cb, 4 Cr]
+        self.modes = [None] * len(mbs)                              # per macroblock: 16 modes by (y / 4) * 4 + x / 4 (an 8x8 mode fills its four 4x4 blocks)
+
+    def neighbour(self, a, dx, dy):
+        """address of the macroblock at (dx, dy) macroblocks from a, or None when it is not available"""
+        x, y = a % self.mbw + dx, a // self.mbw + dy
+        n = y * self.mbw + x
+        return n if 0 <= x < self.mbw and y >= 0 and n >= a - a % self.step and n < a else None
+
+    def locate(self, a, px, py, size):
+        """(macroblock address or None, px, py) of the sample (px, py) relative to macroblock a; px < size, py < size (left, above or inside)"""
+        dx, dy = (-1 if px < 0 else 0), (-1 if py < 0 else 0)
+        return (a if (dx, dy) == (0, 0) else self.neighbour(a, dx, dy)), px % size, py % size
+
+    def n_c(self, a, comp, bx, by):
+        """9.2.1 for the block at (bx, by) (in blocks) of component comp (0 luma: 4x4 blocks, 1 / 2 chroma: 2x2) of macroblock a"""
+        g = 4 if comp == 0 else 2
+        base = (0, 16, 20)[comp]
+        n = []
+        for (qx, qy) in ((bx - 1, by), (bx, by - 1)):
+            mb, qx, qy = self.locate(a, qx, qy, g)
+            n.append(None if mb is None else self.tc[mb][base + qy * g + qx])
+        na, nb = n
+        return (na + nb + 1) >> 1 if na is not None and nb is not None else (na if na is not None else (nb if nb is not None else 0))
+
+    def pred_mode(self, a, x, y):
+        """predIntra4x4PredMode / predIntra8x8PredMode of the block whose upper left sample is (x, y).  With an 8x8 mode stored in all four 4x4 blocks it
+        covers, both clauses read: A is the 4x4 block that holds (x - 4, y), B the one that holds (x, y - 4) -- for an 8x8 block beside an Intra4x4
+        macroblock these are that macroblock's blocks 8x8idx * 4 + 1 and 8x8idx * 4 + 2, as 8.3.2.1 says."""
+        out = []
+        for (qx, qy) in ((x - 4, y), (x, y - 4)):
+            mb, qx, qy = self.locate(a, qx, qy, 16)
+            if mb is None or (self.constrained and self.mbs[mb]["t"] not in INTRA):
+                return 2                                            # dcPredModePredictedFlag
+            out.append(self.modes[mb][(qy // 4) * 4 + qx // 4] if self.mbs[mb]["t"] in ("i4", "i8") else 2)
+        return min(out)
+
+
+def mv_predictor_16x16(st, a, ref):
+    """8.4.1.3 for a 16x16 partition of a P macroblock in a slice of 16x16 inter and intra macroblocks (no P_Skip): neighbours A, B, C (D when C is not
+    available); an intra or unavailable neighbour has no reference; B and C both unavailable and A available: A stands for all three; one matching
+    reference: its vector; else the median."""
+    def of(n):
+        if n is None:
+            return None
+        m = st.mbs[n]
+        assert m["t"] in INTRA or m["t"] == "16x16", "a slice of several macroblocks holds 16x16 inter and intra macroblocks only"
+        return (m["l0"][0], m["l0"][1]) if m["t"] == "16x16" else (None, (0, 0))
+    A, B, C = of(st.neighbour(a, -1, 0)), of(st.neighbour(a, 0, -1)), of(st.neighbour(a, 1, -1))
+    if C is None:
+        C = of(st.neighbour(a, -1, -1))
+    if B is None and C is None and A is not None:
+        B = C = A
+    A, B, C = [(None, (0, 0)) if q is None else q for q in (A, B, C)]
+    same = [q for q in (A, B, C) if q[0] == ref]
+    if len(same) == 1:
+        return same[0][1]
+    return tuple(sorted(q[1][i] for q in (A, B, C))[1] for i in (0, 1))
+
+
+def macroblock_residual(b, st, a, m, lv, high, seen):
+    """residual() of 7.3.5.3 for CAVLC and 4:2:0, and the TotalCoeff bookkeeping of 9.2.1"""
+    tc = st.tc[a]
+    luma, chroma = lv["cbp"]
+    if m["t"] == "i16":
+        residual_block(b, lv["dc16"], st.n_c(a, 0, 0, 0), high, seen)      # Intra16x16DCLevel: nC of block 0; its TotalCoeff is stored nowhere
+    for k in range(16):
+        bx, by = BLK_XY[k][0] // 4, BLK_XY[k][1] // 4
+        if luma >> (k >> 2) & 1:
+            tc[by * 4 + bx] = residual_block(b, lv["y"][k], st.n_c(a, 0, bx, by), high, seen)
+    if chroma:
+        for c in (0, 1):
+            residual_block(b, lv["cdc"][c], -1, high, seen)
+    if chroma == 2:
+        for c in (0, 1):
+            for k in range(4):
+                tc[16 + 4 * c + k] = residual_block(b, lv["cac"][c][k], st.n_c(a, 1 + c, k & 1, k >> 1), high, seen)
+
+
 def slice_header(b, seq, p, pl, first_mb):
     kind = p["kind"]
     b.ue(first_mb)
@@ -296,17 +570,41 @@ def coeff_token_zero(b, nc):
         b.u(6, 3)
 
 
-def write(seq, pics):
-    """The Annex-B stream of the script."""
+def intra_pred_modes(b, st, a, m):
+    """mb_pred of I_NxN (7.3.5.1): prev_intra4x4 / 8x8_pred_mode_flag and rem_intra4x4 / 8x8_pred_mode of every block, in block order"""
+    n = 16 if m["t"] == "i4" else 4
+    assert len(m["modes"]) == n and all(0 <= q <= 8 for q in m["modes"])
+    st.modes[a] = [None] * 16
+    coded = []
+    for k, mode in enumerate(m["modes"]):
+        x, y = BLK_XY[k] if n == 16 else ((k & 1) * 8, (k >> 1) * 8)
+        pred = st.pred_mode(a, x, y)
+        for j in ([0] if n == 16 else [0, 1, 4, 5]):
+            st.modes[a][(y // 4) * 4 + x // 4 + j] = mode
+        flag, rem = (1, None) if mode == pred else (0, mode if mode < pred else mode - 1)
+        assert flag or (0 <= rem <= 7 and (rem if rem < pred else rem + 1) == mode), (mode, pred)
+        b.u(1, flag)
+        if not flag:
+            b.u(3, rem)
+        coded.append((pred, flag, rem))
+    return coded
+
+
+def write(seq, pics, seen=None, coded_modes=None):
+    """The Annex-B stream of the script.  seen: a set that receives what the residual blocks exercised; coded_modes: a dict that receives, per (picture,
+    macroblock), the (predicted mode, prev flag, rem) of every Intra4x4 / Intra8x8 block as written."""
     mbw = (seq["width"] + 15) // 16
     mbh = (seq["height"] + 15) // 16
     n_mbs = mbw * mbh
+    high = seq.get("profile", 66) == 100
+    t8mode = seq.get("transform8x8", 0)
     out = [sps(seq), pps(seq)]
     for k, (p, pl) in enumerate(zip(pics, plan(seq, pics))):
         kind, mbs = p["kind"], p["mbs"]
         assert len(mbs) == n_mbs
         step = layout_step(seq, p)
         mb_qps(seq, p)                                              # its assertions
+        st = PicState(seq, mbs, step)
         for first in range(0, n_mbs, step):
             b = Bits()
             qp, db = slice_fields(seq, p, step, mbs[first])
@@ -315,6 +613,7 @@ def write(seq, pics):
             for a in range(first, min(first + step, n_mbs)):
                 m = mbs[a]
                 t = m["t"]
+                st.tc[a] = [16 if t == "pcm" else 0] * 24            # 9.2.1: I_PCM counts 16, a skipped macroblock and a block without levels 0
                 if t == "skip":
                     assert kind == "P" and step == 1
                     skip_run += 1
@@ -323,21 +622,26 @@ def write(seq, pics):
                     b.ue(skip_run)
                     skip_run = 0
                 intra_base = {"I": 0, "P": 5, "B": 23}[kind]
+                lv = mb_levels(m) if t != "pcm" else None
+                assert "coef" not in m or "resid" not in m
                 if t == "pcm":
                     b.ue(intra_base + 25)
                     b.align_zero()                                  # pcm_alignment_zero_bit
                     b.raw(np.asarray(m["y"], np.uint8).tobytes() + np.asarray(m["cb"], np.uint8).tobytes() + np.asarray(m["cr"], np.uint8).tobytes())
-                elif t == "i16":
-                    b.ue(intra_base + 1 + m["mode"])                # I_16x16_<mode>_0_0
+                    continue
+                if t == "i16":
+                    luma, chroma = lv["cbp"]
+                    b.ue(intra_base + 1 + m["mode"] + 4 * chroma + (12 if luma else 0))      # Table 7-11: I_16x16_<mode>_<chroma>_<luma 0 | 15>
                     b.ue(m["cmode"])                                # intra_chroma_pred_mode
-                    b.se(m.get("dqp", 0))                           # mb_qp_delta
-                    # Intra16x16DCLevel, blkIdx 0: nC from the total_coeff of the blocks left of and above it (9.2.1): 16 in an I_PCM macroblock,
-                    # 0 in every other macroblock a script can hold; a neighbour in another slice is not available
-                    x, y = a % mbw, a // mbw
-                    na = (16 if mbs[a - 1]["t"] == "pcm" else 0) if x > 0 and a - 1 >= first else None
-                    nb = (16 if mbs[a - mbw]["t"] == "pcm" else 0) if y > 0 and a - mbw >= first else None
-                    nc = (na + nb + 1) >> 1 if na is not None and nb is not None else (na if na is not None else (nb if nb is not None else 0))
-                    coeff_token_zero(b, nc)
+                elif t in ("i4", "i8"):
+                    b.ue(intra_base)                                # I_NxN
+                    assert t == "i4" or t8mode, "Intra8x8 needs transform8x8=1"
+                    if t8mode:
+                        b.u(1, int(t == "i8"))                      # transform_size_8x8_flag
+                    coded = intra_pred_modes(b, st, a, m)
+                    if coded_modes is not None:
+                        coded_modes[(k, a)] = coded
+                    b.ue(m["cmode"])                                # intra_chroma_pred_mode
                 else:
                     parts = [(m.get("l0"), m.get("l1"))] if t == "16x16" else [(q, None) for q in m["parts"]]
                     if kind == "P":
@@ -366,24 +670,37 @@ def write(seq, pics):
                                 if i == 1 and (t == "8x16" or parts[0][l][0] == q[l][0]):
                                     mvp = parts[0][l][1]
                             else:
-                                # every macroblock of this slice is the same 16x16 block: as soon as one neighbour exists, every available neighbour holds
-                                # this vector and reference, and each branch of 8.4.1.3 (one neighbour, one matching reference, median) returns it
-                                inter = [q_ for q_ in mbs[first:min(first + step, n_mbs)] if q_["t"] == "16x16"]
-                                assert all(q_ == inter[0] for q_ in inter), "a slice of several macroblocks repeats one 16x16 inter macroblock"
-                                if len(inter) == min(first + step, n_mbs) - first:
-                                    mvp = (0, 0) if a == first else mv
+                                inter = [(q_.get("l0"), q_.get("l1")) for q_ in mbs[first:min(first + step, n_mbs)] if q_["t"] == "16x16"]
+                                whole = len(inter) == min(first + step, n_mbs) - first
+                                if all(q_ == inter[0] for q_ in inter) and (whole or mbw == 1):
+                                    # every macroblock of this slice is the same 16x16 block: as soon as one neighbour exists, every available neighbour
+                                    # holds this vector and reference, and each branch of 8.4.1.3 (one neighbour, one matching reference, median)
+                                    # returns it.  With intra macroblocks in between in a picture ONE macroblock wide: A, C and D lie outside the
+                                    # picture, B is the macroblock above -- inter in this slice: the one neighbour whose reference matches, the
+                                    # predictor is its vector (this vector); intra or in another slice: no reference matches, median(0, 0, 0)
+                                    mvp = ((0, 0) if a == first else mv) if whole else (mv if a > first and mbs[a - 1]["t"] == "16x16" else (0, 0))
+                                    assert kind != "P" or mvp == mv_predictor_16x16(st, a, q[l][0])
                                 else:
-                                    # intra macroblocks in between, pictures ONE macroblock wide only: A, C and D lie outside the picture, B is the
-                                    # macroblock above -- inter in this slice: the one neighbour whose reference matches, the predictor is its vector
-                                    # (this vector); intra or in another slice: no reference matches, median(0, 0, 0)
-                                    assert mbw == 1
-                                    mvp = mv if a > first and mbs[a - 1]["t"] == "16x16" else (0, 0)
+                                    # any mixture of 16x16 P macroblocks and intra macroblocks: 8.4.1.3 typed out
+                                    assert kind == "P" and t == "16x16"
+                                    mvp = mv_predictor_16x16(st, a, q[l][0])
                             b.se(mv[0] - mvp[0]); b.se(mv[1] - mvp[1])
                     if "resid" in m:
-                        assert kind == "P" and step == 1
+                        assert kind == "P" and step == 1 and not t8mode
                         one_dc_coefficient(b, *m["resid"])
+                        continue
+                luma, chroma = lv["cbp"]
+                if t != "i16":
+                    b.ue([c[0 if t in INTRA else 1] for c in CBP_OF_CODENUM].index(luma | chroma << 4))      # coded_block_pattern: me(v), Table 9-4
+                    if t not in INTRA and luma and t8mode:
+                        b.u(1, lv["t8"])                            # transform_size_8x8_flag of an inter macroblock without sub-partitions
                     else:
-                        b.ue(0)                                     # coded_block_pattern 0 (Table 9-4, Inter, codeNum 0)
+                        assert t in INTRA or not lv["t8"], "t8=1 needs transform8x8=1 and luma levels"
+                if t == "i16" or luma or chroma:
+                    b.se(m.get("dqp", 0))                           # mb_qp_delta
+                    macroblock_residual(b, st, a, m, lv, high, seen)
+                else:
+                    assert m.get("dqp", 0) == 0, "a macroblock without levels has no mb_qp_delta"
             if skip_run:
                 b.ue(skip_run)
             b.trailing()
