@@ -52,7 +52,13 @@ jm_amddec_handle jm_amddec_create_handle(void);
  * MPEG-2: the input is any chunking of an ISO/IEC 13818-2 video elementary stream (one start-code unit per call included); frame pictures I / P / B,
  * 4:2:0, progressive and interlaced; MPEG-1, field pictures, dual prime, 4:2:2 / 4:4:4, the scalable extensions and D pictures fail the handle with
  * an error string that names the feature (INTEGRATION.md "MPEG-2").  extra_data, if given, is read as the beginning of the stream.  Stats:
- * dropped_pictures, mpeg2_clamped_mbs, mpeg2_repeat_first_field, mpeg2_profile_level; with option profile k_mpeg2_ns / _n / _pics / _alg_bytes. */
+ * dropped_pictures, mpeg2_clamped_mbs, mpeg2_repeat_first_field, mpeg2_profile_level; with option profile k_mpeg2_ns / _n / _pics / _alg_bytes.
+ * Option "mpeg2_device_vlc" (before init; 0 default / 1; other values and other codecs are refused): 1 = the slice / macroblock / block VLC decode runs on
+ * the device (k_mpeg2_vlc, one lane per slice); the host then only finds every slice's first macroblock address and uploads the picture's parameters, a
+ * slice table and the slice bytes instead of the job list (layout: INTEGRATION.md "MPEG-2").  parse_only and digest handles, and pictures whose slice
+ * headers the prescan cannot accept or whose slices are out of order, take the host path.  Undamaged pictures decode identically, damage is concealed by
+ * the host path's rules; dual prime fails the handle when the engine reads the picture's status.  Stats: mpeg2_dev_pictures, mpeg2_host_pictures,
+ * mpeg2_dev_slices, mpeg2_dev_damaged_slices; with option profile k_mpeg2_vlc_ns / _n / _pics / _alg_bytes.  When it pays: INTEGRATION.md has the figures. */
 int  jm_amddec_init(int codec_type, int out_fmt, char *extra_data, int len, jm_amddec_handle h);
 int  jm_amddec_deinit(jm_amddec_handle h);
 /* in_buf may hold any chunk of an Annex-B stream; (NULL, 0) signals end of stream and then

@@ -185,6 +185,10 @@ int Decoder::set_option(const char *key, long long v) {
         if (inited_ || v < 0 || v > 2) return -1;
         jpeg_dev_entropy_ = (int)v;
     }
+    else if (k == "mpeg2_device_vlc") {      // MPEG-2: 1 = the slices are VLC-decoded on the device (k_mpeg2_vlc), one lane per slice
+        if (inited_ || v < 0 || v > 1) return -1;
+        mpeg2_dev_vlc_ = (int)v;
+    }
     else if (k == "rgb_chroma") {            // RGB output: 1 = chroma interpolated to full resolution at the stream's siting (k_rgb_pack444)
         if (inited_ || v < 0 || v > 1) return -1;
         rgb_chroma_ = (int)v;
@@ -300,6 +304,11 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "dropped_pictures") return stat_dropped_;
     if (k == "mpeg2_clamped_mbs") return stat_m2_clamped_;
     if (k == "mpeg2_repeat_first_field") return stat_m2_rff_;
+    // option mpeg2_device_vlc: pictures whose slices went to k_mpeg2_vlc / to the host decoder, slices of the former, and how many the device found damaged
+    if (k == "mpeg2_dev_pictures") return stat_m2_dev_pics_;
+    if (k == "mpeg2_host_pictures") return stat_m2_host_pics_;
+    if (k == "mpeg2_dev_slices") return stat_m2_dev_slices_;
+    if (k == "mpeg2_dev_damaged_slices") return stat_m2_dev_damaged_;
     if (k == "mpeg2_profile_level") return codec_ == 4 && seq_active_ ? m2seq_.profile_level : 0;
     if (k == "copy_engines") return copier_ ? (long long)copier_->engine_mask() : 0;      // SDMA engines the direct route uses (bit mask)
     if (k == "direct_frames") return stat_direct_;
@@ -340,7 +349,7 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "wait_slot_ns") return stat_wait_slot_ns_;
     if (k == "parse_ns_p") return stat_parse_ns_p_;
     if (k.rfind("k_", 0) == 0 || k.rfind("eng_", 0) == 0) {          // engine-wide (all handles on this device), profile option
-        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5", "rgb_pack444", "mpeg2", "jpeg_entropy"};
+        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5", "rgb_pack444", "mpeg2", "jpeg_entropy", "mpeg2_vlc"};
         if (!engine_) return 0;
         EngineStats es = engine_->stats();
         for (int i = 0; i < kKernelClasses; i++) {
@@ -407,6 +416,7 @@ int Decoder::init(int codec_type, int out_fmt, const uint8_t *extra, int len) {
     if (codec_type == 2 && deint_temporal_) { fail("option deinterlace_temporal is not available for MJPEG (codec_type 2): its surfaces are dealt round robin, "
         "a displayed one cannot be kept for the next picture"); return -1; }
     if (codec_type != 2 && jpeg_dev_entropy_) { fail("option jpeg_device_entropy is only available for MJPEG (codec_type 2)"); return -1; }
+    if (codec_type != 4 && mpeg2_dev_vlc_) { fail("option mpeg2_device_vlc is only available for MPEG-2 (codec_type 4)"); return -1; }
     if (rgb_chroma_ && !rgb_) { fail("option rgb_chroma needs RGB output: set an RGB spec (jm_amddec_set_rgb) before init"); return -1; }
     if (getenv("JM_AMD_DEC_SYNC")) sync_mode_ = true;
     if (const char *js = getenv("JM_AMD_DEC_JOB_SLOTS")) { n_jobs_ = std::max(8, std::min(atoi(js), kMaxJobSlots)); n_jobs_set_ = true; }

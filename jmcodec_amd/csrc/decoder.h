@@ -93,7 +93,10 @@ struct JpegTask { JpegPic pic; std::vector<uint8_t> data; size_t off_first = 0, 
     bool on_device = false, host_error = false; size_t off_tab = 0, off_segs = 0, off_bytes = 0; int n_segs = 0; };
 
 // MPEG-2 picture (codec_type 4): its headers' snapshot with the slices' bytes, the reference surfaces, and where the job list sits in the job buffer
-struct Mpeg2Task { Mpeg2Pic pic; int ref_slot[2] = {-1, -1}; size_t off_mbs = 0, off_entries = 0; int n_entries = 0; };
+// on_device: option mpeg2_device_vlc sends the picture's slices to k_mpeg2_vlc -- the job buffer then holds the picture's VLC parameters, the slice
+// table and the slice bytes (off_par, off_slices, off_bytes), and off_mbs / off_entries are offsets into the slot's device-only buffer
+struct Mpeg2Task { Mpeg2Pic pic; int ref_slot[2] = {-1, -1}; size_t off_mbs = 0, off_entries = 0; int n_entries = 0;
+    bool on_device = false; size_t off_par = 0, off_slices = 0, off_bytes = 0; int n_slices = 0; };
 
 struct PicTask {
     uint64_t seq = 0;
@@ -126,7 +129,8 @@ struct JobSlot {                       // one picture's job list: pinned host bu
     uint8_t *dbrec = nullptr;
     ihipEvent_t *uploaded = nullptr;   // recorded behind the H2D copy on the engine's copy stream
     // MJPEG, option jpeg_device_entropy: what only the device reads and writes (first / count / entries of k_jpeg_entropy): device memory with no
-    // page-locked mirror, grown on demand (Decoder::ensure_dev_only); a parse-only handle records the size and allocates nothing
+    // page-locked mirror, grown on demand (Decoder::ensure_dev_only); a parse-only handle records the size and allocates nothing.  MPEG-2, option
+    // mpeg2_device_vlc: the records and entries of k_mpeg2_vlc likewise
     uint8_t *dev_only = nullptr; size_t dev_only_cap = 0;
     bool busy = false;                 // from dispatch until the engine reports the picture done
     int big = -1;                      // >= 0: host / dev / cap are those of borrowed big buffer `big` (an I picture); the slot's own are kept below
@@ -208,6 +212,8 @@ public:
     void on_picture_md5(const struct EnginePic &p, const uint8_t *digests, int bad);
     // engine: the status words k_jpeg_entropy left for a device-path MJPEG picture (damaged segments, kinds of damage: jpeg_jobs.h)
     void on_jpeg_entropy_status(const struct EnginePic &p, uint32_t damaged, uint32_t kinds);
+    // engine: the kMpeg2StatusWords status words k_mpeg2_vlc left for a device-path MPEG-2 picture (mpeg2_jobs.h)
+    void mpeg2_device_status(const struct EnginePic &p, const uint32_t *words);
     struct EngineDecoderState &engine_state() { return *eng_state_; }
     // display frames that are decoded and packed and that the caller has not fetched yet (the engine asks: is this handle's next picture urgent?)
     int frames_done_unfetched() const { return done_unfetched_.load(std::memory_order_relaxed); }
@@ -273,6 +279,7 @@ private:
     bool mpeg2_activate(const Mpeg2Seq &seq);
     void mpeg2_show_anchor(std::vector<int> &out);
     void mpeg2_parse_task(PicTask *t);
+    bool mpeg2_parse_task_device(PicTask *t);  // option mpeg2_device_vlc: the prescan instead of the VLC decode; false: the host path takes the picture
     void mpeg2_fill_engine_pic(PicTask *t, struct EnginePic &ep);
     void gpu_close();
     void submit_ready();
@@ -438,6 +445,9 @@ private:
     int m2_anchor_[2] = {-1, -1};              // surfaces of the older / newer anchor picture (-1: none)
     bool m2_anchor_shown_ = true;              // the newer anchor has been queued for display (it waits for the next anchor, or the flush)
     std::atomic<long long> stat_dropped_{0}, stat_m2_clamped_{0}, stat_m2_rff_{0};
+    // option mpeg2_device_vlc (before init): 1 = pictures are VLC-decoded by k_mpeg2_vlc, one lane per slice, unless the prescan sends them to the host path
+    int mpeg2_dev_vlc_ = 0;
+    std::atomic<long long> stat_m2_dev_pics_{0}, stat_m2_host_pics_{0}, stat_m2_dev_slices_{0}, stat_m2_dev_damaged_{0};
     uint64_t m2_digest_ = 1469598103934665603ull; long long m2_digest_mbs_ = 0;      // written by the parse worker (sync option)
     struct TraceRec { uint64_t seq; long long t_dispatch, t_parsed, t_submit0, t_submit1; int is_i; };
     std::vector<TraceRec> trace_; bool trace_on_ = false;

@@ -518,6 +518,32 @@ void Engine::launch(Lane &ln, Batch &b) {
         }
     }
     if (any_mpeg2 && profile_ && !b.m2ev[0]) for (auto &e : b.m2ev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
+    // ... of which some are VLC-decoded on the device (option mpeg2_device_vlc): the parameter table of k_mpeg2_vlc, the status words and their pinned
+    // copy, when this slot of the ring first holds one; the lookup tables, once per engine.  A batch without such a picture reaches none of this
+    b.any_m2dev = false; int max_mpeg2_slices = 0;
+    if (any_mpeg2) for (auto &p : b.pics) b.any_m2dev |= p.codec == 4 && p.has_picture && p.mpeg2_on_device;
+    if (b.any_m2dev && (!b.h_m2v || !d_m2vtab_)) {
+        const size_t sb = sizeof(uint32_t) * kMaxBatch * kMpeg2StatusWords;
+        const Mpeg2VlcTables *tab = mpeg2_vlc_tables();
+        bool ok = tab != nullptr;
+        if (ok && !d_m2vtab_) {
+            ok = hipMalloc((void **)&d_m2vtab_, sizeof(Mpeg2VlcTables)) == hipSuccess && hipMemcpy(d_m2vtab_, tab, sizeof(Mpeg2VlcTables), hipMemcpyHostToDevice) == hipSuccess;
+            if (!ok && d_m2vtab_) { hipFree(d_m2vtab_); d_m2vtab_ = nullptr; }
+        }
+        if (ok && !b.h_m2v)
+            ok = hipHostMalloc((void **)&b.h_m2v, sizeof(Mpeg2VlcParams) * kMaxBatch, hipHostMallocDefault) == hipSuccess &&
+                 hipMalloc((void **)&b.d_m2v, sizeof(Mpeg2VlcParams) * kMaxBatch) == hipSuccess &&
+                 hipMalloc((void **)&b.d_m2status, sb) == hipSuccess && hipHostMalloc((void **)&b.h_m2status, sb, hipHostMallocDefault) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            if (b.h_m2v) hipHostFree(b.h_m2v); if (b.d_m2v) hipFree(b.d_m2v); if (b.d_m2status) hipFree(b.d_m2status); if (b.h_m2status) hipHostFree(b.h_m2status);
+            b.h_m2v = nullptr; b.d_m2v = nullptr; b.d_m2status = nullptr; b.h_m2status = nullptr; b.any_m2dev = false;
+            // no quiet fall-back: the pictures' records would never be written
+            for (auto &p : b.pics) if (p.codec == 4 && p.has_picture && p.mpeg2_on_device) { p.has_picture = false; p.dec->on_engine_error("hipMalloc(MPEG-2 VLC parameter table) failed"); }
+            any_mpeg2 = false; for (auto &p : b.pics) any_mpeg2 |= p.codec == 4 && p.has_picture;
+        }
+    }
+    if (b.any_m2dev && profile_ && !b.m2vev[0]) for (auto &e : b.m2vev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
     // pictures to verify (option verify_hash): the result words, when the batch first holds one.  Without them the pictures go unverified, and say so
     b.any_hash = false;
     for (auto &p : b.pics) b.any_hash |= p.codec == 1 && p.has_picture && p.hp.hash_mode != 0;
@@ -566,6 +592,11 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (any_mpeg2) {
             if (p.codec == 4 && p.has_picture) { b.h_mpics[i] = p.mp; max_mpeg2_items = std::max(max_mpeg2_items, p.mp.n_items); b.alg[11] += p.mpeg2_alg_bytes; b.npics[11]++; }
             else b.h_mpics[i].n_items = 0;
+        }
+        if (b.any_m2dev) {
+            if (p.codec == 4 && p.has_picture && p.mpeg2_on_device) { b.h_m2v[i] = p.mv; b.h_m2v[i].tab = d_m2vtab_; b.h_m2v[i].status = b.d_m2status + (size_t)i * kMpeg2StatusWords;
+                max_mpeg2_slices = std::max(max_mpeg2_slices, p.mv.n_slices); b.alg[13] += p.mpeg2_vlc_alg_bytes; b.npics[13]++; }
+            else b.h_m2v[i].n_slices = 0;
         }
         b.h_pics[i] = p.pp;
         if (!p.has_picture || hevc) b.h_pics[i].stages = 0;
@@ -650,6 +681,7 @@ void Engine::launch(Lane &ln, Batch &b) {
     if (any_jpeg) hipMemcpyAsync(b.d_jpics, b.h_jpics, sizeof(JpegPicParams) * n, hipMemcpyHostToDevice, ps);
     if (b.any_jdev) hipMemcpyAsync(b.d_jents, b.h_jents, sizeof(JpegEntropyParams) * n, hipMemcpyHostToDevice, ps);
     if (any_mpeg2) hipMemcpyAsync(b.d_mpics, b.h_mpics, sizeof(Mpeg2PicParams) * n, hipMemcpyHostToDevice, ps);
+    if (b.any_m2dev) hipMemcpyAsync(b.d_m2v, b.h_m2v, sizeof(Mpeg2VlcParams) * n, hipMemcpyHostToDevice, ps);
     b.out.each([&](auto &t) { for (int side : {kBefore, kAfter}) if (t.n[side])
         hipMemcpyAsync(t.dev + side * kOutSideCap, t.h(side), sizeof(*t.host) * t.n[side], hipMemcpyHostToDevice, ps); });
     // job lists were copied on the (in-order) copy stream when the pictures were parsed: waiting for the most recently
@@ -708,6 +740,16 @@ void Engine::launch(Lane &ln, Batch &b) {
     }
     // MPEG-2 pictures of the batch: Engine::form let a stream's further pictures in only when they reference nothing the batch writes, so one launch
     // reconstructs them all (their references were finished by earlier batches on this in-order stream)
+    // MPEG-2 pictures whose slices the device decodes: k_mpeg2_vlc writes the records and entries k_mpeg2_recon reads, on the same in-order stream;
+    // the status words come back behind the kernel (Engine::complete hands them to the handles)
+    if (b.any_m2dev && max_mpeg2_slices > 0) {
+        const bool timed = profile_ && b.m2vev[0] && b.m2vev[1];
+        hipMemsetAsync(b.d_m2status, 0, sizeof(uint32_t) * (size_t)n * kMpeg2StatusWords, st);
+        if (timed) hipEventRecord(b.m2vev[0], st);
+        launch_mpeg2_vlc(b.d_m2v, n, max_mpeg2_slices, st);
+        if (timed) { hipEventRecord(b.m2vev[1], st); b.pmask |= 131072; }
+        hipMemcpyAsync(b.h_m2status, b.d_m2status, sizeof(uint32_t) * (size_t)n * kMpeg2StatusWords, hipMemcpyDeviceToHost, st);
+    }
     if (any_mpeg2 && max_mpeg2_items > 0) {
         const bool timed = profile_ && b.m2ev[0] && b.m2ev[1];
         if (timed) hipEventRecord(b.m2ev[0], st);
@@ -995,6 +1037,7 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
         add(10, 19, 20, b.pmask & 8192); add(10, 21, 22, b.pmask & 16384);
         if (b.pmask & 1024) { float ms = 0; if (hipEventElapsedTime(&ms, b.jev[0], b.jev[1]) == hipSuccess) { st_.ns[7] += ms * 1e6; st_.launches[7]++; } }
         if (b.pmask & 65536) { float ms = 0; if (hipEventElapsedTime(&ms, b.jeev[0], b.jeev[1]) == hipSuccess) { st_.ns[12] += ms * 1e6; st_.launches[12]++; } }
+        if (b.pmask & 131072) { float ms = 0; if (hipEventElapsedTime(&ms, b.m2vev[0], b.m2vev[1]) == hipSuccess) { st_.ns[13] += ms * 1e6; st_.launches[13]++; } }
         if (b.pmask & 32768) { float ms = 0; if (hipEventElapsedTime(&ms, b.m2ev[0], b.m2ev[1]) == hipSuccess) { st_.ns[11] += ms * 1e6; st_.launches[11]++; } }
         if (b.pmask & 4096) { float ms = 0; if (hipEventElapsedTime(&ms, b.mev[0], b.mev[1]) == hipSuccess) { st_.ns[9] += ms * 1e6; st_.launches[9]++; } }
         for (int k = 0; k < kKernelClasses; k++) { st_.pics[k] += b.npics[k]; st_.alg_bytes[k] += b.alg[k]; }
@@ -1063,6 +1106,11 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
     if (b.any_jdev && b.h_jstatus && !failed) for (size_t i = 0; i < b.pics.size(); i++) {
         const EnginePic &p = b.pics[i];
         if (p.codec == 2 && p.has_picture && p.jpeg_on_device) p.dec->on_jpeg_entropy_status(p, b.h_jstatus[i * kJpegStatusWords], b.h_jstatus[i * kJpegStatusWords + 1]);
+    }
+    // option mpeg2_device_vlc: what k_mpeg2_vlc met, per picture
+    if (b.any_m2dev && b.h_m2status && !failed) for (size_t i = 0; i < b.pics.size(); i++) {
+        const EnginePic &p = b.pics[i];
+        if (p.codec == 4 && p.has_picture && p.mpeg2_on_device) p.dec->mpeg2_device_status(p, b.h_m2status + i * kMpeg2StatusWords);
     }
     for (auto &p : b.pics) p.dec->on_engine_done(p, failed);
     b.pics.clear();

@@ -64,6 +64,8 @@ struct EnginePic {
     // option jpeg_device_entropy: k_jpeg_entropy decodes the scan in front of k_jpeg_recon (je.status is set by Engine::launch)
     bool jpeg_on_device = false, jpeg_host_error = false; JpegEntropyParams je; long long jpeg_entropy_alg_bytes = 0;
     Mpeg2PicParams mp; long long mpeg2_alg_bytes = 0;
+    // option mpeg2_device_vlc: k_mpeg2_vlc decodes the slices in front of k_mpeg2_recon (mv.tab and mv.status are set by Engine::launch)
+    bool mpeg2_on_device = false; Mpeg2VlcParams mv; long long mpeg2_vlc_alg_bytes = 0;
     int job_slot = -1;
     ihipEvent_t *uploaded = nullptr; unsigned long long upload_seq = 0;   // job list copy (copy stream), see Engine::upload
     OutSide out[2];                                 // display frames to pack before (kBefore) / after (kAfter) this picture's kernels
@@ -97,8 +99,8 @@ struct EnginePic {
 // per kernel class: 0 recon_inter, 1 intra, 2 deblock (prep+lds), 3 packout (every pack-out kernel), 4 chain (k_chain: recon + deblock),
 // 5 rgb_pack (k_rgb_pack alone: its frames are counted in class 3 too), 6 deint (k_deint alone, likewise), 7 jpeg (k_jpeg_recon),
 // 8 pichash (k_hevc_pichash: pictures hashed, 1.5 w h bytes each), 9 md5 (k_hevc_md5, likewise), 10 rgb_pack444 (k_rgb_pack444 alone),
-// 11 mpeg2 (k_mpeg2_recon), 12 jpeg_entropy (k_jpeg_entropy)
-constexpr int kKernelClasses = 13;
+// 11 mpeg2 (k_mpeg2_recon), 12 jpeg_entropy (k_jpeg_entropy), 13 mpeg2_vlc (k_mpeg2_vlc)
+constexpr int kKernelClasses = 14;
 struct EngineStats {
     double ns[kKernelClasses] = {}; long long launches[kKernelClasses] = {}, pics[kKernelClasses] = {}, alg_bytes[kKernelClasses] = {};
     long long batches = 0, batch_pics = 0, chain_batches = 0, chain_pics = 0, wait_errors = 0, chain_recoveries = 0;
@@ -170,6 +172,10 @@ private:
         bool any_jdev = false;
         // ... and for MPEG-2 pictures, around k_mpeg2_recon
         Mpeg2PicParams *h_mpics = nullptr, *d_mpics = nullptr; ihipEvent_t *m2ev[2] = {nullptr, nullptr};
+        // MPEG-2 pictures with option mpeg2_device_vlc: the parameter table of k_mpeg2_vlc, the status words (kMpeg2StatusWords per picture) with
+        // their pinned copy, the two profile events -- created when the batch first holds such a picture, like h_jents
+        Mpeg2VlcParams *h_m2v = nullptr, *d_m2v = nullptr; uint32_t *d_m2status = nullptr, *h_m2status = nullptr; ihipEvent_t *m2vev[2] = {nullptr, nullptr};
+        bool any_m2dev = false;
         int *d_progress = nullptr;                            // CTB row progress counters of k_hevc_intra
         int *d_ctl = nullptr;                                 // H.264: kMaxBatch control blocks (chain_common.h), cleared once per batch
         int *h_err = nullptr, *d_err = nullptr;               // error words, one per picture: pinned host memory and its device address
@@ -265,6 +271,7 @@ private:
     std::atomic<long long> chain_block_until_ns_{0};
     int chain_linger_streams_ = 2;                  // up to this many active streams the next chain launch waits for the running one (Engine::form)
     std::mutex sm_; EngineStats st_;
+    struct Mpeg2VlcTables *d_m2vtab_ = nullptr;     // option mpeg2_device_vlc: the lookup tables of k_mpeg2_vlc, uploaded when the first such picture arrives (engine thread)
     std::thread th_;
 };
 

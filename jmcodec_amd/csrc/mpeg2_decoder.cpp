@@ -126,6 +126,11 @@ void Decoder::mpeg2_parse_task(PicTask *t) {
     auto pt0 = std::chrono::steady_clock::now();
     Mpeg2Task &mt = *t->mpeg2;
     JobSlot &js = jobs_[t->job_slot];
+    // option mpeg2_device_vlc: the device path, unless the handle wants the host-made lists (parse_only, the digests) or the prescan declines
+    if (mpeg2_dev_vlc_) {
+        if (!parse_only_ && !want_digest_ && !want_job_digest_ && mpeg2_parse_task_device(t)) return;
+        stat_m2_host_pics_++;
+    }
     static thread_local Mpeg2Jobs jobs;
     bool refuse = false;
     const std::string e = mpeg2_decode_picture(mt.pic, jobs, &refuse);
@@ -157,6 +162,60 @@ void Decoder::mpeg2_parse_task(PicTask *t) {
     { std::lock_guard<std::mutex> lk(mtx_); parse_pending_--; cv_.notify_all(); }
 }
 
+// worker, option mpeg2_device_vlc: one pass over the picture's slices finds their first macroblock addresses; the VLC decode itself is k_mpeg2_vlc's
+bool Decoder::mpeg2_parse_task_device(PicTask *t) {
+    auto pt0 = std::chrono::steady_clock::now();
+    Mpeg2Task &mt = *t->mpeg2;
+    JobSlot &js = jobs_[t->job_slot];
+    static thread_local Mpeg2SliceScan scan;
+    if (!mpeg2_slice_scan(mt.pic, scan).empty()) return false;
+    mt.on_device = true;
+    std::vector<uint8_t>().swap(mt.pic.data);
+    const size_t n_mbs = (size_t)mt.pic.seq.mb_w() * mt.pic.seq.mb_h();
+    size_t off = 0;
+    auto place = [&](size_t bytes) { size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
+    // uploaded: the picture's parameters, the slice table, the slice bytes
+    mt.off_par = place(sizeof(Mpeg2VlcPic)); mt.off_slices = place(scan.slices.size() * sizeof(Mpeg2Slice)); mt.off_bytes = place(scan.bytes.size());
+    const size_t up = off;
+    // device only: the records and the entries k_mpeg2_vlc writes and k_mpeg2_recon reads
+    off = 0;
+    mt.off_mbs = place(n_mbs * sizeof(Mpeg2Mb)); mt.off_entries = place((size_t)scan.n_entries * 4);
+    const size_t dev_only = off;
+    mt.n_entries = (int)scan.n_entries; mt.n_slices = (int)scan.slices.size();
+    t->n_slices = 1;
+    if (!ensure_job_cap(js, up + 64) || !ensure_dev_only(js, dev_only + 64)) fail("job buffer allocation failed");
+    else {
+        memset(js.host, 0, up);
+        const Mpeg2VlcPic vp = mpeg2_vlc_pic(mt.pic);
+        memcpy(js.host + mt.off_par, &vp, sizeof vp);
+        memcpy(js.host + mt.off_slices, scan.slices.data(), scan.slices.size() * sizeof(Mpeg2Slice));
+        memcpy(js.host + mt.off_bytes, scan.bytes.data(), scan.bytes.size());
+        t->upload_bytes = up;
+        stat_pictures_++; stat_job_bytes_ += (long long)up;
+        stat_m2_dev_pics_++; stat_m2_dev_slices_ += (long long)scan.slices.size();
+        if (!failed_) t->upload_seq = engine_->upload(js.dev, js.host, up, js.uploaded, false);
+    }
+    (mt.pic.type == 1 ? stat_parse_ns_i_ : stat_parse_ns_p_) += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - pt0).count();
+    t->state.store(1, std::memory_order_release);
+    submit_ready();
+    { std::lock_guard<std::mutex> lk(mtx_); parse_pending_--; cv_.notify_all(); }
+    return true;
+}
+
+// engine thread: what k_mpeg2_vlc reported for a device-path picture.  `errors` counts as mpeg2_parse_task counts: once for a picture with damage (or
+// macroblocks no slice covers), once more for one with clamped vectors; the texts are the host path's.  Dual prime fails the handle, as on the host
+// path -- but here the picture has been reconstructed (concealed from the dual-prime macroblock on) and frames of earlier pictures may be out already
+void Decoder::mpeg2_device_status(const EnginePic &, const uint32_t *words) {
+    const uint32_t damaged = words[0], kinds = words[1], clamped = words[2], flags = words[3];
+    stat_m2_dev_damaged_ += damaged;
+    if (flags & 2) { stat_errors_++; fail(std::string("MPEG-2: ") + mpeg2_vlc_damage_text(kM2DmgDualPrime)); }
+    else if (kinds) {
+        int kind = 1; while (kind < kM2DmgKinds && !(kinds >> kind & 1)) kind++;
+        stat_errors_++; note_error(std::string("MPEG-2: ") + mpeg2_vlc_damage_text(kind));
+    } else if (flags & 1) { stat_errors_++; note_error("MPEG-2: macroblocks that no slice covers"); }
+    if (clamped) { stat_m2_clamped_ += clamped; stat_errors_++; note_error("MPEG-2: vectors that reach outside the reference picture were clamped"); }
+}
+
 // describe the picture to the device engine (called by submit_task)
 void Decoder::mpeg2_fill_engine_pic(PicTask *t, EnginePic &ep) {
     const Mpeg2Task &mt = *t->mpeg2;
@@ -173,7 +232,18 @@ void Decoder::mpeg2_fill_engine_pic(PicTask *t, EnginePic &ep) {
     mp.mb_w = mb_w_; mp.mb_h = mb_h_;
     mp.n_items = mb_h_ * ((mb_w_ + 3) / 4);
     mp.n_entries = mt.n_entries; mp.dc_mult = 8 >> mt.pic.intra_dc_precision;
-    mp.mbs = (const Mpeg2Mb *)(js.dev + mt.off_mbs); mp.entries = (const uint32_t *)(js.dev + mt.off_entries);
+    uint8_t *lists = mt.on_device ? js.dev_only : js.dev;        // (device path: written by k_mpeg2_vlc in front of k_mpeg2_recon; n_entries is the capacity)
+    mp.mbs = (const Mpeg2Mb *)(lists + mt.off_mbs); mp.entries = (const uint32_t *)(lists + mt.off_entries);
+    ep.mpeg2_on_device = mt.on_device;
+    if (mt.on_device) {
+        Mpeg2VlcParams &mv = ep.mv;
+        memset(&mv, 0, sizeof mv);
+        mv.n_slices = mt.n_slices;
+        mv.pic = (const Mpeg2VlcPic *)(js.dev + mt.off_par); mv.slices = (const Mpeg2Slice *)(js.dev + mt.off_slices); mv.bytes = (const uint32_t *)(js.dev + mt.off_bytes);
+        mv.mbs = (Mpeg2Mb *)(lists + mt.off_mbs); mv.entries = (uint32_t *)(lists + mt.off_entries);
+        // algorithmic bytes of k_mpeg2_vlc: what was uploaded in, a record per macroblock out (the entries it writes are not known here)
+        ep.mpeg2_vlc_alg_bytes = (long long)t->upload_bytes + 32ll * mb_w_ * mb_h_;
+    }
     memcpy(mp.w, mt.pic.seq.w, sizeof mp.w);
     // algorithmic bytes: the job list in, the reference rows of each direction in, 1.5 W H out
     ep.mpeg2_alg_bytes = (long long)t->upload_bytes + (long long)(n_refs + 1) * mb_w_ * mb_h_ * 384;

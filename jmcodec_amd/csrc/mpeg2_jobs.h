@@ -47,4 +47,24 @@ struct Mpeg2PicParams {
 // blockIdx.y = picture; a picture with n_items == 0 takes no part.  max_items: the largest n_items of the batch
 void launch_mpeg2_recon(const Mpeg2PicParams *d_pics, int n, int max_items, ihipStream_t *st);
 
+// Option mpeg2_device_vlc: a picture whose slices the device VLC-decodes (k_mpeg2_vlc, in front of k_mpeg2_recon on the same stream).  The host
+// uploads the picture's parameters, a slice table and the slice bytes (mpeg2_vlc.h); the records and entries -- the arrays Mpeg2PicParams names too --
+// exist in device memory only and are written here.  tab: the engine's copy of the lookup tables, set by Engine::launch, as is status: kMpeg2StatusWords
+// words of the batch's status array, zeroed before the launch: [0] counts the picture's damaged slices, [1] collects the kinds of damage (1 << kind,
+// mpeg2_vlc.h), [2] counts the macroblocks whose vectors were clamped, [3] bit 0: holes were concealed, bit 1: dual prime was met.
+struct Mpeg2VlcTables; struct Mpeg2VlcPic; struct Mpeg2Slice;
+constexpr int kMpeg2StatusWords = 4;
+struct Mpeg2VlcParams {
+    int n_slices;                 // 0: the picture takes no part (host path, another codec, no picture)
+    int pad;
+    const Mpeg2VlcPic *pic;
+    const Mpeg2Slice *slices;     // [n_slices]
+    const uint32_t *bytes;
+    const Mpeg2VlcTables *tab;
+    Mpeg2Mb *mbs; uint32_t *entries;
+    uint32_t *status;
+};
+// blockIdx.y = picture, one lane per slice, workgroups of 64 lanes.  max_slices: the largest n_slices of the batch
+void launch_mpeg2_vlc(const Mpeg2VlcParams *d_pics, int n, int max_slices, ihipStream_t *st);
+
 }  // namespace jmamd

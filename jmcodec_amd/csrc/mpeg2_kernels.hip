@@ -1,4 +1,5 @@
 // jmcodec_amd/csrc/mpeg2_kernels.hip -- k_mpeg2_recon: MPEG-2 frame pictures (codec_type 4) from their job lists into NV12 surfaces, gfx950.
+// (k_mpeg2_vlc, which writes those lists on the device with option mpeg2_device_vlc, is at the end of the file with a header of its own.)
 //
 // One wave per work item; blockIdx.y = picture.  An item is four neighbouring macroblocks of one macroblock row: a 64 x 16 luma strip and a 64 x 8
 // strip of interleaved chroma.  Its 24 blocks go through the IDCT in three rounds of eight: round 0 the blocks Y0 Y1 of the four macroblocks, round 1
@@ -29,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include "mpeg2_jobs.h"
 #include "mpeg2_recon.h"
+#include "mpeg2_vlc.h"
 
 namespace jmamd {
 
@@ -121,6 +123,47 @@ __global__ __launch_bounds__(64 * kM2Waves) void k_mpeg2_recon(const Mpeg2PicPar
 void launch_mpeg2_recon(const Mpeg2PicParams *d_pics, int n, int max_items, ihipStream_t *st) {
     if (n <= 0 || max_items <= 0) return;
     hipLaunchKernelGGL(k_mpeg2_recon, dim3((max_items + kM2Waves - 1) / kM2Waves, n), dim3(64 * kM2Waves), 0, st, d_pics);
+}
+
+// k_mpeg2_vlc: option mpeg2_device_vlc -- the slice / macroblock / block VLC decode of the pictures' slices (mpeg2_vlc.h has the routine, the layout of
+// what it reads, the capacity and the bounds of its loops).  blockIdx.y = picture, one lane per slice, 64 consecutive slices of a picture per wave, one
+// wave per workgroup: a wave holds slices of one picture only, so the picture's parameters are wave-uniform (they are read through a uniform
+// pointer and stay in scalar registers).
+// Tables: Mpeg2VlcTables, 15,936 bytes, staged in LDS by the workgroup with 16-byte copies -- 10 workgroups fit the 160 KiB of a CU by LDS.  One
+// barrier follows the copy and every lane of the workgroup reaches it: the only return in front of it is taken by a whole workgroup, lanes beyond
+// the picture's slice count idle behind it.
+// A lane's decode is one chain of dependent steps -- window -> table -> shift -> window -- and 64 lanes are at unrelated places of the syntax
+// (address increment, vectors, coefficients), so the wave runs the union of their branches: divergent and latency-bound, like k_jpeg_entropy; the
+// table reads are LDS reads at unrelated addresses.  This is reasoning from the code; profiles/r20_mpeg2_device_vlc.txt has what was measured, and
+// no bound is claimed beyond it.
+// The slice bytes are read as aligned dwords from global memory (a lane's 64-byte line lasts it 16 refills); a record is two 16-byte vector
+// stores, an entry one 4-byte store -- global_load / global_store: the routine casts the three arrays to global-memory pointers, as flat
+// instructions would tie every table read's wait to the stores in flight -- and the status words are raised with ordinary atomics on vector addresses.  Plain C++, no inline assembly.
+// The predictors (pmv, dc_pred) are indexed by constants only and live in registers.
+// gfx950 compile (-Rpass-analysis=kernel-resource-usage): 121 VGPRs, 106 SGPRs (42 spilled to vector lanes), no scratch,
+// 15,936 bytes of LDS, 3 waves per SIMD by the compiler's count.
+__global__ __launch_bounds__(64) void k_mpeg2_vlc(const Mpeg2VlcParams *pics) {
+    const Mpeg2VlcParams &pp = pics[blockIdx.y];
+    if ((int)blockIdx.x * 64 >= pp.n_slices) return;                    // (the whole workgroup: no barrier is left behind)
+    __shared__ __attribute__((aligned(16))) uint4 sTab[sizeof(Mpeg2VlcTables) / 16];
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(pp.tab);
+        for (int i = threadIdx.x; i < (int)(sizeof(Mpeg2VlcTables) / 16); i += 64) sTab[i] = src[i];
+    }
+    __syncthreads();
+    const int s = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (s >= pp.n_slices) return;
+    const Mpeg2VlcPic pic = *pp.pic;
+    const Mpeg2Slice sl = pp.slices[s];
+    const uint32_t st = mpeg2_vlc_slice(pic, reinterpret_cast<const Mpeg2VlcTables *>(sTab), sl, pp.bytes, pp.mbs, pp.entries, nullptr);
+    if (st & kM2StKindMask) { atomicAdd(pp.status, 1u); atomicOr(pp.status + 1, 1u << (st & kM2StKindMask)); }
+    if (st >> kM2StClampedShift) atomicAdd(pp.status + 2, st >> kM2StClampedShift);
+    if (st & (kM2StHoles | kM2StDualPrime)) atomicOr(pp.status + 3, ((st & kM2StHoles) ? 1u : 0u) | ((st & kM2StDualPrime) ? 2u : 0u));
+}
+
+void launch_mpeg2_vlc(const Mpeg2VlcParams *d_pics, int n, int max_slices, ihipStream_t *st) {
+    if (n <= 0 || max_slices <= 0) return;
+    hipLaunchKernelGGL(k_mpeg2_vlc, dim3((max_slices + 63) / 64, n), dim3(64), 0, st, d_pics);
 }
 
 }  // namespace jmamd

@@ -483,4 +483,116 @@ std::string mpeg2_decode_picture(const Mpeg2Pic &pic, Mpeg2Jobs &jobs, bool *ref
     return d.err;
 }
 
+// ---- option mpeg2_device_vlc -----------------------------------------------------------------------------------------------------------
+namespace {
+// one-level table of mpeg2_vlc.h: by the next `bits` bits, length | (a + 1) << 5
+bool fill_small(int which, uint16_t *look, int bits) {
+    int n; const Mpeg2Vlc *t = mpeg2_table(which, &n);
+    for (int i = 0; i < (1 << bits); i++) look[i] = 0;
+    for (int i = 0; i < n; i++) {
+        if (t[i].len > bits || t[i].a < 0 || t[i].a > 2046) return false;
+        const int sh = bits - t[i].len;
+        for (uint32_t k = 0; k < (1u << sh); k++) look[((uint32_t)t[i].code << sh) | k] = (uint16_t)(t[i].len | (t[i].a + 1) << 5);
+    }
+    return true;
+}
+// two-level table of B-14 / B-15: (length - 1) | run << 4 | level << 10, run 62 = escape, 63 = end of block
+bool fill_dct(int which, uint16_t *look) {
+    int n; const Mpeg2Vlc *t = mpeg2_table(which, &n);
+    for (int i = 0; i < 1280; i++) look[i] = 0;
+    for (int i = 0; i < n; i++) {
+        const int len = t[i].len, run = t[i].a == -1 ? 63 : (t[i].a == -2 ? 62 : t[i].a), level = t[i].a < 0 ? 0 : t[i].b;
+        if (len < 1 || len > 16 || run < 0 || run > 63 || (t[i].a >= 0 && run > 61) || level < 0 || level > 63) return false;
+        const uint16_t e = (uint16_t)((len - 1) | run << 4 | level << 10);
+        const uint32_t c16 = (uint32_t)t[i].code << (16 - len);              // the code at the top of 16 bits
+        if (c16 >> 10) {                                                     // level 1: one of its first six bits is set
+            if (len > 8) return false;
+            for (uint32_t k = 0; k < (1u << (8 - len)); k++) look[(c16 >> 8) | k] = e;
+        } else {
+            for (uint32_t k = 0; k < (1u << (16 - len)); k++) look[256 + ((c16 | k) & 1023)] = e;
+        }
+    }
+    return true;
+}
+}  // namespace
+
+const Mpeg2VlcTables *mpeg2_vlc_tables() {
+    static Mpeg2VlcTables tab;
+    static const bool ok = [] {
+        bool good = fill_small(1, tab.mba, 11) && fill_small(2, tab.mbtype[0], 6) && fill_small(3, tab.mbtype[1], 6) && fill_small(4, tab.mbtype[2], 6) &&
+                    fill_small(9, tab.cbp, 9) && fill_small(10, tab.motion, 10) && fill_small(12, tab.dc_luma, 9) && fill_small(13, tab.dc_chroma, 10) &&
+                    fill_dct(14, tab.dct[0]) && fill_dct(15, tab.dct[1]);
+        memcpy(tab.scan, kMpeg2Scan, sizeof tab.scan);
+        for (int ty = 0; ty < 2; ty++) for (int c = 0; c < 32; c++) tab.qscale[ty][c] = (uint8_t)mpeg2_quantiser_scale(ty, c);
+        return good;
+    }();
+    return ok ? &tab : nullptr;
+}
+
+Mpeg2VlcPic mpeg2_vlc_pic(const Mpeg2Pic &pic) {
+    Mpeg2VlcPic v = {};
+    v.type = pic.type;
+    for (int s = 0; s < 2; s++) for (int t = 0; t < 2; t++) v.f_code[s][t] = pic.f_code[s][t];
+    v.intra_dc_precision = pic.intra_dc_precision; v.frame_pred_frame_dct = pic.frame_pred_frame_dct; v.concealment_mv = pic.concealment_mv;
+    v.q_scale_type = pic.q_scale_type; v.intra_vlc_format = pic.intra_vlc_format; v.alternate_scan = pic.alternate_scan;
+    v.mb_w = pic.seq.mb_w(); v.mb_h = pic.seq.mb_h();
+    return v;
+}
+
+std::string mpeg2_slice_scan(const Mpeg2Pic &pic, Mpeg2SliceScan &out) {
+    const int mb_w = pic.seq.mb_w(), mb_h = pic.seq.mb_h();
+    const uint32_t total = (uint32_t)mb_w * (uint32_t)mb_h;
+    out.slices.clear(); out.bytes.clear(); out.n_entries = 0;
+    const uint8_t *p = pic.data.data(); const size_t n = pic.data.size();
+    size_t o = 0;
+    while (o + 4 <= n) {
+        // the next start code prefix 00 00 01 at or behind o + 4 (memchr for the 01, as Mpeg2Splitter::find_start looks for it)
+        size_t e = n;
+        for (size_t i = o + 6; i < n;) {
+            const uint8_t *q = (const uint8_t *)memchr(p + i, 1, n - i);
+            if (!q) break;
+            const size_t k = (size_t)(q - p);
+            if (p[k - 1] == 0 && p[k - 2] == 0) { e = k - 2; break; }
+            i = k + 1;
+        }
+        const uint8_t *sp = p + o + 4; const size_t L = e - (o + 4);
+        const int row = (int)p[o + 3] - 1;
+        o = e;
+        if (row < 0 || row >= mb_h) return "MPEG-2: a slice outside the picture";
+        Bits b(sp, L);
+        if (b.get(5) == 0) return "MPEG-2: quantiser_scale_code 0";
+        if (b.get(1)) { b.skip(8); while (b.get(1) && !b.over) b.skip(8); }
+        if (b.over || b.left() == 0 || b.peek(23) == 0) continue;            // no macroblock: the slice decode's loop would not run once
+        uint32_t inc = 0;
+        for (;;) {
+            const Mpeg2Vlc *m = b.vlc(lut(1));
+            if (!m) return "MPEG-2: invalid macroblock_address_increment";
+            if (m->a == 34) { inc += 33; if (inc > total) return "MPEG-2: a macroblock address beyond the picture"; continue; }
+            inc += (uint32_t)m->a; break;
+        }
+        const uint32_t s = (uint32_t)row * (uint32_t)mb_w + inc - 1;
+        if (s >= total) return "MPEG-2: a macroblock address beyond the picture";
+        Mpeg2Slice sl = {};                                                  // (lo holds the first address until the table is complete)
+        sl.byte_off = (uint32_t)out.bytes.size(); sl.n_bytes = (uint32_t)L; sl.row = (uint32_t)row; sl.lo = s;
+        if (!out.slices.empty() && s <= out.slices.back().lo) return "MPEG-2: slices that overlap or are out of order";
+        out.slices.push_back(sl);
+        out.bytes.insert(out.bytes.end(), sp, sp + L);
+        out.bytes.resize(sl.byte_off + mpeg2_vlc_padded((uint32_t)L), 0);
+    }
+    if (out.slices.empty()) return "MPEG-2: a picture without slices";
+    uint64_t first_entry = 0;
+    for (size_t i = 0; i < out.slices.size(); i++) {
+        Mpeg2Slice &sl = out.slices[i];
+        sl.hi = i + 1 < out.slices.size() ? out.slices[i + 1].lo : total;
+        if (i == 0) sl.lo = 0;
+    }
+    for (auto &sl : out.slices) {
+        sl.first_entry = (uint32_t)first_entry; sl.entry_cap = mpeg2_vlc_capacity(sl.n_bytes, sl.hi - sl.lo);
+        first_entry += sl.entry_cap;
+    }
+    if (first_entry > 0x7fffffffull) return "MPEG-2: a picture whose entry list would not fit";
+    out.n_entries = (uint32_t)first_entry;
+    return std::string();
+}
+
 }  // namespace jmamd

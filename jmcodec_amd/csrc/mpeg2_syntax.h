@@ -3,6 +3,7 @@
 // refused: INTEGRATION.md "MPEG-2".  No HIP: the parse pool, tests/native/mpeg2_check.cpp and tools/fuzz_mpeg2.cpp all build it.
 #pragma once
 #include "mpeg2_jobs.h"
+#include "mpeg2_vlc.h"
 #include <stddef.h>
 #include <string>
 #include <vector>
@@ -55,6 +56,22 @@ struct Mpeg2Jobs {
 // macroblocks no slice covers) is concealed -- zero-vector forward copies in P and B pictures, grey intra blocks in I pictures -- and the reason is
 // returned ("" = clean).  *refuse is set when the reason is a feature the decoder refuses (dual prime).
 std::string mpeg2_decode_picture(const Mpeg2Pic &pic, Mpeg2Jobs &jobs, bool *refuse);
+
+// ---- option mpeg2_device_vlc: the prescan that replaces the slice decode on the host (the decode itself is mpeg2_vlc_slice, mpeg2_vlc.h) ----
+// The device form of the Annex B tables, built once per process from mpeg2_table(); nullptr if a table does not fit the two-level scheme.
+const Mpeg2VlcTables *mpeg2_vlc_tables();
+// the picture's parameters as the device routine reads them
+Mpeg2VlcPic mpeg2_vlc_pic(const Mpeg2Pic &pic);
+struct Mpeg2SliceScan {
+    std::vector<Mpeg2Slice> slices;    // in stream order; their spans tile [0, mb_w * mb_h)
+    std::vector<uint8_t> bytes;        // every slice's bytes at its byte_off: padded to a multiple of 4, then kMpeg2SliceGuard zero bytes
+    uint32_t n_entries = 0;            // the capacities added up: the size of the device's entry list
+};
+// One pass over pic.data: per slice the header and the first macroblock_address_increment, nothing more.  "" when the picture can take the device
+// path; else why not (a slice header the prescan cannot accept -- quantiser_scale_code 0, a slice outside the picture, an invalid first increment, a
+// first address beyond the picture --, first addresses that do not strictly increase, or no slice at all): the host path decodes such a picture.
+// A slice without a macroblock (nothing but zero bits behind its header) takes no lane: the host path does nothing with it either.
+std::string mpeg2_slice_scan(const Mpeg2Pic &pic, Mpeg2SliceScan &out);
 
 // Incremental front end: feed any chunking of the elementary stream.  Units are cut at start codes, headers are read as they complete, and a picture
 // is handed to the sink when the next picture, group, sequence header or sequence end start code arrives, or at flush.

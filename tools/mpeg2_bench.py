@@ -8,8 +8,12 @@ Per leg and round one JSON line: frames / s, host CPU ms per frame (process CPU 
 decode's share (stats parse_ns_i + parse_ns_p), and -- option profile -- k_mpeg2_recon's microseconds per picture and its algorithmic bytes (job
 list + reference rows + 1.5 W H) against 8 TB/s.  The kernel's time per picture TYPE comes from running the three kinds: I alone, then P from the IP
 run and B from the IBBP run by subtracting the shares already known (`--split`).  Then a summary line with the medians.
+--device-vlc runs every leg twice, option mpeg2_device_vlc at 0 and at 1, alternating within each round on the same group, for every stream count of
+`--streams` (a list: 32,1 adds the lone-stream pair), and adds upload bytes per picture and k_mpeg2_vlc's microseconds per picture; the summary then
+carries min / median / max frames per second of every leg, and the option-0 leg of the same call is the reference of every figure.  A library
+without the option (JM_AMD_DEC_LIB names the parent commit's) runs the option-0 legs only.
 
-    python tools/mpeg2_bench.py [--streams 32] [--groups 8] [--rounds 3] [--kind IBBP] [--stream file.m2v] [--write file.m2v] [--split]
+    python tools/mpeg2_bench.py [--streams 32,1] [--groups 8] [--rounds 3] [--kind IBBP] [--stream file.m2v] [--write file.m2v] [--split] [--device-vlc]
 """
 import argparse
 import ctypes as C
@@ -40,13 +44,15 @@ def make_group(kind, width=W, height=H):
     return S.build(items)
 
 
-def run_leg(L, pics, S_, groups, device):
+def run_leg(L, pics, S_, groups, device, device_vlc=0):
     hs = []
     for _ in range(S_):
         h = api.jm_nvdec_create_handle()
         for k, v in (dict(device_output=1) if device else {}).items():
             assert L.jm_amddec_set_option(h, k.encode(), v) == 0
         assert L.jm_amddec_set_option(h, b"profile", 1) == 0
+        if device_vlc:
+            assert L.jm_amddec_set_option(h, b"mpeg2_device_vlc", device_vlc) == 0
         if api.jm_nvdec_init(4, 0, None, 0, h) != 0:
             raise SystemExit("init failed: " + L.jm_amddec_last_error(h).decode())
         hs.append(h)
@@ -83,12 +89,15 @@ def run_leg(L, pics, S_, groups, device):
     everyone(2, False)                               # warm-up: surfaces, job slots, the engine's tables
     base = sum(counts)
     k0 = (stat(hs[0], b"k_mpeg2_ns"), stat(hs[0], b"k_mpeg2_pics"), stat(hs[0], b"k_mpeg2_alg_bytes"))
+    v0 = (stat(hs[0], b"k_mpeg2_vlc_ns"), stat(hs[0], b"k_mpeg2_vlc_pics"))
     p0 = sum(stat(h, b"parse_ns_i") + stat(h, b"parse_ns_p") for h in hs)
     t0, c0 = time.perf_counter(), time.process_time()
     everyone(groups, True)
     dt, cpu = time.perf_counter() - t0, time.process_time() - c0
     n = sum(counts) - base
     k1 = (stat(hs[0], b"k_mpeg2_ns"), stat(hs[0], b"k_mpeg2_pics"), stat(hs[0], b"k_mpeg2_alg_bytes"))
+    v1 = (stat(hs[0], b"k_mpeg2_vlc_ns"), stat(hs[0], b"k_mpeg2_vlc_pics"))
+    dev_pics = sum(max(0, stat(h, b"mpeg2_dev_pictures")) for h in hs)
     p1 = sum(stat(h, b"parse_ns_i") + stat(h, b"parse_ns_p") for h in hs)
     job = stat(hs[0], b"job_bytes") / max(1, stat(hs[0], b"pictures"))
     for h in hs:
@@ -99,12 +108,14 @@ def run_leg(L, pics, S_, groups, device):
     return dict(frames=n, seconds=round(dt, 3), frames_per_s=round(n / dt, 1), host_cpu_ms_per_frame=round(1e3 * cpu / max(1, n), 3),
                 vlc_ms_per_picture=round((p1 - p0) / 1e6 / max(1, S_ * groups * len(pics)), 3), k_mpeg2_recon_us_per_picture=round(k_us, 2),
                 k_mpeg2_alg_bytes_per_picture=int(k_bytes), k_mpeg2_achieved_TBps=round(k_bytes / max(1e-9, k_us * 1e-6) / 1e12, 4),
-                k_mpeg2_share_of_8TBps=round(k_bytes / max(1e-9, k_us * 1e-6) / 8e12, 4), job_list_bytes_per_picture=int(job))
+                k_mpeg2_share_of_8TBps=round(k_bytes / max(1e-9, k_us * 1e-6) / 8e12, 4), job_list_bytes_per_picture=int(job),
+                k_mpeg2_vlc_us_per_picture=round((v1[0] - v0[0]) / max(1, v1[1] - v0[1]) / 1e3, 2), device_vlc_pictures=int(dev_pics))
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--streams", type=int, default=32)
+    ap.add_argument("--streams", default="32", help="stream counts, comma separated")
+    ap.add_argument("--device-vlc", action="store_true", help="run every leg with option mpeg2_device_vlc at 0 and at 1")
     ap.add_argument("--groups", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--kind", default="IBBP", choices=sorted(KINDS))
@@ -112,6 +123,7 @@ def main():
     ap.add_argument("--write", help="write the group to this file and stop")
     ap.add_argument("--split", action="store_true", help="device leg only, one round: the kernel's time per picture for this kind")
     args = ap.parse_args()
+    counts = [int(v) for v in args.streams.split(",")]
     t0 = time.perf_counter()
     data = open(args.stream, "rb").read() if args.stream else make_group(args.kind)
     if args.write:
@@ -123,16 +135,33 @@ def main():
     L = api.lib()
     L.jm_amddec_output_frame_device.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p]
     if args.split:
-        print(json.dumps(dict(run_leg(L, pics, args.streams, args.groups, True), leg="device", kind=args.kind, split=True)), flush=True)
+        print(json.dumps(dict(run_leg(L, pics, counts[0], args.groups, True), leg="device", kind=args.kind, split=True)), flush=True)
+        return
+    if args.device_vlc:
+        h = api.jm_nvdec_create_handle()
+        has_option = L.jm_amddec_set_option(h, b"mpeg2_device_vlc", 1) == 0
+        api.jm_nvdec_deinit(h)
+        for S_ in counts:
+            legs = [(out, v) for out in ("host", "device") for v in ((0, 1) if has_option else (0,))]
+            res = {leg: [] for leg in legs}
+            for r in range(args.rounds):
+                for leg in (legs if r % 2 == 0 else legs[::-1]):          # alternating: neither setting always runs first
+                    out = run_leg(L, pics, S_, args.groups, leg[0] == "device", leg[1])
+                    res[leg].append(out)
+                    print(json.dumps(dict(out, leg=leg[0], device_vlc=leg[1], streams=S_, round=r, kind=args.kind)), flush=True)
+            for leg, v in res.items():
+                v = sorted(v, key=lambda o: o["frames_per_s"])
+                print(json.dumps({"summary": True, "streams": S_, "kind": args.kind, "leg": leg[0], "device_vlc": leg[1], "frames_per_s_min": v[0]["frames_per_s"],
+                                  "frames_per_s_max": v[-1]["frames_per_s"], "median": v[len(v) // 2]}), flush=True)
         return
     res = {"host": [], "device": []}
     for r in range(args.rounds):
         for leg in ("host", "device"):
-            out = run_leg(L, pics, args.streams, args.groups, leg == "device")
+            out = run_leg(L, pics, counts[0], args.groups, leg == "device")
             res[leg].append(out)
             print(json.dumps(dict(out, leg=leg, round=r, kind=args.kind)), flush=True)
     med = {leg: sorted(v, key=lambda o: o["frames_per_s"])[len(v) // 2] for leg, v in res.items()}
-    print(json.dumps({"summary": True, "streams": args.streams, "kind": args.kind, "median": med}), flush=True)
+    print(json.dumps({"summary": True, "streams": counts[0], "kind": args.kind, "median": med}), flush=True)
 
 
 if __name__ == "__main__":
