@@ -11,6 +11,7 @@ levels of coef=dict(...) are clauses 8.3.1, 8.3.2 and 8.5 typed out in tests/h26
 import numpy as np
 
 import deblock_ref
+import h264_field_ref as fr
 import h264_recon_ref as rr
 import scripted_h264 as sw
 from spec_tables_h264 import NORM_ADJUST_4x4
@@ -22,6 +23,8 @@ def clip1(a):
 
 def window(R, y0, x0, h, w):
     """R[y0 .. y0+h, x0 .. x0+w] with every coordinate clamped into the picture (8.4.2.2.1, equations 8-239 / 8-240; 8-266 .. 8-269 for chroma)."""
+    if isinstance(R, fr.FieldRef):                                  # one parity of a store: its own clamp (the field's border) and line pitch
+        return R.fetch(np.arange(y0, y0 + h), np.arange(x0, x0 + w))
     ys = np.clip(np.arange(y0, y0 + h), 0, R.shape[0] - 1)
     xs = np.clip(np.arange(x0, x0 + w), 0, R.shape[1] - 1)
     return R[np.ix_(ys, xs)].astype(np.int64)
@@ -163,14 +166,42 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong
     """[(Y, Cb, Cr)] per picture in DECODE order, coded size (multiples of 16), uint8.  stats: counters of deblock_ref; unfiltered: a list that receives
     each picture as reconstructed, before 8.7; stale_ref_of = k: picture k alone is predicted from the UNFILTERED picture k - 1 (what a decoder computes
     that reads its reference too early; the host test shows that this is visible).  wrong: wrong-on-purpose switches of tests/h264_recon_ref.py;
-    rstats: a set that receives what the Intra4x4 / Intra8x8 blocks and the residuals exercised."""
-    mbw, mbh = (seq["width"] + 15) // 16, (seq["height"] + 15) // 16
+    rstats: a set that receives what the Intra4x4 / Intra8x8 blocks and the residuals exercised.
+    A stream with field pictures (tests/h264_field_ref.py): a field picture's entry holds the field's own lines (half the rows); a reference name
+    goes through the writer's list to an index and through the restated decoder's list back to a picture; the samples live in frame stores."""
+    frame_seq = seq
     pl = sw.plan(seq, pics)
     wrong = frozenset(wrong)
     lists = rr.scaling_matrices(seq, wrong)
+    paff = fr.has_fields(pics)
+    dec_lists = fr.decoder_lists(seq, pics, wrong) if paff else None
+    st = fr.structure(pics)
+    stores = {}                                                     # picture index -> the (Y, Cb, Cr) frame store it was written into
     out, raw = [], []
     for k, p in enumerate(pics):
         kind = p["kind"]
+        parity = p.get("field")
+        seq = sw.pic_seq(frame_seq, p)                              # a field is a picture of its own: neighbours, slices, QP chain inside the field
+        mbw, mbh = (seq["width"] + 15) // 16, (seq["height"] + 15) // 16
+        scans = fr.decoder_scans(bool(parity), wrong)
+        if paff:
+            cmbh = (frame_seq["height"] + 15) // 16
+            stores[k] = stores[k - 1] if st[k][2] else tuple(np.zeros((cmbh * s, mbw * s), np.uint8) for s in (16, 8, 8))
+
+        def resolve(l, name, k=k):
+            """the picture a decoder reaches through the index that the stream carries for `name`"""
+            if not paff:
+                return name
+            idx = pl[k]["l%d" % l].index(name)
+            got = dec_lists[k][l]
+            assert idx < len(got) or wrong, (k, l, name, got)
+            return got[idx] if idx < len(got) else got[-1]
+
+        def ref_plane(name, c, parity=parity):
+            if not paff:
+                return refs[name][c]
+            i, q = fr.field_of(pics, name)
+            return fr.FieldRef(stores[i][c], q, wrong) if parity else stores[i][c]
         qps = sw.mb_qps(seq, p)
         nxn_modes = rr.mode_tables(seq, p, wrong, rstats)[1]
         refs = out if stale_ref_of != k else out[:k - 1] + [raw[k - 1]]
@@ -187,7 +218,7 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong
             t = m["t"]
 
             avail = rr.mb_avail(seq, p, a)
-            RES = rr.mb_residual(seq, m, qps[a], wrong, lists) if "coef" in m else None
+            RES = rr.mb_residual(seq, m, qps[a], wrong, lists, scans) if "coef" in m else None
             if RES is not None and rstats is not None:
                 rstats.add(("qp", t, qps[a]))
                 for c in (0, 1, 2):
@@ -201,6 +232,12 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong
                     planes[c][y * s:(y + 1) * s, x * s:(x + 1) * s] = m[key]
             elif t in ("i16", "i4", "i8"):
                 al, at = avail(-1, 0), avail(0, -1)
+                saved = None
+                if parity and at and "intra_neighbour_from_other_parity" in wrong:
+                    # the line above in the FRAME: for a bottom field the top field's line of the same number, for a top field the bottom's before it
+                    saved = [pl_[y * s - 1].copy() for pl_, s in zip(planes, (16, 8, 8))]
+                    for pl_, s, S in zip(planes, (16, 8, 8), stores[k]):
+                        pl_[y * s - 1] = S[2 * (y * s) + (parity == "bottom") - 1]
                 assert (t != "i16" or m["mode"] != 3) and m["cmode"] != 3 or (al and at and avail(-1, -1)), "plane prediction needs the corner"
                 assert (t != "i16" or (m["mode"] != 0 or at) and (m["mode"] != 1 or al)) and (m["cmode"] != 2 or at) and (m["cmode"] != 1 or al)
                 if t == "i16":
@@ -209,6 +246,9 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong
                     rr.intra_nxn_luma(planes[0], x * 16, y * 16, m, nxn_modes[a], RES[0] if RES else np.zeros((16, 16), np.int64), avail, wrong, rstats)
                 for c in (1, 2):
                     planes[c][y * 8:(y + 1) * 8, x * 8:(x + 1) * 8] = intra_chroma(planes[c], x * 8, y * 8, m["cmode"], al, at)
+                if saved is not None:
+                    for pl_, s, row in zip(planes, (16, 8, 8), saved):
+                        pl_[y * s - 1] = row
                 if rstats is not None:
                     rstats.add(("kind", kind, t, "T" * at + "L" * al + "C" * avail(-1, -1) + "R" * avail(1, -1)))
                     if t == "i16":
@@ -226,8 +266,12 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong
                         for l, q in enumerate((l0, l1)):
                             if q is None:
                                 continue
-                            R = refs[q[0]][c]
-                            pr[l] = mc_luma(R, X, Yy, W, Hh, q[1]) if c == 0 else mc_chroma(R, X, Yy, W, Hh, q[1])
+                            got = resolve(l, q[0])
+                            R = ref_plane(got, c)
+                            mvc = (q[1][0], q[1][1] + fr.chroma_mvy_offset(parity, fr.field_of(pics, got)[1], wrong)) if paff else q[1]
+                            pr[l] = mc_luma(R, X, Yy, W, Hh, q[1]) if c == 0 else mc_chroma(R, X, Yy, W, Hh, mvc)
+                            if rstats is not None and parity:
+                                rstats.add(("field_ref", parity, fr.field_of(pics, got)[1], st[fr.field_of(pics, got)[0]][0] == st[k][0]))
                             if mode == 1:
                                 wp = p["wp"]
                                 ld = wp["ld_y"] if c == 0 else wp["ld_c"]
@@ -240,7 +284,17 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong
                         if mode == 1:
                             logwd = p["wp"]["ld_y"] if c == 0 else p["wp"]["ld_c"]
                         elif mode == 2 and l0 is not None and l1 is not None:
-                            w0, w1 = implicit_weights(p["poc"], pics[l0[0]]["poc"], pics[l1[0]]["poc"])
+                            if paff:
+                                n0, n1 = resolve(0, l0[0]), resolve(1, l1[0])
+                                pocs = [p["poc"], fr.field_poc(pics, n0), fr.field_poc(pics, n1)]
+                                if "implicit_weights_from_frame_poc" in wrong or not parity:      # a frame's count: the smaller of its two fields'
+                                    fpoc = lambda i: min(pics[j]["poc"] for j in range(len(pics)) if st[j][0] == st[i][0])
+                                    pocs = [fpoc(k), fpoc(fr.field_of(pics, n0)[0]), fpoc(fr.field_of(pics, n1)[0])]
+                                w0, w1 = implicit_weights(*pocs)
+                                if rstats is not None and parity:
+                                    rstats.add(("implicit", parity, w0, w1))
+                            else:
+                                w0, w1 = implicit_weights(p["poc"], pics[l0[0]]["poc"], pics[l1[0]]["poc"])
                             ent = [(w0, 0), (w1, 0)]
                         planes[c][Yy:Yy + Hh, X:X + W] = weighted(pr[0], pr[1], mode, logwd, ent[0], ent[1])
                 if rstats is not None and RES is not None:
@@ -262,7 +316,15 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong
                         rstats.add(("clip1_at_255", t, c))
                     blk[:] = clip1(v)
         raw.append(tuple(planes))
-        out.append(deblock_ref.deblock_picture(seq, pics, pl, k, tuple(planes), stats))
+        out.append(deblock_ref.deblock_picture(seq, pics, pl, k, tuple(planes), stats, wrong))
+        if paff:
+            for S, pl_ in zip(stores[k], out[-1]):
+                if parity:
+                    S[int(parity == "bottom")::2] = pl_
+                else:
+                    S[:] = pl_
+            if st[k][2] and "deblock_across_parities" in wrong:
+                out[-2:] = deblock_ref.woven_filter(frame_seq, pics, pl, k, stores[k], raw[-2:], wrong)
     if unfiltered is not None:
         unfiltered[:] = raw
     return out
@@ -279,11 +341,16 @@ def pack(seq, planes, fmt):
 
 
 def display_order(pics):
+    """decode index of every output frame (of a frame coded as two fields: of its first field), in output order"""
+    if fr.has_fields(pics):
+        return [k for k, _ in fr.output_frames(pics, [()] * len(pics))]
     return sorted(range(len(pics)), key=lambda k: pics[k]["poc"])
 
 
-def expected_frames(seq, pics, fmt, planes=None):
+def expected_frames(seq, pics, fmt, planes=None, wrong=frozenset()):
     planes = planes if planes is not None else expect_h264(seq, pics)
+    if fr.has_fields(pics):
+        return [pack(seq, frame, fmt) for _, frame in fr.output_frames(pics, planes, wrong)]
     return [pack(seq, planes[k], fmt) for k in display_order(pics)]
 
 
@@ -321,6 +388,11 @@ def first_difference(seq, pics, got_frames, fmt, planes=None, units="mbs"):
             bx, by = px * 2 // block, py * 2 // block
         k = order[d]
         a = by * ((w + block - 1) // block) + bx
+        if pics[k].get("field"):                                    # the line's parity says which field; the field's line is half the frame's
+            st = fr.structure(pics)
+            if k + 1 < len(pics) and st[k + 1][2] and (pics[k]["field"] == "bottom") != bool(py & 1):
+                k += 1
+            a = (py // 2) // (block if plane == "Y" else block // 2) * ((w + block - 1) // block) + bx
         entry = describe_mb(pics[k][units][a])
         return (f"display frame {d} (decode index {k}, {pics[k]['kind']}, POC {pics[k]['poc']}), plane {plane}, sample x={px} y={py}, block {a} "
                 f"(x {bx}, y {by}): got {ga[i]} expected {ea[i]}, {int((ga != ea).sum())} bytes differ in this frame; script entry {entry}")

@@ -10,6 +10,7 @@ holds q0; idc 2 leaves slice edges alone; the left and top picture edges are nev
 
 ``stats`` (a dict of counters, keyed "<plane><direction>:<what>" with plane Y / C and direction V / H (vertical / horizontal EDGES)) records which paths
 of the clause the pictures took; tests/test_analytic_host.py asserts from them that the filtering cases really filter on every path."""
+import h264_field_ref as fr
 import scripted_h264 as sw
 from spec_tables_h264 import ALPHA, BETA, QPC_30_51, TC0
 
@@ -34,13 +35,12 @@ def block_motion(m, bx, by, skip_ref):
     return [m["parts"][int(by >= 8 if t == "16x8" else bx >= 8)]]
 
 
-def far(a, b):
-    """a vector component differs by >= 4 in quarter luma frame samples"""
-    return abs(a[0] - b[0]) >= 4 or abs(a[1] - b[1]) >= 4
-
-
-def motion_bs(P, Q):
-    """The last two bullets of 8.7.2.1 that give bS 1, for frame macroblocks: P, Q = block_motion of the two blocks"""
+def motion_bs(P, Q, ylimit=4):
+    """The last two bullets of 8.7.2.1 that give bS 1: P, Q = block_motion of the two blocks.  ylimit: 4 for frame macroblocks; in a field picture
+    the vertical component counts quarter FIELD samples and the limit of 4 quarter frame samples is h264_field_ref.FIELD_MVY_LIMIT."""
+    def far(a, b):
+        """a vector component differs by >= 4 in quarter luma frame samples"""
+        return abs(a[0] - b[0]) >= 4 or abs(a[1] - b[1]) >= ylimit
     if len(P) != len(Q) or sorted(pic for pic, _ in P) != sorted(pic for pic, _ in Q):
         return 1                                                    # different reference pictures or a different number of motion vectors
     if len(P) == 1:
@@ -133,8 +133,12 @@ def mb_table(seq, pics, pl, k):
     return out
 
 
-def deblock_picture(seq, pics, pl, k, planes, stats=None):
-    """planes = (Y, Cb, Cr) of picture k as reconstructed (uint8 arrays); returns the three planes after 8.7, and counts into stats."""
+def deblock_picture(seq, pics, pl, k, planes, stats=None, wrong=frozenset()):
+    """planes = (Y, Cb, Cr) of picture k as reconstructed (uint8 arrays); returns the three planes after 8.7, and counts into stats.  A field picture is
+    filtered as a picture of its own (seq = scripted_h264.pic_seq: its macroblocks, its lines only, nothing across its top edge) under the field
+    rules of 8.7.2.1 (tests/h264_field_ref.py); wrong: that module's switches."""
+    field = bool(pics[k].get("field"))
+    ylimit, refkey = fr.mvy_limit(field, wrong), fr.reference_key(pics, field, wrong)
     import numpy as np
     cnt = stats if stats is not None else {}
     mbw, mbh = (seq["width"] + 15) // 16, (seq["height"] + 15) // 16
@@ -184,14 +188,22 @@ def deblock_picture(seq, pics, pl, k, planes, stats=None):
                     pb = ((qb[0] - 4) % 16, qb[1]) if d == 0 else (qb[0], (qb[1] - 4) % 16)
                     maxdiff = None
                     if e == 0 and (pmb["intra"] or q["intra"]):
-                        bS = 4
+                        bS = fr.intra_edge_bs(field, d == 1, wrong)
+                        if field and d == 1:
+                            hit("H:field_intra_mb_edge_bS%d" % bS)
                     elif pmb["intra"] or q["intra"]:
                         bS = 3
                     elif blk_at[pb] in pmb["coef"] or blk_at[qb] in q["coef"]:
                         bS = 2
                     else:
                         P, Q = block_motion(pmb["m"], pb[0], pb[1], skip_ref), block_motion(q["m"], qb[0], qb[1], skip_ref)
-                        bS = motion_bs(P, Q)
+                        P, Q = [(refkey(r), mv) for r, mv in P], [(refkey(r), mv) for r, mv in Q]
+                        bS = motion_bs(P, Q, ylimit)
+                        if field and len(P) == 1 and len(Q) == 1:
+                            if P[0][0] == Q[0][0] and abs(P[0][1][0] - Q[0][1][0]) < 4:
+                                hit("field_mvy_differs_by_%d_bS%d" % (abs(P[0][1][1] - Q[0][1][1]), bS))
+                            elif P[0][0] != Q[0][0] and fr.structure(pics)[fr.field_of(pics, P[0][0])[0]][0] == fr.structure(pics)[fr.field_of(pics, Q[0][0])[0]][0]:
+                                hit("field_refs_are_the_two_fields_of_one_frame_bS%d" % bS)
                         if len(P) == 1 and len(Q) == 1 and P[0][0] == Q[0][0]:
                             maxdiff = max(abs(P[0][1][0] - Q[0][1][0]), abs(P[0][1][1] - Q[0][1][1]))
                     edge_bs = max(edge_bs, bS)
@@ -242,3 +254,20 @@ def deblock_picture(seq, pics, pl, k, planes, stats=None):
                 if edge_bs and edge_on["C"] and off_c != 0 and max(pmb["qp"], q["qp"]) + off_c >= 30:
                     hit(D + ":chroma_qp_from_table_with_offset")
     return tuple(np.array(pl_, dtype=np.uint8) for pl_ in S)
+
+
+def woven_filter(frame_seq, pics, pl, k, store, raw_pair, wrong):
+    """WRONG ON PURPOSE (h264_field_ref switch deblock_across_parities): what a decoder makes of a frame coded as two fields when it filters the woven
+    frame instead of each field -- the unfiltered fields raw_pair = (picture k - 1, picture k) woven, filtered as a frame picture whose macroblock
+    row r carries what the first field's macroblock row r / 2 carries.  Writes the store and returns the two fields as that decoder holds them."""
+    import numpy as np
+    first, mbw = pics[k - 1], (frame_seq["width"] + 15) // 16
+    t, b = raw_pair if first["field"] == "top" else raw_pair[::-1]
+    woven = tuple(fr.weave(x, y) for x, y in zip(t, b))
+    rows = len(first["mbs"]) // mbw
+    fake = dict({key: v for key, v in first.items() if key != "field"}, mbs=[first["mbs"][(r // 2) * mbw + x] for r in range(2 * rows) for x in range(mbw)])
+    got = deblock_picture(frame_seq, pics[:k - 1] + [fake] + pics[k:], pl, k - 1, woven, None, frozenset(wrong) - {"deblock_across_parities"})
+    for S, g in zip(store, got):
+        S[:] = g
+    tops, bots = tuple(g[0::2] for g in got), tuple(g[1::2] for g in got)
+    return [tops, bots] if first["field"] == "top" else [bots, tops]

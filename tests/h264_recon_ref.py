@@ -172,12 +172,33 @@ def chroma_dc(c, ls00, qpc, wrong=frozenset()):
     return dc
 
 
-def mb_residual(seq, m, qpy, wrong=frozenset(), lists=None):
-    """(Ry 16x16, Rcb 8x8, Rcr 8x8): the residual r of every sample of macroblock m (zeros where nothing is coded), from m["coef"] (raster matrices)."""
+def rescanned(c, scans):
+    """coef as a decoder holds it whose inverse scan is scans = (perm4, perm8) (tests/h264_field_ref.decoder_scans): matrix[j] = script matrix[perm[j]].
+    Every scanned block goes through it: luma 4x4 and 8x8, the Intra16x16 DC matrix, chroma AC (raster positions 1 .. 15); chroma DC has no scan."""
+    p4, p8 = scans
+    take = lambda v, p: [int(np.asarray(v).reshape(-1)[p[j]]) for j in range(len(p))]
+    out = dict(c)
+    if "y" in c:
+        out["y"] = {k: take(v, p4) for k, v in c["y"].items()}
+    if "y8" in c:
+        out["y8"] = {k: take(v, p8) for k, v in c["y8"].items()}
+    if "ydc" in c:
+        out["ydc"] = take(c["ydc"], p4)
+    if "cac" in c:
+        out["cac"] = {k: take([0] + [int(q) for q in v], p4)[1:] for k, v in c["cac"].items()}
+    return out
+
+
+def mb_residual(seq, m, qpy, wrong=frozenset(), lists=None, scans=None):
+    """(Ry 16x16, Rcb 8x8, Rcr 8x8): the residual r of every sample of macroblock m (zeros where nothing is coded), from m["coef"] (raster matrices).
+    scans: None for a frame picture (8.5.6 / 8.5.7 with the zig-zag scans: the matrices are the script's); for a field picture the inverse field
+    scans as a decoder applies them (tests/h264_field_ref.decoder_scans)."""
     R = [np.zeros((16, 16), np.int64), np.zeros((8, 8), np.int64), np.zeros((8, 8), np.int64)]
     c = m.get("coef")
     if not c:
         return R
+    if scans is not None:
+        c = rescanned(c, scans)
     W = lists if lists is not None else scaling_matrices(seq, wrong)
     intra = m["t"] in INTRA or "inter_uses_intra_list" in wrong
     t = m["t"]

@@ -1,4 +1,4 @@
-"""A scripted H.264 stream writer (CAVLC, pic_order_cnt_type 0, frame pictures, 4:2:0, 8 bit; Baseline / Main subset and the High tools below) for the
+"""A scripted H.264 stream writer (CAVLC, pic_order_cnt_type 0, frame and field pictures, 4:2:0, 8 bit; Baseline / Main subset and the High tools below) for the
 analytic known-answer tests.
 
 The test says which macroblock carries which samples, vector, reference, weight, mode and levels; ``write`` turns that script into Annex-B bytes.  The
@@ -40,15 +40,24 @@ The script
 layout "mb": one slice per macroblock (no neighbour is available: every vector predictor is (0, 0), mvd = the vector); "row" / "pic": one slice per
 macroblock row / per picture -- the inter macroblocks of such a slice are 16x16 and not P_Skip.  Where they all repeat ONE vector and reference per list
 the predictor is that vector as soon as a neighbour exists, whichever of 8.4.1.3's branches applies (B slices: only this); any other mixture of 16x16 P
-and intra macroblocks goes through 8.4.1.3 typed out (``mv_predictor_16x16``).  seq may carry frame_mbs_only=0 (frame pictures of a stream that could
-hold fields).
+and intra macroblocks goes through 8.4.1.3 typed out (``mv_predictor_16x16``).
+
+Field pictures (PAFF).  With seq["frame_mbs_only"] = 0 a picture may carry field="top" | "bottom": a field is a picture of its own in pics, its mbs cover
+mbw x mbh / 2 macroblocks, its poc is the FIELD's count; two consecutive fields of opposite parity are a frame (one frame_num; either parity first); a
+first field without the other ends the stream.  Frame pictures of such a stream work as before (both fields have the frame's count).  A reference names a
+FIELD when the current picture is a field: the field picture's index, or (index, "top" | "bottom") for one field of a picture coded as a frame; when the
+current picture is a frame it names a frame or the first-decoded index of a field pair (the woven pair).  Typed from 7.3.3 (field_pic_flag,
+bottom_field_flag, first_mb_in_slice in field macroblocks, num_ref_idx_active up to 32), 8.2.4.1, 8.2.4.2.2, 8.2.4.2.4, 8.2.4.2.5, 8.2.5.3 (``plan_paff``),
+8.5.6 / 8.5.7 (every block of a field in field scan order; scaling lists stay zig-zag) and 7.4.2.1.1 (vertical crop unit of 4 luma rows).  Refused by
+assertion: a frame that names a store holding one field, a field that names a field outside its list.  Out of scope: CABAC, direct prediction and
+B_Skip in B fields (they carry 16x16 macroblocks with explicit vectors), long-term fields, marking operations, MBAFF.
 """
 import re
 
 import numpy as np
 
-from spec_tables_h264 import (CBP_OF_CODENUM, COEFF_TOKEN, RUN_BEFORE, TOTAL_ZEROS_4x4, TOTAL_ZEROS_CHROMA_DC, ZIGZAG_4x4, ZIGZAG_8x8,
-                              parse_code_table)
+from spec_tables_h264 import (CBP_OF_CODENUM, COEFF_TOKEN, FIELD_SCAN_4x4, FIELD_SCAN_8x8, RUN_BEFORE, TOTAL_ZEROS_4x4, TOTAL_ZEROS_CHROMA_DC,
+                              ZIGZAG_4x4 as FRAME_SCAN_4x4, ZIGZAG_8x8 as FRAME_SCAN_8x8, parse_code_table)
 
 
 class Bits:
@@ -165,10 +174,10 @@ def sps(seq):
         b.u(1, 0)                                                   # mb_adaptive_frame_field_flag
     b.u(1, 1)                                                       # direct_8x8_inference_flag
     cr, cb_ = mbw * 16 - w, mbh * 16 - h
-    assert cr % 2 == 0 and cb_ % 2 == 0 and (fmo or cb_ == 0)
+    assert cr % 2 == 0 and cb_ % 2 == 0 and (fmo or cb_ % 4 == 0), "7.4.2.1.1: CropUnitY is SubHeightC * (2 - frame_mbs_only_flag) luma rows"
     if cr or cb_:
         b.u(1, 1)
-        b.ue(0); b.ue(cr // 2); b.ue(0); b.ue(cb_ // 2)             # crop units: two luma samples (4:2:0 frames)
+        b.ue(0); b.ue(cr // 2); b.ue(0); b.ue(cb_ // (2 if fmo else 4))      # crop units: two luma samples; four luma rows when fields may occur
     else:
         b.u(1, 0)
     b.u(1, 0)                                                       # vui_parameters_present_flag
@@ -217,8 +226,96 @@ def ref_lists(pics, k, dpb):
     return l0, l1
 
 
+def pic_seq(seq, p):
+    """The sequence as picture p sees it: a field picture is a picture of its own of half the coded rows (every per-picture routine takes this)."""
+    return dict(seq, height=(seq["height"] + 15) // 16 * 8) if p.get("field") else seq
+
+
+def second_field(pics, k):
+    """picture k is the second field (decoding order) of a frame: the picture before it is a first field of the other parity"""
+    f = pics[k].get("field")
+    return bool(f) and k > 0 and pics[k - 1].get("field") not in (None, f) and not second_field(pics, k - 1)
+
+
+def ref_name(pics, k, parity):
+    """How a field picture's script names the field `parity` of the store that picture k belongs to: the field's own index when it was coded as a field,
+    (index, parity) when it is one field of a picture coded as a frame"""
+    return k if pics[k].get("field") else (k, parity)
+
+
+def alternate_fields(stores, parity):
+    """8.2.4.2.5: from the ordered stores (each {parity: name} of the fields it holds as references) fields are taken alternating in parity, starting
+    with `parity`; a missing field is passed over; when one parity runs out the rest of the other follows in order."""
+    other = "bottom" if parity == "top" else "top"
+    same, opp = [s[parity] for s in stores if parity in s], [s[other] for s in stores if other in s]
+    out = []
+    while same and opp:
+        out += [same.pop(0), opp.pop(0)]
+    return out + same + opp
+
+
+def plan_paff(seq, pics):
+    """``plan`` for a stream with field pictures, short-term references only.  A store is a frame's worth of reference fields; PicNum of a field is
+    2 * FrameNumWrap + 1 for the current parity and 2 * FrameNumWrap for the other (8.2.4.1), which for the list construction only says: stores by
+    descending FrameNumWrap (8.2.4.2.2), then 8.2.4.2.5.  No frame_num wrap occurs (asserted)."""
+    out, stores, frame_num = [], [], 0          # stores: dict(first=index, held={parity: index}, poc={parity: count}, frame_num) in decoding order
+    nrf = seq.get("num_ref_frames", 1)
+    assert not seq.get("frame_mbs_only", 1), "field pictures need frame_mbs_only=0"
+    for k, p in enumerate(pics):
+        par = p.get("field")
+        assert par in (None, "top", "bottom")
+        is_ref = p.get("is_ref", p["kind"] != "B")
+        second = second_field(pics, k)
+        if par and not second:
+            assert k + 1 == len(pics) or second_field(pics, k + 1), "a first field is followed by the other field of its frame, or ends the stream"
+        assert k > 0 or p["kind"] == "I"
+        if second:
+            assert is_ref == out[k - 1]["is_ref"], "both fields of a frame are reference fields or neither is"
+        fn = out[k - 1]["frame_num"] if second else frame_num
+        assert fn < (1 << LOG2_MAX_FRAME_NUM) - 1, "no frame_num wrap in these scripts"
+        full = [s for s in stores if len(s["held"]) == 2]
+        spoc = lambda s: min(s["poc"].values())                     # PicOrderCnt of a frame or pair: the smaller; of a single held field: its own
+        l0, l1 = [], []
+        if p["kind"] == "P" and par:
+            l0 = alternate_fields([{q: ref_name(pics, i, q) for q, i in s["held"].items()} for s in stores[::-1]], par)
+        elif p["kind"] == "P":
+            l0 = [s["first"] for s in full[::-1]]                   # 8.2.4.2.1: frames (or pairs) with both fields marked, PicNum descending
+        elif p["kind"] == "B":
+            assert not is_ref or not par, "B fields are not references in these scripts"
+            pool = stores if par else full
+            cur = p["poc"]
+            before = sorted((s for s in pool if spoc(s) <= cur), key=lambda s: -spoc(s))
+            after = sorted((s for s in pool if spoc(s) > cur), key=spoc)
+            if par:
+                names = lambda ss: alternate_fields([{q: ref_name(pics, i, q) for q, i in s["held"].items()} for s in ss], par)
+            else:
+                names = lambda ss: [s["first"] for s in ss]
+            l0, l1 = names(before + after), names(after + before)
+            if len(l1) > 1 and l0 == l1:
+                l1[0], l1[1] = l1[1], l1[0]
+        cap = 2 * nrf if par else nrf
+        n0, n1 = p.get("num_ref", (max(1, min(cap, len(l0))), max(1, min(cap, len(l1)))))
+        if p["kind"] != "I":
+            assert n0 <= len(l0) and (p["kind"] == "P" or n1 <= len(l1)) and max(n0, n1) <= (32 if par else 16), (k, n0, n1, l0, l1)
+        out.append(dict(frame_num=fn, l0=l0[:n0], l1=l1[:n1], is_ref=is_ref, idr=k == 0, override=(n0, n1) != (nrf, nrf), n=(n0, n1)))
+        if is_ref and second:
+            s = stores[-1]
+            assert s["first"] == k - 1
+            s["held"][par], s["poc"][par] = k, p["poc"]             # 8.2.5.3: no sliding window for the second field of a reference frame
+        elif is_ref:
+            if len(stores) == nrf:
+                stores.pop(0)                                       # sliding window, counted in frames: the smallest FrameNumWrap goes
+            held = {par: k} if par else {"top": k, "bottom": k}
+            stores.append(dict(first=k, held=held, poc={q: p["poc"] for q in held}, frame_num=fn))
+        if is_ref and not second:
+            frame_num = fn + 1
+    return out
+
+
 def plan(seq, pics):
     """Per picture: frame_num, the lists cut to their active length, nal_ref_idc.  Sliding window marking (8.2.5.3)."""
+    if any(p.get("field") for p in pics):
+        return plan_paff(seq, pics)
     out, dpb, frame_num = [], [], 0
     nrf = seq.get("num_ref_frames", 1)
     for k, p in enumerate(pics):
@@ -375,11 +472,13 @@ def residual_block(b, lv, nc, high, seen=None):
     return total
 
 
-def mb_levels(m):
+def mb_levels(m, field=False):
     """The levels of macroblock m in PARSING form, from its coef=dict(...) (every matrix there is in raster order):
     dc16: the 16 Intra16x16DCLevel in scan order or None; y[blk]: 16 (15 for Intra16x16: the AC) levels of every luma 4x4 block in scan order -- under the
     8x8 transform the four interleaved blocks of 7.3.5.3.1 (CAVLC): block i of an 8x8 takes levels 4 k + i of its 64; cdc[plane]: 4; cac[plane][blk]: 15;
-    and the coded_block_pattern that follows from them: (luma bits, chroma 0 | 1 | 2)."""
+    and the coded_block_pattern that follows from them: (luma bits, chroma 0 | 1 | 2).  field: the macroblock belongs to a field picture, where EVERY
+    block is scanned by the field scans of 8.5.6 / 8.5.7 (the Intra16x16 DC matrix and the chroma AC blocks among them)."""
+    ZIGZAG_4x4, ZIGZAG_8x8 = (FIELD_SCAN_4x4, FIELD_SCAN_8x8) if field else (FRAME_SCAN_4x4, FRAME_SCAN_8x8)
     c = m.get("coef", {})
     t = m["t"]
     assert set(c) <= {"y", "y8", "ydc", "cdc", "cac"} and t != "pcm" and t != "skip", (t, sorted(c))
@@ -518,7 +617,9 @@ def slice_header(b, seq, p, pl, first_mb):
     b.ue(0)                                                         # pic_parameter_set_id
     b.u(LOG2_MAX_FRAME_NUM, pl["frame_num"])
     if not seq.get("frame_mbs_only", 1):
-        b.u(1, 0)                                                   # field_pic_flag
+        b.u(1, int(bool(p.get("field"))))                           # field_pic_flag
+        if p.get("field"):
+            b.u(1, int(p["field"] == "bottom"))                     # bottom_field_flag
     if pl["idr"]:
         b.ue(0)                                                     # idr_pic_id
     b.u(LOG2_MAX_POC_LSB, p["poc"] % (1 << LOG2_MAX_POC_LSB))
@@ -599,8 +700,12 @@ def write(seq, pics, seen=None, coded_modes=None):
     high = seq.get("profile", 66) == 100
     t8mode = seq.get("transform8x8", 0)
     out = [sps(seq), pps(seq)]
+    frame_mbs, frame_seq = n_mbs, seq
     for k, (p, pl) in enumerate(zip(pics, plan(seq, pics))):
         kind, mbs = p["kind"], p["mbs"]
+        field = bool(p.get("field"))
+        seq = pic_seq(frame_seq, p)                                 # a field: mbw x mbh / 2 macroblocks, first_mb_in_slice counts them
+        n_mbs = frame_mbs // 2 if field else frame_mbs
         assert len(mbs) == n_mbs
         step = layout_step(seq, p)
         mb_qps(seq, p)                                              # its assertions
@@ -622,7 +727,7 @@ def write(seq, pics, seen=None, coded_modes=None):
                     b.ue(skip_run)
                     skip_run = 0
                 intra_base = {"I": 0, "P": 5, "B": 23}[kind]
-                lv = mb_levels(m) if t != "pcm" else None
+                lv = mb_levels(m, field) if t != "pcm" else None
                 assert "coef" not in m or "resid" not in m
                 if t == "pcm":
                     b.ue(intra_base + 25)
@@ -652,6 +757,7 @@ def write(seq, pics, seen=None, coded_modes=None):
                         b.ue(1 if parts[0][1] is None else (2 if parts[0][0] is None else 3))     # B_L0_16x16, B_L1_16x16, B_Bi_16x16
                     for l in (0, 1):
                         lst, n = pl["l%d" % l], pl["n"][l]
+                        assert all(q[l] is None or q[l][0] in lst for q in parts), ("a reference that is not in the picture's list", k, a, lst)
                         for q in parts:
                             if q[l] is not None and n > 1:
                                 b.te(lst.index(q[l][0]), n - 1)

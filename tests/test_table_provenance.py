@@ -233,6 +233,7 @@ def test_field_scans_in_four_notations():
         assert sorted(out) == list(range(n * n))
         return out
     want4, want8 = from_columns(spec.FIELD_SCAN_4x4_COLUMNS), from_columns(spec.FIELD_SCAN_8x8_COLUMNS)
+    assert spec.FIELD_SCAN_4x4 == want4 and spec.FIELD_SCAN_8x8 == want8, "the (x, y) lists of the tables, which the scripted writer and restatement use"
     assert c_array(GEN_H264, "fs4") == want4 and c_array(GEN_H264, "fs8") == want8
     src = open(ORC_TABLES).read()
     for name, n, want in (("orc_fieldscan4", 4, want4), ("orc_fieldscan8", 8, want8)):
