@@ -58,7 +58,14 @@ jm_amddec_handle jm_amddec_create_handle(void);
  * slice table and the slice bytes instead of the job list (layout: INTEGRATION.md "MPEG-2").  parse_only and digest handles, and pictures whose slice
  * headers the prescan cannot accept or whose slices are out of order, take the host path.  Undamaged pictures decode identically, damage is concealed by
  * the host path's rules; dual prime fails the handle when the engine reads the picture's status.  Stats: mpeg2_dev_pictures, mpeg2_host_pictures,
- * mpeg2_dev_slices, mpeg2_dev_damaged_slices; with option profile k_mpeg2_vlc_ns / _n / _pics / _alg_bytes.  When it pays: INTEGRATION.md has the figures. */
+ * mpeg2_dev_slices, mpeg2_dev_damaged_slices; with option profile k_mpeg2_vlc_ns / _n / _pics / _alg_bytes.  When it pays: INTEGRATION.md has the figures.
+ * Option "mpeg2_field_pictures" (before init; 0 default / 1; other values and other codecs are refused): 1 = field pictures (picture_structure 1 / 2;
+ * I, P and B; field prediction, 16x8 motion compensation), and dual prime in P field and P frame pictures, are decoded instead of failing the handle.
+ * Two field pictures of opposite parity whose types pair (I-I, I-P, P-P, B-B) make one frame in one surface; a first field whose second does not
+ * follow is a lone field: its frame is displayed with the field's lines repeated (bob when deinterlacing) and `errors` increments.  display_poc and
+ * `frames` count frames, i_pictures / p_pictures / b_pictures coded pictures.  With mpeg2_device_vlc as well, field pictures take the host path and
+ * frame pictures stay on the device, where the lane decodes dual prime.  Stats: mpeg2_field_pictures, mpeg2_lone_fields, mpeg2_dual_prime_mbs,
+ * mpeg2_16x8_mbs.  At 0 nothing changes (INTEGRATION.md "MPEG-2"). */
 int  jm_amddec_init(int codec_type, int out_fmt, char *extra_data, int len, jm_amddec_handle h);
 int  jm_amddec_deinit(jm_amddec_handle h);
 /* in_buf may hold any chunk of an Annex-B stream; (NULL, 0) signals end of stream and then

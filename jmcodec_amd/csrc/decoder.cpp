@@ -189,6 +189,10 @@ int Decoder::set_option(const char *key, long long v) {
         if (inited_ || v < 0 || v > 1) return -1;
         mpeg2_dev_vlc_ = (int)v;
     }
+    else if (k == "mpeg2_field_pictures") {  // MPEG-2: 1 = field pictures, 16x8 motion compensation and dual prime are decoded instead of refused
+        if (inited_ || v < 0 || v > 1) return -1;
+        mpeg2_field_pics_ = (int)v;
+    }
     else if (k == "rgb_chroma") {            // RGB output: 1 = chroma interpolated to full resolution at the stream's siting (k_rgb_pack444)
         if (inited_ || v < 0 || v > 1) return -1;
         rgb_chroma_ = (int)v;
@@ -309,6 +313,11 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "mpeg2_host_pictures") return stat_m2_host_pics_;
     if (k == "mpeg2_dev_slices") return stat_m2_dev_slices_;
     if (k == "mpeg2_dev_damaged_slices") return stat_m2_dev_damaged_;
+    // option mpeg2_field_pictures: field pictures decoded, first fields that stayed alone, dual-prime and 16x8 macroblocks
+    if (k == "mpeg2_field_pictures") return stat_m2_fields_;
+    if (k == "mpeg2_lone_fields") return stat_m2_lone_;
+    if (k == "mpeg2_dual_prime_mbs") return stat_m2_dual_;
+    if (k == "mpeg2_16x8_mbs") return stat_m2_16x8_;
     if (k == "mpeg2_profile_level") return codec_ == 4 && seq_active_ ? m2seq_.profile_level : 0;
     if (k == "copy_engines") return copier_ ? (long long)copier_->engine_mask() : 0;      // SDMA engines the direct route uses (bit mask)
     if (k == "direct_frames") return stat_direct_;
@@ -417,6 +426,8 @@ int Decoder::init(int codec_type, int out_fmt, const uint8_t *extra, int len) {
         "a displayed one cannot be kept for the next picture"); return -1; }
     if (codec_type != 2 && jpeg_dev_entropy_) { fail("option jpeg_device_entropy is only available for MJPEG (codec_type 2)"); return -1; }
     if (codec_type != 4 && mpeg2_dev_vlc_) { fail("option mpeg2_device_vlc is only available for MPEG-2 (codec_type 4)"); return -1; }
+    if (codec_type != 4 && mpeg2_field_pics_) { fail("option mpeg2_field_pictures is only available for MPEG-2 (codec_type 4)"); return -1; }
+    m2split_.field_pictures = mpeg2_field_pics_ != 0;
     if (rgb_chroma_ && !rgb_) { fail("option rgb_chroma needs RGB output: set an RGB spec (jm_amddec_set_rgb) before init"); return -1; }
     if (getenv("JM_AMD_DEC_SYNC")) sync_mode_ = true;
     if (const char *js = getenv("JM_AMD_DEC_JOB_SLOTS")) { n_jobs_ = std::max(8, std::min(atoi(js), kMaxJobSlots)); n_jobs_set_ = true; }

@@ -95,8 +95,13 @@ struct JpegTask { JpegPic pic; std::vector<uint8_t> data; size_t off_first = 0, 
 // MPEG-2 picture (codec_type 4): its headers' snapshot with the slices' bytes, the reference surfaces, and where the job list sits in the job buffer
 // on_device: option mpeg2_device_vlc sends the picture's slices to k_mpeg2_vlc -- the job buffer then holds the picture's VLC parameters, the slice
 // table and the slice bytes (off_par, off_slices, off_bytes), and off_mbs / off_entries are offsets into the slot's device-only buffer
+// option mpeg2_field_pictures: structure 1 / 2 = a top / bottom field picture, decoded into the lines of that parity of cur_slot; fref_slot /
+// fref_par: per direction and parity the surface and the lines (parity) of the reference field, -1 = none.  fill: no coded picture -- the missing
+// field of a lone first field of an anchor, written as zero-vector copies of the field that exists (fref names it for both parities), so that
+// later pictures find a whole frame.  ext: the records need the kernel instantiation with the field-picture modes (set by the parse worker)
 struct Mpeg2Task { Mpeg2Pic pic; int ref_slot[2] = {-1, -1}; size_t off_mbs = 0, off_entries = 0; int n_entries = 0;
-    bool on_device = false; size_t off_par = 0, off_slices = 0, off_bytes = 0; int n_slices = 0; };
+    bool on_device = false; size_t off_par = 0, off_slices = 0, off_bytes = 0; int n_slices = 0;
+    int structure = 0; int fref_slot[2][2] = {{-1, -1}, {-1, -1}}, fref_par[2][2] = {{0, 1}, {0, 1}}; bool fill = false, ext = false; };
 
 struct PicTask {
     uint64_t seq = 0;
@@ -278,6 +283,7 @@ private:
     void mpeg2_handle_picture(Mpeg2Pic &pic);
     bool mpeg2_activate(const Mpeg2Seq &seq);
     void mpeg2_show_anchor(std::vector<int> &out);
+    void mpeg2_close_pending();                // option mpeg2_field_pictures: the waiting first field stays a lone field
     void mpeg2_parse_task(PicTask *t);
     bool mpeg2_parse_task_device(PicTask *t);  // option mpeg2_device_vlc: the prescan instead of the VLC decode; false: the host path takes the picture
     void mpeg2_fill_engine_pic(PicTask *t, struct EnginePic &ep);
@@ -447,6 +453,10 @@ private:
     std::atomic<long long> stat_dropped_{0}, stat_m2_clamped_{0}, stat_m2_rff_{0};
     // option mpeg2_device_vlc (before init): 1 = pictures are VLC-decoded by k_mpeg2_vlc, one lane per slice, unless the prescan sends them to the host path
     int mpeg2_dev_vlc_ = 0;
+    // option mpeg2_field_pictures (before init): 1 = field pictures, 16x8 motion compensation and dual prime are decoded; 0 = they fail the handle
+    int mpeg2_field_pics_ = 0;
+    int m2_pend_slot_ = -1, m2_pend_par_ = 0, m2_pend_type_ = 0;      // the frame whose first field picture waits for its second: surface, parity, type
+    std::atomic<long long> stat_m2_fields_{0}, stat_m2_lone_{0}, stat_m2_dual_{0}, stat_m2_16x8_{0};
     std::atomic<long long> stat_m2_dev_pics_{0}, stat_m2_host_pics_{0}, stat_m2_dev_slices_{0}, stat_m2_dev_damaged_{0};
     uint64_t m2_digest_ = 1469598103934665603ull; long long m2_digest_mbs_ = 0;      // written by the parse worker (sync option)
     struct TraceRec { uint64_t seq; long long t_dispatch, t_parsed, t_submit0, t_submit1; int is_i; };

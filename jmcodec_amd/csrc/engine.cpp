@@ -506,7 +506,7 @@ void Engine::launch(Lane &ln, Batch &b) {
     }
     if (b.any_jdev && profile_ && !b.jeev[0]) for (auto &e : b.jeev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
     // ... and the same for MPEG-2 pictures
-    bool any_mpeg2 = false; int max_mpeg2_items = 0;
+    bool any_mpeg2 = false, mpeg2_ext = false; int max_mpeg2_items = 0;     // mpeg2_ext: a field picture or a 16x8 / dual-prime record is in the batch
     for (auto &p : b.pics) any_mpeg2 |= p.codec == 4 && p.has_picture;
     if (any_mpeg2 && !b.h_mpics) {
         if (hipHostMalloc((void **)&b.h_mpics, sizeof(Mpeg2PicParams) * kMaxBatch, hipHostMallocDefault) != hipSuccess ||
@@ -590,7 +590,7 @@ void Engine::launch(Lane &ln, Batch &b) {
             else b.h_jents[i].n_segs = 0;
         }
         if (any_mpeg2) {
-            if (p.codec == 4 && p.has_picture) { b.h_mpics[i] = p.mp; max_mpeg2_items = std::max(max_mpeg2_items, p.mp.n_items); b.alg[11] += p.mpeg2_alg_bytes; b.npics[11]++; }
+            if (p.codec == 4 && p.has_picture) { b.h_mpics[i] = p.mp; max_mpeg2_items = std::max(max_mpeg2_items, p.mp.n_items); mpeg2_ext |= p.mp.ext != 0; b.alg[11] += p.mpeg2_alg_bytes; b.npics[11]++; }
             else b.h_mpics[i].n_items = 0;
         }
         if (b.any_m2dev) {
@@ -753,7 +753,7 @@ void Engine::launch(Lane &ln, Batch &b) {
     if (any_mpeg2 && max_mpeg2_items > 0) {
         const bool timed = profile_ && b.m2ev[0] && b.m2ev[1];
         if (timed) hipEventRecord(b.m2ev[0], st);
-        launch_mpeg2_recon(b.d_mpics, n, max_mpeg2_items, st);
+        launch_mpeg2_recon(b.d_mpics, n, max_mpeg2_items, mpeg2_ext, st);
         if (timed) { hipEventRecord(b.m2ev[1], st); b.pmask |= 32768; }
     }
     b.any_bipred = b.any_field = false;

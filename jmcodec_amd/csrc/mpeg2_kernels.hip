@@ -1,4 +1,4 @@
-// jmcodec_amd/csrc/mpeg2_kernels.hip -- k_mpeg2_recon: MPEG-2 frame pictures (codec_type 4) from their job lists into NV12 surfaces, gfx950.
+// jmcodec_amd/csrc/mpeg2_kernels.hip -- k_mpeg2_recon: MPEG-2 pictures (codec_type 4) from their job lists into NV12 surfaces, gfx950.
 // (k_mpeg2_vlc, which writes those lists on the device with option mpeg2_device_vlc, is at the end of the file with a header of its own.)
 //
 // One wave per work item; blockIdx.y = picture.  An item is four neighbouring macroblocks of one macroblock row: a 64 x 16 luma strip and a 64 x 8
@@ -27,6 +27,22 @@
 // Every barrier is reached by every wave of the workgroup: the three rounds are unconditional, inactive waves and macroblocks beyond the row's end run
 // with empty blocks and store nothing, and the only early return is taken by a whole workgroup before the first barrier.  No lane leaves before the
 // last shuffle.
+//
+// Two instantiations, chosen per launch (launch_mpeg2_recon): k_mpeg2_recon<false> is the kernel frame pictures have always run -- a batch without a
+// field picture and without a 16x8 or dual-prime record runs it, unchanged.  k_mpeg2_recon<true> (option mpeg2_field_pictures) adds:
+//   field pictures   Mpeg2PicParams::structure 1 / 2: mb_h / 2 rows of strips (mb_h and n_items are the field's), every store goes to the lines of the
+//                    field's parity -- base + (structure - 1) pitch, lines 2 pitch apart, luma and interleaved chroma alike -- and nothing of the
+//                    other parity is written; the prediction reads the reference FIELDS of Mpeg2PicParams::fref (mpeg2_recon8x);
+//   16x8, dual prime which vector a row uses, and the second fetch with the average of dual prime, in frame pictures too.
+// A frame picture without such a record computes in <true> what it computes in <false> (mpeg2_recon8x hands it to mpeg2_recon8), so a mixed batch is
+// exact.  The barrier argument above holds for both: structure and the modes only change addresses and what pass 2 fetches; no barrier and no
+// shuffle sits inside a branch on them.  The LDS layout is the same.
+// gfx950 compile (-Rpass-analysis=kernel-resource-usage), read from the compiler, not measured:
+//   k_mpeg2_recon<false>  78 VGPRs, 85 SGPRs, 68 bytes of scratch per lane, 18,944 bytes of LDS, 6 waves per SIMD
+//                         (the kernel before the split: 78 VGPRs, 84 SGPRs, 68 bytes of scratch, 6 waves)
+//   k_mpeg2_recon<true>   90 VGPRs, 96 SGPRs, 68 bytes of scratch per lane, 18,944 bytes of LDS, 5 waves per SIMD
+// The 68 bytes of scratch were there before the split.  Presumably they are the two macroblock records a lane holds (ms, mp), whose count[] and mv[]
+// are indexed by values the compiler does not know; that has not been examined.
 #include <hip/hip_runtime.h>
 #include "mpeg2_jobs.h"
 #include "mpeg2_recon.h"
@@ -37,7 +53,7 @@ namespace jmamd {
 constexpr int kM2Waves = 4;
 constexpr int kM2FStride = 72, kM2GRow = 12, kM2GStride = 112;
 
-__global__ __launch_bounds__(64 * kM2Waves) void k_mpeg2_recon(const Mpeg2PicParams *pics) {
+template <bool EXT> __global__ __launch_bounds__(64 * kM2Waves) void k_mpeg2_recon(const Mpeg2PicParams *pics) {
     const Mpeg2PicParams &pp = pics[blockIdx.y];
     if ((int)blockIdx.x * kM2Waves >= pp.n_items) return;              // (the whole workgroup: no barrier is left behind)
     __shared__ __attribute__((aligned(16))) int16_t sF[kM2Waves][8][kM2FStride];
@@ -47,7 +63,11 @@ __global__ __launch_bounds__(64 * kM2Waves) void k_mpeg2_recon(const Mpeg2PicPar
     const bool active = item < pp.n_items;
     const int spr = (pp.mb_w + 3) >> 2;                                 // strips per macroblock row
     const int row = item / spr, mbx0 = (item - row * spr) * 4;
-    const int W = pp.mb_w * 16, H = pp.mb_h * 16;
+    const int W = pp.mb_w * 16, H = pp.mb_h * 16;                      // (a field picture: mb_h and H are the field's)
+    // EXT: a field picture stores the lines of its parity only -- from line structure - 1 on, 2 pitch apart
+    const int structure = EXT ? pp.structure : 0;
+    const int sp = structure ? 2 * pp.pitch : pp.pitch;
+    uint8_t *const surf = pp.surf + (structure ? (size_t)(structure - 1) * pp.pitch : 0);
     const int b = l >> 3, i = l & 7;                                    // scatter and pass 1: block b, entry lane / column i
     const int bb = l & 7, y = l >> 3;                                   // pass 2: row y of block bb
     // the macroblock whose blocks this lane scatters (ms) and the one whose samples it reconstructs (mp)
@@ -92,18 +112,22 @@ __global__ __launch_bounds__(64 * kM2Waves) void k_mpeg2_recon(const Mpeg2PicPar
             const int sr = (mp.flags & M2_FIELD_DCT) ? 2 * y + r : 8 * r + y;
             const int X = (mbx0 + (bb >> 1)) * 16 + (bb & 1) * 8, Y = row * 16 + sr;
             if (valid_p) {
-                mpeg2_recon8(mp, pp.ref, pp.pitch, 1, false, W, H, X, Y, res, s);
+                if (EXT) { const uint8_t *fld[2][2]; mpeg2_ref_fields(pp, 0, fld); mpeg2_recon8x(mp, fld, pp.pitch, 1, false, W, H, X, Y, structure, res, s); }
+                else mpeg2_recon8(mp, pp.ref, pp.pitch, 1, false, W, H, X, Y, res, s);
                 uint2 px;
                 px.x = (uint32_t)s[0] | (uint32_t)s[1] << 8 | (uint32_t)s[2] << 16 | (uint32_t)s[3] << 24;
                 px.y = (uint32_t)s[4] | (uint32_t)s[5] << 8 | (uint32_t)s[6] << 16 | (uint32_t)s[7] << 24;
-                if (X + 8 <= W && Y < H) *reinterpret_cast<uint2 *>(pp.surf + (size_t)Y * pp.pitch + X) = px;
+                if (X + 8 <= W && Y < H) *reinterpret_cast<uint2 *>(surf + (size_t)Y * sp + X) = px;
             }
         } else {
             const int c = bb & 1, X = (mbx0 + (bb >> 1)) * 8, Y = row * 8 + y;
             s[0] = s[1] = s[2] = s[3] = s[4] = s[5] = s[6] = s[7] = 0;
             if (valid_p) {
-                const uint8_t *refc[2] = {pp.ref[0] ? pp.ref[0] + pp.chroma_offset + c : nullptr, pp.ref[1] ? pp.ref[1] + pp.chroma_offset + c : nullptr};
-                mpeg2_recon8(mp, refc, pp.pitch, 2, true, W >> 1, H >> 1, X, Y, res, s);
+                if (EXT) { const uint8_t *fld[2][2]; mpeg2_ref_fields(pp, pp.chroma_offset + c, fld); mpeg2_recon8x(mp, fld, pp.pitch, 2, true, W >> 1, H >> 1, X, Y, structure, res, s); }
+                else {
+                    const uint8_t *refc[2] = {pp.ref[0] ? pp.ref[0] + pp.chroma_offset + c : nullptr, pp.ref[1] ? pp.ref[1] + pp.chroma_offset + c : nullptr};
+                    mpeg2_recon8(mp, refc, pp.pitch, 2, true, W >> 1, H >> 1, X, Y, res, s);
+                }
             }
             // the Cb lane keeps samples 0..3 and gets Cr's 0..3; the Cr lane keeps 4..7 and gets Cb's 4..7
             const uint32_t lo = (uint32_t)s[0] | (uint32_t)s[1] << 8 | (uint32_t)s[2] << 16 | (uint32_t)s[3] << 24;
@@ -114,15 +138,17 @@ __global__ __launch_bounds__(64 * kM2Waves) void k_mpeg2_recon(const Mpeg2PicPar
             px.x = (cb & 0xff) | (cr & 0xff) << 8 | (cb & 0xff00) << 8 | (cr & 0xff00) << 16;
             px.y = (cb >> 16 & 0xff) | (cr >> 16 & 0xff) << 8 | (cb >> 24) << 16 | (cr >> 24) << 24;
             if (valid_p && 2 * X + 16 <= W && Y < (H >> 1))
-                *reinterpret_cast<uint2 *>(pp.surf + pp.chroma_offset + (size_t)Y * pp.pitch + 2 * X + c * 8) = px;
+                *reinterpret_cast<uint2 *>(surf + pp.chroma_offset + (size_t)Y * sp + 2 * X + c * 8) = px;
         }
         __syncthreads();                                                // (sG is read above and written by the next round's pass 1)
     }
 }
 
-void launch_mpeg2_recon(const Mpeg2PicParams *d_pics, int n, int max_items, ihipStream_t *st) {
+void launch_mpeg2_recon(const Mpeg2PicParams *d_pics, int n, int max_items, bool ext, ihipStream_t *st) {
     if (n <= 0 || max_items <= 0) return;
-    hipLaunchKernelGGL(k_mpeg2_recon, dim3((max_items + kM2Waves - 1) / kM2Waves, n), dim3(64 * kM2Waves), 0, st, d_pics);
+    const dim3 grid((max_items + kM2Waves - 1) / kM2Waves, n), block(64 * kM2Waves);
+    if (ext) hipLaunchKernelGGL(k_mpeg2_recon<true>, grid, block, 0, st, d_pics);
+    else hipLaunchKernelGGL(k_mpeg2_recon<false>, grid, block, 0, st, d_pics);
 }
 
 // k_mpeg2_vlc: option mpeg2_device_vlc -- the slice / macroblock / block VLC decode of the pictures' slices (mpeg2_vlc.h has the routine, the layout of
@@ -140,8 +166,8 @@ void launch_mpeg2_recon(const Mpeg2PicParams *d_pics, int n, int max_items, ihip
 // stores, an entry one 4-byte store -- global_load / global_store: the routine casts the three arrays to global-memory pointers, as flat
 // instructions would tie every table read's wait to the stores in flight -- and the status words are raised with ordinary atomics on vector addresses.  Plain C++, no inline assembly.
 // The predictors (pmv, dc_pred) are indexed by constants only and live in registers.
-// gfx950 compile (-Rpass-analysis=kernel-resource-usage): 121 VGPRs, 106 SGPRs (42 spilled to vector lanes), no scratch,
-// 15,936 bytes of LDS, 3 waves per SIMD by the compiler's count.
+// gfx950 compile (-Rpass-analysis=kernel-resource-usage): 129 VGPRs, 106 SGPRs (48 spilled to vector lanes), no scratch,
+// 15,936 bytes of LDS, 3 waves per SIMD by the compiler's count (before the lane learned dual prime: 121 VGPRs, 42 spilled, 3 waves).
 __global__ __launch_bounds__(64) void k_mpeg2_vlc(const Mpeg2VlcParams *pics) {
     const Mpeg2VlcParams &pp = pics[blockIdx.y];
     if ((int)blockIdx.x * 64 >= pp.n_slices) return;                    // (the whole workgroup: no barrier is left behind)
@@ -155,7 +181,9 @@ __global__ __launch_bounds__(64) void k_mpeg2_vlc(const Mpeg2VlcParams *pics) {
     if (s >= pp.n_slices) return;
     const Mpeg2VlcPic pic = *pp.pic;
     const Mpeg2Slice sl = pp.slices[s];
-    const uint32_t st = mpeg2_vlc_slice(pic, reinterpret_cast<const Mpeg2VlcTables *>(sTab), sl, pp.bytes, pp.mbs, pp.entries, nullptr);
+    uint32_t n_dual = 0;
+    const uint32_t st = mpeg2_vlc_slice(pic, reinterpret_cast<const Mpeg2VlcTables *>(sTab), sl, pp.bytes, pp.mbs, pp.entries, nullptr, &n_dual);
+    if (n_dual) atomicAdd(pp.status + 3, n_dual << 8);                  // (bits 8.. of the flag word count the dual-prime records; the flags are ORed into bits 0 and 1)
     if (st & kM2StKindMask) { atomicAdd(pp.status, 1u); atomicOr(pp.status + 1, 1u << (st & kM2StKindMask)); }
     if (st >> kM2StClampedShift) atomicAdd(pp.status + 2, st >> kM2StClampedShift);
     if (st & (kM2StHoles | kM2StDualPrime)) atomicOr(pp.status + 3, ((st & kM2StHoles) ? 1u : 0u) | ((st & kM2StDualPrime) ? 2u : 0u));

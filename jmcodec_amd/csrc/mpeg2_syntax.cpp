@@ -29,6 +29,8 @@ static const Mpeg2Vlc kCbp[] = {
     {0x12, 5, 48, 0}, {0x1a, 8, 49, 0}, {0x16, 8, 50, 0}, {0x12, 8, 51, 0}, {0xd, 5, 52, 0}, {0x9, 8, 53, 0}, {0x5, 8, 54, 0}, {0x5, 9, 55, 0},
     {0xc, 5, 56, 0}, {0x8, 8, 57, 0}, {0x4, 8, 58, 0}, {0x4, 9, 59, 0}, {0x7, 3, 60, 0}, {0xa, 5, 61, 0}, {0x8, 5, 62, 0}, {0xc, 6, 63, 0}};
 // B-10 motion_code, magnitudes (codes of a != 0 are followed by the sign bit)
+// B-11 dmvector: a = the value
+static const Mpeg2Vlc kDmv[] = {{0x0, 1, 0, 0}, {0x2, 2, 1, 0}, {0x3, 2, -1, 0}};
 static const Mpeg2Vlc kMotion[] = {{0x1, 1, 0, 0}, {0x1, 2, 1, 0}, {0x1, 3, 2, 0}, {0x1, 4, 3, 0}, {0x3, 6, 4, 0}, {0x5, 7, 5, 0}, {0x4, 7, 6, 0},
                                    {0x3, 7, 7, 0}, {0xb, 9, 8, 0}, {0xa, 9, 9, 0}, {0x9, 9, 10, 0}, {0x11, 10, 11, 0}, {0x10, 10, 12, 0}, {0xf, 10, 13, 0},
                                    {0xe, 10, 14, 0}, {0xd, 10, 15, 0}, {0xc, 10, 16, 0}};
@@ -91,6 +93,7 @@ const Mpeg2Vlc *mpeg2_table(int which, int *n) {
     case 4: *n = M2_N(kMbTypeB); return kMbTypeB;
     case 9: *n = M2_N(kCbp); return kCbp;
     case 10: *n = M2_N(kMotion); return kMotion;
+    case 11: *n = M2_N(kDmv); return kDmv;
     case 12: *n = M2_N(kDcLuma); return kDcLuma;
     case 13: *n = M2_N(kDcChroma); return kDcChroma;
     case 14: *n = M2_N(kDct0); return kDct0;
@@ -130,6 +133,9 @@ const Lut &lut(int which) {
     switch (which) { case 1: return l1; case 2: return l2; case 3: return l3; case 4: return l4; case 9: return l9; case 10: return l10;
                      case 12: return l12; case 13: return l13; case 14: return l14; default: return l15; }
 }
+
+// B-11 has a function of its own: every call of lut() passes the guards of all its tables, and lut() is called per symbol
+const Lut &lut_dmv() { static const Lut l(11); return l; }
 
 // MSB-first bit reader over [p, p + n): bits beyond the end read as zero, and `over` says that one was consumed
 struct Bits {
@@ -257,9 +263,10 @@ void Mpeg2Splitter::header_unit(int code, const uint8_t *p, size_t n) {
         pic_.intra_vlc_format = (int)b.get(1); pic_.alternate_scan = (int)b.get(1); pic_.repeat_first_field = (int)b.get(1);
         b.skip(1); pic_.progressive_frame = (int)b.get(1);
         if (b.over) { damaged_headers++; in_pic_ = false; return; }
-        if (pic_.picture_structure == 1 || pic_.picture_structure == 2) { refuse("MPEG-2: field pictures are not supported"); return; }
-        if (pic_.picture_structure != 3) { damaged_headers++; in_pic_ = false; return; }
-        pic_.have_ext = true;
+        if ((pic_.picture_structure == 1 || pic_.picture_structure == 2) && !field_pictures) {
+            refuse("MPEG-2: field pictures are not supported (option mpeg2_field_pictures decodes them)"); return; }
+        if (pic_.picture_structure == 0) { damaged_headers++; in_pic_ = false; return; }
+        pic_.have_ext = true; pic_.field_pictures = field_pictures;
         return;
     }
     if (code >= 0x01 && code <= 0xAF && in_pic_ && !pic_.have_ext)
@@ -269,9 +276,14 @@ void Mpeg2Splitter::header_unit(int code, const uint8_t *p, size_t n) {
 
 // ---- slices -----------------------------------------------------------------------------------------------------------------------------
 namespace {
-struct SliceDec {
+// EXT = the picture's handle has option mpeg2_field_pictures on.  EXT = false is the slice decode of before the option, to the instruction: every
+// branch on field pictures, 16x8 and dual prime is compiled out of it (fp() is false, frame_motion_type 3 is refused), so a handle at option 0
+// pays nothing for them -- this loop runs once per macroblock of every stream
+template <bool EXT> struct SliceDec {
     const Mpeg2Pic &pic; Mpeg2Jobs &jobs; std::vector<uint8_t> &covered;
-    int mb_w, mb_h, W, H;
+    int mb_w, mb_h, W, H;              // of the picture: a field picture's mb_h and H are the field's
+    bool fieldpic_; int par;           // a field picture, and its parity (0 top, 1 bottom)
+    bool fp() const { return EXT && fieldpic_; }
     int pmv[2][2][2], dc_pred[3], qscale = 2;
     uint16_t prev_dir = M2_FWD;
     bool refuse = false; std::string err;
@@ -298,33 +310,62 @@ struct SliceDec {
         *out = v;
         return true;
     }
-    // motion_vectors(s) of a frame picture; the vectors land in rec.mv[2 s + r] and the predictors move as Table 7-9 / 7.6.3.4 say
-    bool motion_vectors(Bits &b, int s, bool field, Mpeg2Mb &rec) {
-        for (int r = 0; r < (field ? 2 : 1); r++) {
-            if (field) rec.flags |= (uint16_t)(b.get(1) << (M2_SEL_SHIFT + 2 * s + r));
+    // motion_vectors(s): the vectors land in rec.mv[2 s + r] and the predictors move as Table 7-9 / 7.6.3.4 say.  Table 7-12 / 7-13 by mode:
+    // kFrame one vector; kField2 field prediction in a frame picture: two vectors with their selects, the vertical predictor halved and stored back
+    // doubled; kField field prediction in a field picture: one vector with its select; k16x8: two such; kDual one vector without select, a dmvector
+    // behind each component's residual (in a frame picture the vertical predictor is halved, as for kField2).
+    // X = false knows kFrame and kField2 only: the instantiation the macroblocks of frame pictures without dual prime run, which compiles to the
+    // routine of before option mpeg2_field_pictures (this loop is per macroblock of every stream); X = true knows every mode
+    enum { kFrame, kField2, kField, k16x8, kDual };
+    template <bool X> bool motion_vectors(Bits &b, int s, int mode, Mpeg2Mb &rec, int dmv[2] = nullptr) {
+        const bool dual = X && mode == kDual, two = mode == kField2 || (X && mode == k16x8);
+        const bool sel = mode == kField2 || (X && (mode == kField || mode == k16x8)), half = mode == kField2 || (dual && !fp());
+        for (int r = 0; r < (two ? 2 : 1); r++) {
+            if (sel) rec.flags |= (uint16_t)(b.get(1) << (M2_SEL_SHIFT + 2 * s + r));
             int x = 0, y = 0;
             if (!mv_component(b, pic.f_code[s][0], pmv[r][s][0], &x)) return false;
-            if (!mv_component(b, pic.f_code[s][1], field ? pmv[r][s][1] >> 1 : pmv[r][s][1], &y)) return false;
-            pmv[r][s][0] = x; pmv[r][s][1] = field ? y * 2 : y;
+            if (dual) { const Mpeg2Vlc *d = b.vlc(lut_dmv()); if (!d) return bad("invalid dmvector"); dmv[0] = d->a; }
+            if (!mv_component(b, pic.f_code[s][1], half ? pmv[r][s][1] >> 1 : pmv[r][s][1], &y)) return false;
+            if (dual) { const Mpeg2Vlc *d = b.vlc(lut_dmv()); if (!d) return bad("invalid dmvector"); dmv[1] = d->a; }
+            pmv[r][s][0] = x; pmv[r][s][1] = half ? y * 2 : y;
             rec.mv[2 * s + r][0] = (int16_t)x; rec.mv[2 * s + r][1] = (int16_t)y;
         }
-        if (!field) { pmv[1][s][0] = pmv[0][s][0]; pmv[1][s][1] = pmv[0][s][1]; }
+        if (!two) { pmv[1][s][0] = pmv[0][s][0]; pmv[1][s][1] = pmv[0][s][1]; }
         return true;
     }
-    // the standard forbids vectors that reach outside the reference picture; a hostile stream does not: clamp, mark, count
-    void clamp_vectors(Mpeg2Mb &rec, int mx, int my) {
+    // 7.6.3.6: the vectors of the opposite parity from the transmitted one (in rec.mv[0]) and dmvector
+    void derive_dual(Mpeg2Mb &rec, const int dmv[2]) {
+        const int vx = rec.mv[0][0], vy = rec.mv[0][1];
+        auto put = [&](int slot, int m, int e) {           // (mpeg2_vlc.h: the arithmetic the device-VLC lane runs too)
+            int x, y; mpeg2_dual_vector(vx, vy, dmv[0], dmv[1], m, e, &x, &y);
+            rec.mv[slot][0] = (int16_t)x; rec.mv[slot][1] = (int16_t)y;
+        };
+        if (fp()) put(2, 1, par ? 1 : -1);                                     // the field predicted: top -1, bottom +1
+        else { put(2, pic.top_field_first ? 1 : 3, -1); put(3, pic.top_field_first ? 3 : 1, 1); }      // [2] the top lines, [3] the bottom lines
+    }
+    // the select bits of "the field of the picture's own parity" for both directions (0 in a frame picture)
+    uint16_t own_parity() const { return fp() ? (uint16_t)(par << M2_SEL_SHIFT | par << (M2_SEL_SHIFT + 2)) : (uint16_t)0; }
+    // the standard forbids vectors that reach outside the reference picture; a hostile stream does not: clamp, mark, count.  Each vector's block --
+    // 16 lines of the frame; 8 lines of a field of it (field and dual-prime vectors of a frame picture); 16 lines of the reference field (a field
+    // picture); 8 of them for each 16x8 vector -- stays inside what it reads from.  X as for motion_vectors: false = a frame picture's record
+    // without dual prime
+    template <bool X> void clamp_vectors(Mpeg2Mb &rec, int mx, int my) {
         if (rec.flags & M2_INTRA) return;
-        const bool field = (rec.flags & M2_FIELD_MV) != 0;
+        const bool field = (rec.flags & M2_FIELD_MV) != 0, dual = X && (rec.flags & M2_DUAL) != 0, m16x8 = X && (rec.flags & M2_16X8) != 0, fp = X && fieldpic_;
         bool cl = false;
-        for (int s = 0; s < 2; s++) {
+        auto one = [&](int slot, int r) {
+            int16_t *v = rec.mv[slot];
+            const int x_lo = -2 * mx * 16, x_hi = 2 * (W - 16 - mx * 16);
+            const int pos = fp ? my * 16 + (m16x8 ? 8 * r : 0) : (field || dual ? my * 8 : my * 16);
+            const int span = fp ? (m16x8 ? 8 : 16) : (field || dual ? 8 : 16), size = !fp && (field || dual) ? H / 2 : H;
+            const int y_lo = -2 * pos, y_hi = 2 * (size - span - pos);
+            const int x = v[0] < x_lo ? x_lo : (v[0] > x_hi ? x_hi : v[0]), y = v[1] < y_lo ? y_lo : (v[1] > y_hi ? y_hi : v[1]);
+            if (x != v[0] || y != v[1]) { cl = true; v[0] = (int16_t)x; v[1] = (int16_t)y; }
+        };
+        if (dual) { one(0, 0); one(2, 0); if (!fp) one(3, 0); }
+        else for (int s = 0; s < 2; s++) {
             if (!(rec.flags & (s ? M2_BWD : M2_FWD))) continue;
-            for (int r = 0; r < (field ? 2 : 1); r++) {
-                int16_t *v = rec.mv[2 * s + r];
-                const int x_lo = -2 * mx * 16, x_hi = 2 * (W - 16 - mx * 16);
-                const int y_lo = field ? -2 * my * 8 : -2 * my * 16, y_hi = field ? 2 * (H / 2 - 8 - my * 8) : 2 * (H - 16 - my * 16);
-                const int x = v[0] < x_lo ? x_lo : (v[0] > x_hi ? x_hi : v[0]), y = v[1] < y_lo ? y_lo : (v[1] > y_hi ? y_hi : v[1]);
-                if (x != v[0] || y != v[1]) { cl = true; v[0] = (int16_t)x; v[1] = (int16_t)y; }
-            }
+            for (int r = 0; r < (field || m16x8 ? 2 : 1); r++) one(2 * s + r, r);
         }
         if (cl) { rec.flags |= M2_CLAMPED; jobs.clamped++; }
     }
@@ -367,33 +408,53 @@ struct SliceDec {
     }
     void put(int addr, const Mpeg2Mb &rec) {
         Mpeg2Mb r = rec;
-        clamp_vectors(r, addr % mb_w, addr / mb_w);
+        if (EXT && (fieldpic_ || (r.flags & M2_DUAL))) {
+            clamp_x(r, addr % mb_w, addr / mb_w);
+            if (r.flags & M2_16X8) jobs.n_16x8++;
+            if (r.flags & M2_DUAL) jobs.n_dual++;
+        } else clamp_vectors<false>(r, addr % mb_w, addr / mb_w);
         jobs.mbs[(size_t)addr] = r; covered[(size_t)addr] = 1;
     }
     void skipped(int addr) {
         Mpeg2Mb rec = {};
         rec.first = (uint32_t)jobs.entries.size(); rec.qscale = (uint8_t)qscale;
         reset_dc();
-        if (pic.type == 2) { reset_pmv(); rec.flags = M2_FWD; }
+        if (pic.type == 2) { reset_pmv(); rec.flags = M2_FWD | own_parity(); }      // (a field picture: from the field of its own parity)
         else {                                                    // B: the direction(s) of the macroblock before it, frame prediction from the predictors
-            rec.flags = prev_dir;
+            rec.flags = prev_dir | own_parity();                  // (a field picture: field prediction from the same-parity field(s))
             for (int s = 0; s < 2; s++) { rec.mv[2 * s][0] = (int16_t)pmv[0][s][0]; rec.mv[2 * s][1] = (int16_t)pmv[0][s][1]; }
         }
         put(addr, rec);
     }
-    bool macroblock(Bits &b, int addr) {
+    // One macroblock (6.2.5).  FP = a field picture: field_motion_type with every forward or backward macroblock, no dct_type, a field select with
+    // every vector but dual prime's, the concealment vector included.  FP = false, a frame picture, is the routine of before option
+    // mpeg2_field_pictures with one branch more: frame_motion_type 3 goes to the vector routine that knows dual prime
+    // (the instantiations only field pictures and dual prime reach are called through these, out of line: the frame-picture path keeps its size)
+    __attribute__((noinline)) bool macroblock_field(Bits &b, int addr) { return macroblock_t<true>(b, addr); }
+    __attribute__((noinline)) bool vectors_x(Bits &b, int s, int mode, Mpeg2Mb &rec, int dmv[2]) { return motion_vectors<true>(b, s, mode, rec, dmv); }
+    __attribute__((noinline)) void clamp_x(Mpeg2Mb &rec, int mx, int my) { clamp_vectors<true>(rec, mx, my); }
+    bool macroblock(Bits &b, int addr) { return fp() ? macroblock_field(b, addr) : macroblock_t<false>(b, addr); }
+    template <bool FP> bool macroblock_t(Bits &b, int addr) {
         const Mpeg2Vlc *t = b.vlc(lut(pic.type == 1 ? 2 : (pic.type == 2 ? 3 : 4)));
         if (!t) return bad("invalid macroblock_type");
         const int ty = t->a;
         const bool quant = ty & 1, mf = (ty & 2) != 0, mb = (ty & 4) != 0, pattern = (ty & 8) != 0, intra = (ty & 16) != 0;
-        bool field_mv = false, field_dct = false;
-        if ((mf || mb) && !pic.frame_pred_frame_dct) {
+        bool field_dct = false;
+        int mode = FP ? kField : kFrame;
+        if (FP) {
+            if (mf || mb) {
+                const int fmt = (int)b.get(2);                     // field_motion_type: always present
+                if (fmt == 0) return bad("reserved field_motion_type");
+                mode = fmt == 1 ? kField : (fmt == 2 ? k16x8 : kDual);
+            }
+        } else if ((mf || mb) && !pic.frame_pred_frame_dct) {
             const int fmt = (int)b.get(2);                         // frame_motion_type
-            if (fmt == 3) { refuse = true; return bad("dual-prime prediction is not supported"); }
+            if (fmt == 3 && !EXT) { refuse = true; return bad("dual-prime prediction is not supported"); }
             if (fmt == 0) return bad("reserved frame_motion_type");
-            field_mv = fmt == 1;
+            mode = fmt == 1 ? kField2 : (fmt == 2 || !EXT ? kFrame : kDual);
         }
-        if (!pic.frame_pred_frame_dct && (intra || pattern)) field_dct = b.get(1) != 0;
+        if (EXT && mode == kDual && (pic.type != 2 || !mf)) return bad("dual-prime prediction in a B picture");
+        if (!FP && !pic.frame_pred_frame_dct && (intra || pattern)) field_dct = b.get(1) != 0;
         if (quant) { const int c = (int)b.get(5); if (c == 0) return bad("quantiser_scale_code 0"); qscale = mpeg2_quantiser_scale(pic.q_scale_type, c); }
         Mpeg2Mb rec = {};
         rec.first = (uint32_t)jobs.entries.size(); rec.qscale = (uint8_t)qscale;
@@ -402,15 +463,23 @@ struct SliceDec {
             rec.flags |= M2_INTRA;
             if (pic.concealment_mv) {                              // parsed, with their marker bit; they move the predictors and are otherwise unused
                 Mpeg2Mb scratch = {};
-                if (!motion_vectors(b, 0, false, scratch)) return false;
+                if (!(FP ? vectors_x(b, 0, kField, scratch, nullptr) : motion_vectors<false>(b, 0, kFrame, scratch))) return false;
                 if (!b.get(1)) return bad("the marker bit behind concealment vectors is 0");
             } else reset_pmv();
         } else {
             reset_dc();
-            if (mf) { rec.flags |= M2_FWD; if (!motion_vectors(b, 0, field_mv, rec)) return false; }
-            if (mb) { rec.flags |= M2_BWD; if (!motion_vectors(b, 1, field_mv, rec)) return false; }
-            if (field_mv) rec.flags |= M2_FIELD_MV;
-            if (!mf && !mb) { if (pic.type != 2) return bad("a macroblock without prediction in a B picture"); rec.flags |= M2_FWD; reset_pmv(); }
+            if (FP || (EXT && mode == kDual)) {
+                int dmv[2] = {0, 0};
+                if (mf) { rec.flags |= M2_FWD; if (!vectors_x(b, 0, mode, rec, dmv)) return false; }
+                if (mb) { rec.flags |= M2_BWD; if (!vectors_x(b, 1, mode, rec, dmv)) return false; }
+                if (mode == k16x8) rec.flags |= M2_16X8;
+                if (mode == kDual) { rec.flags |= M2_DUAL; derive_dual(rec, dmv); }
+            } else {
+                if (mf) { rec.flags |= M2_FWD; if (!motion_vectors<false>(b, 0, mode, rec)) return false; }
+                if (mb) { rec.flags |= M2_BWD; if (!motion_vectors<false>(b, 1, mode, rec)) return false; }
+                if (mode == kField2) rec.flags |= M2_FIELD_MV;
+            }
+            if (!mf && !mb) { if (pic.type != 2) return bad("a macroblock without prediction in a B picture"); rec.flags |= M2_FWD | (FP ? own_parity() : 0); reset_pmv(); }
             prev_dir = rec.flags & (M2_FWD | M2_BWD);
         }
         int cbp = intra ? 63 : 0;
@@ -452,11 +521,12 @@ struct SliceDec {
 };
 }  // namespace
 
-std::string mpeg2_decode_picture(const Mpeg2Pic &pic, Mpeg2Jobs &jobs, bool *refuse) {
-    const int mb_w = pic.seq.mb_w(), mb_h = pic.seq.mb_h();
-    jobs.mbs.assign((size_t)mb_w * mb_h, Mpeg2Mb{}); jobs.entries.clear(); jobs.clamped = 0;
+// (each instantiation out of line, so that option 0 runs a body of its own, laid out as before)
+template <bool EXT> static __attribute__((noinline)) std::string decode_picture_t(const Mpeg2Pic &pic, Mpeg2Jobs &jobs, bool *refuse) {
+    const int mb_w = pic.seq.mb_w(), mb_h = pic.mb_h();
+    jobs.mbs.assign((size_t)mb_w * mb_h, Mpeg2Mb{}); jobs.entries.clear(); jobs.clamped = 0; jobs.n_16x8 = jobs.n_dual = 0;
     std::vector<uint8_t> covered((size_t)mb_w * mb_h, 0);
-    SliceDec d{pic, jobs, covered, mb_w, mb_h, mb_w * 16, mb_h * 16, {}, {}, 2, M2_FWD, false, std::string()};
+    SliceDec<EXT> d{pic, jobs, covered, mb_w, mb_h, mb_w * 16, mb_h * 16, pic.field(), pic.picture_structure == 2 ? 1 : 0, {}, {}, 2, M2_FWD, false, std::string()};
     // the picture's data: units 00 00 01 vpos ...; each runs up to the next one (the splitter cut them at start codes, so none hides inside)
     const uint8_t *p = pic.data.data(); const size_t n = pic.data.size();
     size_t o = 0;
@@ -468,7 +538,7 @@ std::string mpeg2_decode_picture(const Mpeg2Pic &pic, Mpeg2Jobs &jobs, bool *ref
         if (d.refuse) { *refuse = true; return d.err; }
         o = e;
     }
-    // macroblocks no slice covers: zero-vector forward copies (P, B), grey intra blocks (I)
+    // macroblocks no slice covers: zero-vector forward copies (P, B; a field picture: of the field of its own parity), grey intra blocks (I)
     bool holes = false;
     for (size_t a = 0; a < covered.size(); a++) if (!covered[a]) {
         holes = true;
@@ -476,11 +546,15 @@ std::string mpeg2_decode_picture(const Mpeg2Pic &pic, Mpeg2Jobs &jobs, bool *ref
         rec.first = (uint32_t)jobs.entries.size(); rec.qscale = 2;
         if (pic.type == 1) { rec.flags = M2_INTRA; rec.cbp = 63;
             for (int k = 0; k < 6; k++) { jobs.entries.push_back((uint32_t)(128 << pic.intra_dc_precision) << 16); rec.count[k] = 1; } }
-        else rec.flags = M2_FWD;
+        else rec.flags = M2_FWD | d.own_parity();
         jobs.mbs[a] = rec;
     }
     if (holes && d.err.empty()) d.err = "MPEG-2: macroblocks that no slice covers";
     return d.err;
+}
+
+std::string mpeg2_decode_picture(const Mpeg2Pic &pic, Mpeg2Jobs &jobs, bool *refuse) {
+    return pic.field_pictures ? decode_picture_t<true>(pic, jobs, refuse) : decode_picture_t<false>(pic, jobs, refuse);
 }
 
 // ---- option mpeg2_device_vlc -----------------------------------------------------------------------------------------------------------
@@ -536,6 +610,7 @@ Mpeg2VlcPic mpeg2_vlc_pic(const Mpeg2Pic &pic) {
     v.intra_dc_precision = pic.intra_dc_precision; v.frame_pred_frame_dct = pic.frame_pred_frame_dct; v.concealment_mv = pic.concealment_mv;
     v.q_scale_type = pic.q_scale_type; v.intra_vlc_format = pic.intra_vlc_format; v.alternate_scan = pic.alternate_scan;
     v.mb_w = pic.seq.mb_w(); v.mb_h = pic.seq.mb_h();
+    v.dual_prime = pic.field_pictures ? 1 : 0; v.top_field_first = pic.top_field_first;
     return v;
 }
 

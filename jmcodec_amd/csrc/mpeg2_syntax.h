@@ -14,7 +14,7 @@ namespace jmamd {
 struct Mpeg2Vlc { uint16_t code; uint8_t len; int16_t a, b; };
 // the tables as the decoder holds them (tests compare them with the restatement's).  which: 1 B-1 (a = increment; 34 = escape), 2 / 3 / 4 B-2 / B-3 /
 // B-4 (a = flags: 1 quant, 2 forward, 4 backward, 8 pattern, 16 intra), 9 B-9 (a = cbp), 10 B-10 (a = |motion_code|, the sign bit follows codes of
-// a != 0), 12 / 13 B-12 / B-13 (a = dct_dc_size), 14 / 15 B-14 / B-15 (a = run, b = level, the sign bit follows; a = -1: end of block, -2: escape)
+// a != 0), 11 B-11 (a = dmvector), 12 / 13 B-12 / B-13 (a = dct_dc_size), 14 / 15 B-14 / B-15 (a = run, b = level, the sign bit follows; a = -1: end of block, -2: escape)
 const Mpeg2Vlc *mpeg2_table(int which, int *n);
 // scan[alternate_scan][k]: natural position of the k-th coefficient (Figures 7-2, 7-3); the default intra matrix in natural order (6.3.11);
 // quantiser_scale of a code (Table 7-6)
@@ -44,17 +44,26 @@ struct Mpeg2Pic {
     int intra_dc_precision = 0, picture_structure = 3, top_field_first = 0, frame_pred_frame_dct = 1, concealment_mv = 0, q_scale_type = 0,
         intra_vlc_format = 0, alternate_scan = 0, repeat_first_field = 0, progressive_frame = 1;
     bool have_ext = false;
+    bool field_pictures = false;                             // option mpeg2_field_pictures (Mpeg2Splitter::field_pictures when the picture was cut): field
+                                                             // pictures, 16x8 motion compensation and dual prime are decoded, not refused
+    bool field() const { return picture_structure == 1 || picture_structure == 2; }
+    int mb_h() const { return field() ? seq.mb_h() / 2 : seq.mb_h(); }      // macroblock rows of the picture: a field has half the frame's
     std::vector<uint8_t> data;                               // the picture's slice units, each with its start code 00 00 01 xx in front
 };
 
 struct Mpeg2Jobs {
-    std::vector<Mpeg2Mb> mbs;          // [mb_w * mb_h], raster order
+    std::vector<Mpeg2Mb> mbs;          // [mb_w * mb_h], raster order (a field picture: mb_h / 2 rows, Mpeg2Pic::mb_h)
     std::vector<uint32_t> entries;
     int clamped = 0;                   // macroblocks with a vector the host had to clamp
+    int n_16x8 = 0, n_dual = 0;        // records with M2_16X8 / M2_DUAL (a picture with one needs Mpeg2PicParams::ext)
 };
 // Decode the slices of `pic` into records and entries.  Every macroblock gets a record whatever happens: damage (an invalid code, a truncated slice,
 // macroblocks no slice covers) is concealed -- zero-vector forward copies in P and B pictures, grey intra blocks in I pictures -- and the reason is
-// returned ("" = clean).  *refuse is set when the reason is a feature the decoder refuses (dual prime).
+// returned ("" = clean).  *refuse is set when the reason is a feature the decoder refuses (dual prime without pic.field_pictures).
+// With pic.field_pictures: the macroblock syntax of field pictures (field_motion_type, no dct_type, a field select with every vector but dual
+// prime's), 16x8 and dual prime in P pictures of both structures (in a B picture: damage).  The dual-prime vectors of the opposite parity are derived
+// here (7.6.3.6) and every vector, the derived ones included, is clamped so that its block stays inside the reference FIELD.  Concealment in a field
+// picture: zero-vector copies of the reference field of the picture's own parity.
 std::string mpeg2_decode_picture(const Mpeg2Pic &pic, Mpeg2Jobs &jobs, bool *refuse);
 
 // ---- option mpeg2_device_vlc: the prescan that replaces the slice decode on the host (the decode itself is mpeg2_vlc_slice, mpeg2_vlc.h) ----
@@ -100,6 +109,7 @@ public:
     bool refused() const { return refused_; }
     const Mpeg2Seq &seq() const { return seq_; }
     long long damaged_headers = 0;     // headers that were too short or broke a marker bit (counted, the stream goes on)
+    bool field_pictures = false;       // option mpeg2_field_pictures: set before the first feed.  false: field pictures fail the stream, as ever
 
 private:
     static constexpr size_t npos = (size_t)-1;

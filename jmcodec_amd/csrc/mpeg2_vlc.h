@@ -51,8 +51,11 @@
 // Damage: the kinds below, in the host path's wording (mpeg2_vlc_damage_text).  The macroblock that met it and the rest of the SLICE are dropped; every
 // address of the span that no decoded or skipped macroblock covered is concealed as the tail of mpeg2_decode_picture does -- zero-vector forward
 // records with qscale 2 in P and B pictures, intra records with six DC entries of 128 << intra_dc_precision in I pictures -- and the status says
-// "holes".  A macroblock at or beyond `hi` ends the lane silently: on the host path the next slice overwrites it.  frame_motion_type 3 (dual prime)
-// sets its own status bit and ends the lane like damage; the handle fails when the engine reads it.
+// "holes".  A macroblock at or beyond `hi` ends the lane silently: on the host path the next slice overwrites it.  frame_motion_type 3 (dual prime):
+// when Mpeg2VlcPic::dual_prime is set (option mpeg2_field_pictures) the lane decodes it as the host does -- one vector in field format, a dmvector
+// (one or two bits, read without a table) behind each component, the derived vectors from mpeg2_dual_vector, the host's clamp -- and writes the host's
+// record (M2_DUAL; in a B picture it is damage); 44 bits at most, fewer than the four vectors the guard's chain allows for.  Otherwise it sets its own
+// status bit and ends the lane like damage; the handle fails when the engine reads it.
 #pragma once
 #include <stdint.h>
 #include "mpeg2_jobs.h"
@@ -89,7 +92,9 @@ struct Mpeg2VlcPic {                       // 64 bytes
     int32_t f_code[2][2];
     int32_t intra_dc_precision, frame_pred_frame_dct, concealment_mv, q_scale_type, intra_vlc_format, alternate_scan;
     int32_t mb_w, mb_h;
-    int32_t pad[3];
+    int32_t dual_prime;                    // option mpeg2_field_pictures: the lane decodes frame_motion_type 3 (0: it reports kM2StDualPrime, the handle fails)
+    int32_t top_field_first;               // ... which needs it: which derived vector of a dual-prime macroblock is scaled by 1 and which by 3
+    int32_t pad[1];
 };
 static_assert(sizeof(Mpeg2VlcPic) == 64, "Mpeg2VlcPic is 64 bytes");
 
@@ -116,7 +121,7 @@ M2V_HD long long mpeg2_vlc_iteration_bound(uint32_t n_bytes, uint32_t n_mbs) { r
 enum : int {
     kM2DmgNone = 0, kM2DmgFcode, kM2DmgMotionCode, kM2DmgDcSize, kM2DmgDcRange, kM2DmgDctCode, kM2DmgEmptyBlock, kM2DmgEscapeLevel, kM2DmgBlockLength,
     kM2DmgMbType, kM2DmgMotionType, kM2DmgQuantCode, kM2DmgMarker, kM2DmgNoPrediction, kM2DmgCbp, kM2DmgSliceEnd, kM2DmgIncrement, kM2DmgAddress,
-    kM2DmgSkippedInI, kM2DmgCapacity, kM2DmgDualPrime, kM2DmgKinds
+    kM2DmgSkippedInI, kM2DmgCapacity, kM2DmgDualPrime, kM2DmgDualPrimeInB, kM2DmgKinds
 };
 // the routine's result: kind of damage | holes concealed | dual prime met | clamped macroblocks << 8
 constexpr uint32_t kM2StKindMask = 31, kM2StHoles = 32, kM2StDualPrime = 64;
@@ -127,8 +132,16 @@ inline const char *mpeg2_vlc_damage_text(int kind) {
         "invalid DCT coefficient code", "an empty coded block", "a forbidden escape level", "a block with more than 64 coefficients", "invalid macroblock_type",
         "reserved frame_motion_type", "quantiser_scale_code 0", "the marker bit behind concealment vectors is 0", "a macroblock without prediction in a B picture",
         "invalid coded_block_pattern", "a slice ends inside a macroblock", "invalid macroblock_address_increment", "a macroblock address beyond the picture",
-        "a skipped macroblock in an I picture", "more entries than the slice's bytes can code", "dual-prime prediction is not supported"};
+        "a skipped macroblock in an I picture", "more entries than the slice's bytes can code", "dual-prime prediction is not supported",
+        "dual-prime prediction in a B picture"};
     return kind > 0 && kind < kM2DmgKinds ? t[kind] : "";
+}
+
+// 7.6.3.6: one vector of the opposite parity of a dual-prime macroblock from the transmitted vector (vx, vy) and dmvector: m = 1 or 3, e = -1 when
+// the lines predicted belong to a top field, +1 to a bottom field.  The host's slice decode and the lane both call this: one copy of the arithmetic
+M2V_HD void mpeg2_dual_vector(int vx, int vy, int dmv0, int dmv1, int m, int e, int *x, int *y) {
+    *x = ((vx * m + (vx > 0 ? 1 : 0)) >> 1) + dmv0;
+    *y = ((vy * m + (vy > 0 ? 1 : 0)) >> 1) + e + dmv1;
 }
 
 namespace m2v {
@@ -210,6 +223,24 @@ template <int S> M2V_HD int motion_vectors(Bits &b, const Mpeg2VlcTables *t, con
     return 0;
 }
 
+// B-11 dmvector: 0 -> 0, 10 -> 1, 11 -> -1 (two bits at most: read from the window, no table)
+M2V_HD int dmvector(Bits &b) { if (!b.get(1)) return 0; return b.get(1) ? -1 : 1; }
+
+// motion_vectors(0) of a dual-prime macroblock of a P frame picture (the host's kDual): one vector in field format -- the vertical predictor halved,
+// stored back doubled -- a dmvector behind each component, PMV[1] = PMV[0]; mv0 = the vector, mv2 / mv3 = the derived vectors of the top / bottom lines
+M2V_HD int dual_vectors(Bits &b, const Mpeg2VlcTables *t, const Mpeg2VlcPic &pic, State &st, uint32_t *mv0, uint32_t *mv2, uint32_t *mv3) {
+    int x = 0, y = 0, dx, dy;
+    if (const int d = mv_component(b, t, pic.f_code[0][0], st.pmv[0][0][0], &x)) return d;
+    const int dmv0 = dmvector(b);
+    if (const int d = mv_component(b, t, pic.f_code[0][1], st.pmv[0][0][1] >> 1, &y)) return d;
+    const int dmv1 = dmvector(b);
+    st.pmv[0][0][0] = st.pmv[1][0][0] = x; st.pmv[0][0][1] = st.pmv[1][0][1] = y * 2;
+    *mv0 = pack_mv(x, y);
+    mpeg2_dual_vector(x, y, dmv0, dmv1, pic.top_field_first ? 1 : 3, -1, &dx, &dy); *mv2 = pack_mv(dx, dy);
+    mpeg2_dual_vector(x, y, dmv0, dmv1, pic.top_field_first ? 3 : 1, 1, &dx, &dy); *mv3 = pack_mv(dx, dy);
+    return 0;
+}
+
 // clamp_vectors on one packed vector
 M2V_HD uint32_t clamp_one(uint32_t v, int x_lo, int x_hi, int y_lo, int y_hi, bool *cl) {
     const int vx = (int16_t)(v & 0xffff), vy = (int16_t)(v >> 16);
@@ -223,12 +254,13 @@ struct Rec { uint32_t flags, qscale, cbp, mv[4], first; uint64_t counts; };
 M2V_HD void put(M2V_GLOBAL Mpeg2Mb *mbs, const Mpeg2VlcPic &pic, State &st, uint32_t addr, Rec r) {
     if (!(r.flags & M2_INTRA)) {
         const int mx = (int)(addr % (uint32_t)pic.mb_w), my = (int)(addr / (uint32_t)pic.mb_w), W = pic.mb_w * 16, H = pic.mb_h * 16;
-        const bool field = (r.flags & M2_FIELD_MV) != 0;
+        const bool dual = (r.flags & M2_DUAL) != 0, field = (r.flags & M2_FIELD_MV) != 0 || dual;      // (dual prime: 8 lines of a field, as field vectors)
         const int x_lo = -2 * mx * 16, x_hi = 2 * (W - 16 - mx * 16);
         const int y_lo = field ? -2 * my * 8 : -2 * my * 16, y_hi = field ? 2 * (H / 2 - 8 - my * 8) : 2 * (H - 16 - my * 16);
         bool cl = false;
-        if (r.flags & M2_FWD) { r.mv[0] = clamp_one(r.mv[0], x_lo, x_hi, y_lo, y_hi, &cl); if (field) r.mv[1] = clamp_one(r.mv[1], x_lo, x_hi, y_lo, y_hi, &cl); }
-        if (r.flags & M2_BWD) { r.mv[2] = clamp_one(r.mv[2], x_lo, x_hi, y_lo, y_hi, &cl); if (field) r.mv[3] = clamp_one(r.mv[3], x_lo, x_hi, y_lo, y_hi, &cl); }
+        if (dual) { r.mv[0] = clamp_one(r.mv[0], x_lo, x_hi, y_lo, y_hi, &cl); r.mv[2] = clamp_one(r.mv[2], x_lo, x_hi, y_lo, y_hi, &cl); r.mv[3] = clamp_one(r.mv[3], x_lo, x_hi, y_lo, y_hi, &cl); }
+        else if (r.flags & M2_FWD) { r.mv[0] = clamp_one(r.mv[0], x_lo, x_hi, y_lo, y_hi, &cl); if (field) r.mv[1] = clamp_one(r.mv[1], x_lo, x_hi, y_lo, y_hi, &cl); }
+        if (!dual && (r.flags & M2_BWD)) { r.mv[2] = clamp_one(r.mv[2], x_lo, x_hi, y_lo, y_hi, &cl); if (field) r.mv[3] = clamp_one(r.mv[3], x_lo, x_hi, y_lo, y_hi, &cl); }
         if (cl) { r.flags |= M2_CLAMPED; st.clamped++; }
     }
     M2V_GLOBAL Quad *q = (M2V_GLOBAL Quad *)(mbs + addr);
@@ -241,9 +273,9 @@ M2V_HD void put(M2V_GLOBAL Mpeg2Mb *mbs, const Mpeg2VlcPic &pic, State &st, uint
 
 // Decodes slice sl of picture pic.  t: the tables; bytes: the picture's slice bytes (4-byte aligned); mbs: the picture's records (16-byte aligned);
 // entries: the picture's entry list.  Writes the record of every address in [sl.lo, sl.hi) and their entries; returns the status (kM2St*).
-// *iters (may be null) receives the number of loop iterations.
+// *iters (may be null) receives the number of loop iterations, *n_dual (may be null) the number of dual-prime records written.
 M2V_HD uint32_t mpeg2_vlc_slice(const Mpeg2VlcPic &pic, const Mpeg2VlcTables *t, const Mpeg2Slice &sl, const uint32_t *bytes_, Mpeg2Mb *mbs_,
-                                uint32_t *entries_, long long *iters) {
+                                uint32_t *entries_, long long *iters, uint32_t *n_dual = nullptr) {
     using namespace m2v;
     const M2V_GLOBAL uint32_t *bytes = (const M2V_GLOBAL uint32_t *)bytes_;
     M2V_GLOBAL Mpeg2Mb *mbs = (M2V_GLOBAL Mpeg2Mb *)mbs_;
@@ -257,7 +289,7 @@ M2V_HD uint32_t mpeg2_vlc_slice(const Mpeg2VlcPic &pic, const Mpeg2VlcTables *t,
     State st = {};
     uint32_t e = sl.first_entry, next = sl.lo;          // next: the lowest address of the span that has no record yet
     int damage = 0; bool holes = false;
-    long long it = 0;
+    long long it = 0; uint32_t duals = 0;
 
     // a concealed macroblock: what the tail of mpeg2_decode_picture writes
     auto conceal = [&](uint32_t from, uint32_t to) {
@@ -314,10 +346,14 @@ M2V_HD uint32_t mpeg2_vlc_slice(const Mpeg2VlcPic &pic, const Mpeg2VlcTables *t,
             const int ty = vlc(b, t->mbtype[is_i ? 0 : (pic.type == 2 ? 1 : 2)], 6);
             if (ty < 0) { dmg = kM2DmgMbType; break; }
             const bool quant = ty & 1, mf = (ty & 2) != 0, mbk = (ty & 4) != 0, pattern = (ty & 8) != 0, intra = (ty & 16) != 0;
-            bool field_mv = false, field_dct = false;
+            bool field_mv = false, field_dct = false, dual = false;
             if ((mf || mbk) && !pic.frame_pred_frame_dct) {
                 const int fmt = (int)b.get(2);
-                if (fmt == 3) { dmg = kM2DmgDualPrime; break; }
+                if (fmt == 3) {
+                    if (!pic.dual_prime) { dmg = kM2DmgDualPrime; break; }
+                    if (pic.type != 2 || !mf) { dmg = kM2DmgDualPrimeInB; break; }
+                    dual = true;
+                }
                 if (fmt == 0) { dmg = kM2DmgMotionType; break; }
                 field_mv = fmt == 1;
             }
@@ -334,7 +370,8 @@ M2V_HD uint32_t mpeg2_vlc_slice(const Mpeg2VlcPic &pic, const Mpeg2VlcTables *t,
                 } else reset_pmv(st);
             } else {
                 st.dc0 = st.dc1 = st.dc2 = dc_reset;
-                if (mf) { rec.flags |= M2_FWD; if ((dmg = motion_vectors<0>(b, t, pic, st, field_mv, &rec.flags, &rec.mv[0], &rec.mv[1])) != 0) break; }
+                if (dual) { rec.flags |= M2_FWD | M2_DUAL; if ((dmg = dual_vectors(b, t, pic, st, &rec.mv[0], &rec.mv[2], &rec.mv[3])) != 0) break; }
+                else if (mf) { rec.flags |= M2_FWD; if ((dmg = motion_vectors<0>(b, t, pic, st, field_mv, &rec.flags, &rec.mv[0], &rec.mv[1])) != 0) break; }
                 if (mbk) { rec.flags |= M2_BWD; if ((dmg = motion_vectors<1>(b, t, pic, st, field_mv, &rec.flags, &rec.mv[2], &rec.mv[3])) != 0) break; }
                 if (field_mv) rec.flags |= M2_FIELD_MV;
                 if (!mf && !mbk) {
@@ -396,11 +433,13 @@ M2V_HD uint32_t mpeg2_vlc_slice(const Mpeg2VlcPic &pic, const Mpeg2VlcTables *t,
         } while (false);
         if (dmg) { e = e0; damage = dmg; break; }
         m2v::put(mbs, pic, st, addr, rec);
+        if (rec.flags & M2_DUAL) duals++;
         next = addr + 1; prev = addr; first = false;
     }
     // every address of the span that has no record yet
     if (next < sl.hi) conceal(next, sl.hi);
     if (iters) *iters = it;
+    if (n_dual) *n_dual = duals;
     return (uint32_t)damage | (holes ? kM2StHoles : 0u) | (damage == kM2DmgDualPrime ? kM2StDualPrime : 0u) | st.clamped << kM2StClampedShift;
 }
 

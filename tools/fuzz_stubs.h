@@ -43,7 +43,7 @@ void launch_hevc_pichash(const HevcPicParams *, int, int, uint32_t *, ihipStream
 void launch_hevc_md5(const HevcPicParams *, int, uint32_t *, ihipStream_t *) { abort(); }
 void launch_jpeg_recon(const JpegPicParams *, int, int, ihipStream_t *) { abort(); }
 void launch_jpeg_entropy(const JpegEntropyParams *, int, int, ihipStream_t *) { abort(); }
-void launch_mpeg2_recon(const Mpeg2PicParams *, int, int, ihipStream_t *) { abort(); }
+void launch_mpeg2_recon(const Mpeg2PicParams *, int, int, bool, ihipStream_t *) { abort(); }
 void launch_mpeg2_vlc(const Mpeg2VlcParams *, int, int, ihipStream_t *) { abort(); }
 void hevc_kernels_init() {}
 }

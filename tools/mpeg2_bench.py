@@ -12,8 +12,13 @@ run and B from the IBBP run by subtracting the shares already known (`--split`).
 `--streams` (a list: 32,1 adds the lone-stream pair), and adds upload bytes per picture and k_mpeg2_vlc's microseconds per picture; the summary then
 carries min / median / max frames per second of every leg, and the option-0 leg of the same call is the reference of every figure.  A library
 without the option (JM_AMD_DEC_LIB names the parent commit's) runs the option-0 legs only.
+--field-pictures compares field pictures with frame pictures (option mpeg2_field_pictures 1 in every leg): the same kind of group written twice for
+a 1080i sequence (progressive_sequence 0), once as frame pictures and once with every frame as two field pictures (tests/scripted_mpeg2_field.py:
+field, 16x8 and dual-prime macroblocks), legs frame / field x host / device alternating within each round; `--stream` and `--write` then name the
+frame-picture file and the field-picture file goes beside it with ".fields" appended.
 
     python tools/mpeg2_bench.py [--streams 32,1] [--groups 8] [--rounds 3] [--kind IBBP] [--stream file.m2v] [--write file.m2v] [--split] [--device-vlc]
+                                [--field-pictures]
 """
 import argparse
 import ctypes as C
@@ -29,6 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import scripted_mpeg2 as S  # noqa: E402
+import scripted_mpeg2_field as SF  # noqa: E402
 from jmcodec_amd import api  # noqa: E402
 
 W, H = 1920, 1080
@@ -44,7 +50,20 @@ def make_group(kind, width=W, height=H):
     return S.build(items)
 
 
-def run_leg(L, pics, S_, groups, device, device_vlc=0):
+def make_interlaced_group(kind, fields, width=W, height=H):
+    """one group of a 1080i sequence in coding order: frame pictures (frame and field prediction, both DCT types), or every frame as two field
+    pictures, top field first"""
+    rng = np.random.default_rng(0x4D504733)
+    items = [("seq", dict(width=width, height=height, frame_rate_code=4, progressive_sequence=0))]
+    for i, t in enumerate(KINDS[kind]):
+        if fields:
+            items += [("pic", SF.random_field_picture(rng, t, width, height, s, temporal_reference=i, concealment_mv=0)) for s in (1, 2)]
+        else:
+            items.append(("pic", S.random_picture(rng, t, width, height, 0, temporal_reference=i, frame_pred_frame_dct=0, concealment_mv=0, progressive_frame=0)))
+    return SF.build(items)
+
+
+def run_leg(L, pics, S_, groups, device, device_vlc=0, field_pictures=0):
     hs = []
     for _ in range(S_):
         h = api.jm_nvdec_create_handle()
@@ -53,6 +72,8 @@ def run_leg(L, pics, S_, groups, device, device_vlc=0):
         assert L.jm_amddec_set_option(h, b"profile", 1) == 0
         if device_vlc:
             assert L.jm_amddec_set_option(h, b"mpeg2_device_vlc", device_vlc) == 0
+        if field_pictures:
+            assert L.jm_amddec_set_option(h, b"mpeg2_field_pictures", field_pictures) == 0
         if api.jm_nvdec_init(4, 0, None, 0, h) != 0:
             raise SystemExit("init failed: " + L.jm_amddec_last_error(h).decode())
         hs.append(h)
@@ -116,6 +137,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--streams", default="32", help="stream counts, comma separated")
     ap.add_argument("--device-vlc", action="store_true", help="run every leg with option mpeg2_device_vlc at 0 and at 1")
+    ap.add_argument("--field-pictures", action="store_true", help="a 1080i group as frame pictures against the same kind as field pictures")
     ap.add_argument("--groups", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--kind", default="IBBP", choices=sorted(KINDS))
@@ -125,9 +147,15 @@ def main():
     args = ap.parse_args()
     counts = [int(v) for v in args.streams.split(",")]
     t0 = time.perf_counter()
-    data = open(args.stream, "rb").read() if args.stream else make_group(args.kind)
+    if args.field_pictures:
+        data = open(args.stream, "rb").read() if args.stream else make_interlaced_group(args.kind, False)
+        fdata = open(args.stream + ".fields", "rb").read() if args.stream else make_interlaced_group(args.kind, True)
+    else:
+        data = open(args.stream, "rb").read() if args.stream else make_group(args.kind)
     if args.write:
         open(args.write, "wb").write(data)
+        if args.field_pictures:
+            open(args.write + ".fields", "wb").write(fdata)
         print(json.dumps({"wrote": args.write, "bytes": len(data), "seconds": round(time.perf_counter() - t0, 1)}))
         return
     pics = api.split_mpeg2_pictures(data)
@@ -136,6 +164,21 @@ def main():
     L.jm_amddec_output_frame_device.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p]
     if args.split:
         print(json.dumps(dict(run_leg(L, pics, counts[0], args.groups, True), leg="device", kind=args.kind, split=True)), flush=True)
+        return
+    if args.field_pictures:
+        fpics = api.split_mpeg2_pictures(fdata)
+        legs = [(out, coded) for out in ("host", "device") for coded in ("frame", "field")]
+        res = {leg: [] for leg in legs}
+        for r in range(args.rounds):
+            for leg in (legs if r % 2 == 0 else legs[::-1]):
+                out = run_leg(L, fpics if leg[1] == "field" else pics, counts[0], args.groups, leg[0] == "device", field_pictures=1)
+                out["k_mpeg2_recon_us_per_frame"] = round(out["k_mpeg2_recon_us_per_picture"] * (2 if leg[1] == "field" else 1), 2)
+                res[leg].append(out)
+                print(json.dumps(dict(out, leg=leg[0], pictures=leg[1], streams=counts[0], round=r, kind=args.kind)), flush=True)
+        for leg, v in res.items():
+            v = sorted(v, key=lambda o: o["frames_per_s"])
+            print(json.dumps({"summary": True, "streams": counts[0], "kind": args.kind, "leg": leg[0], "pictures": leg[1], "frames_per_s_min": v[0]["frames_per_s"],
+                              "frames_per_s_max": v[-1]["frames_per_s"], "median": v[len(v) // 2]}), flush=True)
         return
     if args.device_vlc:
         h = api.jm_nvdec_create_handle()
