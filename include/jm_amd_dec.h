@@ -37,7 +37,7 @@ extern "C" {
 typedef void *jm_amddec_handle;
 
 jm_amddec_handle jm_amddec_create_handle(void);
-/* codec_type: 0 = H.264, 1 = H.265 / HEVC Main, 2 = MJPEG, 4 = MPEG-2 video (enum nv_dec.h:37-46; the other values are refused); out_fmt: 0 = NV12, 1 = "YV12" = planar Y,U,V.
+/* codec_type: 0 = H.264, 1 = H.265 / HEVC Main, 2 = MJPEG, 4 = MPEG-2 video, 5 = VP8 key frames with option vp8 1 (enum nv_dec.h:37-46; the other values are refused); out_fmt: 0 = NV12, 1 = "YV12" = planar Y,U,V.
  * MJPEG: the input is any chunking of a byte stream of concatenated baseline JPEG pictures (SOI .. EOI; 4:2:0 / 4:2:2 / 4:4:4 / grey, 8 bits, one
  * interleaved Huffman scan), every picture lands in the usual NV12 surface and every output option applies; progressive, arithmetic, lossless, 12-bit,
  * CMYK and other samplings fail the handle with an error string (INTEGRATION.md "MJPEG").  extra_data is not used.  Stats: jpeg_pictures, jpeg_sampling
@@ -66,6 +66,14 @@ jm_amddec_handle jm_amddec_create_handle(void);
  * `frames` count frames, i_pictures / p_pictures / b_pictures coded pictures.  With mpeg2_device_vlc as well, field pictures take the host path and
  * frame pictures stay on the device, where the lane decodes dual prime.  Stats: mpeg2_field_pictures, mpeg2_lone_fields, mpeg2_dual_prime_mbs,
  * mpeg2_16x8_mbs.  At 0 nothing changes (INTEGRATION.md "MPEG-2"). */
+/* VP8 (codec_type 5): KEY frames of RFC 6386 (lossy WebP pictures, all-key-frame streams).  Option "vp8" 1 (before init) turns the codec on: without it
+ * init(5) stays refused as for 3, 6 and 7, so nothing changes for a caller that does not ask (other codecs refuse the option).  The input is an IVF byte stream ("DKIF", any chunking) or one
+ * whole frame per call; RIFF / WebP wrappers are not parsed.  Every key-frame feature is decoded (segmentation, both loop filters, 1-8 token partitions,
+ * all quantiser deltas, B_PRED); an inter frame fails the handle with "VP8 inter frames are not built", as do a first frame that is no key frame, a bad
+ * start code and sizes above 8192; deinterlace_temporal is refused at init; jm_amddec_feed_annexb is refused (no start codes).  extra_data is not
+ * used.  An odd display size is handed out as the even size just above.  RGB auto: BT.601 limited range, chroma centred (INTEGRATION.md "VP8").
+ * Stats: vp8_key_frames, vp8_hidden_frames, vp8_empty_frames, vp8_partitions, vp8_segments, vp8_filter_type, vp8_color_space, vp8_scale,
+ * vp8_bpred_mbs, vp8_skipped_mbs; with option profile k_vp8_recon_* and k_vp8_filter_* (_ns / _n / _pics / _alg_bytes). */
 int  jm_amddec_init(int codec_type, int out_fmt, char *extra_data, int len, jm_amddec_handle h);
 int  jm_amddec_deinit(jm_amddec_handle h);
 /* in_buf may hold any chunk of an Annex-B stream; (NULL, 0) signals end of stream and then

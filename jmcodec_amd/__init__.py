@@ -24,4 +24,5 @@ from .api import (  # noqa: F401
     split_nalus,
     split_jpegs,
     split_mpeg2_pictures,
+    webp_to_ivf,
 )

@@ -420,6 +420,24 @@ def split_mpeg2_pictures(data):
     return [data[a:b] for a, b in zip(cuts, cuts[1:] + [len(data)])] if data else []
 
 
+def webp_to_ivf(data):
+    """The `VP8 ` chunk of a lossy RIFF / WebP file as a one-frame IVF byte stream for a codec_type 5 handle (the library itself parses no RIFF wrapper).
+    Raises ValueError for a file without such a chunk (lossless `VP8L`, or no WebP at all); an `ALPH` chunk is ignored."""
+    data = bytes(data)
+    if data[:4] != b"RIFF" or data[8:12] != b"WEBP":
+        raise ValueError("not a RIFF / WebP file")
+    o = 12
+    while o + 8 <= len(data):
+        n = int.from_bytes(data[o + 4:o + 8], "little")
+        if data[o:o + 4] == b"VP8 ":
+            f = data[o + 8:o + 8 + n]
+            head = b"DKIF" + (0).to_bytes(2, "little") + (32).to_bytes(2, "little") + b"VP80" + bytes(4) + (30).to_bytes(4, "little") + \
+                (1).to_bytes(4, "little") + (1).to_bytes(4, "little") + bytes(4)
+            return head + len(f).to_bytes(4, "little") + bytes(8) + f
+        o += 8 + n + (n & 1)
+    raise ValueError("no VP8 chunk (a lossless or animated WebP file?)")
+
+
 def annexb_to_avcc(data, length_size=4):
     """(avcC record, [length-prefixed packets]) of an Annex-B stream: what a demuxer hands test_player for an MP4 source when no
     h264_mp4toannexb filter is in the way (test_player.cpp:221-226).  One packet per access unit (split before each first slice)."""
@@ -472,7 +490,8 @@ def annexb_to_hvcc(data, length_size=4):
 class JmAmdDec:
     """Convenience wrapper reproducing test_nv_dec's main loop (test_nv_dec.cpp:163-259).
 
-    codec_type: 0 H.264, 1 HEVC, 2 MJPEG, 4 MPEG-2 video (frame pictures, 4:2:0: INTEGRATION.md "MPEG-2"); the other values of the
+    codec_type: 0 H.264, 1 HEVC, 2 MJPEG, 4 MPEG-2 video (frame pictures, 4:2:0: INTEGRATION.md "MPEG-2"), 5 VP8 key frames (needs options={"vp8": 1}; an IVF byte
+    stream in any chunking or one frame per call: INTEGRATION.md "VP8"; `webp_to_ivf` wraps a lossy WebP file); the other values of the
     reference's NV_CODEC_TYPE are refused at init."""
 
     def __init__(self, codec_type=0, out_fmt=1, options=None, extra_data=None, rgb=None):

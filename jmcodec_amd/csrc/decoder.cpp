@@ -193,6 +193,10 @@ int Decoder::set_option(const char *key, long long v) {
         if (inited_ || v < 0 || v > 1) return -1;
         mpeg2_field_pics_ = (int)v;
     }
+    else if (k == "vp8") {                   // 1 = codec_type 5 (VP8 key frames) is accepted at init; 0 (default): it is refused, as before the codec existed
+        if (inited_ || v < 0 || v > 1) return -1;
+        vp8_on_ = (int)v;
+    }
     else if (k == "rgb_chroma") {            // RGB output: 1 = chroma interpolated to full resolution at the stream's siting (k_rgb_pack444)
         if (inited_ || v < 0 || v > 1) return -1;
         rgb_chroma_ = (int)v;
@@ -318,6 +322,18 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "mpeg2_lone_fields") return stat_m2_lone_;
     if (k == "mpeg2_dual_prime_mbs") return stat_m2_dual_;
     if (k == "mpeg2_16x8_mbs") return stat_m2_16x8_;
+    // VP8: key frames decoded, of them not shown (show_frame 0), empty IVF frames skipped; of the last picture: token partitions, segments in use,
+    // filter type, color_space | clamping_type << 1, horizontal | vertical << 2 scale (recorded, not applied); B_PRED and skipped macroblocks so far
+    if (k == "vp8_key_frames") return stat_v8_key_;
+    if (k == "vp8_hidden_frames") return stat_v8_hidden_;
+    if (k == "vp8_empty_frames") return stat_v8_empty_;
+    if (k == "vp8_partitions") return stat_v8_parts_;
+    if (k == "vp8_segments") return stat_v8_segments_;
+    if (k == "vp8_filter_type") return stat_v8_filter_;
+    if (k == "vp8_color_space") return stat_v8_color_;
+    if (k == "vp8_scale") return stat_v8_scale_;
+    if (k == "vp8_bpred_mbs") return stat_v8_bpred_;
+    if (k == "vp8_skipped_mbs") return stat_v8_skipped_;
     if (k == "mpeg2_profile_level") return codec_ == 4 && seq_active_ ? m2seq_.profile_level : 0;
     if (k == "copy_engines") return copier_ ? (long long)copier_->engine_mask() : 0;      // SDMA engines the direct route uses (bit mask)
     if (k == "direct_frames") return stat_direct_;
@@ -358,7 +374,7 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "wait_slot_ns") return stat_wait_slot_ns_;
     if (k == "parse_ns_p") return stat_parse_ns_p_;
     if (k.rfind("k_", 0) == 0 || k.rfind("eng_", 0) == 0) {          // engine-wide (all handles on this device), profile option
-        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5", "rgb_pack444", "mpeg2", "jpeg_entropy", "mpeg2_vlc"};
+        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5", "rgb_pack444", "mpeg2", "jpeg_entropy", "mpeg2_vlc", "vp8_recon", "vp8_filter"};
         if (!engine_) return 0;
         EngineStats es = engine_->stats();
         for (int i = 0; i < kKernelClasses; i++) {
@@ -418,8 +434,12 @@ long long Decoder::get_stat(const char *key) const {
 // MI355X-class device can be opened, because silently continuing would mean a CPU fallback.
 int Decoder::init(int codec_type, int out_fmt, const uint8_t *extra, int len) {
     codec_ = codec_type; out_fmt_ = out_fmt ? 1 : 0;
-    if (codec_type != 0 && codec_type != 1 && codec_type != 2 && codec_type != 4) {
-        fail("only codec_type 0 (H.264), 1 (HEVC), 2 (MJPEG) and 4 (MPEG-2) are implemented"); return -1; }
+    // VP8 key frames are there for the handle that asks for them (option vp8 1 before init): without the option codec_type 5 stays refused, as before
+    if (codec_type != 0 && codec_type != 1 && codec_type != 2 && codec_type != 4 && !(codec_type == 5 && vp8_on_)) {
+        fail("only codec_type 0 (H.264), 1 (HEVC), 2 (MJPEG) and 4 (MPEG-2) are implemented in full, and 5 (VP8) for key frames with option vp8 1"); return -1; }
+    if (codec_type != 5 && vp8_on_) { fail("option vp8 is only available for VP8 (codec_type 5)"); return -1; }
+    if (codec_type == 5 && deint_temporal_) { fail("option deinterlace_temporal is not available for VP8 (codec_type 5): its surfaces are dealt round robin, "
+        "a displayed one cannot be kept for the next picture"); return -1; }
     if (codec_type == 4 && deint_temporal_) { fail("option deinterlace_temporal is not available for MPEG-2 (codec_type 4): keeping the previous display "
         "surface is tied to the H.264 / HEVC picture buffer"); return -1; }
     if (codec_type == 2 && deint_temporal_) { fail("option deinterlace_temporal is not available for MJPEG (codec_type 2): its surfaces are dealt round robin, "
@@ -470,7 +490,8 @@ int Decoder::init(int codec_type, int out_fmt, const uint8_t *extra, int len) {
     // optional SPS/PPS given up front (nv_dec.cpp:334-360).  FFmpeg hands test_player either Annex-B parameter sets or, for MP4 /
     // MKV sources, an AVCDecoderConfigurationRecord ("avcC", ISO/IEC 14496-15 5.2.4.1); with avcC the packets that follow are
     // length-prefixed NAL units unless a bitstream filter already converted them (test_player.cpp:221-226 uses h264_mp4toannexb).
-    if (codec_ == 4) { if (extra && len > 0) feed(extra, (size_t)len); }      // (sequence headers given up front: part of the stream)
+    if (codec_ == 5) { }                                                      // (VP8 has no out-of-band headers: extra_data is not used)
+    else if (codec_ == 4) { if (extra && len > 0) feed(extra, (size_t)len); }      // (sequence headers given up front: part of the stream)
     else if (extra && len > 0 && codec_ == 1 && len >= 23 && extra[0] == 1) {
         // HEVCDecoderConfigurationRecord ("hvcC", ISO/IEC 14496-15 8.3.3.1): what a demuxer hands test_player for HEVC in MP4 / MKV
         avcc_len_size_ = (extra[21] & 3) + 1;
@@ -773,8 +794,9 @@ bool Decoder::gpu_alloc_sequence() {
     if (getenv("JM_AMD_DEC_JOB_WORST_CASE")) job_cap_ = job_cap_max_;
     if (codec_ == 1) job_cap_ = n_mbs * 128 + (1u << 20);            // HEVC job lists vary a lot in size: start small, grow on demand (ensure_job_cap)
     if (codec_ == 4) job_cap_ = n_mbs * 224 + (1u << 16);            // MPEG-2: a 32-byte record per macroblock + a typical share of levels; grown on demand too
+    if (codec_ == 5) job_cap_ = n_mbs * 160 + (1u << 16);            // VP8: a 32-byte record per macroblock + a typical share of levels; grown on demand too
     if (codec_ == 2) job_cap_ = n_mbs * 160 + (1u << 16);            // MJPEG: 6 block records per macroblock + a typical share of levels; grown on demand too
-    if (!n_jobs_set_) n_jobs_ = codec_ == 2 || codec_ == 4 ? kJpegJobSlots : codec_ == 0 && n_mbs <= 8704 ? kJobSlotsSmall : kJobSlots;      // (decoder.h)
+    if (!n_jobs_set_) n_jobs_ = codec_ == 2 || codec_ == 4 || codec_ == 5 ? kJpegJobSlots : codec_ == 0 && n_mbs <= 8704 ? kJobSlotsSmall : kJobSlots;      // (decoder.h)
     if (!n_jobs_set_ && rgb_ && !parse_only_) {
         // an RGB frame is 2-8x an NV12 one and the handle keeps n_jobs_ + 4 output slots: at most 1 GiB of them (device staging + page-locked), at least
         // 8 job slots
@@ -879,6 +901,7 @@ OutSlot *Decoder::alloc_out_slot() {   // mtx_ held
 // front end: Annex-B splitting (replaces the NAL scanning half of cuvidParseVideoData, nv_dec.cpp:394)
 // =============================================================================================
 void Decoder::feed(const uint8_t *buf, size_t len) {
+    if (codec_ == 5) { vp8_feed(buf, len); return; }       // an IVF byte stream cut anywhere, or one VP8 frame per call (vp8_decoder.cpp)
     if (codec_ == 4) { mpeg2_feed(buf, len); return; }     // an MPEG-2 elementary stream, cut anywhere (mpeg2_decoder.cpp)
     if (codec_ == 2) { jpeg_feed(buf, len); return; }      // concatenated JPEG pictures, cut anywhere (jpeg_decoder.cpp)
     if (avcc_len_size_ && !have_start_ && in_.empty()) {
@@ -936,6 +959,7 @@ void Decoder::feed(const uint8_t *buf, size_t len) {
 void Decoder::flush_stream() {
     if (codec_ == 2) jpeg_flush();
     if (codec_ == 4) mpeg2_flush();
+    if (codec_ == 5) vp8_flush();
     if (have_start_) {
         size_t end = in_.size();
         while (end > nal_start_ && in_[end - 1] == 0) end--;
@@ -1093,7 +1117,7 @@ int Decoder::compute_poc(const SliceHeader &sh, DpbPic &store) {
 }
 
 void Decoder::flush_dpb(std::vector<int> &out) {
-    if (codec_ == 2) return;                       // (a JPEG picture is displayed by its own task: nothing waits)
+    if (codec_ == 2 || codec_ == 5) return;        // (a JPEG picture or a VP8 key frame is displayed by its own task: nothing waits)
     if (codec_ == 4) { mpeg2_show_anchor(out); return; }      // (the last anchor picture)
     if (codec_ == 1) { for (int i = 0; i < n_surf_; i++) if (i != cur_) dpb_[i].ref = 0; hevc_bump(out, true, true);
         for (int i = 0; i < n_surf_; i++) if (i != cur_ && !dpb_[i].wait_output) dpb_[i].in_use = false; return; }
@@ -1684,6 +1708,7 @@ void Decoder::parse_task(PicTask *t, ParseScratch &scratch) {
     if (t->hevc) { hevc_parse_task(t); return; }
     if (t->jpeg) { jpeg_parse_task(t); return; }
     if (t->mpeg2) { mpeg2_parse_task(t); return; }
+    if (t->vp8) { vp8_parse_task(t); return; }
     auto pt0 = std::chrono::steady_clock::now();
     JobSlot &js = jobs_[t->job_slot];
     const int n_mbs = t->sps.mb_w * t->sps.mb_h;
@@ -1956,6 +1981,7 @@ void Decoder::submit_task(PicTask *t) {
     else if (t->hevc && (t->hevc->hash.type > 0 || (t->hevc->hash.type == 0 && verify_md5_)) && !parse_only_) stat_hash_unchecked_++;      // (a failed handle's picture is not decoded: nothing to compare)
     else if (ep.has_picture && t->jpeg) jpeg_fill_engine_pic(t, ep);
     else if (ep.has_picture && t->mpeg2) mpeg2_fill_engine_pic(t, ep);
+    else if (ep.has_picture && t->vp8) vp8_fill_engine_pic(t, ep);
     else if (ep.has_picture) {
         JobSlot &js = jobs_[t->job_slot];
         const int n_mbs = t->sps.mb_w * t->sps.mb_h;
@@ -2170,7 +2196,7 @@ int Decoder::decode(const uint8_t *buf, int len, int *got_frame) {
                      "Elapsed Time:\t%d ms\n"
                      "Decode FPS:\t%f fps\n"
                      "==========================================\n",
-                     codec_ == 0 ? "H.264" : (codec_ == 1 ? "H.265" : (codec_ == 4 ? "MPEG-2" : "MJPEG")), out_w_, out_h_, fmt, deint, place, (int)num_frames_,
+                     codec_ == 0 ? "H.264" : (codec_ == 1 ? "H.265" : (codec_ == 4 ? "MPEG-2" : (codec_ == 5 ? "VP8" : "MJPEG"))), out_w_, out_h_, fmt, deint, place, (int)num_frames_,
                      (int)elapsed_ms_, elapsed_ms_ > 0 ? (double)num_frames_ * 1000.0 / elapsed_ms_ : 0.0);
         }
     }

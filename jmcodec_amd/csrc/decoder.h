@@ -13,6 +13,7 @@
 #include "hevc_sei.h"
 #include "jpeg_syntax.h"
 #include "mpeg2_syntax.h"
+#include "vp8_syntax.h"
 #include "jobs.h"
 #include "scale_packed.h"    // build_scale_taps
 #include "chroma_packed.h"   // build_chroma_taps
@@ -103,6 +104,11 @@ struct Mpeg2Task { Mpeg2Pic pic; int ref_slot[2] = {-1, -1}; size_t off_mbs = 0,
     bool on_device = false; size_t off_par = 0, off_slices = 0, off_bytes = 0; int n_slices = 0;
     int structure = 0; int fref_slot[2][2] = {{-1, -1}, {-1, -1}}, fref_par[2][2] = {{0, 1}, {0, 1}}; bool fill = false, ext = false; };
 
+// VP8 key frame (codec_type 5): the frame's bytes and what its first ten say; the parse worker fills in the rest of the header and where the job list
+// (records, entries: vp8_jobs.h) sits in the job buffer
+struct Vp8Task { Vp8FrameTag tag; std::vector<uint8_t> data; bool truncated = false; size_t off_mbs = 0, off_entries = 0; int n_entries = 0;
+    int filter_type = 0, sharpness = 0; bool filtered = false; int16_t dq[4][6] = {{0}}; };
+
 struct PicTask {
     uint64_t seq = 0;
     bool has_picture = false;
@@ -114,6 +120,7 @@ struct PicTask {
     std::unique_ptr<HevcTask> hevc;            // codec_type 1
     std::unique_ptr<JpegTask> jpeg;            // codec_type 2
     std::unique_ptr<Mpeg2Task> mpeg2;          // codec_type 4
+    std::unique_ptr<Vp8Task> vp8;              // codec_type 5
     std::vector<int> out_before, out_after;    // frames to display before / after this picture (Decoder::display_entry)
     bool wait_prev_pack = false;               // current surface was displayed by the previous picture (no cooling slack)
     // written by the parse worker
@@ -196,6 +203,9 @@ public:
     bool field_rate() const { return deint_mode_ && deint_rate_; }     // options deinterlace + deinterlace_rate: a picture may leave as two frames
     char *info() { return info_; }
     const char *last_error();
+    int codec() const { return codec_; }
+    // a call this codec does not offer: the reason is left for last_error(), the handle goes on
+    void refuse_call(const std::string &msg) { note_error(msg); }
     int  set_option(const char *key, long long v);
     int  set_rgb(const RgbSpec *spec);         // before init; nullptr = Y'CbCr output again
     long long get_stat(const char *key) const;
@@ -287,6 +297,13 @@ private:
     void mpeg2_parse_task(PicTask *t);
     bool mpeg2_parse_task_device(PicTask *t);  // option mpeg2_device_vlc: the prescan instead of the VLC decode; false: the host path takes the picture
     void mpeg2_fill_engine_pic(PicTask *t, struct EnginePic &ep);
+    // ---- VP8 front end (vp8_decoder.cpp) ----
+    void vp8_feed(const uint8_t *buf, size_t len);
+    void vp8_flush();
+    void vp8_handle_frame(const uint8_t *p, size_t n, bool truncated);
+    bool vp8_activate(const Vp8FrameTag &tag);
+    void vp8_parse_task(PicTask *t);
+    void vp8_fill_engine_pic(PicTask *t, struct EnginePic &ep);
     void gpu_close();
     void submit_ready();
     void submit_task(PicTask *t);
@@ -459,6 +476,12 @@ private:
     std::atomic<long long> stat_m2_fields_{0}, stat_m2_lone_{0}, stat_m2_dual_{0}, stat_m2_16x8_{0};
     std::atomic<long long> stat_m2_dev_pics_{0}, stat_m2_host_pics_{0}, stat_m2_dev_slices_{0}, stat_m2_dev_damaged_{0};
     uint64_t m2_digest_ = 1469598103934665603ull; long long m2_digest_mbs_ = 0;      // written by the parse worker (sync option)
+    // VP8 state (front end only unless noted)
+    int vp8_on_ = 0;                           // option vp8 (before init): 1 = init accepts codec_type 5
+    Vp8Splitter v8split_; int v8_w_ = 0, v8_h_ = 0; long long v8_key_seen_ = 0;
+    // (the last five describe the last picture parsed, written by the parse worker: read them after the handle has drained, or with option sync)
+    std::atomic<long long> stat_v8_key_{0}, stat_v8_hidden_{0}, stat_v8_empty_{0}, stat_v8_bpred_{0}, stat_v8_skipped_{0};
+    std::atomic<int> stat_v8_parts_{0}, stat_v8_segments_{0}, stat_v8_filter_{0}, stat_v8_color_{0}, stat_v8_scale_{0};
     struct TraceRec { uint64_t seq; long long t_dispatch, t_parsed, t_submit0, t_submit1; int is_i; };
     std::vector<TraceRec> trace_; bool trace_on_ = false;
 };

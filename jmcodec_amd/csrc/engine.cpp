@@ -518,6 +518,19 @@ void Engine::launch(Lane &ln, Batch &b) {
         }
     }
     if (any_mpeg2 && profile_ && !b.m2ev[0]) for (auto &e : b.m2ev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
+    // ... and for VP8 key frames
+    bool any_vp8 = false, vp8_filtered = false;
+    for (auto &p : b.pics) any_vp8 |= p.codec == 5 && p.has_picture;
+    if (any_vp8 && !b.h_vpics) {
+        if (hipHostMalloc((void **)&b.h_vpics, sizeof(Vp8PicParams) * kMaxBatch, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc((void **)&b.d_vpics, sizeof(Vp8PicParams) * kMaxBatch) != hipSuccess) {
+            (void)hipGetLastError();
+            if (b.h_vpics) hipHostFree(b.h_vpics);
+            b.h_vpics = nullptr; b.d_vpics = nullptr; any_vp8 = false;
+            for (auto &p : b.pics) if (p.codec == 5 && p.has_picture) { p.has_picture = false; p.dec->on_engine_error("hipMalloc(VP8 parameter table) failed"); }
+        }
+    }
+    if (any_vp8 && profile_ && !b.v8ev[0]) for (auto &e : b.v8ev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
     // ... of which some are VLC-decoded on the device (option mpeg2_device_vlc): the parameter table of k_mpeg2_vlc, the status words and their pinned
     // copy, when this slot of the ring first holds one; the lookup tables, once per engine.  A batch without such a picture reaches none of this
     b.any_m2dev = false; int max_mpeg2_slices = 0;
@@ -592,6 +605,11 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (any_mpeg2) {
             if (p.codec == 4 && p.has_picture) { b.h_mpics[i] = p.mp; max_mpeg2_items = std::max(max_mpeg2_items, p.mp.n_items); mpeg2_ext |= p.mp.ext != 0; b.alg[11] += p.mpeg2_alg_bytes; b.npics[11]++; }
             else b.h_mpics[i].n_items = 0;
+        }
+        if (any_vp8) {
+            if (p.codec == 5 && p.has_picture) { b.h_vpics[i] = p.vp; b.alg[14] += p.vp8_recon_alg_bytes; b.npics[14]++;
+                if (p.vp.filtered) { vp8_filtered = true; b.alg[15] += p.vp8_filter_alg_bytes; b.npics[15]++; } }
+            else b.h_vpics[i].mb_w = 0;
         }
         if (b.any_m2dev) {
             if (p.codec == 4 && p.has_picture && p.mpeg2_on_device) { b.h_m2v[i] = p.mv; b.h_m2v[i].tab = d_m2vtab_; b.h_m2v[i].status = b.d_m2status + (size_t)i * kMpeg2StatusWords;
@@ -682,6 +700,7 @@ void Engine::launch(Lane &ln, Batch &b) {
     if (b.any_jdev) hipMemcpyAsync(b.d_jents, b.h_jents, sizeof(JpegEntropyParams) * n, hipMemcpyHostToDevice, ps);
     if (any_mpeg2) hipMemcpyAsync(b.d_mpics, b.h_mpics, sizeof(Mpeg2PicParams) * n, hipMemcpyHostToDevice, ps);
     if (b.any_m2dev) hipMemcpyAsync(b.d_m2v, b.h_m2v, sizeof(Mpeg2VlcParams) * n, hipMemcpyHostToDevice, ps);
+    if (any_vp8) hipMemcpyAsync(b.d_vpics, b.h_vpics, sizeof(Vp8PicParams) * n, hipMemcpyHostToDevice, ps);
     b.out.each([&](auto &t) { for (int side : {kBefore, kAfter}) if (t.n[side])
         hipMemcpyAsync(t.dev + side * kOutSideCap, t.h(side), sizeof(*t.host) * t.n[side], hipMemcpyHostToDevice, ps); });
     // job lists were copied on the (in-order) copy stream when the pictures were parsed: waiting for the most recently
@@ -755,6 +774,18 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (timed) hipEventRecord(b.m2ev[0], st);
         launch_mpeg2_recon(b.d_mpics, n, max_mpeg2_items, mpeg2_ext, st);
         if (timed) { hipEventRecord(b.m2ev[1], st); b.pmask |= 32768; }
+    }
+    // VP8 key frames of the batch reference nothing: one launch reconstructs them all, one workgroup per picture; the loop filter follows as its
+    // own launch, so no prediction sees a filtered sample
+    if (any_vp8) {
+        const bool timed = profile_ && b.v8ev[0] && b.v8ev[1] && b.v8ev[2];
+        if (timed) hipEventRecord(b.v8ev[0], st);
+        launch_vp8_recon(b.d_vpics, n, st);
+        if (timed) { hipEventRecord(b.v8ev[1], st); b.pmask |= 262144; }
+        if (vp8_filtered) {
+            launch_vp8_filter(b.d_vpics, n, st);
+            if (timed) { hipEventRecord(b.v8ev[2], st); b.pmask |= 524288; }
+        }
     }
     b.any_bipred = b.any_field = false;
     for (auto &p : b.pics) { b.any_bipred |= p.has_picture && p.codec == 0 && p.bipred; b.any_field |= p.has_picture && p.codec == 0 && p.pp.field != 0; }
@@ -1039,6 +1070,8 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
         if (b.pmask & 65536) { float ms = 0; if (hipEventElapsedTime(&ms, b.jeev[0], b.jeev[1]) == hipSuccess) { st_.ns[12] += ms * 1e6; st_.launches[12]++; } }
         if (b.pmask & 131072) { float ms = 0; if (hipEventElapsedTime(&ms, b.m2vev[0], b.m2vev[1]) == hipSuccess) { st_.ns[13] += ms * 1e6; st_.launches[13]++; } }
         if (b.pmask & 32768) { float ms = 0; if (hipEventElapsedTime(&ms, b.m2ev[0], b.m2ev[1]) == hipSuccess) { st_.ns[11] += ms * 1e6; st_.launches[11]++; } }
+        if (b.pmask & 262144) { float ms = 0; if (hipEventElapsedTime(&ms, b.v8ev[0], b.v8ev[1]) == hipSuccess) { st_.ns[14] += ms * 1e6; st_.launches[14]++; } }
+        if (b.pmask & 524288) { float ms = 0; if (hipEventElapsedTime(&ms, b.v8ev[1], b.v8ev[2]) == hipSuccess) { st_.ns[15] += ms * 1e6; st_.launches[15]++; } }
         if (b.pmask & 4096) { float ms = 0; if (hipEventElapsedTime(&ms, b.mev[0], b.mev[1]) == hipSuccess) { st_.ns[9] += ms * 1e6; st_.launches[9]++; } }
         for (int k = 0; k < kKernelClasses; k++) { st_.pics[k] += b.npics[k]; st_.alg_bytes[k] += b.alg[k]; }
         st_.batches++; st_.batch_pics += (long long)b.pics.size();

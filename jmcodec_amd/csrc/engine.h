@@ -18,6 +18,7 @@
 #include "hevc_jobs.h"
 #include "jpeg_jobs.h"
 #include "mpeg2_jobs.h"
+#include "vp8_jobs.h"
 #include <atomic>
 #include <condition_variable>
 #include <deque>
@@ -64,6 +65,7 @@ struct EnginePic {
     // option jpeg_device_entropy: k_jpeg_entropy decodes the scan in front of k_jpeg_recon (je.status is set by Engine::launch)
     bool jpeg_on_device = false, jpeg_host_error = false; JpegEntropyParams je; long long jpeg_entropy_alg_bytes = 0;
     Mpeg2PicParams mp; long long mpeg2_alg_bytes = 0;
+    Vp8PicParams vp; long long vp8_recon_alg_bytes = 0, vp8_filter_alg_bytes = 0;      // codec 5 = VP8 key frame (vp; hp as for MJPEG)
     // option mpeg2_device_vlc: k_mpeg2_vlc decodes the slices in front of k_mpeg2_recon (mv.tab and mv.status are set by Engine::launch)
     bool mpeg2_on_device = false; Mpeg2VlcParams mv; long long mpeg2_vlc_alg_bytes = 0;
     int job_slot = -1;
@@ -90,7 +92,7 @@ struct EnginePic {
     // chaining: the engine currently forms chain launches -- an intra picture that can join one stays on the ordinary lane
     int lane(bool chaining = false) const {
         // MJPEG and MPEG-2 pictures ride the HEVC lane: its batches run everything on the lane's stream, with no pre-stream and no chain logic
-        if (codec == 2 || codec == 4) return kHevcLane;
+        if (codec == 2 || codec == 4 || codec == 5) return kHevcLane;      // (VP8 key frames ride it too)
         if (codec == 1) return (has_picture && hp.n_pus == 0 && hp.n_itbs > 0) ? kHevcIntraLane : kHevcLane;
         return (has_picture && (pp.stages & PS_INTRA_LDS) && !(chaining && chain_intra)) ? kIntraLane : kOrdinaryLane;
     }
@@ -99,8 +101,9 @@ struct EnginePic {
 // per kernel class: 0 recon_inter, 1 intra, 2 deblock (prep+lds), 3 packout (every pack-out kernel), 4 chain (k_chain: recon + deblock),
 // 5 rgb_pack (k_rgb_pack alone: its frames are counted in class 3 too), 6 deint (k_deint alone, likewise), 7 jpeg (k_jpeg_recon),
 // 8 pichash (k_hevc_pichash: pictures hashed, 1.5 w h bytes each), 9 md5 (k_hevc_md5, likewise), 10 rgb_pack444 (k_rgb_pack444 alone),
-// 11 mpeg2 (k_mpeg2_recon), 12 jpeg_entropy (k_jpeg_entropy), 13 mpeg2_vlc (k_mpeg2_vlc)
-constexpr int kKernelClasses = 14;
+// 11 mpeg2 (k_mpeg2_recon), 12 jpeg_entropy (k_jpeg_entropy), 13 mpeg2_vlc (k_mpeg2_vlc),
+// 14 vp8_recon (k_vp8_recon), 15 vp8_filter (k_vp8_filter: the pictures it filtered)
+constexpr int kKernelClasses = 16;
 struct EngineStats {
     double ns[kKernelClasses] = {}; long long launches[kKernelClasses] = {}, pics[kKernelClasses] = {}, alg_bytes[kKernelClasses] = {};
     long long batches = 0, batch_pics = 0, chain_batches = 0, chain_pics = 0, wait_errors = 0, chain_recoveries = 0;
@@ -172,6 +175,8 @@ private:
         bool any_jdev = false;
         // ... and for MPEG-2 pictures, around k_mpeg2_recon
         Mpeg2PicParams *h_mpics = nullptr, *d_mpics = nullptr; ihipEvent_t *m2ev[2] = {nullptr, nullptr};
+        // ... and for VP8 key frames, around k_vp8_recon ([0], [1]) and k_vp8_filter ([1], [2])
+        Vp8PicParams *h_vpics = nullptr, *d_vpics = nullptr; ihipEvent_t *v8ev[3] = {nullptr, nullptr, nullptr};
         // MPEG-2 pictures with option mpeg2_device_vlc: the parameter table of k_mpeg2_vlc, the status words (kMpeg2StatusWords per picture) with
         // their pinned copy, the two profile events -- created when the batch first holds such a picture, like h_jents
         Mpeg2VlcParams *h_m2v = nullptr, *d_m2v = nullptr; uint32_t *d_m2status = nullptr, *h_m2status = nullptr; ihipEvent_t *m2vev[2] = {nullptr, nullptr};

@@ -324,6 +324,8 @@ static int rgb_rect_device(const void *src, int pitch, int chroma_offset, int w,
 
 __attribute__((visibility("default"))) long jm_amddec_feed_annexb(const unsigned char *buf, long len, int passes, unsigned char *out, int out_cap,
     jm_amddec_handle h) {
+    // VP8 has no start codes to cut at: the call is refused for codec_type 5 (feed an IVF stream or one frame per call through jm_amddec_decode_frame)
+    if (h && D(h)->codec() == 5) { D(h)->refuse_call("jm_amddec_feed_annexb is not available for VP8 (codec_type 5): the stream has no start codes"); return -1; }
     if (!h || !buf || len < 4) return -1;       // out == NULL: frames stay on the device (jm_amddec_output_frame_device), nothing is copied
     // NAL boundaries as find_nalu sees them: a start code is 00 00 01, or 00 00 00 01 (then the NAL starts one byte earlier)
     std::vector<long> starts;

@@ -97,6 +97,7 @@ JM_EXPORT jm_amdintel_handle jm_amdintel_create_handle(void) { Ctx *c = new Ctx(
 JM_EXPORT int jm_amdintel_init(int codec_type, int out_fmt, jm_amdintel_handle h) {
     if (!h || C(h)->inited) return -1;
     if (codec_type == 2) return -1;      // in this API's enum 2 is MPEG-2 (jm_intel_dec.h), not MJPEG: refused as before
+    if (codec_type == 5) return -1;      // (VP8 key frames are offered through jm_amddec_* / jm_nvdec_* only)
     int rc = jm_amddec_init(codec_type, out_fmt, nullptr, 0, C(h)->dec);
     C(h)->inited = rc == 0;
     if (rc == 0) C(h)->feeder = std::thread([c = C(h)] { c->feed_loop(); });

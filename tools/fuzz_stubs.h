@@ -37,6 +37,7 @@ void launch_frame_to_nv12_pitch(const uint8_t *, int, int, int, uint8_t *, int, 
 #include "../jmcodec_amd/csrc/hevc_kernels.h"
 #include "../jmcodec_amd/csrc/jpeg_jobs.h"
 #include "../jmcodec_amd/csrc/mpeg2_jobs.h"
+#include "../jmcodec_amd/csrc/vp8_jobs.h"
 namespace jmamd {
 void launch_hevc_picture_batch(const HevcPicParams *, int, const HevcBatchDims &, int *, ihipStream_t *, ihipEvent_t **, uint32_t *) { abort(); }
 void launch_hevc_pichash(const HevcPicParams *, int, int, uint32_t *, ihipStream_t *) { abort(); }
@@ -45,5 +46,7 @@ void launch_jpeg_recon(const JpegPicParams *, int, int, ihipStream_t *) { abort(
 void launch_jpeg_entropy(const JpegEntropyParams *, int, int, ihipStream_t *) { abort(); }
 void launch_mpeg2_recon(const Mpeg2PicParams *, int, int, bool, ihipStream_t *) { abort(); }
 void launch_mpeg2_vlc(const Mpeg2VlcParams *, int, int, ihipStream_t *) { abort(); }
+void launch_vp8_recon(const Vp8PicParams *, int, ihipStream_t *) { abort(); }
+void launch_vp8_filter(const Vp8PicParams *, int, ihipStream_t *) { abort(); }
 void hevc_kernels_init() {}
 }
