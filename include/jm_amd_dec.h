@@ -73,7 +73,14 @@ jm_amddec_handle jm_amddec_create_handle(void);
  * start code and sizes above 8192; deinterlace_temporal is refused at init; jm_amddec_feed_annexb is refused (no start codes).  extra_data is not
  * used.  An odd display size is handed out as the even size just above.  RGB auto: BT.601 limited range, chroma centred (INTEGRATION.md "VP8").
  * Stats: vp8_key_frames, vp8_hidden_frames, vp8_empty_frames, vp8_partitions, vp8_segments, vp8_filter_type, vp8_color_space, vp8_scale,
- * vp8_bpred_mbs, vp8_skipped_mbs; with option profile k_vp8_recon_* and k_vp8_filter_* (_ns / _n / _pics / _alg_bytes). */
+ * vp8_bpred_mbs, vp8_skipped_mbs; with option profile k_vp8_recon_* and k_vp8_filter_* (_ns / _n / _pics / _alg_bytes).
+ * Option "vp8_inter" 1 (before init; only with codec_type 5 and "vp8" 1, init fails by name otherwise): INTER frames are decoded instead of failing the
+ * handle -- last / golden / altref references with the buffer copies and sign biases of RFC 6386 9.7, ZERO / NEAREST / NEAR / NEW / SPLIT vectors, six-tap
+ * (version 0) and bilinear (versions 1-3) prediction by k_vp8_inter, intra macroblocks inside inter frames, the inter-frame loop-filter deltas and
+ * thresholds; probabilities, segment map and deltas are carried from frame to frame, so a stream's frames are parsed in order, on the calling thread.
+ * A first frame that is no key frame stays refused.  There is NO independent decoder behind the inter-frame tests (INTEGRATION.md "VP8").  At 0 nothing
+ * changes.  Stats: vp8_inter_frames (p_pictures counts them too), vp8_golden_refs, vp8_altref_refs (macroblocks predicted from them), vp8_split_mbs,
+ * vp8_intra_in_inter_mbs; with option profile k_vp8_inter_*. */
 int  jm_amddec_init(int codec_type, int out_fmt, char *extra_data, int len, jm_amddec_handle h);
 int  jm_amddec_deinit(jm_amddec_handle h);
 /* in_buf may hold any chunk of an Annex-B stream; (NULL, 0) signals end of stream and then

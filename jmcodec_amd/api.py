@@ -491,8 +491,10 @@ class JmAmdDec:
     """Convenience wrapper reproducing test_nv_dec's main loop (test_nv_dec.cpp:163-259).
 
     codec_type: 0 H.264, 1 HEVC, 2 MJPEG, 4 MPEG-2 video (frame pictures, 4:2:0: INTEGRATION.md "MPEG-2"), 5 VP8 key frames (needs options={"vp8": 1}; an IVF byte
-    stream in any chunking or one frame per call: INTEGRATION.md "VP8"; `webp_to_ivf` wraps a lossy WebP file); the other values of the
-    reference's NV_CODEC_TYPE are refused at init."""
+    stream in any chunking or one frame per call: INTEGRATION.md "VP8"; `webp_to_ivf` wraps a lossy WebP file; options={"vp8": 1, "vp8_inter": 1} decodes inter frames too --
+    golden / altref references, motion vectors, six-tap and bilinear prediction; without "vp8_inter" an inter frame fails the handle, and the option is
+    refused for every other codec_type and without "vp8"; stats vp8_inter_frames, vp8_golden_refs, vp8_altref_refs, vp8_split_mbs,
+    vp8_intra_in_inter_mbs); the other values of the reference's NV_CODEC_TYPE are refused at init."""
 
     def __init__(self, codec_type=0, out_fmt=1, options=None, extra_data=None, rgb=None):
         self.h = jm_nvdec_create_handle()

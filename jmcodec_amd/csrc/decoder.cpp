@@ -197,6 +197,10 @@ int Decoder::set_option(const char *key, long long v) {
         if (inited_ || v < 0 || v > 1) return -1;
         vp8_on_ = (int)v;
     }
+    else if (k == "vp8_inter") {             // VP8: 1 = inter frames (golden / altref references, motion vectors, six-tap prediction) are decoded instead of refused
+        if (inited_ || v < 0 || v > 1) return -1;
+        vp8_inter_ = (int)v;
+    }
     else if (k == "rgb_chroma") {            // RGB output: 1 = chroma interpolated to full resolution at the stream's siting (k_rgb_pack444)
         if (inited_ || v < 0 || v > 1) return -1;
         rgb_chroma_ = (int)v;
@@ -334,6 +338,12 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "vp8_scale") return stat_v8_scale_;
     if (k == "vp8_bpred_mbs") return stat_v8_bpred_;
     if (k == "vp8_skipped_mbs") return stat_v8_skipped_;
+    // option vp8_inter: inter frames decoded; macroblocks that reference golden / altref, SPLITMV macroblocks, intra macroblocks of inter frames
+    if (k == "vp8_inter_frames") return stat_v8_inter_;
+    if (k == "vp8_golden_refs") return stat_v8_golden_;
+    if (k == "vp8_altref_refs") return stat_v8_altref_;
+    if (k == "vp8_split_mbs") return stat_v8_split_;
+    if (k == "vp8_intra_in_inter_mbs") return stat_v8_intra_in_inter_;
     if (k == "mpeg2_profile_level") return codec_ == 4 && seq_active_ ? m2seq_.profile_level : 0;
     if (k == "copy_engines") return copier_ ? (long long)copier_->engine_mask() : 0;      // SDMA engines the direct route uses (bit mask)
     if (k == "direct_frames") return stat_direct_;
@@ -374,7 +384,7 @@ long long Decoder::get_stat(const char *key) const {
     if (k == "wait_slot_ns") return stat_wait_slot_ns_;
     if (k == "parse_ns_p") return stat_parse_ns_p_;
     if (k.rfind("k_", 0) == 0 || k.rfind("eng_", 0) == 0) {          // engine-wide (all handles on this device), profile option
-        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5", "rgb_pack444", "mpeg2", "jpeg_entropy", "mpeg2_vlc", "vp8_recon", "vp8_filter"};
+        static const char *kn[kKernelClasses] = {"inter", "intra", "deblock", "packout", "chain", "rgb_pack", "deint", "jpeg", "pichash", "md5", "rgb_pack444", "mpeg2", "jpeg_entropy", "mpeg2_vlc", "vp8_recon", "vp8_filter", "vp8_inter"};
         if (!engine_) return 0;
         EngineStats es = engine_->stats();
         for (int i = 0; i < kKernelClasses; i++) {
@@ -434,6 +444,7 @@ long long Decoder::get_stat(const char *key) const {
 // MI355X-class device can be opened, because silently continuing would mean a CPU fallback.
 int Decoder::init(int codec_type, int out_fmt, const uint8_t *extra, int len) {
     codec_ = codec_type; out_fmt_ = out_fmt ? 1 : 0;
+    if (vp8_inter_ && !(codec_type == 5 && vp8_on_)) { fail("option vp8_inter is only available for VP8 (codec_type 5) with option vp8 1"); return -1; }
     // VP8 key frames are there for the handle that asks for them (option vp8 1 before init): without the option codec_type 5 stays refused, as before
     if (codec_type != 0 && codec_type != 1 && codec_type != 2 && codec_type != 4 && !(codec_type == 5 && vp8_on_)) {
         fail("only codec_type 0 (H.264), 1 (HEVC), 2 (MJPEG) and 4 (MPEG-2) are implemented in full, and 5 (VP8) for key frames with option vp8 1"); return -1; }
@@ -1697,7 +1708,10 @@ void Decoder::push_task(std::unique_ptr<PicTask> t) {
         if (raw->has_picture) parse_pending_++;
         inflight_.push_back(std::move(t));
     }
-    if (raw->has_picture) pool_submit(this, raw);
+    // (VP8 with option vp8_inter: frame n + 1 parses with what frame n left behind, so a stream's frames are parsed in order, here on the caller
+    //  thread -- the streams of different handles still parse side by side, and nothing depends on the number of parse workers)
+    if (raw->has_picture && raw->vp8 && vp8_inter_) vp8_parse_task(raw);
+    else if (raw->has_picture) pool_submit(this, raw);
     else { raw->state.store(1, std::memory_order_release); submit_ready(); }
 }
 

@@ -107,7 +107,9 @@ struct Mpeg2Task { Mpeg2Pic pic; int ref_slot[2] = {-1, -1}; size_t off_mbs = 0,
 // VP8 key frame (codec_type 5): the frame's bytes and what its first ten say; the parse worker fills in the rest of the header and where the job list
 // (records, entries: vp8_jobs.h) sits in the job buffer
 struct Vp8Task { Vp8FrameTag tag; std::vector<uint8_t> data; bool truncated = false; size_t off_mbs = 0, off_entries = 0; int n_entries = 0;
-    int filter_type = 0, sharpness = 0; bool filtered = false; int16_t dq[4][6] = {{0}}; };
+    int filter_type = 0, sharpness = 0; bool filtered = false; int16_t dq[4][6] = {{0}};
+    // option vp8_inter: an inter frame's reference surfaces (last, golden, altref; chosen by the caller thread), and what the parse adds
+    int ref_slot[3] = {-1, -1, -1}; bool inter = false; int interp = 0, n_intra = 0, n_split = 0, n_inter = 0; size_t off_split = 0; };
 
 struct PicTask {
     uint64_t seq = 0;
@@ -303,6 +305,7 @@ private:
     void vp8_handle_frame(const uint8_t *p, size_t n, bool truncated);
     bool vp8_activate(const Vp8FrameTag &tag);
     void vp8_parse_task(PicTask *t);
+    void vp8_update_refs(const Vp8Pic &pic, int cur);      // option vp8_inter
     void vp8_fill_engine_pic(PicTask *t, struct EnginePic &ep);
     void gpu_close();
     void submit_ready();
@@ -479,6 +482,11 @@ private:
     // VP8 state (front end only unless noted)
     int vp8_on_ = 0;                           // option vp8 (before init): 1 = init accepts codec_type 5
     Vp8Splitter v8split_; int v8_w_ = 0, v8_h_ = 0; long long v8_key_seen_ = 0;
+    // option vp8_inter (before init): 1 = inter frames are decoded; 0 = they fail the handle ("VP8 inter frames are not built").  With it a stream's
+    // frames are parsed in order on the caller thread (frame n + 1 reads the probabilities, the segment map and the deltas frame n left: v8_state_),
+    // and last / golden / altref are slots of the surface pool (v8_ref_; -1 before the first key frame) that the round robin skips
+    int vp8_inter_ = 0; Vp8State v8_state_; int v8_ref_[3] = {-1, -1, -1};
+    std::atomic<long long> stat_v8_inter_{0}, stat_v8_golden_{0}, stat_v8_altref_{0}, stat_v8_split_{0}, stat_v8_intra_in_inter_{0};
     // (the last five describe the last picture parsed, written by the parse worker: read them after the handle has drained, or with option sync)
     std::atomic<long long> stat_v8_key_{0}, stat_v8_hidden_{0}, stat_v8_empty_{0}, stat_v8_bpred_{0}, stat_v8_skipped_{0};
     std::atomic<int> stat_v8_parts_{0}, stat_v8_segments_{0}, stat_v8_filter_{0}, stat_v8_color_{0}, stat_v8_scale_{0};

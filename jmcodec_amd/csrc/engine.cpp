@@ -519,7 +519,7 @@ void Engine::launch(Lane &ln, Batch &b) {
     }
     if (any_mpeg2 && profile_ && !b.m2ev[0]) for (auto &e : b.m2ev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
     // ... and for VP8 key frames
-    bool any_vp8 = false, vp8_filtered = false;
+    bool any_vp8 = false, vp8_filtered = false, vp8_intra = false; int vp8_inter_mbs = 0;
     for (auto &p : b.pics) any_vp8 |= p.codec == 5 && p.has_picture;
     if (any_vp8 && !b.h_vpics) {
         if (hipHostMalloc((void **)&b.h_vpics, sizeof(Vp8PicParams) * kMaxBatch, hipHostMallocDefault) != hipSuccess ||
@@ -607,7 +607,10 @@ void Engine::launch(Lane &ln, Batch &b) {
             else b.h_mpics[i].n_items = 0;
         }
         if (any_vp8) {
-            if (p.codec == 5 && p.has_picture) { b.h_vpics[i] = p.vp; b.alg[14] += p.vp8_recon_alg_bytes; b.npics[14]++;
+            if (p.codec == 5 && p.has_picture) { b.h_vpics[i] = p.vp;
+                // an inter frame: k_vp8_inter predicts its inter macroblocks; k_vp8_recon has work only where a picture has intra macroblocks
+                if (p.vp.inter) { vp8_inter_mbs = std::max(vp8_inter_mbs, p.vp.mb_w * p.vp.mb_h); b.alg[16] += p.vp8_inter_alg_bytes; b.npics[16]++; }
+                if (!p.vp.inter || p.vp.n_intra > 0) { vp8_intra = true; b.alg[14] += p.vp8_recon_alg_bytes; b.npics[14]++; }
                 if (p.vp.filtered) { vp8_filtered = true; b.alg[15] += p.vp8_filter_alg_bytes; b.npics[15]++; } }
             else b.h_vpics[i].mb_w = 0;
         }
@@ -776,14 +779,21 @@ void Engine::launch(Lane &ln, Batch &b) {
         if (timed) { hipEventRecord(b.m2ev[1], st); b.pmask |= 32768; }
     }
     // VP8 key frames of the batch reference nothing: one launch reconstructs them all, one workgroup per picture; the loop filter follows as its
-    // own launch, so no prediction sees a filtered sample
+    // own launch, so no prediction sees a filtered sample.  Inter frames (option vp8_inter) reference surfaces that earlier batches finished
+    // (Engine::form: ref_mask): k_vp8_inter predicts their inter macroblocks first, one wave each, and k_vp8_recon -- launched only when some picture
+    // of the batch has an intra macroblock -- fills in the intra ones behind it on the same stream, reading the inter ones as neighbours
     if (any_vp8) {
-        const bool timed = profile_ && b.v8ev[0] && b.v8ev[1] && b.v8ev[2];
+        const bool timed = profile_ && b.v8ev[0] && b.v8ev[1] && b.v8ev[2] && b.v8ev[3];
+        if (vp8_inter_mbs > 0) {
+            if (timed) hipEventRecord(b.v8ev[3], st);
+            launch_vp8_inter(b.d_vpics, n, vp8_inter_mbs, st);
+            if (timed) b.pmask |= 1048576;
+        }
         if (timed) hipEventRecord(b.v8ev[0], st);
-        launch_vp8_recon(b.d_vpics, n, st);
-        if (timed) { hipEventRecord(b.v8ev[1], st); b.pmask |= 262144; }
+        if (vp8_intra) launch_vp8_recon(b.d_vpics, n, vp8_inter_mbs > 0, st);
+        if (timed) { hipEventRecord(b.v8ev[1], st); if (vp8_intra) b.pmask |= 262144; }
         if (vp8_filtered) {
-            launch_vp8_filter(b.d_vpics, n, st);
+            launch_vp8_filter(b.d_vpics, n, vp8_inter_mbs > 0, st);
             if (timed) { hipEventRecord(b.v8ev[2], st); b.pmask |= 524288; }
         }
     }
@@ -1072,6 +1082,7 @@ void Engine::complete(Lane &ln, Batch &b, bool failed) {
         if (b.pmask & 32768) { float ms = 0; if (hipEventElapsedTime(&ms, b.m2ev[0], b.m2ev[1]) == hipSuccess) { st_.ns[11] += ms * 1e6; st_.launches[11]++; } }
         if (b.pmask & 262144) { float ms = 0; if (hipEventElapsedTime(&ms, b.v8ev[0], b.v8ev[1]) == hipSuccess) { st_.ns[14] += ms * 1e6; st_.launches[14]++; } }
         if (b.pmask & 524288) { float ms = 0; if (hipEventElapsedTime(&ms, b.v8ev[1], b.v8ev[2]) == hipSuccess) { st_.ns[15] += ms * 1e6; st_.launches[15]++; } }
+        if (b.pmask & 1048576) { float ms = 0; if (hipEventElapsedTime(&ms, b.v8ev[3], b.v8ev[0]) == hipSuccess) { st_.ns[16] += ms * 1e6; st_.launches[16]++; } }
         if (b.pmask & 4096) { float ms = 0; if (hipEventElapsedTime(&ms, b.mev[0], b.mev[1]) == hipSuccess) { st_.ns[9] += ms * 1e6; st_.launches[9]++; } }
         for (int k = 0; k < kKernelClasses; k++) { st_.pics[k] += b.npics[k]; st_.alg_bytes[k] += b.alg[k]; }
         st_.batches++; st_.batch_pics += (long long)b.pics.size();

@@ -65,7 +65,7 @@ struct EnginePic {
     // option jpeg_device_entropy: k_jpeg_entropy decodes the scan in front of k_jpeg_recon (je.status is set by Engine::launch)
     bool jpeg_on_device = false, jpeg_host_error = false; JpegEntropyParams je; long long jpeg_entropy_alg_bytes = 0;
     Mpeg2PicParams mp; long long mpeg2_alg_bytes = 0;
-    Vp8PicParams vp; long long vp8_recon_alg_bytes = 0, vp8_filter_alg_bytes = 0;      // codec 5 = VP8 key frame (vp; hp as for MJPEG)
+    Vp8PicParams vp; long long vp8_recon_alg_bytes = 0, vp8_filter_alg_bytes = 0, vp8_inter_alg_bytes = 0;      // codec 5 = VP8 frame (vp; hp as for MJPEG)
     // option mpeg2_device_vlc: k_mpeg2_vlc decodes the slices in front of k_mpeg2_recon (mv.tab and mv.status are set by Engine::launch)
     bool mpeg2_on_device = false; Mpeg2VlcParams mv; long long mpeg2_vlc_alg_bytes = 0;
     int job_slot = -1;
@@ -102,8 +102,9 @@ struct EnginePic {
 // 5 rgb_pack (k_rgb_pack alone: its frames are counted in class 3 too), 6 deint (k_deint alone, likewise), 7 jpeg (k_jpeg_recon),
 // 8 pichash (k_hevc_pichash: pictures hashed, 1.5 w h bytes each), 9 md5 (k_hevc_md5, likewise), 10 rgb_pack444 (k_rgb_pack444 alone),
 // 11 mpeg2 (k_mpeg2_recon), 12 jpeg_entropy (k_jpeg_entropy), 13 mpeg2_vlc (k_mpeg2_vlc),
-// 14 vp8_recon (k_vp8_recon), 15 vp8_filter (k_vp8_filter: the pictures it filtered)
-constexpr int kKernelClasses = 16;
+// 14 vp8_recon (k_vp8_recon: the pictures with intra macroblocks), 15 vp8_filter (k_vp8_filter: the pictures it filtered), 16 vp8_inter (k_vp8_inter:
+// the inter frames)
+constexpr int kKernelClasses = 17;
 struct EngineStats {
     double ns[kKernelClasses] = {}; long long launches[kKernelClasses] = {}, pics[kKernelClasses] = {}, alg_bytes[kKernelClasses] = {};
     long long batches = 0, batch_pics = 0, chain_batches = 0, chain_pics = 0, wait_errors = 0, chain_recoveries = 0;
@@ -175,8 +176,8 @@ private:
         bool any_jdev = false;
         // ... and for MPEG-2 pictures, around k_mpeg2_recon
         Mpeg2PicParams *h_mpics = nullptr, *d_mpics = nullptr; ihipEvent_t *m2ev[2] = {nullptr, nullptr};
-        // ... and for VP8 key frames, around k_vp8_recon ([0], [1]) and k_vp8_filter ([1], [2])
-        Vp8PicParams *h_vpics = nullptr, *d_vpics = nullptr; ihipEvent_t *v8ev[3] = {nullptr, nullptr, nullptr};
+        // ... and for VP8 frames, around k_vp8_inter ([3], [0]), k_vp8_recon ([0], [1]) and k_vp8_filter ([1], [2])
+        Vp8PicParams *h_vpics = nullptr, *d_vpics = nullptr; ihipEvent_t *v8ev[4] = {nullptr, nullptr, nullptr, nullptr};
         // MPEG-2 pictures with option mpeg2_device_vlc: the parameter table of k_mpeg2_vlc, the status words (kMpeg2StatusWords per picture) with
         // their pinned copy, the two profile events -- created when the batch first holds such a picture, like h_jents
         Mpeg2VlcParams *h_m2v = nullptr, *d_m2v = nullptr; uint32_t *d_m2status = nullptr, *h_m2status = nullptr; ihipEvent_t *m2vev[2] = {nullptr, nullptr};

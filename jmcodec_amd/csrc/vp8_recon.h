@@ -1,5 +1,6 @@
-// jmcodec_amd/csrc/vp8_recon.h -- the sample arithmetic of VP8 key-frame decode (codec_type 5), INTEGRATION.md "VP8": dequantisation, the inverse
-// Walsh-Hadamard transform and the inverse DCT of RFC 6386 section 14, the intra prediction of section 12 and the loop filters of section 15, as
+// jmcodec_amd/csrc/vp8_recon.h -- the sample arithmetic of VP8 decode (codec_type 5), INTEGRATION.md "VP8": dequantisation, the inverse
+// Walsh-Hadamard transform and the inverse DCT of RFC 6386 section 14, the intra prediction of section 12, the loop filters of section 15 and (option
+// vp8_inter; k_vp8_inter, tests/native/vp8_inter_check.cpp, tools/vp8_inter_asan.cpp) the inter prediction of section 18, as
 // __host__ __device__ LANE routines: each takes the lane number and does that lane's share of one macroblock, on a small work area (LDS in the
 // kernels, plain memory on the host).  k_vp8_recon / k_vp8_filter (vp8_kernels.hip) call them with threadIdx; tests/native/vp8_check.cpp,
 // tools/vp8_asan.cpp and tools/fuzz_vp8.cpp call them for lane 0..63 in turn, phase after phase, macroblocks in the kernels' wavefront order -- so the
@@ -9,6 +10,7 @@
 #include "jpeg_recon.h"     // JR_HD, JR_UNROLL, jpeg_clip
 #include "vp8_jobs.h"
 #include <stddef.h>
+#include <string.h>
 
 namespace jmamd {
 
@@ -240,11 +242,13 @@ JR_HD int vp8_c(int v) { return v < -128 ? -128 : (v > 127 ? 127 : v); }
 JR_HD int vp8_abs(int v) { return v < 0 ? -v : v; }
 
 // interior limit, sub-block edge limit, macroblock edge limit and the key-frame hev threshold of a level (15.2, 15.3)
-JR_HD void vp8_filter_limits(int level, int sharpness, int *interior, int *sub_limit, int *mb_limit, int *thresh) {
+// (inter: the thresholds of frames that are no key frames -- 40 -> 3, 20 -> 2, 15 -> 1)
+JR_HD void vp8_filter_limits(int level, int sharpness, int *interior, int *sub_limit, int *mb_limit, int *thresh, int inter = 0) {
     int il = level;
     if (sharpness) { il >>= sharpness > 4 ? 2 : 1; if (il > 9 - sharpness) il = 9 - sharpness; }
     if (il < 1) il = 1;
-    *interior = il; *sub_limit = level * 2 + il; *mb_limit = (level + 2) * 2 + il; *thresh = level >= 40 ? 2 : (level >= 15 ? 1 : 0);
+    *interior = il; *sub_limit = level * 2 + il; *mb_limit = (level + 2) * 2 + il;
+    *thresh = inter ? (level >= 40 ? 3 : (level >= 20 ? 2 : (level >= 15 ? 1 : 0))) : (level >= 40 ? 2 : (level >= 15 ? 1 : 0));
 }
 
 // p points at q0, samples st apart across the edge
@@ -313,11 +317,11 @@ JR_HD void vp8_filt_copy_lane(Vp8FiltWork &w, uint8_t *surf, int pitch, int chro
 // phase 0: the vertical edges (the macroblock's left edge, then its inner ones, left to right) -- lane = one row: 0..15 luma, 16..31 the rows of U and V;
 // phase 1: the horizontal edges (top edge, then the inner ones) -- lane = one column: 0..15 luma, 16..31 the interleaved chroma columns.
 // RFC 6386 15: all vertical edges of a macroblock before its horizontal ones; rows (columns) are independent of each other within a phase.
-JR_HD void vp8_filter_lane(Vp8FiltWork &w, const Vp8Mb &mb, int filter_type, int sharpness, int mbx, int mby, int phase, int lane) {
+JR_HD void vp8_filter_lane(Vp8FiltWork &w, const Vp8Mb &mb, int filter_type, int sharpness, int mbx, int mby, int phase, int lane, int inter = 0) {
     const int level = mb.level > 63 ? 63 : mb.level;
     if (!level || lane >= 32 || (filter_type && lane >= 16)) return;
     int interior, sub_limit, mb_limit, thresh;
-    vp8_filter_limits(level, sharpness, &interior, &sub_limit, &mb_limit, &thresh);
+    vp8_filter_limits(level, sharpness, &interior, &sub_limit, &mb_limit, &thresh, inter);
     const bool inner = (mb.flags & VP8_MB_INNER) != 0, edge = phase ? mby > 0 : mbx > 0;
     uint8_t *p; int st, step, n_inner;      // st: across the edge; step: from one edge to the next inner one
     if (lane < 16) {
@@ -334,12 +338,159 @@ JR_HD void vp8_filter_lane(Vp8FiltWork &w, const Vp8Mb &mb, int filter_type, int
     }
 }
 
+// ---- inter prediction (RFC 6386 section 18; option vp8_inter) --------------------------------------------------------------------------------------
+// A macroblock is predicted in REGIONS, each n x n samples of one plane with one vector: a whole macroblock has 3 (luma 16, U 8, V 8), a SPLITMV
+// macroblock 24 (16 luma and 2 x 4 chroma blocks of 4 x 4; blocks with equal vectors give the same samples one by one as together).  Per region the
+// (n + 5) x (n + 5) window of the reference -- rows and columns -2 .. n + 2 around the displaced block, coordinates clamped to the decoded area, which
+// is the RFC's "as if replicated without end" -- is fetched into the work area, filtered horizontally over all n + 5 rows into tmp (+64 >> 7, clamped
+// to 8 bits) and then vertically (the same), the residual added.  Bilinear (versions 1 .. 3) is the same procedure with taps {0, 0, 128 - 16 k, 16 k,
+// 0, 0}: its first pass needs row n only, the others meet zero taps.  A fraction of 0 is the tap row {0, 0, 128, 0, 0, 0}: exact.
+constexpr int kVp8WinBytes = 24 * 81 + 8, kVp8TmpBytes = 24 * 36;          // (whole macroblock: 441 + 2 x 169 = 779 and 336 + 2 x 104 = 544)
+struct Vp8InterWork {
+    Vp8Work w;                     // coefficients and residuals as for intra macroblocks; y, u, v take the finished samples
+    uint8_t win[kVp8WinBytes];
+    uint8_t tmp[kVp8TmpBytes];
+    int16_t mv[24][2];             // per region: x, y in eighth samples of its plane
+};
+struct Vp8Region { int plane, n, bx, by, win, tmp; };      // bx, by: the block inside the macroblock; win, tmp: offsets (strides n + 5 and n)
+
+JR_HD Vp8Region vp8_region(bool split, int r) {
+    Vp8Region R;
+    if (split) {
+        const int q = r < 16 ? r : (r - 16) & 3;
+        R.plane = r < 16 ? 0 : (r < 20 ? 1 : 2); R.n = 4;
+        R.bx = r < 16 ? (q & 3) * 4 : (q & 1) * 4; R.by = r < 16 ? (q >> 2) * 4 : (q >> 1) * 4;
+        R.win = r * 81; R.tmp = r * 36;
+    } else {
+        R.plane = r; R.n = r ? 8 : 16; R.bx = R.by = 0;
+        R.win = r == 0 ? 0 : (r == 1 ? 441 : 610); R.tmp = r == 0 ? 0 : (r == 1 ? 336 : 440);
+    }
+    return R;
+}
+// the six taps of fraction f (eighths), for samples -2 .. +3
+JR_HD void vp8_taps(int interp, int f, int *t) {
+    f &= 7;
+    if (interp) { t[0] = t[1] = t[4] = t[5] = 0; t[2] = 128 - 16 * f; t[3] = 16 * f; return; }
+    switch (f) {
+    case 0: t[0] = 0; t[1] = 0; t[2] = 128; t[3] = 0; t[4] = 0; t[5] = 0; break;
+    case 1: t[0] = 0; t[1] = -6; t[2] = 123; t[3] = 12; t[4] = -1; t[5] = 0; break;
+    case 2: t[0] = 2; t[1] = -11; t[2] = 108; t[3] = 36; t[4] = -8; t[5] = 1; break;
+    case 3: t[0] = 0; t[1] = -9; t[2] = 93; t[3] = 50; t[4] = -6; t[5] = 0; break;
+    case 4: t[0] = 3; t[1] = -16; t[2] = 77; t[3] = 77; t[4] = -16; t[5] = 3; break;
+    case 5: t[0] = 0; t[1] = -6; t[2] = 50; t[3] = 93; t[4] = -9; t[5] = 0; break;
+    case 6: t[0] = 1; t[1] = -8; t[2] = 36; t[3] = 108; t[4] = -11; t[5] = 2; break;
+    default: t[0] = 0; t[1] = -1; t[2] = 12; t[3] = 123; t[4] = -6; t[5] = 0; break;
+    }
+}
+
+// lanes 0..23: the vector of region `lane`.  sv: the macroblock's entry of the picture's split list (SPLITMV), else unused
+JR_HD void vp8_inter_mvs_lane(Vp8InterWork &iw, const Vp8InterInfo &ii, const Vp8SplitMv *sv, int lane) {
+    const bool split = ii.split != 0 && sv != nullptr;
+    if (lane >= (split ? 24 : 3)) return;
+    if (split) {
+        const int16_t *v = lane < 16 ? sv->y[lane] : sv->c[(lane - 16) & 3];
+        iw.mv[lane][0] = v[0]; iw.mv[lane][1] = v[1];
+    } else {
+        const int lx = ii.mvx, ly = ii.mvy, cx = ii.cmvx, cy = ii.cmvy;      // (values, not a choice between two addresses inside ii: that would put ii into scratch)
+        iw.mv[lane][0] = (int16_t)(lane ? cx : lx); iw.mv[lane][1] = (int16_t)(lane ? cy : ly);
+    }
+}
+// the windows.  Reads of ref: luma (x, y) with 0 <= x < 16 mb_w, 0 <= y < 16 mb_h; chroma (x, y) with 0 <= x < 8 mb_w, 0 <= y < 8 mb_h -- whatever the vectors
+JR_HD void vp8_inter_fetch_lane(Vp8InterWork &iw, bool split, const uint8_t *ref, int pitch, int chroma_offset, int mb_w, int mb_h, int mbx, int mby, int lane) {
+    const int total = split ? 24 * 81 : 779;
+    for (int i = lane; i < total; i += 64) {
+        const int r = split ? i / 81 : (i < 441 ? 0 : (i < 610 ? 1 : 2));
+        const Vp8Region R = vp8_region(split, r);
+        const int j = i - R.win, ws = R.n + 5, wy = j / ws, wx = j - wy * ws;
+        const int unit = R.plane ? 8 : 16, pw = unit * mb_w, ph = unit * mb_h;
+        int x = mbx * unit + R.bx + (iw.mv[r][0] >> 3) - 2 + wx, y = mby * unit + R.by + (iw.mv[r][1] >> 3) - 2 + wy;
+        x = x < 0 ? 0 : (x > pw - 1 ? pw - 1 : x); y = y < 0 ? 0 : (y > ph - 1 ? ph - 1 : y);
+        iw.win[i] = R.plane ? ref[chroma_offset + (size_t)y * pitch + 2 * x + (R.plane - 1)] : ref[(size_t)y * pitch + x];
+    }
+}
+// first pass: every row of every window, horizontally
+JR_HD void vp8_inter_hpass_lane(Vp8InterWork &iw, bool split, int interp, int lane) {
+    const int total = split ? 24 * 36 : 544;
+    for (int i = lane; i < total; i += 64) {
+        const int r = split ? i / 36 : (i < 336 ? 0 : (i < 440 ? 1 : 2));
+        const Vp8Region R = vp8_region(split, r);
+        const int j = i - R.tmp, row = j / R.n, col = j - row * R.n;
+        int t[6];
+        vp8_taps(interp, iw.mv[r][0], t);
+        const uint8_t *s = &iw.win[R.win + row * (R.n + 5) + col];
+        const int sum = s[0] * t[0] + s[1] * t[1] + s[2] * t[2] + s[3] * t[3] + s[4] * t[4] + s[5] * t[5];
+        iw.tmp[i] = vp8_clamp255((sum + 64) >> 7);
+    }
+}
+// second pass, vertically, plus the residual (has_res: the macroblock has entries), into w.y / w.u / w.v where vp8_inter_store_lane finds them
+JR_HD void vp8_inter_vpass_lane(Vp8InterWork &iw, bool split, int interp, bool has_res, int lane) {
+    for (int i = lane; i < 384; i += 64) {
+        int r, row, col;
+        if (split) { r = i >> 4; row = (i >> 2) & 3; col = i & 3; }
+        else if (i < 256) { r = 0; row = i >> 4; col = i & 15; }
+        else { r = i < 320 ? 1 : 2; row = (i >> 3) & 7; col = i & 7; }
+        const Vp8Region R = vp8_region(split, r);
+        int t[6];
+        vp8_taps(interp, iw.mv[r][1], t);
+        const uint8_t *s = &iw.tmp[R.tmp + row * R.n + col];
+        const int n = R.n, sum = s[0] * t[0] + s[n] * t[1] + s[2 * n] * t[2] + s[3 * n] * t[3] + s[4 * n] * t[4] + s[5 * n] * t[5];
+        int v = vp8_clamp255((sum + 64) >> 7);
+        const int yy = R.by + row, xx = R.bx + col;
+        if (has_res) v = vp8_clamp255(v + iw.w.res[R.plane ? 16 + 4 * (R.plane - 1) + (yy >> 2) * 2 + (xx >> 2) : (yy >> 2) * 4 + (xx >> 2)][(yy & 3) * 4 + (xx & 3)]);
+        if (R.plane == 0) iw.w.y[(yy + 1) * kVp8YS + 4 + xx] = (uint8_t)v;
+        else (R.plane == 1 ? iw.w.u : iw.w.v)[(yy + 1) * kVp8CS + 4 + xx] = (uint8_t)v;
+    }
+}
+JR_HD void vp8_inter_store_lane(const Vp8InterWork &iw, uint8_t *surf, int pitch, int chroma_offset, int mbx, int mby, int lane) {
+    const int o = ((lane >> 3) + 1) * kVp8CS + 4 + (lane & 7);
+    vp8_store_lane(iw.w, surf, pitch, chroma_offset, mbx, mby, (uint32_t)iw.w.u[o] | (uint32_t)iw.w.v[o] << 8, lane);
+}
+// the record's Vp8InterInfo, every field the device indexes with clamped: ref 1..3 (0: the picture lacks that reference -- the macroblock is left alone)
+// b: the four dwords of the record's bmodes bytes
+JR_HD bool vp8_inter_info(const Vp8PicParams &pp, const uint32_t b[4], Vp8InterInfo &ii, const uint8_t *&ref, const Vp8SplitMv *&sv) {
+    ii.ref = (uint8_t)(b[0] & 0xff); ii.split = (uint8_t)(b[0] >> 8 & 0xff); ii.pad[0] = ii.pad[1] = 0;
+    ii.mvx = (int16_t)(b[1] & 0xffff); ii.mvy = (int16_t)(b[1] >> 16); ii.cmvx = (int16_t)(b[2] & 0xffff); ii.cmvy = (int16_t)(b[2] >> 16); ii.split_idx = b[3];
+    if (ii.ref < 1 || ii.ref > 3) return false;
+    ref = pp.ref[ii.ref - 1];
+    sv = nullptr;
+    if (ii.split) { if (!pp.split || ii.split_idx >= (uint32_t)pp.n_split) return false; sv = pp.split + ii.split_idx; }
+    return ref != nullptr;
+}
+
 #if !defined(__HIP_DEVICE_COMPILE__)
+// k_vp8_inter played on the CPU: the macroblocks in raster order (on the device they run side by side: none reads what another writes), per
+// macroblock the phases of vp8_kernels.hip with lanes 0..63 in turn
+inline void vp8_inter_mb_host(const Vp8PicParams &pp, Vp8InterWork &iw, int mbx, int mby) {
+    const Vp8Mb &mb = pp.mbs[(size_t)mby * pp.mb_w + mbx];
+    if (!(mb.flags & VP8_MB_INTER)) return;
+    Vp8InterInfo ii; const uint8_t *ref; const Vp8SplitMv *sv;
+    uint32_t words[4]; memcpy(words, mb.bmodes, 16);
+    if (!vp8_inter_info(pp, words, ii, ref, sv)) return;
+    const bool split = sv != nullptr, has_res = mb.count != 0;
+    if (has_res) {
+        for (int l = 0; l < 64; l++) vp8_zero_lane(iw.w, l);
+        for (int l = 0; l < 64; l++) vp8_scatter_lane(iw.w, mb, pp.entries, pp.n_entries, pp.dq[mb.segment & 3], l);
+        if (mb.ymode != VP8_B_PRED && (mb.nz >> 24 & 1)) for (int l = 0; l < 64; l++) vp8_wht_lane(iw.w, l);
+        for (int l = 0; l < 64; l++) vp8_idct_lane(iw.w, mb, l);
+    }
+    for (int l = 0; l < 64; l++) vp8_inter_mvs_lane(iw, ii, sv, l);
+    for (int l = 0; l < 64; l++) vp8_inter_fetch_lane(iw, split, ref, pp.pitch, pp.chroma_offset, pp.mb_w, pp.mb_h, mbx, mby, l);
+    for (int l = 0; l < 64; l++) vp8_inter_hpass_lane(iw, split, pp.interp, l);
+    for (int l = 0; l < 64; l++) vp8_inter_vpass_lane(iw, split, pp.interp, has_res, l);
+    for (int l = 0; l < 64; l++) vp8_inter_store_lane(iw, pp.surf, pp.pitch, pp.chroma_offset, mbx, mby, l);
+}
+inline void vp8_inter_host(const Vp8PicParams &pp) {
+    if (pp.mb_w <= 0 || pp.mb_h <= 0 || !pp.inter) return;
+    Vp8InterWork iw;
+    for (int y = 0; y < pp.mb_h; y++) for (int x = 0; x < pp.mb_w; x++) vp8_inter_mb_host(pp, iw, x, y);
+}
+
 // Host: the two kernels played on the CPU in their own order -- bands of 16 macroblock rows, per band the steps s = 0 .. mb_w + 2 (rows - 1) - 1, per step
 // "wave" w = 0..15 with macroblock (s - 2 w, row0 + w), per macroblock the phases of vp8_kernels.hip with lanes 0..63 in turn.  The surface is as
 // the device's: pitch a multiple of 4, 16 mb_w x 16 mb_h luma samples, chroma at chroma_offset.
 inline void vp8_recon_mb_host(const Vp8PicParams &pp, Vp8Work &w, int mbx, int mby) {
     const Vp8Mb &mb = pp.mbs[(size_t)mby * pp.mb_w + mbx];
+    if (mb.flags & VP8_MB_INTER) return;          // (k_vp8_inter has put it on the surface)
     const bool bpred = mb.ymode >= VP8_B_PRED;
     for (int l = 0; l < 64; l++) vp8_zero_lane(w, l);
     for (int l = 0; l < 64; l++) vp8_scatter_lane(w, mb, pp.entries, pp.n_entries, pp.dq[mb.segment & 3], l);
@@ -355,7 +506,7 @@ inline void vp8_filter_mb_host(const Vp8PicParams &pp, Vp8FiltWork &w, int mbx, 
     const Vp8Mb &mb = pp.mbs[(size_t)mby * pp.mb_w + mbx];
     if (!mb.level) return;
     for (int l = 0; l < 64; l++) vp8_filt_copy_lane(w, pp.surf, pp.pitch, pp.chroma_offset, mbx, mby, false, l);
-    for (int ph = 0; ph < 2; ph++) for (int l = 0; l < 64; l++) vp8_filter_lane(w, mb, pp.filter_type, pp.sharpness, mbx, mby, ph, l);
+    for (int ph = 0; ph < 2; ph++) for (int l = 0; l < 64; l++) vp8_filter_lane(w, mb, pp.filter_type, pp.sharpness, mbx, mby, ph, l, pp.inter);
     for (int l = 0; l < 64; l++) vp8_filt_copy_lane(w, pp.surf, pp.pitch, pp.chroma_offset, mbx, mby, true, l);
 }
 template <class PerMb> inline void vp8_wavefront_host(const Vp8PicParams &pp, PerMb &&per_mb) {
@@ -367,7 +518,7 @@ template <class PerMb> inline void vp8_wavefront_host(const Vp8PicParams &pp, Pe
     }
 }
 inline void vp8_reconstruct_host(const Vp8PicParams &pp) {
-    if (pp.mb_w <= 0 || pp.mb_h <= 0) return;
+    if (pp.mb_w <= 0 || pp.mb_h <= 0 || (pp.inter && pp.n_intra == 0)) return;
     Vp8Work w;
     vp8_wavefront_host(pp, [&](int x, int y) { vp8_recon_mb_host(pp, w, x, y); });
 }

@@ -1,5 +1,6 @@
-// jmcodec_amd/csrc/vp8_syntax.cpp -- VP8 key frames (codec_type 5): frame header, modes and tokens into the job list (vp8_syntax.h, vp8_jobs.h).
-// RFC 6386 sections 9 (frame header), 11 (key-frame modes), 13 (tokens), 14.1 (quantiser); what is accepted and refused: INTEGRATION.md "VP8".
+// jmcodec_amd/csrc/vp8_syntax.cpp -- VP8 (codec_type 5): frame header, modes, vectors and tokens into the job list (vp8_syntax.h, vp8_jobs.h).
+// RFC 6386 sections 9 (frame header), 11 (key-frame modes), 13 (tokens), 14.1 (quantiser), and for inter frames (option vp8_inter) 9.7, 9.10, 9.11, 16
+// (modes and vectors of inter frames), 17 (vector decoding); what is accepted and refused: INTEGRATION.md "VP8".
 #include "vp8_syntax.h"
 #include <algorithm>
 #include <cstdio>
@@ -123,6 +124,28 @@ const uint8_t kVp8CatProbs[6][12] = {{159, 0}, {165, 145, 0}, {173, 148, 140, 0}
                                      {254, 254, 243, 230, 196, 177, 153, 140, 133, 130, 129, 0}};
 const uint8_t kVp8CatBase[6] = {5, 7, 11, 19, 35, 67};
 
+// inter frames: 16.2 (modes of frames that are no key frames), 16.3 (mode and vector contexts), 17.2 (vector probabilities)
+const uint8_t kVp8YmodeProb[4] = {112, 86, 140, 37}, kVp8UvModeProb[3] = {162, 101, 204};
+const uint8_t kVp8BmodeProb[9] = {120, 90, 79, 133, 87, 85, 80, 111, 151};
+const int8_t kVp8YmodeTree[8] = {-VP8_DC_PRED, 2, 4, 6, -VP8_V_PRED, -VP8_H_PRED, -VP8_TM_PRED, -VP8_B_PRED};
+// leaves: 0 ZERO, 1 NEAREST, 2 NEAR, 3 NEW, 4 SPLIT (VP8_MV_* - 1)
+const int8_t kVp8MvRefTree[8] = {-0, 2, -1, 4, -2, 6, -3, -4};
+// leaves: 0 LEFT4x4, 1 ABOVE4x4, 2 ZERO4x4, 3 NEW4x4
+const int8_t kVp8SubMvRefTree[6] = {-0, 2, -1, 4, -2, -3};
+// leaves: 0 16x8 (top / bottom), 1 8x16 (left / right), 2 quarters, 3 sixteen 4x4
+const int8_t kVp8SplitTree[6] = {-3, 2, -2, 4, -0, -1};
+const int8_t kVp8SmallMvTree[14] = {2, 8, 4, 6, -0, -1, -2, -3, 10, 12, -4, -5, -6, -7};
+const uint8_t kVp8ModeContexts[6][4] = {{7, 1, 1, 143}, {14, 18, 14, 107}, {135, 64, 57, 68}, {60, 56, 128, 65}, {159, 134, 128, 34}, {234, 188, 128, 28}};
+// contexts: 0 normal, 1 left is zero, 2 above is zero, 3 left equals above, 4 both zero
+const uint8_t kVp8SubMvRefProbs[5][3] = {{147, 136, 18}, {106, 145, 1}, {179, 121, 1}, {223, 1, 34}, {208, 1, 1}};
+const uint8_t kVp8SplitProbs[3] = {110, 111, 150};
+const uint8_t kVp8MvDefaultProbs[2][19] = {{162, 128, 225, 146, 172, 147, 214, 39, 156, 128, 129, 132, 75, 145, 178, 206, 239, 254, 254},
+                                           {164, 128, 204, 170, 119, 235, 140, 230, 228, 128, 130, 130, 74, 148, 180, 203, 236, 254, 254}};
+const uint8_t kVp8MvUpdateProbs[2][19] = {{237, 246, 253, 253, 254, 254, 254, 254, 254, 254, 254, 254, 254, 254, 250, 250, 252, 254, 254},
+                                          {231, 243, 245, 253, 254, 254, 254, 254, 254, 254, 254, 254, 254, 254, 251, 251, 254, 254, 254}};
+const uint8_t kVp8Splits[4][16] = {{0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1}, {0, 0, 1, 1, 0, 0, 1, 1, 0, 0, 1, 1, 0, 0, 1, 1},
+                                   {0, 0, 1, 1, 0, 0, 1, 1, 2, 2, 3, 3, 2, 2, 3, 3}, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}};
+
 const uint8_t kVp8KfBmodeProbs[10][10][9] = {
     {{231, 120, 48, 89, 115, 113, 120, 152, 112}, {152, 179, 64, 126, 170, 118, 46, 70, 95}, {175, 69, 143, 80, 85, 82, 72, 155, 103},
      {56, 58, 10, 171, 218, 189, 17, 13, 152}, {144, 71, 10, 38, 171, 213, 144, 34, 26}, {114, 26, 17, 163, 44, 195, 21, 10, 173},
@@ -167,13 +190,14 @@ const uint8_t kVp8KfBmodeProbs[10][10][9] = {
 };
 
 // ---- frame tag ------------------------------------------------------------------------------------------------------------------------------------
-std::string vp8_read_tag(const uint8_t *p, size_t n, bool first, Vp8FrameTag &tag) {
+std::string vp8_read_tag(const uint8_t *p, size_t n, bool first, Vp8FrameTag &tag, bool inter_ok) {
     uint8_t b[10] = {0};
     memcpy(b, p, n < 10 ? n : 10);                       // (a frame shorter than its header reads zeros, like a partition that ends early)
     const uint32_t t = b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16;
     tag.key = !(t & 1); tag.version = (int)(t >> 1 & 7); tag.show = (int)(t >> 4 & 1); tag.part1 = t >> 5;
-    if (!tag.key) return first ? "VP8: the first frame is not a key frame" : "VP8 inter frames are not built";
+    if (!tag.key && (first || !inter_ok)) return first ? "VP8: the first frame is not a key frame" : "VP8 inter frames are not built";
     if (tag.version > 3) { char m[96]; snprintf(m, sizeof m, "VP8: version %d is not defined (RFC 6386 9.1)", tag.version); return m; }
+    if (!tag.key) return "";                             // (an inter frame has no start code and no size: it keeps the key frame's)
     if (b[3] != 0x9d || b[4] != 0x01 || b[5] != 0x2a) return "VP8: bad start code";
     tag.width = (b[6] | b[7] << 8) & 0x3fff; tag.hscale = b[7] >> 6;
     tag.height = (b[8] | b[9] << 8) & 0x3fff; tag.vscale = b[9] >> 6;
@@ -183,7 +207,7 @@ std::string vp8_read_tag(const uint8_t *p, size_t n, bool first, Vp8FrameTag &ta
     return "";
 }
 
-// ---- key frame ------------------------------------------------------------------------------------------------------------------------------------
+// ---- one frame ------------------------------------------------------------------------------------------------------------------------------------
 namespace {
 
 inline int clampq(int i) { return i < 0 ? 0 : (i > 127 ? 127 : i); }
@@ -210,45 +234,110 @@ inline int vp8_block_tokens(Vp8Bool &d, const uint8_t probs[8][3][11], int ctx, 
     return i > first ? 1 : 0;
 }
 
+// ---- inter frames: vectors (RFC 6386 16.3, 17) ----
+struct Mv { int16_t r = 0, c = 0; bool zero() const { return !r && !c; } bool operator==(const Mv &o) const { return r == o.r && c == o.c; } };
+// what the near-vector search and the split contexts read of a macroblock; everything outside the frame is an intra macroblock with zero vectors
+struct MbMv { uint8_t ref = 0, split = 0; Mv mv; Mv b[16]; };
+
+// 17.2: one component, in quarter samples; the caller doubles it
+inline int vp8_read_mv_comp(Vp8Bool &d, const uint8_t *p) {
+    int x = 0;
+    if (d.read(p[0])) {                                   // the long form: bits 0, 1, 2, then 9 down to 4, then bit 3 -- which is read only when some
+        for (int i = 0; i < 3; i++) x += d.read(p[9 + i]) << i;       // higher bit is set: a long vector of less than 8 would have been a short one
+        for (int i = 9; i > 3; i--) x += d.read(p[9 + i]) << i;
+        if (!(x & 0xfff0) || d.read(p[9 + 3])) x += 8;
+    } else x = d.tree(kVp8SmallMvTree, p + 2);
+    if (x && d.read(p[1])) x = -x;
+    return x;
+}
+inline Mv vp8_read_mv(Vp8Bool &d, const uint8_t mvp[2][19], Mv base) {
+    Mv m;
+    const int r = vp8_read_mv_comp(d, mvp[0]) * 2, c = vp8_read_mv_comp(d, mvp[1]) * 2;
+    m.r = (int16_t)(base.r + r); m.c = (int16_t)(base.c + c);      // (16-bit sums: whatever a damaged stream adds up wraps, on the device as here)
+    return m;
+}
+inline int16_t clamp_i16(int v, int lo, int hi) { return (int16_t)(v < lo ? lo : (v > hi ? hi : v)); }
+
 }  // namespace
 
-void vp8_decode_frame(const uint8_t *p, size_t n, Vp8Pic &pic) {
+void Vp8State::reset_key(int w, int h) {
+    memcpy(e.coef, kVp8CoefProbs, sizeof e.coef); memcpy(e.mv, kVp8MvDefaultProbs, sizeof e.mv);
+    memcpy(e.ymode, kVp8YmodeProb, sizeof e.ymode); memcpy(e.uvmode, kVp8UvModeProb, sizeof e.uvmode);
+    seg_abs = 0;
+    for (int i = 0; i < 4; i++) seg_q[i] = seg_lf[i] = ref_delta[i] = mode_delta[i] = sign_bias[i] = 0;
+    mb_w = w; mb_h = h;
+    seg_map.assign((size_t)w * h, 0);
+}
+
+void vp8_decode_frame(const uint8_t *p, size_t n, Vp8Pic &pic, Vp8State *st) {
     const Vp8FrameTag &tag = pic.tag;
-    pic.damaged = n < 10;
-    const uint8_t *body = n > 10 ? p + 10 : p + n;
-    const size_t body_n = n > 10 ? n - 10 : 0;
+    const bool key = tag.key || !st;           // (without a state there are only key frames: vp8_read_tag refused the others)
+    const size_t hdr = key ? 10 : 3;
+    pic.damaged = n < hdr;
+    const uint8_t *body = n > hdr ? p + hdr : p + n;
+    const size_t body_n = n > hdr ? n - hdr : 0;
     size_t part1 = tag.part1;
     if (part1 > body_n) { part1 = body_n; pic.damaged = true; }
+    const int mb_w = (tag.width + 15) >> 4, mb_h = (tag.height + 15) >> 4;
+    // what the frames before left behind: nothing for a key frame (9.3, 9.6, 9.7: segmentation, the loop filter deltas, the sign biases and every
+    // probability start from their defaults), and nothing either for an inter frame whose state is of another size (a caller's mistake, kept harmless)
+    Vp8State local;
+    Vp8State &S = st ? *st : local;
+    if (key || S.mb_w != mb_w || S.mb_h != mb_h || S.seg_map.size() != (size_t)mb_w * mb_h) S.reset_key(mb_w, mb_h);
     Vp8Bool d; d.init(body, part1);
-    pic.color_space = d.literal(1); pic.clamping = d.literal(1);
-    // segmentation (9.3) and the loop filter deltas (9.6) start from nothing on a key frame
-    int seg_q[4] = {0, 0, 0, 0}, seg_lf[4] = {0, 0, 0, 0}; uint8_t seg_probs[3] = {255, 255, 255};
-    pic.seg_abs = 0; pic.update_map = 0;
+    pic.color_space = pic.clamping = 0;
+    if (key) { pic.color_space = d.literal(1); pic.clamping = d.literal(1); }
+    // segmentation (9.3): the data and the map persist until a frame updates them
+    int (&seg_q)[4] = S.seg_q, (&seg_lf)[4] = S.seg_lf; uint8_t seg_probs[3] = {255, 255, 255};
+    pic.update_map = 0;
     pic.seg_on = d.literal(1);
     if (pic.seg_on) {
         pic.update_map = d.literal(1);
         if (d.literal(1)) {
-            pic.seg_abs = d.literal(1);
+            S.seg_abs = d.literal(1);
             for (int &q : seg_q) q = d.flagged(7);
             for (int &l : seg_lf) l = d.flagged(6);
         }
         if (pic.update_map) for (uint8_t &pr : seg_probs) pr = d.literal(1) ? (uint8_t)d.literal(8) : 255;
     }
+    pic.seg_abs = S.seg_abs;
     pic.filter_type = d.literal(1); pic.level = d.literal(6); pic.sharpness = d.literal(3);
-    int ref_delta[4] = {0, 0, 0, 0}, mode_delta[4] = {0, 0, 0, 0};
+    // the loop filter deltas (9.6): a delta whose flag is clear keeps its value
+    int (&ref_delta)[4] = S.ref_delta, (&mode_delta)[4] = S.mode_delta;
     pic.delta_on = d.literal(1);
-    if (pic.delta_on && d.literal(1)) { for (int &v : ref_delta) v = d.flagged(6); for (int &v : mode_delta) v = d.flagged(6); }
+    if (pic.delta_on && d.literal(1)) {
+        for (int &v : ref_delta) if (d.literal(1)) { v = d.literal(6); if (d.literal(1)) v = -v; }
+        for (int &v : mode_delta) if (d.literal(1)) { v = d.literal(6); if (d.literal(1)) v = -v; }
+    }
     pic.n_parts = 1 << d.literal(2);
     const int yac = d.literal(7);
     const int ydc = d.flagged(4), y2dc = d.flagged(4), y2ac = d.flagged(4), uvdc = d.flagged(4), uvac = d.flagged(4);
-    pic.refresh_entropy = d.literal(1);        // parsed; the next key frame starts from the default probabilities either way
-    uint8_t probs[4][8][3][11];
-    memcpy(probs, kVp8CoefProbs, sizeof probs);
+    pic.refresh_golden = pic.refresh_alt = pic.copy_to_golden = pic.copy_to_alt = 0; pic.refresh_last = 1;
+    if (!key) {                                // 9.7: which references this frame becomes, and which take over another's picture
+        pic.refresh_golden = d.literal(1); pic.refresh_alt = d.literal(1);
+        if (!pic.refresh_golden) pic.copy_to_golden = d.literal(2);
+        if (!pic.refresh_alt) pic.copy_to_alt = d.literal(2);
+        S.sign_bias[2] = d.literal(1); S.sign_bias[3] = d.literal(1);
+    }
+    // 9.11: refresh_entropy_probs 0 -- what this frame changes of the probabilities is dropped when the frame is done
+    pic.refresh_entropy = d.literal(1);
+    Vp8Entropy saved;
+    if (!pic.refresh_entropy) saved = S.e;
+    if (!key) pic.refresh_last = d.literal(1);
+    uint8_t (&probs)[4][8][3][11] = S.e.coef;
     pic.prob_updates = 0;
     for (int i = 0; i < 4; i++) for (int j = 0; j < 8; j++) for (int k = 0; k < 3; k++) for (int l = 0; l < 11; l++)
         if (d.read(kVp8CoefUpdateProbs[i][j][k][l])) { probs[i][j][k][l] = (uint8_t)d.literal(8); pic.prob_updates++; }
     pic.no_coeff_skip = d.literal(1);
     const int prob_skip = pic.no_coeff_skip ? d.literal(8) : 0;
+    pic.prob_intra = pic.prob_last = pic.prob_gf = pic.mode_prob_updates = pic.mv_prob_updates = 0;
+    if (!key) {                                // 9.10, 16.2, 17.2
+        pic.prob_intra = d.literal(8); pic.prob_last = d.literal(8); pic.prob_gf = d.literal(8);
+        if (d.literal(1)) { for (uint8_t &v : S.e.ymode) v = (uint8_t)d.literal(8); pic.mode_prob_updates++; }
+        if (d.literal(1)) { for (uint8_t &v : S.e.uvmode) v = (uint8_t)d.literal(8); pic.mode_prob_updates++; }
+        for (int i = 0; i < 2; i++) for (int j = 0; j < 19; j++)
+            if (d.read(kVp8MvUpdateProbs[i][j])) { const int x = d.literal(7); S.e.mv[i][j] = (uint8_t)(x ? x << 1 : 1); pic.mv_prob_updates++; }
+    }
     // 9.6, 14.1: the dequantisation factors per segment
     for (int s = 0; s < 4; s++) {
         int base = yac;
@@ -274,11 +363,15 @@ void vp8_decode_frame(const uint8_t *p, size_t n, Vp8Pic &pic) {
         parts[k].init(rest + at, len);
         o = at + len;
     }
-    const int mb_w = (tag.width + 15) >> 4, mb_h = (tag.height + 15) >> 4;
     pic.mb_w = mb_w; pic.mb_h = mb_h;
     pic.mbs.assign((size_t)mb_w * mb_h, Vp8Mb());
-    pic.entries.clear();
+    pic.entries.clear(); pic.split.clear();
     pic.bpred_mbs = pic.skipped_mbs = 0; pic.segments_used = 0; pic.filtered = false;
+    pic.inter_mbs = pic.golden_mbs = pic.alt_mbs = pic.split_mbs = pic.intra_mbs = 0;
+    // inter frames: the vectors of the frame's macroblocks inside a border of "intra, zero vector" (16.3: so counts everything outside the frame)
+    const int ms = mb_w + 1;
+    static thread_local std::vector<MbMv> mvs;
+    if (!key) mvs.assign((size_t)ms * (mb_h + 1), MbMv());
     // contexts: sub-block modes of the macroblocks above (their bottom row), non-zero flags above (4 Y, 2 U, 2 V, 1 Y2 per column)
     std::vector<uint8_t> above_b((size_t)mb_w * 4, VP8_B_DC), above_nz((size_t)mb_w * 9, 0);
     static const uint8_t implied[4] = {VP8_B_DC, VP8_B_VE, VP8_B_HE, VP8_B_TM};
@@ -288,19 +381,98 @@ void vp8_decode_frame(const uint8_t *p, size_t n, Vp8Pic &pic) {
         for (int mx = 0; mx < mb_w; mx++) {
             Vp8Mb &m = pic.mbs[(size_t)my * mb_w + mx];
             memset(&m, 0, sizeof m);
-            m.segment = pic.update_map ? (uint8_t)d.tree(kVp8SegmentTree, seg_probs) : 0;
+            uint8_t &seg = S.seg_map[(size_t)my * mb_w + mx];
+            if (pic.update_map) seg = (uint8_t)d.tree(kVp8SegmentTree, seg_probs);
+            m.segment = seg;                    // (a frame that does not update the map keeps the one it found: all zero behind a key frame)
             const int skip = pic.no_coeff_skip ? d.read(prob_skip) : 0;
-            m.ymode = (uint8_t)d.tree(kVp8KfYmodeTree, kVp8KfYmodeProb);
+            int ref = 0;                        // 0 intra, 1 last, 2 golden, 3 altref
             uint8_t *ab = &above_b[(size_t)mx * 4];
-            if (m.ymode == VP8_B_PRED) {
-                for (int b = 0; b < 16; b++) {
-                    const int A = b < 4 ? ab[b & 3] : m.bmodes[b - 4], L = (b & 3) ? m.bmodes[b - 1] : left_b[b >> 2];
-                    m.bmodes[b] = (uint8_t)d.tree(kVp8BmodeTree, kVp8KfBmodeProbs[A][L]);
+            if (!key && d.read(pic.prob_intra)) {
+                // ---- an inter macroblock (16.3) ----
+                ref = 1;
+                if (d.read(pic.prob_last)) ref = 2 + d.read(pic.prob_gf);
+                const MbMv &A = mvs[(size_t)my * ms + mx + 1], &L = mvs[(size_t)(my + 1) * ms + mx], &AL = mvs[(size_t)my * ms + mx];
+                MbMv &cur = mvs[(size_t)(my + 1) * ms + mx + 1];
+                // the near-vector search: above and left weigh 2, above-left 1; a neighbour whose reference has the other sign bias counts inverted
+                Mv near[4]; int cnt[4] = {0, 0, 0, 0}, k = 0;
+                const MbMv *nb[3] = {&A, &L, &AL};
+                for (int q = 0; q < 3; q++) {
+                    const MbMv &o = *nb[q];
+                    if (!o.ref) continue;
+                    if (!o.mv.zero()) {
+                        Mv t = o.mv;
+                        if (S.sign_bias[o.ref] != S.sign_bias[ref]) { t.r = (int16_t)-t.r; t.c = (int16_t)-t.c; }
+                        if (q == 0 || !(t == near[k])) near[++k] = t;
+                        cnt[k] += q < 2 ? 2 : 1;
+                    } else cnt[0] += q < 2 ? 2 : 1;
                 }
-                pic.bpred_mbs++;
-            } else memset(m.bmodes, implied[m.ymode], 16);
-            for (int k = 0; k < 4; k++) { ab[k] = m.bmodes[12 + k]; left_b[k] = m.bmodes[4 * k + 3]; }
-            m.uvmode = (uint8_t)d.tree(kVp8UvModeTree, kVp8KfUvModeProb);
+                if (cnt[3] && near[k] == near[1]) cnt[1] += 1;        // three distinct vectors found, and the last equals the first
+                cnt[3] = ((A.split ? 1 : 0) + (L.split ? 1 : 0)) * 2 + (AL.split ? 1 : 0);
+                if (cnt[2] > cnt[1]) { std::swap(cnt[1], cnt[2]); std::swap(near[1], near[2]); }
+                if (cnt[1] >= cnt[0]) near[0] = near[1];
+                // best, nearest and near are clamped to the window a macroblock beyond the frame's edges (16.3; the vectors that are read are not)
+                const int lo_c = -(mx * 128) - 128, hi_c = (mb_w - 1 - mx) * 128 + 128, lo_r = -(my * 128) - 128, hi_r = (mb_h - 1 - my) * 128 + 128;
+                for (int q = 0; q < 3; q++) { near[q].r = clamp_i16(near[q].r, lo_r, hi_r); near[q].c = clamp_i16(near[q].c, lo_c, hi_c); }
+                uint8_t mp[4];
+                for (int q = 0; q < 4; q++) mp[q] = kVp8ModeContexts[cnt[q]][q];
+                const int mode = d.tree(kVp8MvRefTree, mp);
+                m.mvmode = (uint8_t)(mode + 1);
+                Vp8InterInfo ii; memset(&ii, 0, sizeof ii);
+                ii.ref = (uint8_t)ref;
+                cur.ref = (uint8_t)ref;
+                if (mode == 4) {
+                    const int kind = d.tree(kVp8SplitTree, kVp8SplitProbs);
+                    static const int n_parts_of[4] = {2, 2, 4, 16};
+                    for (int j = 0; j < n_parts_of[kind]; j++) {
+                        int b0 = 0;
+                        while (kVp8Splits[kind][b0] != j) b0++;
+                        const Mv lm = (b0 & 3) ? cur.b[b0 - 1] : L.b[b0 + 3], am = (b0 >> 2) ? cur.b[b0 - 4] : A.b[b0 + 12];
+                        const int ctx = lm == am ? (lm.zero() ? 4 : 3) : (am.zero() ? 2 : (lm.zero() ? 1 : 0));
+                        const int sub = d.tree(kVp8SubMvRefTree, kVp8SubMvRefProbs[ctx]);
+                        const Mv v = sub == 0 ? lm : (sub == 1 ? am : (sub == 2 ? Mv() : vp8_read_mv(d, S.e.mv, near[0])));
+                        for (int b = 0; b < 16; b++) if (kVp8Splits[kind][b] == j) cur.b[b] = v;
+                    }
+                    cur.mv = cur.b[15]; cur.split = 1;
+                    ii.split = (uint8_t)(1 + kind); ii.split_idx = (uint32_t)pic.split.size();
+                    Vp8SplitMv sv;
+                    for (int b = 0; b < 16; b++) { sv.y[b][0] = cur.b[b].c; sv.y[b][1] = cur.b[b].r; }
+                    for (int g = 0; g < 4; g++) {
+                        const int b = (g >> 1) * 8 + (g & 1) * 2;
+                        int sc = cur.b[b].c + cur.b[b + 1].c + cur.b[b + 4].c + cur.b[b + 5].c, sr = cur.b[b].r + cur.b[b + 1].r + cur.b[b + 4].r + cur.b[b + 5].r;
+                        sc = (sc < 0 ? sc - 4 : sc + 4) / 8; sr = (sr < 0 ? sr - 4 : sr + 4) / 8;       // (the sum of four, rounded away from zero)
+                        if (tag.version == 3) { sc &= ~7; sr &= ~7; }
+                        sv.c[g][0] = (int16_t)sc; sv.c[g][1] = (int16_t)sr;
+                    }
+                    pic.split.push_back(sv);
+                    pic.split_mbs++;
+                    m.ymode = VP8_B_PRED;       // (no Y2 block, inner edges always filtered: what the device and the token loop below read of it)
+                } else {
+                    cur.mv = mode == 0 ? Mv() : (mode == 1 ? near[1] : (mode == 2 ? near[2] : vp8_read_mv(d, S.e.mv, near[0])));
+                    for (Mv &b : cur.b) b = cur.mv;
+                    m.ymode = VP8_DC_PRED;
+                }
+                ii.mvx = cur.mv.c; ii.mvy = cur.mv.r;
+                int cc = (cur.mv.c + (cur.mv.c < 0 ? -1 : 1)) / 2, cr = (cur.mv.r + (cur.mv.r < 0 ? -1 : 1)) / 2;
+                if (tag.version == 3) { cc &= ~7; cr &= ~7; }
+                ii.cmvx = (int16_t)cc; ii.cmvy = (int16_t)cr;
+                memcpy(m.bmodes, &ii, sizeof ii);
+                m.flags |= VP8_MB_INTER;
+                pic.inter_mbs++; if (ref == 2) pic.golden_mbs++; if (ref == 3) pic.alt_mbs++;
+                memset(ab, VP8_B_DC, 4); memset(left_b, VP8_B_DC, 4);
+            } else {
+                m.ymode = key ? (uint8_t)d.tree(kVp8KfYmodeTree, kVp8KfYmodeProb) : (uint8_t)d.tree(kVp8YmodeTree, S.e.ymode);
+                if (m.ymode == VP8_B_PRED) {
+                    for (int b = 0; b < 16; b++) {
+                        const int A = b < 4 ? ab[b & 3] : m.bmodes[b - 4], L = (b & 3) ? m.bmodes[b - 1] : left_b[b >> 2];
+                        // (16.2: outside key frames the sub-block modes are coded without contexts)
+                        m.bmodes[b] = (uint8_t)d.tree(kVp8BmodeTree, key ? kVp8KfBmodeProbs[A][L] : kVp8BmodeProb);
+                    }
+                    pic.bpred_mbs++;
+                } else memset(m.bmodes, implied[m.ymode], 16);
+                for (int k = 0; k < 4; k++) { ab[k] = m.bmodes[12 + k]; left_b[k] = m.bmodes[4 * k + 3]; }
+                m.uvmode = (uint8_t)d.tree(kVp8UvModeTree, key ? kVp8KfUvModeProb : S.e.uvmode);
+                pic.intra_mbs++;
+            }
             if (pic.seg_on) pic.segments_used |= 1 << m.segment;
             // residual data (13)
             uint8_t *an = &above_nz[(size_t)mx * 9];
@@ -329,7 +501,14 @@ void vp8_decode_frame(const uint8_t *p, size_t n, Vp8Pic &pic) {
             int lv = pic.level;
             if (pic.seg_on) lv = pic.seg_abs ? seg_lf[m.segment] : pic.level + seg_lf[m.segment];
             lv = std::min(std::max(lv, 0), 63);
-            if (pic.delta_on) { lv += ref_delta[0]; if (m.ymode == VP8_B_PRED) lv += mode_delta[0]; lv = std::min(std::max(lv, 0), 63); }
+            // (inter frames, 9.6 and the decoder's filter set-up: the delta of the reference, then that of the mode class -- B_PRED for intra
+            //  macroblocks, ZERO, SPLIT or "another vector mode" for inter ones)
+            if (pic.delta_on) {
+                lv += ref_delta[ref];
+                if (!ref) { if (m.ymode == VP8_B_PRED) lv += mode_delta[0]; }
+                else lv += mode_delta[m.mvmode == VP8_MV_ZERO ? 1 : (m.mvmode == VP8_MV_SPLIT ? 3 : 2)];
+                lv = std::min(std::max(lv, 0), 63);
+            }
             m.level = (uint8_t)lv;
             pic.filtered |= lv != 0;
         }
@@ -338,13 +517,22 @@ void vp8_decode_frame(const uint8_t *p, size_t n, Vp8Pic &pic) {
     for (int k = 0; k < pic.n_parts; k++) past = std::max(past, parts[k].past);
     // a bool decoder holds two bytes beyond what it has consumed: up to two zeros past the end are not damage (INTEGRATION.md "VP8")
     if (past > 2) pic.damaged = true;
+    if (!pic.refresh_entropy) S.e = saved;
 }
 
 std::string vp8_validate_jobs(const Vp8Pic &pic) {
     if (pic.mb_w <= 0 || pic.mb_h <= 0 || pic.mbs.size() != (size_t)pic.mb_w * pic.mb_h) return "VP8 job list: macroblock count";
     for (const Vp8Mb &m : pic.mbs) {
         if (m.ymode > VP8_B_PRED || m.uvmode > VP8_TM_PRED || m.segment > 3 || m.level > 63) return "VP8 job list: a mode, segment or level is out of range";
-        for (uint8_t b : m.bmodes) if (b > VP8_B_HU) return "VP8 job list: a sub-block mode is out of range";
+        if (m.flags & VP8_MB_INTER) {
+            Vp8InterInfo ii; memcpy(&ii, m.bmodes, sizeof ii);
+            if (pic.tag.key || ii.ref < 1 || ii.ref > 3 || ii.split > 4 || (ii.split != 0) != (m.mvmode == VP8_MV_SPLIT) || m.mvmode < VP8_MV_ZERO || m.mvmode > VP8_MV_SPLIT ||
+                (ii.split && ii.split_idx >= pic.split.size()) || (m.ymode != VP8_DC_PRED && m.ymode != VP8_B_PRED) || (m.ymode == VP8_B_PRED) != (ii.split != 0))
+                return "VP8 job list: an inter macroblock's reference, mode or vector index is out of range";
+        } else {
+            if (m.mvmode) return "VP8 job list: an intra macroblock with a vector mode";
+            for (uint8_t b : m.bmodes) if (b > VP8_B_HU) return "VP8 job list: a sub-block mode is out of range";
+        }
         if (m.count > kVp8MaxMbEntries || (size_t)m.first + m.count > pic.entries.size()) return "VP8 job list: a macroblock's entries lie outside the list";
         for (uint32_t e = 0; e < m.count; e++) {
             const uint32_t v = pic.entries[m.first + e]; const int blk = (int)(v >> 4 & 31);

@@ -1,5 +1,6 @@
 // jmcodec_amd/csrc/vp8_syntax.h -- VP8 (codec_type 5): IVF / frame-per-call input, the frame header, the bool decoder, the per-macroblock modes of the
-// first partition and the token decode of the token partitions of a KEY frame (RFC 6386), into the job list of vp8_jobs.h.
+// first partition and the token decode of the token partitions of a key frame and, with option vp8_inter, of an inter frame (RFC 6386), into the job
+// list of vp8_jobs.h.  An inter frame's parse depends on what the frames before it left behind (Vp8State): a stream's frames are parsed in order.
 // What is accepted and what is refused: INTEGRATION.md "VP8".  No HIP: the parse pool, tests/native/vp8_check.cpp and tools/fuzz_vp8.cpp build it.
 #pragma once
 #include "vp8_jobs.h"
@@ -22,6 +23,12 @@ extern const int8_t kVp8KfYmodeTree[8], kVp8UvModeTree[6], kVp8BmodeTree[18], kV
 extern const uint8_t kVp8CoefBands[16], kVp8Zigzag[16];
 extern const uint8_t kVp8CatProbs[6][12];                 // zero-terminated
 extern const uint8_t kVp8CatBase[6];
+// inter frames (sections 16.2, 16.3, 17.2 and the decoder printed in the RFC); tests/test_vp8_inter_host.py compares them with the restatement's own
+extern const uint8_t kVp8YmodeProb[4], kVp8UvModeProb[3], kVp8BmodeProb[9];      // the defaults of frames that are no key frames
+extern const int8_t kVp8YmodeTree[8], kVp8MvRefTree[8], kVp8SubMvRefTree[6], kVp8SplitTree[6], kVp8SmallMvTree[14];
+extern const uint8_t kVp8ModeContexts[6][4], kVp8SubMvRefProbs[5][3], kVp8SplitProbs[3];
+extern const uint8_t kVp8MvDefaultProbs[2][19], kVp8MvUpdateProbs[2][19];        // [0] rows, [1] columns: is_short, sign, 7 short-tree, 10 long bits
+extern const uint8_t kVp8Splits[4][16];                                          // the partition each luma block belongs to: 16x8, 8x16, 8x8, 4x4
 
 constexpr int kVp8MaxDim = 8192;                          // (the MJPEG path's limit)
 
@@ -50,10 +57,24 @@ struct Vp8FrameTag {
     bool key = false; int version = 0, show = 0; uint32_t part1 = 0;
     int width = 0, height = 0, hscale = 0, vscale = 0;
 };
-// "" or why the frame is refused (a handle fails on it).  first: no key frame has been decoded yet
-std::string vp8_read_tag(const uint8_t *p, size_t n, bool first, Vp8FrameTag &tag);
+// "" or why the frame is refused (a handle fails on it).  first: no key frame has been decoded yet.  inter_ok (option vp8_inter): a frame that is
+// no key frame is accepted behind a key frame; its three bytes carry no size -- width and height stay what the caller put into tag
+std::string vp8_read_tag(const uint8_t *p, size_t n, bool first, Vp8FrameTag &tag, bool inter_ok = false);
 
-// one decoded key frame: header fields, what the stream exercised, the job list
+// What a stream's frames hand to the next one (RFC 6386 9.3, 9.6, 9.7, 9.10, 9.11): the probabilities, the segment map and data, the loop-filter deltas,
+// the sign biases, and per macroblock what the near-vector search of the NEXT ROW reads.  A key frame resets all of it.
+struct Vp8Entropy { uint8_t coef[4][8][3][11], mv[2][19], ymode[4], uvmode[3]; };
+struct Vp8State {
+    Vp8Entropy e;
+    int seg_abs = 0, seg_q[4] = {0, 0, 0, 0}, seg_lf[4] = {0, 0, 0, 0};
+    int ref_delta[4] = {0, 0, 0, 0}, mode_delta[4] = {0, 0, 0, 0};
+    int sign_bias[4] = {0, 0, 0, 0};       // indexed by reference: 2 golden, 3 altref (0 and 1 stay 0)
+    int mb_w = 0, mb_h = 0;
+    std::vector<uint8_t> seg_map;          // [mb_w * mb_h]
+    void reset_key(int w, int h);
+};
+
+// one decoded frame: header fields, what the stream exercised, the job list
 struct Vp8Pic {
     Vp8FrameTag tag;
     int mb_w = 0, mb_h = 0;
@@ -67,9 +88,15 @@ struct Vp8Pic {
     int bpred_mbs = 0, skipped_mbs = 0, segments_used = 0;     // segments_used: bit mask
     std::vector<Vp8Mb> mbs;
     std::vector<uint32_t> entries;
+    // inter frames (all zero / empty on a key frame)
+    int refresh_golden = 0, refresh_alt = 0, copy_to_golden = 0, copy_to_alt = 0, refresh_last = 1;
+    int prob_intra = 0, prob_last = 0, prob_gf = 0, mode_prob_updates = 0, mv_prob_updates = 0;
+    int inter_mbs = 0, golden_mbs = 0, alt_mbs = 0, split_mbs = 0, intra_mbs = 0;
+    std::vector<Vp8SplitMv> split;     // one per SPLITMV macroblock, in raster order of those macroblocks
 };
-// Decode the key frame p[0 .. n) (vp8_read_tag accepted it).  Every macroblock gets a record whatever the bytes hold.
-void vp8_decode_frame(const uint8_t *p, size_t n, Vp8Pic &pic);
+// Decode the frame p[0 .. n) (vp8_read_tag accepted it).  Every macroblock gets a record whatever the bytes hold.  st: the stream's state, read and
+// left for the next frame; nullptr: key frames only, each from the defaults (the frames of a handle without option vp8_inter).
+void vp8_decode_frame(const uint8_t *p, size_t n, Vp8Pic &pic, Vp8State *st = nullptr);
 // every field the device indexes with: modes, segment, level, first / count against the entry list, block numbers; "" or what is wrong
 std::string vp8_validate_jobs(const Vp8Pic &pic);
 

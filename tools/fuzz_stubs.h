@@ -46,7 +46,8 @@ void launch_jpeg_recon(const JpegPicParams *, int, int, ihipStream_t *) { abort(
 void launch_jpeg_entropy(const JpegEntropyParams *, int, int, ihipStream_t *) { abort(); }
 void launch_mpeg2_recon(const Mpeg2PicParams *, int, int, bool, ihipStream_t *) { abort(); }
 void launch_mpeg2_vlc(const Mpeg2VlcParams *, int, int, ihipStream_t *) { abort(); }
-void launch_vp8_recon(const Vp8PicParams *, int, ihipStream_t *) { abort(); }
-void launch_vp8_filter(const Vp8PicParams *, int, ihipStream_t *) { abort(); }
+void launch_vp8_inter(const Vp8PicParams *, int, int, ihipStream_t *) { abort(); }
+void launch_vp8_recon(const Vp8PicParams *, int, bool, ihipStream_t *) { abort(); }
+void launch_vp8_filter(const Vp8PicParams *, int, bool, ihipStream_t *) { abort(); }
 void hevc_kernels_init() {}
 }
