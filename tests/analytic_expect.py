@@ -12,6 +12,7 @@ import numpy as np
 
 import deblock_ref
 import h264_field_ref as fr
+import h264_motion_ref as mr
 import h264_recon_ref as rr
 import scripted_h264 as sw
 from spec_tables_h264 import NORM_ADJUST_4x4
@@ -162,13 +163,15 @@ def partitions(m):
     return [(0, 0, 16, 8, a, None), (0, 8, 16, 8, b, None)] if m["t"] == "16x8" else [(0, 0, 8, 16, a, None), (8, 0, 8, 16, b, None)]
 
 
-def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong=frozenset(), rstats=None):
+def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong=frozenset(), rstats=None, mcov=None):
     """[(Y, Cb, Cr)] per picture in DECODE order, coded size (multiples of 16), uint8.  stats: counters of deblock_ref; unfiltered: a list that receives
     each picture as reconstructed, before 8.7; stale_ref_of = k: picture k alone is predicted from the UNFILTERED picture k - 1 (what a decoder computes
     that reads its reference too early; the host test shows that this is visible).  wrong: wrong-on-purpose switches of tests/h264_recon_ref.py;
     rstats: a set that receives what the Intra4x4 / Intra8x8 blocks and the residuals exercised.
     A stream with field pictures (tests/h264_field_ref.py): a field picture's entry holds the field's own lines (half the rows); a reference name
-    goes through the writer's list to an index and through the restated decoder's list back to a picture; the samples live in frame stores."""
+    goes through the writer's list to an index and through the restated decoder's list back to a picture; the samples live in frame stores.
+    A stream with macroblocks that state syntax, not motion (t="mv", skipped macroblocks among neighbours): their per-4x4 motion is derived by
+    tests/h264_motion_ref.py (wrong: its switches too; mcov: a dict that receives its branch counts); every other form is handled as before."""
     frame_seq = seq
     pl = sw.plan(seq, pics)
     wrong = frozenset(wrong)
@@ -176,6 +179,10 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong
     paff = fr.has_fields(pics)
     dec_lists = fr.decoder_lists(seq, pics, wrong) if paff else None
     st = fr.structure(pics)
+    derived = None
+    if any(sw.uses_new_forms(sw.pic_seq(seq, p), p) for p in pics):
+        derived = mr.derive(seq, pics, pl, wrong & frozenset(mr.SWITCHES), mcov)[0]
+    dpics = list(pics)                                              # for 8.7: the same pictures, the derived motion beside the syntax
     stores = {}                                                     # picture index -> the (Y, Cb, Cr) frame store it was written into
     out, raw = [], []
     for k, p in enumerate(pics):
@@ -206,7 +213,7 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong
         nxn_modes = rr.mode_tables(seq, p, wrong, rstats)[1]
         refs = out if stale_ref_of != k else out[:k - 1] + [raw[k - 1]]
         planes = [np.zeros((mbh * 16, mbw * 16), np.uint8), np.zeros((mbh * 8, mbw * 8), np.uint8), np.zeros((mbh * 8, mbw * 8), np.uint8)]
-        step = {"mb": 1, "row": mbw, "pic": mbw * mbh}[p.get("layout", "mb" if kind != "I" else "pic")]
+        step = sw.layout_step(seq, p)
         mode = 0
         if kind == "P" and seq.get("weighted_pred", 0):
             mode = 1
@@ -255,9 +262,13 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong
                         rstats.add(("i16", m["mode"], m["cmode"], bool(RES and np.asarray(m["coef"].get("ydc", [0])).any()),
                                     bool(RES and m["coef"].get("y")), bool(RES and np.asarray(m["coef"].get("cdc", [0])).any()), bool(RES and m["coef"].get("cac"))))
             else:
-                if t == "skip":
-                    m = dict(t="16x16", l0=(pl[k]["l0"][0], (0, 0)))        # 8.4.1.1: no neighbour available -> zero vector, RefPicList0[0]
-                for (px, py, w, h, l0, l1) in partitions(m):
+                if derived is not None and t in ("mv", "skip"):
+                    rects = mr.rectangles(derived[k][a])
+                elif t == "skip":
+                    rects = partitions(dict(t="16x16", l0=(pl[k]["l0"][0], (0, 0))))        # 8.4.1.1: no neighbour available -> zero vector, RefPicList0[0]
+                else:
+                    rects = partitions(m)
+                for (px, py, w, h, l0, l1) in rects:
                     for c in (0, 1, 2):
                         sub = 1 if c == 0 else 2
                         X, Yy, W, Hh = (x * 16 + px) // sub, (y * 16 + py) // sub, w // sub, h // sub
@@ -316,7 +327,9 @@ def expect_h264(seq, pics, stats=None, unfiltered=None, stale_ref_of=None, wrong
                         rstats.add(("clip1_at_255", t, c))
                     blk[:] = clip1(v)
         raw.append(tuple(planes))
-        out.append(deblock_ref.deblock_picture(seq, pics, pl, k, tuple(planes), stats, wrong))
+        if derived is not None:
+            dpics[k] = dict(p, mbs=[dict(m, blocks=derived[k][a]) if m["t"] in ("mv", "skip") else m for a, m in enumerate(p["mbs"])])
+        out.append(deblock_ref.deblock_picture(seq, dpics, pl, k, tuple(planes), stats, wrong))
         if paff:
             for S, pl_ in zip(stores[k], out[-1]):
                 if parity:

@@ -28,6 +28,8 @@ def qpc(qpy, off):
 def block_motion(m, bx, by, skip_ref):
     """[(reference picture, vector)] of the 4x4 block at (bx, by) of inter macroblock m: one entry per vector in use"""
     t = m["t"]
+    if "blocks" in m:                                               # motion derived from the syntax (tests/h264_motion_ref.py): one entry per 4x4 block
+        return [q for q in m["blocks"][(by // 4) * 4 + bx // 4] if q is not None]
     if t == "skip":
         return [(skip_ref, (0, 0))]
     if t == "16x16":

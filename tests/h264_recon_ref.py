@@ -11,6 +11,7 @@ macroblocks would notice; tests/test_h264_recon_host.py asserts that each change
 """
 import numpy as np
 
+import scripted_h264 as sw
 from spec_tables_h264 import (DEFAULT_4x4_INTER, DEFAULT_4x4_INTRA, DEFAULT_8x8_INTER, DEFAULT_8x8_INTRA, NORM_ADJUST_4x4, NORM_ADJUST_8x8, QPC_30_51,
                               ZIGZAG_4x4, ZIGZAG_8x8)
 
@@ -361,7 +362,7 @@ def mb_avail(seq, p, a):
     decoded, and, under constrained_intra_pred_flag, not inter (8.3.1.2, 8.3.2.2, 8.3.3, 8.3.4)"""
     mbw = (seq["width"] + 15) // 16
     mbh = (seq["height"] + 15) // 16
-    step = {"mb": 1, "row": mbw, "pic": mbw * mbh}[p.get("layout", "mb" if p["kind"] != "I" else "pic")]
+    step = sw.layout_step(seq, p)
 
     def avail(dx, dy):
         n = a + dx + dy * mbw
@@ -440,7 +441,7 @@ def mode_tables(seq, p, wrong=frozenset(), stats=None):
     mbw = (seq["width"] + 15) // 16
     mbs = p["mbs"]
     kind = p["kind"]
-    step = {"mb": 1, "row": mbw, "pic": len(mbs)}[p.get("layout", "mb" if kind != "I" else "pic")]
+    step = sw.layout_step(seq, p)
     constrained = seq.get("constrained_intra", 0)
 
     def derive(store, a, idx, N, wr):

@@ -3,7 +3,7 @@ analytic known-answer tests.
 
 The test says which macroblock carries which samples, vector, reference, weight, mode and levels; ``write`` turns that script into Annex-B bytes.  The
 decoded picture follows from the script by arithmetic alone (tests/analytic_expect.py, tests/h264_recon_ref.py).  Typed from the syntax clauses (7.3.2.1,
-7.3.2.1.1.1, 7.3.2.2, 7.3.3, 7.3.4, 7.3.5, 7.3.5.1, 7.3.5.3, 9.1, 9.2) -- not from tools/h264gen.c, the oracle or the product: a fourth typing of the
+7.3.2.1.1.1, 7.3.2.2, 7.3.3, 7.3.4, 7.3.5, 7.3.5.1, 7.3.5.2, 7.3.5.3, 9.1, 9.2) -- not from tools/h264gen.c, the oracle or the product: a fourth typing of the
 syntax is part of the value.  The code tables are the separately typed ones of tests/spec_tables_h264.py.
 
 The script
@@ -11,7 +11,8 @@ The script
                 constrained_intra=0) and, with profile=100 only: transform8x8=0 | 1, second_chroma_qp_off, sps_lists, pps_lists -- eight scaling lists
                 each (Intra Y, Cb, Cr, Inter Y, Cb, Cr 4x4, Intra Y, Inter Y 8x8): None (absent: the fall-back rule of Table 7-2 applies), "default" (the
                 first delta_scale gives nextScale 0) or the 16 / 64 values in zig-zag order; key absent: no matrix in that parameter set
-    pics = [dict(kind="I" | "P" | "B", poc=even int, layout="mb" | "row" | "pic", mbs=[...], and optionally
+    pics = [dict(kind="I" | "P" | "B", poc=even int, layout="mb" | "row" | "pic" | n (slices of n macroblocks), mbs=[...], and optionally
+                 direct_spatial (B: direct_spatial_mv_pred_flag, default 1),
                  is_ref (default: kind != "B"), qp (slice QP, default init_qp), deblock=(disable_idc, alpha_div2, beta_div2) (default (1, 0, 0)),
                  num_ref=(n0, n1) (active entries, sent with num_ref_idx_active_override), wp=dict(ld_y, ld_c, l0=[entry..], l1=[entry..]) with
                  entry = None (both flags 0) or dict(y=(w, o) | None, c=((w, o), (w, o)) | None))]
@@ -23,6 +24,14 @@ The script
         dict(t="skip")                                             P_Skip
         dict(t="16x16", l0=(pic, (mvx, mvy)) | None, l1=(pic, (mvx, mvy)) | None)      pic = index into pics (decode order), vectors in quarter samples
         dict(t="16x8" | "8x16", parts=[(pic, mv), (pic, mv)])      P only
+        dict(t="mv", mb=<name of Table 7-13 / 7-14>, sub=[4 names of Table 7-17 / 7-18] (P_8x8, P_8x8ref0, B_8x8),
+             ref=([ref_idx_l0 per partition | None], [ref_idx_l1 ..]), mvd=([[(dx, dy) per sub-partition] | None per partition], [.. l1]))
+                                                                   SYNTAX, not motion: the writer derives no vector for it (tests/h264_motion_ref.py
+                                                                   does, for the expectation); B_Direct_16x16 carries mb only; resid= is allowed.  In a
+                                                                   picture that holds one, every inter macroblock is of this form or t="skip" (P_Skip /
+                                                                   B_Skip, in slices of any length: mb_skip_run spans macroblocks and ends slices).
+                                                                   seq["direct_8x8_inference"] (default 1) is the SPS flag.  Refused: field pictures,
+                                                                   direct prediction with an empty list 1, |mvd| > MVD_RANGE, ref_idx outside the list
     any of these but pcm and skip may carry levels, every matrix in RASTER order:
         coef=dict(y={blkIdx: 16 levels} (Intra16x16: the AC, element 0 is 0) or, under the 8x8 transform (t="i8", or t8=1 on an inter macroblock),
                   y8={8x8 block: 64 levels}; ydc=16 levels (Intra16x16 DC, the matrix c of 8.5.10); cdc=(4 Cb, 4 Cr); cac={(plane, blk): 15 levels, raster
@@ -56,8 +65,8 @@ import re
 
 import numpy as np
 
-from spec_tables_h264 import (CBP_OF_CODENUM, COEFF_TOKEN, FIELD_SCAN_4x4, FIELD_SCAN_8x8, RUN_BEFORE, TOTAL_ZEROS_4x4, TOTAL_ZEROS_CHROMA_DC,
-                              ZIGZAG_4x4 as FRAME_SCAN_4x4, ZIGZAG_8x8 as FRAME_SCAN_8x8, parse_code_table)
+from spec_tables_h264 import (CBP_OF_CODENUM, COEFF_TOKEN, FIELD_SCAN_4x4, FIELD_SCAN_8x8, MB_TYPE_B, MB_TYPE_P, RUN_BEFORE, SUB_MB_TYPE_B, SUB_MB_TYPE_P,
+                              TOTAL_ZEROS_4x4, TOTAL_ZEROS_CHROMA_DC, ZIGZAG_4x4 as FRAME_SCAN_4x4, ZIGZAG_8x8 as FRAME_SCAN_8x8, parse_code_table)
 
 
 class Bits:
@@ -172,7 +181,8 @@ def sps(seq):
     b.u(1, fmo)                                                     # frame_mbs_only_flag
     if not fmo:
         b.u(1, 0)                                                   # mb_adaptive_frame_field_flag
-    b.u(1, 1)                                                       # direct_8x8_inference_flag
+    assert fmo or seq.get("direct_8x8_inference", 1), "7.4.2.1.1: frame_mbs_only_flag 0 needs direct_8x8_inference_flag 1"
+    b.u(1, seq.get("direct_8x8_inference", 1))                      # direct_8x8_inference_flag
     cr, cb_ = mbw * 16 - w, mbh * 16 - h
     assert cr % 2 == 0 and cb_ % 2 == 0 and (fmo or cb_ % 4 == 0), "7.4.2.1.1: CropUnitY is SubHeightC * (2 - frame_mbs_only_flag) luma rows"
     if cr or cb_:
@@ -348,7 +358,11 @@ def slice_fields(seq, p, step, m):
 
 def layout_step(seq, p):
     mbw, mbh = (seq["width"] + 15) // 16, (seq["height"] + 15) // 16
-    return {"mb": 1, "row": mbw, "pic": mbw * mbh}[p.get("layout", "mb" if p["kind"] != "I" else "pic")]
+    lay = p.get("layout", "mb" if p["kind"] != "I" else "pic")
+    if isinstance(lay, int):                                        # slices of `lay` macroblocks each: a slice may begin in mid-row
+        assert 1 <= lay <= mbw * mbh
+        return lay
+    return {"mb": 1, "row": mbw, "pic": mbw * mbh}[lay]
 
 
 def mb_qps(seq, p):
@@ -610,6 +624,98 @@ def macroblock_residual(b, st, a, m, lv, high, seen):
                 tc[16 + 4 * c + k] = residual_block(b, lv["cac"][c][k], st.n_c(a, 1 + c, k & 1, k >> 1), high, seen)
 
 
+MVD_RANGE = 8191                                                    # the largest |mvd| (quarter samples) these scripts state through se(v)
+_P_NAMES, _B_NAMES = [q[0] for q in MB_TYPE_P], [q[0] for q in MB_TYPE_B]
+_PSUB_NAMES, _BSUB_NAMES = [q[0] for q in SUB_MB_TYPE_P], [q[0] for q in SUB_MB_TYPE_B]
+
+
+def uses_new_forms(seq, p):
+    """The picture holds a macroblock that states syntax, not motion (t="mv"), or a skipped macroblock whose vector a neighbour may decide"""
+    step = layout_step(seq, p)
+    return any(m["t"] == "mv" or (m["t"] == "skip" and (step > 1 or p["kind"] == "B")) for m in p["mbs"])
+
+
+def mv_shape(kind, m):
+    """Of a t="mv" macroblock: (mb_type value, name, [prediction mode per partition], [sub-partition count per partition], [sub_mb_type values] or
+    None, [(x, y, w, h) of every partition's every sub-partition]) from Tables 7-13 / 7-14 / 7-17 / 7-18 and 6.4.2.1 / 6.4.2.2"""
+    names, table = (_P_NAMES, MB_TYPE_P) if kind == "P" else (_B_NAMES, MB_TYPE_B)
+    assert kind in ("P", "B") and m["mb"] in names, (kind, m["mb"])
+    v = names.index(m["mb"])
+    name, nparts, modes, pw, ph = table[v]
+    if name == "B_Direct_16x16":
+        assert not ({"ref", "mvd", "sub"} & set(m)), "B_Direct_16x16 carries no motion syntax"
+        return v, name, ["Direct"] * 4, [4] * 4, None, [[(8 * (i & 1) + 4 * (j & 1), 8 * (i >> 1) + 4 * (j >> 1), 4, 4) for j in range(4)] for i in range(4)]
+    if modes is not None:
+        assert "sub" not in m
+        rects = [[((i * pw) % 16, (i * pw) // 16 * ph, pw, ph)] for i in range(nparts)]
+        return v, name, list(modes), [1] * nparts, None, rects
+    snames, stable = (_PSUB_NAMES, SUB_MB_TYPE_P) if kind == "P" else (_BSUB_NAMES, SUB_MB_TYPE_B)
+    assert len(m["sub"]) == 4 and all(s in snames for s in m["sub"]), m["sub"]
+    subs = [snames.index(s) for s in m["sub"]]
+    rects = []
+    for i, s in enumerate(subs):
+        _, n, _, w, h = stable[s]
+        rects.append([(8 * (i & 1) + (j * w) % 8, 8 * (i >> 1) + (j * w) // 8 * h, w, h) for j in range(n)])
+    return v, name, [stable[s][2] for s in subs], [stable[s][1] for s in subs], subs, rects
+
+
+def transform8x8_flag_allowed(seq, kind, m):
+    """7.3.5: the condition under which transform_size_8x8_flag follows a non-zero luma pattern of an inter macroblock: no sub-macroblock partition
+    smaller than 8x8, a direct sub-macroblock or B_Direct_16x16 only with direct_8x8_inference_flag"""
+    _, name, modes, counts, subs, _ = mv_shape(kind, m)
+    inf = seq.get("direct_8x8_inference", 1)
+    if name == "B_Direct_16x16":
+        return bool(inf)
+    if subs is None:
+        return True
+    return all((inf if mode == "Direct" else n == 1) for mode, n in zip(modes, counts))
+
+
+def inter_syntax(b, kind, pl, m):
+    """mb_type and mb_pred() / sub_mb_pred() (7.3.5.1, 7.3.5.2) of a macroblock that states its syntax: ref_idx per partition and list, mvd per
+    (sub-)partition and list.  Nothing is derived."""
+    v, name, modes, counts, subs, _ = mv_shape(kind, m)
+    b.ue(v)
+    if name == "B_Direct_16x16":
+        return
+    for s in subs or []:
+        b.ue(s)
+    ref, mvd = m["ref"], m["mvd"]
+    uses = lambda l, i: modes[i] in (("L0", "Bi"), ("L1", "Bi"))[l]
+    assert kind == "B" or all(q is None for q in ref[1]) and all(q is None for q in mvd[1])
+    for l in (0, 1):
+        assert len(ref[l]) == len(modes) and len(mvd[l]) == len(modes)
+        for i in range(len(modes)):
+            if not uses(l, i):
+                assert ref[l][i] is None and mvd[l][i] is None, ("this partition does not use list %d" % l, name, i)
+                continue
+            assert ref[l][i] is not None and 0 <= ref[l][i] < pl["n"][l], ("ref_idx outside the active list", name, l, i, ref[l][i], pl["n"])
+            if name == "P_8x8ref0":
+                assert ref[l][i] == 0                                   # not sent: inferred 0
+            elif pl["n"][l] > 1:
+                b.te(ref[l][i], pl["n"][l] - 1)                       # range 1: nothing sent; 2: the inverted bit; more: ue(v)
+    for l in (0, 1):
+        for i in range(len(modes)):
+            if uses(l, i):
+                assert len(mvd[l][i]) == counts[i], (name, l, i)
+                for d in mvd[l][i]:
+                    assert all(-MVD_RANGE <= c <= MVD_RANGE for c in d), ("mvd outside the scripted range of se(v)", d)
+                    b.se(d[0]); b.se(d[1])
+
+
+def one_dc_coefficient_in_slice(b, st, a, blk, sign, t8_flag, high):
+    """``one_dc_coefficient`` where neighbouring macroblocks may be available: nC from the TotalCoeff bookkeeping of 9.2.1; t8_flag: transform_size_8x8_
+    flag is present (and 0: the coefficient belongs to a 4x4 block)"""
+    b8 = blk >> 2
+    b.ue([c[1] for c in CBP_OF_CODENUM].index(1 << b8))
+    if t8_flag:
+        b.u(1, 0)
+    b.se(0)                                                         # mb_qp_delta
+    for k in range(4 * b8, 4 * b8 + 4):
+        bx, by = BLK_XY[k][0] // 4, BLK_XY[k][1] // 4
+        st.tc[a][by * 4 + bx] = residual_block(b, [sign if k == blk else 0] + [0] * 15, st.n_c(a, 0, bx, by), high)
+
+
 def slice_header(b, seq, p, pl, first_mb):
     kind = p["kind"]
     b.ue(first_mb)
@@ -624,7 +730,7 @@ def slice_header(b, seq, p, pl, first_mb):
         b.ue(0)                                                     # idr_pic_id
     b.u(LOG2_MAX_POC_LSB, p["poc"] % (1 << LOG2_MAX_POC_LSB))
     if kind == "B":
-        b.u(1, 1)                                                   # direct_spatial_mv_pred_flag
+        b.u(1, p.get("direct_spatial", 1))                          # direct_spatial_mv_pred_flag
     if kind != "I":
         b.u(1, int(pl["override"]))
         if pl["override"]:
@@ -710,6 +816,10 @@ def write(seq, pics, seen=None, coded_modes=None):
         step = layout_step(seq, p)
         mb_qps(seq, p)                                              # its assertions
         st = PicState(seq, mbs, step)
+        new_forms = uses_new_forms(seq, p)
+        if new_forms:
+            assert not field and frame_seq.get("frame_mbs_only", 1), "the forms that state syntax are for frame pictures of progressive streams"
+            assert all(m["t"] in INTRA + ("mv", "skip") for m in mbs), "a picture states its motion syntax in every inter macroblock or in none"
         for first in range(0, n_mbs, step):
             b = Bits()
             qp, db = slice_fields(seq, p, step, mbs[first])
@@ -720,7 +830,8 @@ def write(seq, pics, seen=None, coded_modes=None):
                 t = m["t"]
                 st.tc[a] = [16 if t == "pcm" else 0] * 24            # 9.2.1: I_PCM counts 16, a skipped macroblock and a block without levels 0
                 if t == "skip":
-                    assert kind == "P" and step == 1
+                    assert kind == "P" and step == 1 or (kind != "I" and new_forms)
+                    assert kind == "P" or pl["l1"], "B_Skip is direct prediction: RefPicList1[0] must exist"
                     skip_run += 1
                     continue
                 if kind != "I":
@@ -747,6 +858,18 @@ def write(seq, pics, seen=None, coded_modes=None):
                     if coded_modes is not None:
                         coded_modes[(k, a)] = coded
                     b.ue(m["cmode"])                                # intra_chroma_pred_mode
+                elif t == "mv":
+                    assert "coef" not in m and "t8" not in m, "the forms that state syntax carry resid= at most"
+                    assert "Direct" not in mv_shape(kind, m)[2] or pl["l1"], "direct prediction: RefPicList1[0] must exist"
+                    inter_syntax(b, kind, pl, m)
+                    flag = bool(t8mode) and transform8x8_flag_allowed(frame_seq, kind, m)
+                    if seen is not None:
+                        seen.add(("transform_size_8x8_flag_possible", m["mb"], flag, "resid" in m))
+                    if "resid" in m:
+                        one_dc_coefficient_in_slice(b, st, a, m["resid"][0], m["resid"][1], flag, high)
+                    else:
+                        b.ue([c[1] for c in CBP_OF_CODENUM].index(0))    # coded_block_pattern 0: nothing follows
+                    continue
                 else:
                     parts = [(m.get("l0"), m.get("l1"))] if t == "16x16" else [(q, None) for q in m["parts"]]
                     if kind == "P":
